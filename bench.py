@@ -17,7 +17,12 @@ buckets are sharded by owner; each rank holds its own K-bucket shard and
 merges its own pre-routed n-message stream (weak scaling, no data-path
 collective).  value = all merges of all ranks / max-over-ranks time.
 
-Beside it, the same JSON line carries `owner_routed`: C2's fixed total
+A plain run (`--gpus N --steps S --warmup W`) does only that: set up, warm
+up, time the S steps, write the outputs if `--dump-outputs DIR` is given, and
+print the line.  `--full` adds the CPU baseline and the objects below, each
+with its in-run parity check.
+
+With `--full`, the same JSON line carries `owner_routed`: C2's fixed total
 (K buckets, n messages per step) hash-sharded by name over the N GPUs, every
 rank drawing n/N messages over ALL buckets as they arrive from peers, packed
 by owner on the GPU (phip_route_pack, sender-side combine), moved by RCCL
@@ -45,6 +50,7 @@ T0 = 1_700_000_000_000_000_000
 BYTES_PER_MERGE = 88     # msg 32 + slot key 8 + state read 24 + state write 24
 HBM_PEAK_GBS = 8000.0    # MI355X_MICROARCH.md chip-level parameters (spec)
 DOMINANT = "k_receive_fast"
+POOL_BYTES = 64 << 30        # c2: HBM for the step batches (28 of 100M messages)
 CPU_REPS = 5                 # median of 5 runs per thread count
 CPU_SLOW_SAMPLE = 2_000_000  # messages per run at 1 and nproc (> 16) threads
 
@@ -60,8 +66,19 @@ def parse():
     p.add_argument("--zipf", type=float, default=1.1)
     p.add_argument("--cpu-sample", type=int, default=10_000_000)
     p.add_argument("--cpu-threads", type=int, default=0)
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--seed", type=int, default=1234)
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the CPU baseline (unless --no-cpu) and, for c2, the "
+                        "owner_routed, c2_variants, c3, c4 and anti_entropy objects with their "
+                        "in-run parity checks (each can be dropped with its --no-... option); "
+                        "without it the run sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="c2: after the timed steps write what the last step produced as "
+                        "DIR/<name>.npy (dump_outputs())")
+    p.add_argument("--pool-bytes", type=int, default=POOL_BYTES,
+                   help="c2: HBM for the step batches (24 B per message each); a run of more "
+                        "steps than fit reuses them, moved up in place between timed spans")
     p.add_argument("--no-combine", action="store_true",
                    help="c4: no sender-side combine of hot names (PHIP_ROUTE_COMBINE)")
     p.add_argument("--route-world", type=int, default=8,
@@ -209,6 +226,31 @@ def replica_states(torch, gen, n, step, dev):
     return added.view(torch.int64), taken.view(torch.int64), elapsed
 
 
+def pool_size(args, n):
+    """How many step batches of n messages (24 B each) stay in HBM: one per
+    step while they fit --pool-bytes, at least 2."""
+    return min(args.warmup + args.steps, max(2, args.pool_bytes // (24 * n)))
+
+
+def pool_spans(lo, hi, pool):
+    """[lo, hi) cut where the batch pool is recycled (every `pool` steps)."""
+    while lo < hi:
+        cut = min(hi, (lo // pool + 1) * pool)
+        yield lo, cut
+        lo = cut
+
+
+def recycle_batches(torch, batches, pool):
+    """Every batch of the pool moved up in place by `pool` steps' worth:
+    replica_states' shift by the step index, `pool` steps further (taken is a
+    whole number below 2^53, so its sum is exact; added stays >= taken:
+    rounding is monotonic)."""
+    for a, t, e in batches:
+        a.view(torch.float64).add_(pool * 2e6)
+        t.view(torch.float64).add_(pool * 2e6)
+        e.add_(pool * (1 << 40))
+
+
 # ---------------------------------------------------------- CPU baseline ---
 def cpu_thread_counts(args):
     """1, the box's CPU share (16) and nproc threads (1 and nproc)."""
@@ -320,6 +362,54 @@ def pmc_traffic(key, workload, kernel, build):
         return None, (f"PMC entry for {key} is from build {d.get('build_id')}, this run is "
                       f"build {build}")
     return d.get("hbm_bytes_per_step"), d.get("source")
+
+
+DUMP_STATUS_SAMPLE = 1 << 21   # statuses written (float32, and their float64 indices: 24 MiB)
+DUMP_BUCKET_SAMPLE = 1 << 19   # buckets written (4 float64 columns: 16 MiB)
+
+
+def dump_outputs(args, torch, dev, repo, rank, base, K, n, status):
+    """--dump-outputs DIR: what the c2 step left after the last timed step,
+    as DIR/<name>.npy (rank r > 0: <name>.rank<r>.npy), 40 MiB at the most.  The
+    inputs depend only on the arguments (seeded generators), and a merge is
+    a field-wise maximum, so two builds given the same arguments must write
+    the same arrays.
+      status         float32: the last step's per-message status column (what
+                     a Receive caller gets back) at status_index
+      status_index   float64: the message indices sampled (seeded; all of
+                     them when the batch has at most 2^21 messages)
+      status_counts  float64[256]: how often each status value occurs in the
+                     whole column
+      bucket_ids, added, taken, elapsed
+                     float64: a seeded sample of 2^19 bucket ids beside the
+                     256 hottest, and their states in the table after the
+                     last step, read back through phip_export_datagrams
+                     (added and taken are the float64 the bits stand for)"""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    rng = np.random.default_rng(args.seed + 4242)
+    out = {}
+    if status is not None:
+        idx = np.arange(n) if n <= DUMP_STATUS_SAMPLE else \
+            np.sort(rng.choice(n, DUMP_STATUS_SAMPLE, replace=False))
+        out["status_index"] = idx.astype(np.float64)
+        out["status"] = status[torch.from_numpy(idx).to(dev)].cpu().numpy().astype(np.float32)
+        out["status_counts"] = torch.bincount(status.to(torch.int64), minlength=256) \
+            .cpu().numpy().astype(np.float64)
+    samp = np.arange(K) if K <= DUMP_BUCKET_SAMPLE else \
+        np.union1d(rng.choice(K, DUMP_BUCKET_SAMPLE, replace=False),
+                   (np.arange(256, dtype=np.int64) * zipf_mult(K)) % K)
+    ids = torch.from_numpy(samp.astype(np.int64)).to(dev) + base
+    sb, so = names_for_ids(torch, ids, args.name_len)
+    ga, gt, ge, found = repo.export_states_device(sb, so, ids.numel())
+    if not bool(found.all()):
+        raise RuntimeError("--dump-outputs: a seeded bucket is missing from the table")
+    out["bucket_ids"] = ids.cpu().numpy().astype(np.float64)
+    out["added"] = ga.contiguous().view(torch.float64).cpu().numpy()
+    out["taken"] = gt.contiguous().view(torch.float64).cpu().numpy()
+    out["elapsed"] = ge.cpu().numpy().astype(np.float64)
+    tail = f".rank{rank}" if rank else ""
+    for name, arr in out.items():
+        np.save(os.path.join(args.dump_outputs, f"{name}{tail}.npy"), arr)
 
 
 def datagrams(torch, blob, offs, a, t, e):
@@ -747,13 +837,16 @@ def run_routed(args, torch, dist, dev, local, rank, world):
     ids = zipf_ids(torch, gen, m, K, args.zipf, dev)
     blob, offs = names_for_ids(torch, ids, args.name_len)
     del ids
-    batches = [replica_states(torch, gen, m, j, dev) for j in range(args.warmup + args.steps)]
+    # (as the headline: at most --pool-bytes of batches in HBM, recycled with
+    # the clock stopped when the run has more steps)
+    pool = pool_size(args, m)
+    batches = [replica_states(torch, gen, m, j, dev) for j in range(pool)]
     torch.cuda.synchronize()
     merged = []
     group = open_group(args, dist, repo, rank, world)
 
     def step(j):
-        a, t, e = batches[j]
+        a, t, e = batches[j % pool]
         if group is not None:
             _, got = group.receive([(blob, offs, a, t, e)], T0 + j, combine=True)
             k = got[0]
@@ -766,16 +859,24 @@ def run_routed(args, torch, dist, dev, local, rank, world):
         if j >= args.warmup:
             merged.append(k)
 
-    for j in range(args.warmup):
-        step(j)
-    dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for j in range(args.warmup, args.warmup + args.steps):
-        step(j)
-    torch.cuda.synchronize()
-    dist.barrier()
-    el = time.perf_counter() - t0
+    for lo, hi in pool_spans(0, args.warmup, pool):
+        if lo and lo % pool == 0:
+            torch.cuda.synchronize()
+            recycle_batches(torch, batches, pool)
+        for j in range(lo, hi):
+            step(j)
+    el = 0.0
+    for lo, hi in pool_spans(args.warmup, args.warmup + args.steps, pool):
+        if lo and lo % pool == 0:   # untimed: the next `pool` batches
+            recycle_batches(torch, batches, pool)
+        dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for j in range(lo, hi):
+            step(j)
+        torch.cuda.synchronize()
+        dist.barrier()
+        el += time.perf_counter() - t0
     tt = torch.tensor([el, float(np.mean(merged)), float(owned)], dtype=torch.float64,
                       device=dev if args.dist_backend == "nccl" else "cpu")
     mx = tt.clone()
@@ -1347,8 +1448,11 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    routed = (args.workload == "c2" and not (c1 or args.no_routed or args.wire or args.insert or
-                                             args.ring))
+    if args.dump_outputs and args.workload != "c2":
+        raise SystemExit("bench.py: --dump-outputs covers the c2 workload only")
+    # the extra legs (and the CPU baselines below) belong to --full
+    routed = (args.full and args.workload == "c2" and
+              not (c1 or args.no_routed or args.wire or args.insert or args.ring))
     if world > 1 or args.workload in ("c4", "c5") or routed:
         # c4/c5 and the owner-routed line exercise the collectives
         # (all-to-all, all-reduce) even on one GPU
@@ -1382,6 +1486,7 @@ def main():
     assert len(repo) == K
 
     c5_check = None
+    pool, recycle = args.warmup + args.steps, None   # (c2: the batches kept in HBM, see below)
     owned = K
     c3_cpu = None
     if args.workload == "c3":
@@ -1399,7 +1504,14 @@ def main():
     else:
         ids = zipf_ids(torch, gen, n, K, args.zipf, dev)
         blob, offs = names_for_ids(torch, ids + base, args.name_len)
-        batches = [replica_states(torch, gen, n, j, dev) for j in range(args.warmup + args.steps)]
+        # One batch per step while they fit POOL_BYTES of HBM (the recorded
+        # runs: 25 batches of 2.4 GB).  A longer run reuses the buffers: after
+        # every `pool` steps the clock stops and each batch moves up by `pool`
+        # steps' worth (recycle(), below), so every step is still a first
+        # application of states later than all before it.
+        if not (args.ring or args.wire or args.insert):
+            pool = pool_size(args, n)
+        batches = [replica_states(torch, gen, n, j, dev) for j in range(pool)]
         # the per-message status column a Receive caller reads (merge vs incast);
         # two, alternating: a queued batch's outputs stay untouched until the
         # next call finishes it (PHIP_RECV_ASYNC), so batch j+1 writes the other
@@ -1471,46 +1583,66 @@ def main():
             # its offsets (the binding's default checks them: ~0.1 ms per
             # 100M messages, patrolhip.h phip_msgs.names_len)
             def step(j):
-                a, t, e = batches[j]
+                a, t, e = batches[j % pool]
                 repo.receive_soa(blob, a, t, e, T0 + j, name_offs=offs, n=n, status=c2_status[j % 2],
                                  device=True, queue=not args.sync_receive,
                                  names_len=0 if not args.check_names else None)
 
+            def recycle():
+                recycle_batches(torch, batches, pool)
+
     extra = {}
-    for j in range(args.warmup):
-        step(j)
+
+    def spans(lo, hi):
+        return pool_spans(lo, hi, pool)
+
+    for lo, hi in spans(0, args.warmup):
+        if lo and lo % pool == 0:
+            repo.flush()
+            recycle()
+        for j in range(lo, hi):
+            step(j)
     repo.flush()   # (a queued receive batch: finished and checked here)
     # HIP events around every kernel of the timed steps, kept by the library
-    # and read once after the timed region (reading them synchronises).
+    # and read after each timed span (reading them synchronises).
     # (c5's step reads its own per-call timings from the shard layer.)
-    repo.set_timing(True, accumulate=True)
     kern = {}
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
     launches = {}
-    step_tl = []
-    for j in range(args.warmup, args.warmup + args.steps):
-        tl = step(j)
-        if tl is not None:
-            step_tl.append(tl)
-    repo.flush()   # the last queued batch finished (its misses / dirty buckets) inside the timing
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    el = time.perf_counter() - t0
-    # per step: a kernel launched several times in a step (chunks) is summed
-    for tl in (step_tl or [repo.timings()]):
-        for name, ms in tl:
-            kern[name] = kern.get(name, 0.0) + ms / (1 if step_tl else args.steps)
-            launches[name] = launches.get(name, 0) + 1
-    kern = {k: [v / (args.steps if step_tl else 1)] for k, v in kern.items()}
+    el = 0.0
+    for lo, hi in spans(args.warmup, args.warmup + args.steps):
+        if lo and lo % pool == 0:   # untimed: the next `pool` batches
+            recycle()
+        repo.set_timing(True, accumulate=True)
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        step_tl = []
+        for j in range(lo, hi):
+            tl = step(j)
+            if tl is not None:
+                step_tl.append(tl)
+        repo.flush()   # the last queued batch finished (its misses / dirty buckets) inside the timing
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        el += time.perf_counter() - t0
+        # per step: a kernel launched several times in a step (chunks) is summed
+        for tl in (step_tl or [repo.timings()]):
+            for name, ms in tl:
+                kern[name] = kern.get(name, 0.0) + ms / args.steps
+                launches[name] = launches.get(name, 0) + 1
+    kern = {k: [v] for k, v in kern.items()}
     repo.set_timing(False)
+    if args.dump_outputs:
+        dump_outputs(args, torch, dev, repo, rank, base, K, n,
+                     c2_status[(args.warmup + args.steps - 1) % 2] if not
+                     (args.no_status or args.ring or args.wire or args.insert) else None)
     if args.workload == "c2":
         st4 = repo.last_stats()   # the last batch: directory entries, folded through it, misses
         extra["hot_directory"] = {"entries": int(st4[0]), "folded": int(st4[1]),
                                   "misses": int(st4[2])}
+        extra["batches_in_hbm"] = pool
     if world > 1:
         tt = torch.tensor([el], dtype=torch.float64,
                           device=dev if args.dist_backend == "nccl" else "cpu")
@@ -1622,7 +1754,7 @@ def main():
         "config": {"workload": workload, "keys_per_gpu": K, "messages_per_step_per_gpu": n,
                    "slots_per_gpu": 1 << args.log2_slots, "parallelism": f"shard{world}",
                    "name_bytes": args.name_len or "2-8 (b<id>)",
-                   "world_size": world,
+                   "world_size": world, "full": args.full,
                    # the headline is C2 weak scaling: every rank merges its own
                    # pre-routed stream, no owner routing (that is owner_routed / c4)
                    "exchange": False,
@@ -1637,12 +1769,13 @@ def main():
         "build_id": build,
     }
     out["config"].update(extra)
-    if rank == 0 and world == 1 and not args.no_cpu and args.workload == "c2":
+    cpu_leg = args.full and not args.no_cpu and rank == 0 and world == 1
+    if cpu_leg and args.workload == "c2":
         try:
             out["cpu_baseline"] = cpu_baseline(args, K, ids.cpu())
         except Exception as ex:  # the baseline must never hide the GPU result
             out["cpu_baseline"] = {"error": repr(ex)}
-    elif rank == 0 and world == 1 and not args.no_cpu and c3_cpu is not None:
+    elif cpu_leg and c3_cpu is not None:
         try:
             out["cpu_baseline"] = c3_cpu()
         except Exception as ex:

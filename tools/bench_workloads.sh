@@ -18,11 +18,11 @@ step() {  # step NAME SECONDS ARGS...
   tail -1 "$OUT/$name.log" > "$OUT/$name.json"
 }
 
-step c1 300 --workload c1
+step c1 300 --workload c1 --full
 step c2_wire 300 --wire --no-cpu
 step c2_insert 300 --insert --no-cpu
 step c2_ring 300 --ring --no-cpu
-step c3 300 --workload c3
+step c3 300 --workload c3 --full
 step c4 300 --workload c4 --no-cpu
 step c5 300 --workload c5 --no-cpu
 echo done | tee -a "$OUT/steps.log"

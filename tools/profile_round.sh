@@ -19,7 +19,7 @@ step() {  # step NAME SECONDS CMD...
   if [ $rc -ne 0 ]; then tail -20 "$OUT/$name.log"; exit $rc; fi
 }
 
-step bench 600 python3 -u bench.py
+step bench 600 python3 -u bench.py --full
 tail -1 "$OUT/bench.log" > "$OUT/bench.json"
 step rocprof_stats 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/stats" -o run -- python3 -u bench.py --no-cpu --steps 3 --warmup 1
 # PMC: one block's worth of counters per pass (MI355X_MICROARCH.md: FETCH_SIZE
