@@ -193,7 +193,10 @@ typedef struct phip_state {
  *     PHIP_ST_NOT_PROCESSED (a queued batch reports it from the call that
  *     finishes it);
  *   - phip_upsert_soa / phip_apply_mixed (phip_ops.names_len): nothing of the
- *     batch is applied.
+ *     batch is applied;
+ *   - phip_route_pack: nothing is packed;
+ *   - phip_group_receive: none of the process's batches is applied (see
+ *     there).
  * With names_len == 0 a device batch's offsets are trusted: a wild offset is
  * a read of device memory the kernels do not own.  A queued batch's input
  * columns must stay untouched until it is finished (PHIP_RECV_ASYNC): a
@@ -563,7 +566,18 @@ phip_handle* phip_group_handle(phip_group* g, uint32_t i);
  * and merged.  A world of one (without PHIP_GROUP_RCCL_SELF) has nothing to
  * route: the batch is merged as it came, PHIP_ROUTE_COMBINE is ignored (the
  * fast path's hot directory does what the combine would) and sent / merged
- * are the batch's raw message count. */
+ * are the batch's raw message count.
+ *
+ * Checked batches (phip_msgs.names_len != 0): every local member's offset
+ * column is checked in full (one pass, the rule of phip_msgs) before any of
+ * its chunks is packed.  If any local batch holds a malformed entry, none of
+ * this process's batches is applied -- in a world of one included, where
+ * phip_receive_soa alone would apply the messages before it -- the call
+ * returns PHIP_ERR_INVALID and phip_group_last_error names the member and the
+ * message.  The process still takes part in the exchange, with empty batches
+ * (sent[i] = 0; merged[i] counts what its peers sent it), so the other ranks
+ * of a multi-process group do not wait for it.  No name of a malformed entry
+ * is hashed or copied.  With names_len == 0 the offsets are trusted. */
 int phip_group_receive(phip_group* g, const phip_msgs* batches, int64_t now, uint64_t* sent,
                        uint64_t* merged, uint32_t flags);
 /* Anti-entropy round over simulated replicas (BASELINE configs[4]):
@@ -607,7 +621,11 @@ void phip_set_timing(phip_handle* h, int on);
  * that missed the table (inserted); out[3] table growths (rehashes) since
  * phip_open; out[4] messages of the batch that went through the ordered path
  * (the dirty buckets' sub-batch, or the suffix from the first dirty
- * message: phip_receive_soa).  Returns the number written (<= 5). */
+ * message: phip_receive_soa).  Returns the number written (<= 5).
+ * Not a plain counter read: a batch queued with PHIP_RECV_ASYNC is finished
+ * first (the call waits for it), so that the counters are that batch's.  The
+ * call has no status to return an error in: if finishing the batch fails, its
+ * error is kept and returned by the handle's next call that returns one. */
 int phip_last_stats(phip_handle* h, uint64_t* out, int max);
 /* Placement quality of the table (one scan of the slots): out[0] buckets,
  * out[1] slots, out[2] the longest probe distance of a bucket from its home

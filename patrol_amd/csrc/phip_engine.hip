@@ -61,7 +61,7 @@ enum BufId {
   B_OPS, B_HOFF, B_HOP, B_HVAL, B_RPOS, B_RST, B_RUNN, B_SEGEX, B_WOFF, B_SUMS, B_WRUN,
   B_WING, B_SEGXF, B_FOLDDBG, B_SMALL, B_HUGE2, B_LONG2,
   B_STATES, B_NAME1, B_HOT, B_ROUTE, B_EXPORT, B_MSHARD, B_MSCNT, B_FSCNT, B_DEDUP, B_DSET, B_TSTATS, B_SEGT, B_RHOT,
-  B_DLIST, B_DTAB, B_DMARK, B_SMAP, B_SOFF, B_SLEN, B_SA, B_ST, B_SE, B_SSTAT, B_SREP,
+  B_DLIST, B_DTAB, B_DMARK, B_SMAP, B_SOFF, B_SLEN, B_SA, B_ST, B_SE, B_SSTAT, B_SREP, B_NCHK,
   B_COUNT_
 };
 
@@ -675,8 +675,8 @@ int dirty_set(phip_handle* h, DirtySet* d, u32** dlist) {
   *d = DirtySet::at(b);
   return PHIP_OK;
 }
-// The ordered sub-batch dirty_finish builds (at most 3 entries per dirty
-// message).
+// The ordered sub-batch dirty_finish builds (kSubBatchCap entries: at most 5
+// per dirty message).
 struct SubBatch {
   uint64_t *off, *a, *t;
   int64_t* e;
@@ -684,7 +684,7 @@ struct SubBatch {
   u32* map;
 };
 int sub_batch(phip_handle* h, SubBatch* b) {
-  constexpr size_t m = 3 * (size_t)kDirtyCap;
+  constexpr size_t m = kSubBatchCap;
   int rc;
   if ((rc = ensure(h, B_SOFF, m, &b->off)) || (rc = ensure(h, B_SLEN, m, &b->len)) ||
       (rc = ensure(h, B_SA, m, &b->a)) || (rc = ensure(h, B_ST, m, &b->t)) ||
@@ -816,9 +816,9 @@ int fast_back(phip_handle* h, In in, u32 n, const FastFront& ff, bool queued) {
       HIPCHK(h, hipGetLastError());
     }
     k_batch_end<In><<<1, kShards, 0, h->stream>>>(
-        in, ff.c, dset.key, table(h), SubOut{sb.off, sb.len, sb.a, sb.t, sb.e, sb.map}, msh.cnt,
-        h->ctr_map, kCtrWords, queued ? fast_counts(h, ff.par ^ 1u) : nullptr,
-        fctr(h, ff.par ^ 1u));
+        in, ff.c, dset.key, table(h),
+        SubOut{sb.off, sb.len, sb.a, sb.t, sb.e, sb.map, kSubBatchCap}, msh.cnt, h->ctr_map,
+        kCtrWords, queued ? fast_counts(h, ff.par ^ 1u) : nullptr, fctr(h, ff.par ^ 1u));
   } else {
     k_shard_scan<<<1, kShards, 0, h->stream>>>(msh.cnt, ff.c, 2, h->ctr_map, kCtrWords,
                                                queued ? fast_counts(h, ff.par ^ 1u) : nullptr,
@@ -1449,9 +1449,14 @@ inline OutView shifted(OutView o, u32 k) {
 template <class Src>
 int run_deferred(phip_handle* h, Src src, i64 now, const OutView& ow) {
   const u32 nd = h->ndef;   // (the last fast pass's: a second pass rebuilt it)
+  // (kSubBatchOver included: dirty_finish counted more entries than the
+  // sub-batch holds and wrote none)
+  if (nd > kSubBatchCap) {
+    h->stats[3] = 0;
+    return set_err(h, PHIP_ERR_HIP, "ordered sub-batch over its %u entries", kSubBatchCap);
+  }
   h->stats[3] = nd;
   if (nd == 0) return PHIP_OK;
-  if (nd > 3 * kDirtyCap) return set_err(h, PHIP_ERR_HIP, "ordered sub-batch of %u entries", nd);
   int rc;
   SubBatch sb;
   u8* st2 = nullptr;
@@ -1892,6 +1897,28 @@ static int route_pack_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32
   k_route_totals<<<1, kRouteMaxWorld, 0, st>>>(cnt, bytes, cbase, bbase, p.ntile, world, counts,
                                                nbytes);
   HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
+}
+
+// A checked batch's offset column (names_len != 0) in one pass on `st`,
+// before anything of the batch is routed: *first_bad is its first malformed
+// entry (NamesOffs::bad), ~0 when there is none or the batch is unchecked.
+// Synchronises `st`.
+static int check_offsets_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32* first_bad) {
+  *first_bad = ~0u;
+  if (m.n == 0 || m.names_len == 0) return PHIP_OK;
+  u32* d;
+  int rc;
+  if ((rc = ensure(h, B_NCHK, 1, &d))) return rc;
+  HIPCHK(h, hipMemsetAsync(d, 0xFF, sizeof(u32), st));
+  {
+    Launch l(h, "k_offs_check", st);
+    k_offs_check<<<grid_for(m.n), kBlock, 0, st>>>(NamesOffs{m.names, m.name_offs, m.names_len},
+                                                   m.n, d);
+  }
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(first_bad, d, sizeof(u32), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
   return PHIP_OK;
 }
 
@@ -2741,6 +2768,14 @@ int phip_route_pack(phip_handle* h, const phip_msgs* m, uint32_t world, uint8_t*
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = begin_call(h)) return rc0;
   int rc;
+  // (the route kernels do not check as they go: a checked batch's offsets
+  // first, so that no malformed entry is ever hashed or copied)
+  u32 first_bad;
+  if ((rc = check_offsets_on(h, h->stream, *m, &first_bad))) return rc;
+  if (first_bad != ~0u)
+    return set_err(h, PHIP_ERR_INVALID,
+                   "malformed name offsets at message %u (names_len check): nothing packed",
+                   first_bad);
   const void* dir = nullptr;
   if ((flags & PHIP_ROUTE_COMBINE) && (rc = route_dir_on(h, h->stream, *m, world, &dir))) return rc;
   if ((rc = route_pack_on(h, h->stream, *m, world, dir, send_names, send_lens, send_added,
@@ -2901,6 +2936,11 @@ int route_pack(phip_handle* h, void* stream, const phip_msgs* m, uint32_t world,
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = finish_queued(h)) return rc0;
   return route_pack_on(h, (hipStream_t)stream, *m, world, dir, names, lens, a, t, e, counts, nbytes);
+}
+int check_offsets(phip_handle* h, void* stream, const phip_msgs* m, uint32_t* first_bad) {
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = finish_queued(h)) return rc0;
+  return check_offsets_on(h, (hipStream_t)stream, *m, first_bad);
 }
 const char* last_error(phip_handle* h) { return h ? h->err.c_str() : ""; }
 int handle_device(const phip_handle* h) { return h ? h->device : -1; }

@@ -799,6 +799,36 @@ phip_handle* phip_group_handle(phip_group* g, uint32_t i) {
 int phip_group_receive(phip_group* g, const phip_msgs* batches, int64_t now, uint64_t* sent,
                        uint64_t* merged, uint32_t flags) {
   if (!g || !batches || !(flags & PHIP_DEVICE_PTRS)) return PHIP_ERR_INVALID;
+  // Checked batches (names_len): every local member's offset column in full
+  // before any chunk is packed (the route kernels do not check as they go).
+  // One malformed entry anywhere and none of this process's batches is
+  // applied; the members still run the exchange, with empty batches, so that
+  // the peers of a multi-rank group never wait for a rank that left early.
+  const size_t nl = g->m.size();
+  std::vector<uint32_t> bad(nl, ~0u);
+  if (int rc = for_members(g, [&](size_t i) {
+        Member& mb = g->m[i];
+        GHIP(mb, hipSetDevice(mb.device));
+        if (phip_host::check_offsets(mb.h, phip_host::handle_stream(mb.h), &batches[i], &bad[i]) !=
+            PHIP_OK)
+          return fail(mb, PHIP_ERR_HIP, "name offsets check: %s", phip_host::last_error(mb.h));
+        return (int)PHIP_OK;
+      }))
+    return rc;
+  size_t ib = 0;
+  while (ib < nl && bad[ib] == ~0u) ++ib;
+  if (ib < nl) {
+    std::vector<phip_msgs> none(batches, batches + nl);
+    for (phip_msgs& m : none) m.n = 0;
+    const int rc = for_members(g, [&](size_t i) {
+      return member_receive(g, g->m[i], none[i], now, sent ? sent + i : nullptr,
+                            merged ? merged + i : nullptr, flags);
+    });
+    const std::string xerr = rc != PHIP_OK ? "; and the empty exchange failed: " + g->err : "";
+    g->err = "member " + std::to_string(ib) + ": malformed name offsets at message " +
+             std::to_string(bad[ib]) + " (names_len check): no local batch applied" + xerr;
+    return PHIP_ERR_INVALID;
+  }
   return for_members(g, [&](size_t i) {
     return member_receive(g, g->m[i], batches[i], now, sent ? sent + i : nullptr,
                           merged ? merged + i : nullptr, flags);

@@ -25,6 +25,12 @@ int route_dir(phip_handle* h, void* stream, const phip_msgs* m, uint32_t world, 
 int route_pack(phip_handle* h, void* stream, const phip_msgs* m, uint32_t world, const void* dir,
                uint8_t* names, uint32_t* lens, uint64_t* a, uint64_t* t, int64_t* e,
                uint64_t* counts, uint64_t* nbytes);
+// The route kernels do not check a batch's name offsets as they go.
+// check_offsets: one pass over a checked batch's offset column (names_len !=
+// 0; NamesOffs::bad's rule) on `stream`, which it synchronises: *first_bad is
+// the first malformed message, ~0 when there is none (or names_len == 0).
+// phip_group_receive runs it over every local batch before any pack.
+int check_offsets(phip_handle* h, void* stream, const phip_msgs* m, uint32_t* first_bad);
 const char* last_error(phip_handle* h);
 
 // The request parsing of API.takeBucket (api.go:55-65): the name-length check

@@ -428,9 +428,9 @@ __device__ inline void note_dirty(bool d, u32 i, u32* ctr) { note_min(d, i, &ctr
 //     maximum of the clean messages between one of its dirty messages and
 //     the next (E-encoded, as the table's fields);
 // and dirty_finish turns the dirty messages and the non-empty cells into an
-// ordered sub-batch of at most 3 * kDirtyCap entries (a dirty message, then
-// the merge of its cell), which the ordered path applies after the rest of
-// the batch.  Exact: every bucket sees the Go loop's sequence of states at
+// ordered sub-batch of at most kSubBatchCap entries (a bucket's pre cell,
+// then each dirty message followed by the merge of its cell), which the
+// ordered path applies after the rest of the batch.  Exact: every bucket sees the Go loop's sequence of states at
 // its dirty messages.  Up to kDirtyCap dirty messages with names of at most
 // kShortName bytes (the names the set compares exactly); otherwise the batch
 // keeps the prefix rule.
@@ -439,6 +439,14 @@ constexpr u32 kCtrNDefer = 18;       // entries of the ordered sub-batch (dirty_
 constexpr u32 kCtrNSorted = 19;      // dirty messages in the set (before the batch's stop)
 constexpr u32 kDirtyCap = 4096;
 constexpr u32 kDirtySlots = 2 * kDirtyCap;
+// Capacity of the ordered sub-batch.  dirty_finish emits, per dirty message,
+// the message and its post cell, and per dirty bucket its pre cell; a cell is
+// 0 entries (empty), 1, or 2 (maxima that read (+0, +0, 0) are split in two
+// merges).  With nd dirty messages in B buckets that is at most
+// nd * (1 + 2) + 2 * B <= 5 * nd entries (B <= nd; reached by one dirty
+// message per bucket with both cells split).
+constexpr u32 kSubBatchCap = 5 * kDirtyCap;
+constexpr u32 kSubBatchOver = ~0u;   // ctr[kCtrNDefer]: more entries than SubOut::cap, none written
 constexpr u64 kRecDirty = 4u;        // record flag: its bucket is in the batch's dirty set
 __device__ inline void note_dirty_list(bool d, u32 i, u32* ctr, u32* dlist) {
   const u32 pos = wave_append(&ctr[kCtrNDirty], d);
@@ -1894,7 +1902,8 @@ __global__ void k_decode(const u8* __restrict__ bytes, const uint64_t* __restric
 // reply go back to: the message itself, a pre cell's first message (its
 // merge may create the bucket: PHIP_ST_CREATED), ~0 for a later cell's merge
 // (its messages keep PHIP_ST_MERGED: the bucket exists by then).
-// The entry count lands in ctr[kCtrNDefer].
+// The entry count lands in ctr[kCtrNDefer]; a count above so.cap (never,
+// by kSubBatchCap's bound) writes no entry and leaves kSubBatchOver there.
 // (one workgroup of kShards lanes; k_batch_end runs it before the batch's
 // shard scan, in one launch)
 struct SubOut {
@@ -1904,6 +1913,7 @@ struct SubOut {
   uint64_t* t;
   int64_t* e;
   u32* map;
+  u32 cap;   // entries each array holds (kSubBatchCap)
 };
 template <class In>
 __device__ inline void dirty_finish(const In& in, u32* ctr, const DirtySet& D, const Table& T,
@@ -1922,7 +1932,8 @@ __device__ inline void dirty_finish(const In& in, u32* ctr, const DirtySet& D, c
     return;
   }
   const u32 nv = ctr[kCtrNSorted];
-  // thread tid: set entries [j0, j1), up to three sub-batch entries each
+  // thread tid: set entries [j0, j1), up to five sub-batch entries each
+  // (kSubBatchCap)
   const u32 per = (nv + kShards - 1) / kShards;
   const u32 j0 = min(nv, tid * per), j1 = min(nv, j0 + per);
   // entries of a cell's merge: 0 (empty), 1, or 2 (maxima +0, +0, 0 read
@@ -1950,6 +1961,10 @@ __device__ inline void dirty_finish(const In& in, u32* ctr, const DirtySet& D, c
     __syncthreads();
     part[tid] += v;
     __syncthreads();
+  }
+  if (part[kShards - 1] > so.cap) {   // (uniform: every lane reads the total)
+    if (tid == kShards - 1) ctr[kCtrNDefer] = kSubBatchOver;
+    return;
   }
   u32 o = part[tid] - c;
   auto emit_cell = [&](const u64* cl, u64 off, u32 len, u32 to) {
@@ -4516,6 +4531,17 @@ __global__ void k_hash_names(NamesOffs src, u32 n, uint64_t* out) {
   Name nm;
   load_name_wide<false>(src.blob, off, len, nm);
   out[i] = nm.h;
+}
+
+// A checked batch's offset column alone (names_len != 0), before a pass that
+// does not check as it goes (the owner routing: k_route_sample / _count /
+// _scatter): the first entry NamesOffs::bad rejects, min-reduced into *first
+// (the caller sets it to ~0).  4 bytes per message; reads no name.
+__global__ __launch_bounds__(kBlock) void k_offs_check(NamesOffs src, u32 n, u32* first) {
+  const u64 i = (u64)blockIdx.x * kBlock + threadIdx.x;
+  bool b = false;
+  if (i < n) b = src.bad(src.offs[i], src.offs[i + 1]);
+  note_min(b, (u32)i, first);
 }
 
 // Egress batching (phip_export_datagrams; SURVEY §8f, repo.go:129-169): the

@@ -504,7 +504,15 @@ class GPUGroup:
         rccl_self (PHIP_GROUP_RCCL_SELF, testing): every segment, the
         member's own included, travels through ncclSend/ncclRecv.
         small_chunks (PHIP_GROUP_SMALL_CHUNKS, testing): the pipelined
-        exchange runs in chunks of 4096 messages."""
+        exchange runs in chunks of 4096 messages.
+
+        The batches are checked (names_len = the names tensor's length):
+        every local batch's name_offs column is verified in full before
+        anything is packed.  A malformed entry in any of them raises
+        PatrolHipError (code -1, PHIP_ERR_INVALID; the message names the
+        member and the message index) and none of the batches is applied;
+        the members still run the exchange with empty batches, so peer
+        ranks are not left waiting."""
         k = len(batches)
         msgs = (phip_msgs * k)()
         for i, (names, offs, a, t, e) in enumerate(batches):

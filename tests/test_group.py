@@ -183,6 +183,102 @@ def test_shared_device_group_receive_pipelined_vs_oracle(pa, dirty):
     g.close()
 
 
+def _union(repos):
+    got = {}
+    for repo in repos:
+        got.update(_dump(repo))
+    return got
+
+
+@pytest.mark.parametrize("case", ["plain", "rccl_self_combine", "shared_world2"])
+def test_group_receive_rejects_corrupted_offsets(pa, case):
+    """A device batch whose offset column holds one corrupted entry
+    (offs[k] = 0x7FFF0000, past names_len: entries k-1 and k are malformed)
+    through phip_group_receive: PHIP_ERR_INVALID naming the member and the
+    first malformed message, every member's table as it was (no bucket ""
+    from an entry read as the empty name, nothing of the clean member's
+    batch either), and the same batches with the column repaired then merge
+    and equal the oracle.
+      plain: world 1, the batch merged as it came (2^16 messages);
+      rccl_self_combine: world 1 through the pack and RCCL, 2^20 messages
+        (the combine's sampled directory; entry k is a sampled one);
+      shared_world2: two shards on one GPU, member 0's batch corrupted,
+        member 1's clean."""
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(1200)
+    world = 2 if case == "shared_world2" else 1
+    n = 1 << 20 if case == "rccl_self_combine" else 1 << 16
+    k = 64 * 5000 if case == "rccl_self_combine" else 40001   # (the sample's stride is 64)
+    kw = dict(combine=True, rccl_self=case == "rccl_self_combine")
+    g = pa.GPUGroup.open_all([0] * world, log2_slots=14)
+    o = O.Repo()
+    # tables with something in them first
+    per = [_batch(rng, 3000, 20000, dev) for _ in range(world)]
+    torch.cuda.synchronize()
+    g.receive([b[4] for b in per], _gen.T0, **kw)
+    for names, a, t, e, _ in per:
+        o.receive_soa(names, a, t, e, _gen.T0)
+    before = [_dump(r) for r in g.repos]
+    assert _union(g.repos) == o.dump()
+    per = [_batch(rng, n, 20000, dev) for _ in range(world)]
+    offs = per[0][4][1]
+    good = int(offs[k])
+    offs[k] = 0x7FFF0000
+    torch.cuda.synchronize()
+    with pytest.raises(pa.PatrolHipError) as ei:
+        g.receive([b[4] for b in per], _gen.T0 + 1, **kw)
+    assert ei.value.code == -1
+    assert "member 0" in str(ei.value) and "message %d " % (k - 1) in str(ei.value)
+    after = [_dump(r) for r in g.repos]
+    assert after == before and all(b"" not in d for d in after)
+    # repaired: the group still works, and nothing of the failed call stuck
+    offs[k] = good
+    torch.cuda.synchronize()
+    sent, merged = g.receive([b[4] for b in per], _gen.T0 + 1, **kw)
+    assert sum(sent) == sum(merged) and 0 < sum(merged) <= world * n
+    for names, a, t, e, _ in per:
+        o.receive_soa(names, a, t, e, _gen.T0 + 1)
+    assert _union(g.repos) == o.dump()
+    g.close()
+
+
+def test_route_pack_rejects_corrupted_offsets(pa):
+    """phip_route_pack itself on a checked batch (names_len) with one
+    corrupted offset: PHIP_ERR_INVALID and nothing packed (the send buffers
+    and split counts stay as they were); repaired, it packs every message."""
+    import ctypes as C
+    from patrol_amd import _lib
+    from patrol_amd.engine import phip_msgs
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(1300)
+    n, world, k = 1 << 16, 3, 12345
+    _, _, _, _, (blob, offs, da, dt, de) = _batch(rng, n, 20000, dev)
+    repo = pa.GPURepo(log2_slots=10)
+    s_names = torch.zeros(blob.numel() + 64, dtype=torch.uint8, device=dev)
+    s_lens = torch.zeros(n, dtype=torch.int32, device=dev)
+    s_a, s_t, s_e = (torch.zeros(n, dtype=torch.int64, device=dev) for _ in range(3))
+    cnt = torch.zeros(world, dtype=torch.int64, device=dev)
+    nb = torch.zeros(world, dtype=torch.int64, device=dev)
+    m = phip_msgs(n, blob.numel(), blob.data_ptr(), offs.data_ptr(), da.data_ptr(), dt.data_ptr(),
+                  de.data_ptr())
+
+    def pack():
+        torch.cuda.synchronize()
+        return _lib.load().phip_route_pack(repo.h, C.byref(m), world, s_names.data_ptr(),
+                                           s_lens.data_ptr(), s_a.data_ptr(), s_t.data_ptr(),
+                                           s_e.data_ptr(), cnt.data_ptr(), nb.data_ptr(),
+                                           _lib.DEVICE_PTRS)
+    good = int(offs[k])
+    offs[k] = 0x7FFF0000
+    assert pack() == -1
+    for x in (s_names, s_lens, s_a, s_t, s_e, cnt, nb):
+        assert not bool(x.any())
+    offs[k] = good
+    assert pack() == 0
+    assert sum(cnt.cpu().tolist()) == n and sum(nb.cpu().tolist()) == int(offs[n])
+    repo.close()
+
+
 def test_shared_device_group_anti_entropy(pa):
     from patrol_amd import shard
     R, B, world = 3, 5000, 3

@@ -501,27 +501,44 @@ def dirty_mask(a, t, e):
     return ((a == 0) & (t == 0) & (e == 0)) | (a == NEG0) | (t == NEG0)
 
 
-def deferred_count(names, dirty):
+def deferred_count(names, dirty, a=None, t=None, e=None):
     """Entries of the ordered sub-batch (dirty_finish): per dirty bucket,
     one merge of its clean messages before its first dirty message (if any),
     then every dirty message, each followed by one merge of the clean
-    messages after it and before the bucket's next dirty message (if any)."""
+    messages after it and before the bucket's next dirty message (if any).
+    With the replica fields (a, t: float64 bits; e), a run of clean messages
+    whose field-wise maxima are (+0.0, +0.0, 0) counts 2: its merge would
+    read as an incast and is split in two.  The runs it models must hold
+    finite values only (no NaN; a -0.0 field is dirty, so never in a run):
+    the plain float maximum is then the E-order maximum."""
     pos = {}
     for i, x in enumerate(names):
         pos.setdefault(x, []).append(i)
+    split = a is not None
+    if split:
+        af, tf = a.view(np.float64), t.view(np.float64)
     total = 0
     for x, ps in pos.items():
+        ps = np.asarray(ps)
         d = dirty[ps]
         if not d.any():
             continue
         total += int(d.sum())
-        run = False
-        for k in range(len(ps)):
+        k = 0
+        while k < len(ps):
             if d[k]:
-                run = False
-            elif not run:
-                run = True
-                total += 1
+                k += 1
+                continue
+            j = k
+            while j < len(ps) and not d[j]:
+                j += 1
+            total += 1
+            if split:
+                run = ps[k:j]
+                assert np.isfinite(af[run]).all() and np.isfinite(tf[run]).all()
+                if af[run].max() == 0.0 and tf[run].max() == 0.0 and e[run].max() == 0:
+                    total += 1
+            k = j
     return total
 
 
@@ -747,3 +764,249 @@ def test_dirty_isolation_policy(pa):
     g2.receive_soa(_gen.key_names(ids), a, t, e, now)
     names_run = [nm for nm, _ in g2.timings()]
     assert "k_receive_fast" in names_run and "k_dirty_build" not in names_run, names_run
+
+
+# ---- the ordered sub-batch at its edges: 5 entries per dirty message, the
+# dirty cap (4096), one past it ----
+DIRTY_CAP = 4096
+M5, M3 = np.float64(-5.0).view(np.uint64), np.float64(-3.0).view(np.uint64)
+# A bucket's five messages: two clean ones whose maxima read (+0, +0, 0), an
+# incast, the two clean ones again.  Both cells (before and after the incast)
+# are split in two merges: 2 + 1 + 2 entries.
+FIVE = ((M5, 0, 0), (0, M3, 0), (0, 0, 0), (M5, 0, 0), (0, M3, 0))
+
+
+def seeded_negative(pa, rng, K, nneg, log2_slots=15):
+    """K buckets b0..b{K-1}, the first nneg of them with a negative state
+    (added = taken = -10, elapsed = -5: a merge of (+0, +0, 0) raises all three
+    fields), on two isolating handles and in the oracle."""
+    names = _gen.key_names(np.arange(K))
+    a, t, e = _gen.clean_states(rng, K)
+    a[:nneg] = t[:nneg] = np.float64(-10.0).view(np.uint64)
+    e[:nneg] = -5
+    created = np.full(K, _gen.T0 - SEC, np.int64)
+    gs = pa.GPURepo(log2_slots=log2_slots, isolate=True)
+    gc = pa.GPURepo(log2_slots=log2_slots, isolate=True)
+    o = O.Repo()
+    for r in (gs, gc, o):
+        r.seed(names, a, t, e, created)
+    return gs, gc, o
+
+
+def five_per_bucket(rng, n, buckets, lo, hi):
+    """A batch of n messages: FIVE, in that order, at scattered positions for
+    every id of `buckets`; clean traffic on ids [lo, hi) everywhere else."""
+    B = len(buckets)
+    ids = rng.integers(lo, hi, n)
+    a, t, e = _gen.clean_states(rng, n)
+    pos = rng.choice(n, 5 * B, replace=False).reshape(B, 5)
+    pos.sort(axis=1)
+    for r, (x, y, z) in enumerate(FIVE):
+        p = pos[:, r]
+        ids[p], a[p], t[p], e[p] = buckets, x, y, z
+    return ids, a, t, e
+
+
+def wire(names, a, t, e):
+    import struct
+    return [struct.pack(">QQQ", int(a[i]), int(t[i]), int(e[i]) & (2**64 - 1)) +
+            bytes([len(names[i])]) + names[i] for i in range(len(names))]
+
+
+def run_form(form, gs, gc, o, names, a, t, e, now):
+    """form "soa": run_all (the host-pointer call on gs, the queued device
+    batch on gc); "datagrams": phip_receive_datagrams on gs (the sub-batch
+    read from the wire).  Statuses and incast replies against the oracle;
+    returns the oracle's statuses and the handles that ran."""
+    if form == "soa":
+        return run_all(gs, gc, o, names, a, t, e, now), (gs, gc)
+    dgs = wire(names, a, t, e)
+    out = gs.receive_datagrams(dgs, now)
+    st, ra, rt, re, stop = o.receive(dgs, now)
+    assert out["stop"] == stop == len(names)
+    check(out["status"], (out["reply"]["a"], out["reply"]["t"], out["reply"]["e"]), st, ra, rt, re)
+    return st, (gs,)
+
+
+@pytest.mark.parametrize("form", ["soa", "datagrams"])
+def test_sub_batch_worst_case_five_entries_per_dirty_message(pa, form):
+    """The sub-batch at its proven bound (kSubBatchCap = 5 * kDirtyCap): 4096
+    negative-state buckets with one incast each, the clean messages before
+    and after it both reading (+0, +0, 0) as a cell: split pre cell, incast,
+    split cell = 5 entries per dirty message, 20,480 in all (the arrays held
+    12,288 before).  Exactly that many ordered entries, and statuses, incast
+    replies and tables bit-exact against the oracle."""
+    rng = np.random.default_rng(101)
+    K, B, n = 8192, DIRTY_CAP, 1 << 16
+    gs, gc, o = seeded_negative(pa, rng, K, B)
+    ids, a, t, e = five_per_bucket(rng, n, np.arange(B), B, K)
+    names = _gen.key_names(ids)
+    dirty = dirty_mask(a, t, e)
+    assert dirty.sum() == B
+    want = deferred_count(names, dirty, a, t, e)
+    assert want == 5 * B == 20480
+    _, ran = run_form(form, gs, gc, o, names, a, t, e, _gen.T0)
+    for g in ran:
+        assert g.last_stats()[4] == 5 * B
+        same(dump(g), o.dump())
+
+
+@pytest.mark.parametrize("B,absent", [(DIRTY_CAP, 1.0), (600, 0.5)])
+def test_sub_batch_split_cells_on_new_buckets(pa, B, absent):
+    """The same five messages for buckets the table does not hold (their
+    dirty-set entry has no record: the pre cell's merge creates the bucket, so
+    its first message reads PHIP_ST_CREATED, a later cell's messages
+    PHIP_ST_MERGED); all 4096 absent, and 600 of which half are seeded with a
+    negative state.  The oracle decides every status."""
+    rng = np.random.default_rng(102)
+    K, n = 8192, 1 << 16
+    gs, gc, o = seeded_negative(pa, rng, K, B)
+    buckets = np.arange(B)
+    new = rng.random(B) < absent
+    buckets[new] += K + 10**6
+    ids, a, t, e = five_per_bucket(rng, n, buckets, B, K)
+    names = _gen.key_names(ids)
+    dirty = dirty_mask(a, t, e)
+    want = deferred_count(names, dirty, a, t, e)
+    assert dirty.sum() == B and want == 5 * B
+    st, _ = run_form("soa", gs, gc, o, names, a, t, e, _gen.T0)
+    first = np.array([names.index(x) for x in _gen.key_names(buckets[new][:50])])
+    assert (st[first] == 0x81).all()    # PHIP_ST_CREATED | MERGED at the pre cell's first message
+    for g in (gs, gc):
+        assert g.last_stats()[4] == want
+        same(dump(g), o.dump())
+
+
+def cap_batch(rng, n, K):
+    """DIRTY_CAP dirty messages (incasts and -0.0 fields) naming DIRTY_CAP
+    distinct buckets b0..b4095, among clean traffic over all K buckets (so
+    the dirty buckets have pre and post cells)."""
+    ids = rng.integers(0, K, n)
+    a, t, e = _gen.clean_states(rng, n)
+    pos = rng.choice(n, DIRTY_CAP, replace=False)
+    ids[pos] = rng.permutation(DIRTY_CAP)
+    kind = rng.integers(0, 3, pos.size)
+    for p, k in zip(pos, kind):
+        if k == 0:
+            a[p], t[p], e[p] = 0, 0, 0
+        else:
+            (a if k == 1 else t)[p] = NEG0
+    return ids, a, t, e
+
+
+def test_dirty_cap_distinct_buckets_isolated(pa):
+    """Exactly kDirtyCap dirty messages in as many buckets (the dirty set at
+    load 0.5, the sort at P == nd == 4096): still isolated."""
+    rng = np.random.default_rng(103)
+    K, n = 8192, 1 << 16
+    gs, gc, o = seeded_negative(pa, rng, K, 2048)
+    ids, a, t, e = cap_batch(rng, n, K)
+    names = _gen.key_names(ids)
+    dirty = dirty_mask(a, t, e)
+    assert dirty.sum() == DIRTY_CAP and len({names[i] for i in np.nonzero(dirty)[0]}) == DIRTY_CAP
+    want = deferred_count(names, dirty, a, t, e)
+    assert want < n - int(np.argmax(dirty))
+    run_all(gs, gc, o, names, a, t, e, _gen.T0)
+    for g in (gs, gc):
+        assert g.last_stats()[4] == want
+        same(dump(g), o.dump())
+
+
+def test_dirty_cap_plus_one_keeps_prefix_rule(pa):
+    """The same batch with one more dirty message (4097): the prefix rule."""
+    rng = np.random.default_rng(103)
+    K, n = 8192, 1 << 16
+    gs, gc, o = seeded_negative(pa, rng, K, 2048)
+    ids, a, t, e = cap_batch(rng, n, K)
+    p = int(np.nonzero(~dirty_mask(a, t, e))[0][n // 2])   # a clean message becomes an incast
+    ids[p], a[p], t[p], e[p] = DIRTY_CAP + 7, 0, 0, 0
+    names = _gen.key_names(ids)
+    dirty = dirty_mask(a, t, e)
+    assert dirty.sum() == DIRTY_CAP + 1
+    run_all(gs, gc, o, names, a, t, e, _gen.T0)
+    for g in (gs, gc):
+        assert g.last_stats()[4] == n - int(np.argmax(dirty))
+        same(dump(g), o.dump())
+
+
+def test_dirty_cap_one_bucket_isolated(pa):
+    """kDirtyCap dirty messages that all name one (hot, negative-state)
+    bucket: incasts and -0.0 fields mixed, clean messages of the bucket (the
+    two zero-reading ones and ordinary states) between some of them.  One
+    bucket start in dirty_finish, its run spanning every thread's share."""
+    rng = np.random.default_rng(104)
+    K, n = 8192, 1 << 16
+    gs, gc, o = seeded_negative(pa, rng, K, 16)
+    ids = rng.integers(1, K, n)
+    a, t, e = _gen.clean_states(rng, n)
+    pos = rng.choice(n, DIRTY_CAP + 3000, replace=False)
+    ids[pos] = 0
+    for p in pos[:DIRTY_CAP]:
+        k = rng.integers(0, 3)
+        if k == 0:
+            a[p], t[p], e[p] = 0, 0, 0
+        else:
+            (a if k == 1 else t)[p] = NEG0
+    for p in pos[DIRTY_CAP:]:
+        k = rng.integers(0, 3)
+        if k < 2:
+            a[p], t[p], e[p] = FIVE[k]
+    names = _gen.key_names(ids)
+    dirty = dirty_mask(a, t, e)
+    assert dirty.sum() == DIRTY_CAP and {names[i] for i in np.nonzero(dirty)[0]} == {b"b0"}
+    want = deferred_count(names, dirty, a, t, e)
+    assert DIRTY_CAP < want < n - int(np.argmax(dirty))
+    run_all(gs, gc, o, names, a, t, e, _gen.T0)
+    for g in (gs, gc):
+        assert g.last_stats()[4] == want
+        same(dump(g), o.dump())
+
+
+@pytest.mark.parametrize("seed,nd", [(111, 1237), (112, 2911)])
+def test_sub_batch_random_split_and_plain_cells(pa, seed, nd):
+    """nd dirty messages (not a power of two) over 300 buckets, 120 of them
+    negative-state, with clean messages of those buckets drawn from
+    (-5, +0, 0), (+0, -3, 0) and ordinary positive states: split and plain
+    cells, before and after dirty messages, interleaved.  The count against
+    the model and the oracle's results; then the batch twice more, queued
+    back to back (both parity counter sets build the same sub-batch)."""
+    rng = np.random.default_rng(seed)
+    K, n, D = 8192, 1 << 16, 300
+    gs, gc, o = seeded_negative(pa, rng, K, 120)
+    ids = rng.integers(D, K, n)
+    a, t, e = _gen.clean_states(rng, n)
+    pos = rng.choice(n, nd + 6000, replace=False)
+    ids[pos] = rng.integers(0, D, pos.size)
+    for p in pos[:nd]:
+        k = rng.integers(0, 3)
+        if k == 0:
+            a[p], t[p], e[p] = 0, 0, 0
+        else:
+            (a if k == 1 else t)[p] = NEG0
+    for p in pos[nd:]:
+        k = rng.integers(0, 5)
+        if k < 4:
+            a[p], t[p], e[p] = FIVE[k & 1]
+    names = _gen.key_names(ids)
+    dirty = dirty_mask(a, t, e)
+    assert dirty.sum() == nd
+    want = deferred_count(names, dirty, a, t, e)
+    assert want > deferred_count(names, dirty)      # some cells are split
+    now = _gen.T0
+    run_all(gs, gc, o, names, a, t, e, now)
+    for g in (gs, gc):
+        assert g.last_stats()[4] == want
+        same(dump(g), o.dump())
+    bs = []
+    for _ in range(2):
+        b = device_batch(names, a, t, e)
+        queue_batch(gc, b, now + SEC)
+        bs.append(b)
+    gc.flush()
+    assert gc.last_stats()[4] == want
+    o.receive_soa(names, a, t, e, now + SEC)
+    st, ra, rt, re = o.receive_soa(names, a, t, e, now + SEC)
+    r = bs[1]["reply"].cpu().numpy()
+    check(bs[1]["status"].cpu().numpy(), (r[:, 0].view(np.uint64), r[:, 1].view(np.uint64), r[:, 2]),
+          st, ra, rt, re)
+    same(dump(gc), o.dump())
