@@ -294,6 +294,58 @@ int phip_restore(phip_handle* h, const uint8_t* in, uint64_t len);
  * pointers (PHIP_DEVICE_PTRS). */
 int phip_export_datagrams(phip_handle* h, const uint8_t* names, const uint32_t* name_offs,
                           uint32_t n, uint8_t* out, uint8_t* found, uint32_t flags);
+
+/* Evict idle buckets (the reference has no counterpart: repo.go:175 is a map
+ * that only grows, and a restarted Go process starts with an empty one).
+ *
+ * Rule.  last = created + elapsed, exact in 128 bits as Take computes it
+ * (bucket.go:198); idle = now - last, 0 when now < last (a replica's merged
+ * elapsed can run ahead of the local clock) and saturating at INT64_MAX.  A
+ * bucket is idle iff idle >= idle_ns.  idle_ns <= 0 is PHIP_ERR_INVALID.
+ *
+ * Semantics.  Evicting a bucket is, for that bucket, what a node restart is
+ * in the reference: the next GetBucket creates it afresh with created = now
+ * and reports PHIP_ST_CREATED / phip_take_reply.created, so the caller sends
+ * the zero-state incast request (repo.go:96-106) and the peers' states merge
+ * back in as they arrive.
+ *
+ * Choosing idle_ns.  Keep idle_ns >= per for every rate served.  Then the
+ * first Take on a recreated bucket returns the same (ok, remaining) as it
+ * would have on the evicted one: dt >= per makes Tokens(dt) >= Freq, so the
+ * refill clamps to capacity - tokens (bucket.go:210-213) and have == capacity
+ * either way.
+ *
+ * Two passes.  k_evict_count reads every slot once and counts the idle
+ * buckets, the survivors and the survivors' long-name bytes.  On a dry run
+ * (PHIP_EVICT_DRY_RUN), or with fewer than min_evict idle buckets (the
+ * caller's hysteresis; 0 is treated as 1), the call returns there: *out is
+ * filled, nothing is rebuilt.  Otherwise k_evict_move moves the survivors into
+ * a fresh table and their long names into a fresh, byte-packed arena (of at
+ * least the handle's opening arena_bytes), and the old ones are freed: no
+ * tombstones, no lookup kernel changes.  With PHIP_EVICT_SHRINK the new table
+ * has 2^L' slots, L' the smallest with L_open <= L' <= L_now and survivors <=
+ * load_limit(2^L', max_load_pct) / 2 (L_open: the log2_slots the handle was
+ * opened with; growth doubles at the limit, so the population must double
+ * before the table grows again); without it the slot count is unchanged.
+ * On any failure (PHIP_ERR_FULL when device memory runs out, HIP errors) the
+ * old table and arena stay live and unchanged.  Unknown flag bits are
+ * PHIP_ERR_INVALID.  The call is serialised with every other call of the
+ * handle (the Take batcher's dispatcher included); a batch queued with
+ * PHIP_RECV_ASYNC is finished first, and its error is this call's.
+ * phip_snapshot / phip_restore keep working: the image has the new
+ * log2_slots and arena bytes. */
+#define PHIP_EVICT_SHRINK  0x40u  /* also pick a smaller table (rule above) */
+#define PHIP_EVICT_DRY_RUN 0x80u  /* count only; the table is not touched   */
+typedef struct phip_evict_stats {
+  uint64_t idle;        /* buckets that met the rule                          */
+  uint64_t evicted;     /* buckets removed (0 on a dry run or under min_evict)*/
+  uint64_t buckets;     /* phip_len afterwards                                */
+  uint64_t slots;       /* phip_capacity afterwards                           */
+  uint64_t arena_used;  /* long-name arena bytes in use afterwards            */
+  uint64_t arena_freed; /* bytes the compaction gave back                     */
+} phip_evict_stats;
+int phip_evict_idle(phip_handle* h, int64_t now, int64_t idle_ns, uint64_t min_evict,
+                    phip_evict_stats* out /* may be NULL */, uint32_t flags);
 int phip_dump(phip_handle* h, uint8_t* names, uint64_t names_cap, uint64_t* name_offs,
               phip_state* states, uint64_t max_n, uint64_t* n_out, uint64_t* names_bytes_out);
 
@@ -587,6 +639,13 @@ int phip_group_receive(phip_group* g, const phip_msgs* batches, int64_t now, uin
  * replica of every member is the CvRDT join of all of them. */
 int phip_group_anti_entropy(phip_group* g, int64_t* const* replicas, uint32_t nrep,
                             uint64_t nbuckets, uint32_t flags);
+/* phip_evict_idle on every local member, concurrently (one host thread
+ * each).  Eviction is local per shard, so there is no exchange: each member
+ * sweeps its own table by the same rule.  out (optional) receives one record
+ * per local member. */
+int phip_group_evict_idle(phip_group* g, int64_t now, int64_t idle_ns, uint64_t min_evict,
+                          phip_evict_stats* out /* one per local member, may be NULL */,
+                          uint32_t flags);
 /* Stage timing of the group's calls (off by default): with it on, every
  * later phip_group_receive / phip_group_anti_entropy records HIP events
  * around each chunk's work on the stream it runs on, and

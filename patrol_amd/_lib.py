@@ -29,6 +29,7 @@ EXPORTS = [
     "phip_group_close", "phip_group_last_error", "phip_group_world", "phip_group_local",
     "phip_group_handle", "phip_group_receive", "phip_group_anti_entropy",
     "phip_group_set_timing", "phip_group_stage_ms", "phip_group_rccl_info",
+    "phip_evict_idle", "phip_group_evict_idle",
 ]
 
 PHIP_OK = 0
@@ -48,6 +49,8 @@ ROUTE_COMBINE = 0x2
 GROUP_RCCL_SELF = 0x4
 GROUP_SMALL_CHUNKS = 0x8
 RECV_ASYNC = 0x20
+EVICT_SHRINK = 0x40
+EVICT_DRY_RUN = 0x80
 PACKET_SIZE = 256
 BUCKET_FIXED_SIZE = 25   # PHIP_BUCKET_FIXED_SIZE: added, taken, elapsed, name length
 
@@ -85,6 +88,11 @@ class phip_take_reply(C.Structure):
     _fields_ = [("remaining", C.c_uint64), ("ok", C.c_uint8), ("created", C.c_uint8),
                 ("datagram_len", C.c_uint16), ("reserved", C.c_uint32), ("seq", C.c_uint64),
                 ("state", phip_state), ("datagram", C.c_uint8 * 256)]
+
+
+class phip_evict_stats(C.Structure):
+    _fields_ = [("idle", C.c_uint64), ("evicted", C.c_uint64), ("buckets", C.c_uint64),
+                ("slots", C.c_uint64), ("arena_used", C.c_uint64), ("arena_freed", C.c_uint64)]
 
 
 class phip_results(C.Structure):
@@ -206,5 +214,9 @@ def load(path: str = LIB_PATH):
         L.phip_group_stage_ms.argtypes = [vp, u32, C.POINTER(C.c_float)]
         L.phip_group_rccl_info.argtypes = [vp, u32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                            C.c_char_p, u32]
+    # (a variant library built from older sources, PATROLHIP_LIB, lacks them)
+    if hasattr(L, "phip_evict_idle"):
+        L.phip_evict_idle.argtypes = [vp, i64, i64, u64, C.POINTER(phip_evict_stats), u32]
+        L.phip_group_evict_idle.argtypes = [vp, i64, i64, u64, C.POINTER(phip_evict_stats), u32]
     _lib = L
     return L

@@ -122,6 +122,14 @@ __device__ inline i64 take_dt(i64 created, i64 elapsed, i64 now) {
   return dd > (__int128)0x7FFFFFFFFFFFFFFFll ? 0x7FFFFFFFFFFFFFFFll : (i64)dd;
 }
 
+// The eviction sweep's rule (phip_evict_idle): idle = now - (created +
+// elapsed) is exactly Take's dt -- the exact 128-bit `last`, 0 when now <
+// last (a merged elapsed ahead of the local clock), saturating at INT64_MAX
+// -- and a bucket is idle iff idle >= idle_ns (idle_ns > 0).
+__device__ inline bool bucket_idle(i64 created, i64 elapsed, i64 now, i64 idle_ns) {
+  return take_dt(created, elapsed, now) >= idle_ns;
+}
+
 struct TakeResult {
   u64 remaining;
   u64 have_bits;

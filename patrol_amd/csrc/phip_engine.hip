@@ -62,6 +62,7 @@ enum BufId {
   B_WING, B_SEGXF, B_FOLDDBG, B_SMALL, B_HUGE2, B_LONG2,
   B_STATES, B_NAME1, B_HOT, B_ROUTE, B_EXPORT, B_MSHARD, B_MSCNT, B_FSCNT, B_DEDUP, B_DSET, B_TSTATS, B_SEGT, B_RHOT,
   B_DLIST, B_DTAB, B_DMARK, B_SMAP, B_SOFF, B_SLEN, B_SA, B_ST, B_SE, B_SSTAT, B_SREP, B_NCHK,
+  B_EVICT,
   B_COUNT_
 };
 
@@ -107,6 +108,7 @@ struct phip_handle {
   std::mutex mu;
   std::string err;
   u32 L = 0;
+  u32 L_open = 0;            // log2_slots at phip_open: phip_evict_idle shrinks no further
   u64 cap = 0;
   u64 max_load = 0;
   u32 load_pct = 90;
@@ -118,6 +120,7 @@ struct phip_handle {
   u32* aux = nullptr;
   u8* arena = nullptr;
   u64 arena_cap = 0;
+  u64 arena_open = 0;        // arena bytes at phip_open: a compacted arena is no smaller
   u64* arena_cursor = nullptr;
   u32* ctr = nullptr;        // device counters: kCtrWords general, then two fast-pass sets (fctr)
   u32* ctr_host = nullptr;   // pinned mirror
@@ -1943,14 +1946,14 @@ int phip_open(const phip_config* cfg, phip_handle** out) {
   if (cfg->device < 0 || cfg->device >= ndev) return PHIP_ERR_NO_DEVICE;
   phip_handle* h = new phip_handle;
   h->device = cfg->device;
-  h->L = cfg->log2_slots;
+  h->L = h->L_open = cfg->log2_slots;
   h->cap = 1ull << h->L;
   h->load_pct = cfg->max_load_pct ? std::min<u32>(cfg->max_load_pct, 95) : 90;
   h->max_load = load_limit(h->cap, h->load_pct);
   h->grow = !(cfg->flags & PHIP_CFG_NO_GROW);
   h->iso_always = cfg->flags & PHIP_CFG_ISOLATE;
   h->small = !(cfg->flags & PHIP_CFG_NO_SMALL);
-  h->arena_cap = cfg->arena_bytes ? cfg->arena_bytes : (1ull << 20);
+  h->arena_cap = h->arena_open = cfg->arena_bytes ? cfg->arena_bytes : (1ull << 20);
   if (cfg->debug_tag_bits && cfg->debug_tag_bits < 64) h->tag_mask = (1ull << cfg->debug_tag_bits) - 1;
   if (cfg->flags & PHIP_CFG_FIXED_SEED) {
     h->seed = cfg->hash_seed;
@@ -2881,6 +2884,134 @@ int phip_set_stream(phip_handle* h, void* stream) {
   return PHIP_OK;
 }
 
+// Eviction sweep (patrolhip.h "Evict idle buckets"): the count pass, then --
+// unless it is a dry run or too little is idle -- grow_table's sequence with
+// k_evict_move in k_rehash's place: allocate and clear the new table (and a
+// new arena when the old one holds anything), move, read the counters, swap,
+// free.  Until the swap every error frees the new memory and leaves the old
+// table and arena as they were.  Nothing else in the handle holds slot
+// numbers or arena offsets across calls (a queued batch, the one thing that
+// could, was finished by begin_call), so, as after growth, nothing is reset.
+static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_evict_stats* out,
+                      u32 flags) {
+  int rc;
+  u64* ev;
+  if ((rc = ensure(h, B_EVICT, kEvWords, &ev))) return rc;
+  HIPCHK(h, hipMemsetAsync(ev, 0, kEvWords * sizeof(u64), h->stream));
+  {
+    Launch l(h, "k_evict_count");
+    k_evict_count<<<std::min<unsigned>(grid_for(h->cap), 8u * (unsigned)h->ncu), kBlock, 0,
+                    h->stream>>>(h->recs, h->cap, now, idle_ns, ev);
+  }
+  HIPCHK(h, hipGetLastError());
+  u64 c[kEvWords] = {};
+  HIPCHK(h, hipMemcpyAsync(c, ev, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  const u64 used = arena_used(h);   // (synchronises)
+  if (used == ~0ull) return set_err(h, PHIP_ERR_HIP, "evict: arena cursor read failed");
+  const u64 n_idle = c[kEvIdle], keep = c[kEvKeep], long_bytes = c[kEvLongBytes];
+  phip_evict_stats st{};
+  st.idle = n_idle;
+  st.buckets = h->n_buckets;
+  st.slots = h->cap;
+  st.arena_used = used;
+  if (out) *out = st;
+  if ((flags & PHIP_EVICT_DRY_RUN) || n_idle < std::max<u64>(min_evict, 1)) return PHIP_OK;
+
+  u32 newL = h->L;
+  if (flags & PHIP_EVICT_SHRINK)
+    for (u32 l = std::min(h->L_open, h->L); l < h->L; ++l)
+      if (keep <= load_limit(1ull << l, h->load_pct) / 2) {
+        newL = l;
+        break;
+      }
+  const u64 ncap = 1ull << newL;
+  const u64 narena_cap = used ? std::max(h->arena_open, long_bytes) : 0;
+  Rec* nrecs = nullptr;
+  u32* naux = nullptr;
+  u8* narena = nullptr;
+  if (hipMalloc(&nrecs, ncap * sizeof(Rec)) != hipSuccess ||
+      hipMalloc(&naux, ncap * sizeof(u32)) != hipSuccess ||
+      (narena_cap && hipMalloc(&narena, narena_cap + 64) != hipSuccess)) {
+    (void)hipGetLastError();
+    if (nrecs) (void)hipFree(nrecs);
+    if (naux) (void)hipFree(naux);
+    return set_err(h, PHIP_ERR_FULL, "evict: device memory for 2^%u slots and %llu arena bytes",
+                   newL, (unsigned long long)narena_cap);
+  }
+  // from here on an error frees the new table and arena (the old ones stay live)
+  auto drop_new = [&](int err) {
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(nrecs);
+    (void)hipFree(naux);
+    if (narena) (void)hipFree(narena);
+    return err;
+  };
+  if (hipMemsetAsync(nrecs, 0, ncap * sizeof(Rec), h->stream) != hipSuccess ||
+      hipMemsetAsync(naux, 0, ncap * sizeof(u32), h->stream) != hipSuccess ||
+      hipMemsetAsync(h->ctr + 7, 0, 2 * sizeof(u32), h->stream) != hipSuccess)
+    return drop_new(set_err(h, PHIP_ERR_HIP, "evict: clearing the new table failed"));
+  Table nt = table(h);
+  nt.recs = nrecs;
+  nt.aux = naux;
+  nt.arena = narena ? narena : h->arena;
+  nt.L = newL;
+  {
+    Launch l(h, "k_evict_move");
+    k_evict_move<<<grid_for(h->cap, kEvictBlock), kEvictBlock, 0, h->stream>>>(
+        h->recs, h->aux, h->cap, h->arena, used, now, idle_ns, nt, ncap, narena, narena_cap, ev,
+        h->ctr);
+  }
+  if (hipGetLastError() != hipSuccess)
+    return drop_new(set_err(h, PHIP_ERR_HIP, "k_evict_move launch failed"));
+  if (hipMemcpyAsync(c, ev, sizeof c, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+    return drop_new(set_err(h, PHIP_ERR_HIP, "evict: counter read failed"));
+  if ((rc = read_ctr(h))) return drop_new(rc);   // synchronises: the old table is no longer read
+  if (h->ctr_host[8]) return drop_new(set_err(h, PHIP_ERR_INVALID, "internal: evict probe wrapped"));
+  if (h->ctr_host[7] || c[kEvCursor] != long_bytes)
+    return drop_new(set_err(h, PHIP_ERR_INVALID,
+                            "internal: evict moved %llu long-name bytes, counted %llu",
+                            (unsigned long long)c[kEvCursor], (unsigned long long)long_bytes));
+  if (narena &&
+      (hipMemcpyAsync(h->arena_cursor, &c[kEvCursor], sizeof(u64), hipMemcpyHostToDevice,
+                      h->stream) != hipSuccess ||
+       hipStreamSynchronize(h->stream) != hipSuccess))
+    return drop_new(set_err(h, PHIP_ERR_HIP, "evict: setting the arena cursor failed"));
+  Rec* orecs = h->recs;
+  u32* oaux = h->aux;
+  u8* oarena = narena ? h->arena : nullptr;
+  h->recs = nrecs;
+  h->aux = naux;
+  h->L = newL;
+  h->cap = ncap;
+  h->max_load = load_limit(ncap, h->load_pct);
+  h->n_buckets = keep;
+  if (narena) {
+    h->arena = narena;
+    h->arena_cap = narena_cap;
+  }
+  st.evicted = n_idle;
+  st.buckets = keep;
+  st.slots = ncap;
+  st.arena_used = narena ? c[kEvCursor] : used;
+  st.arena_freed = used - st.arena_used;
+  if (out) *out = st;
+  HIPCHK(h, hipFree(orecs));
+  HIPCHK(h, hipFree(oaux));
+  if (oarena) HIPCHK(h, hipFree(oarena));
+  return PHIP_OK;
+}
+
+int phip_evict_idle(phip_handle* h, int64_t now, int64_t idle_ns, uint64_t min_evict,
+                    phip_evict_stats* out, uint32_t flags) {
+  if (!h) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;   // (finishes a queued PHIP_RECV_ASYNC batch)
+  if (idle_ns <= 0) return set_err(h, PHIP_ERR_INVALID, "evict: idle_ns must be positive");
+  if (flags & ~(PHIP_EVICT_SHRINK | PHIP_EVICT_DRY_RUN))
+    return set_err(h, PHIP_ERR_INVALID, "evict: unknown flag bits 0x%x", flags);
+  return evict_idle(h, now, idle_ns, min_evict, out, flags);
+}
+
 int phip_table_stats(phip_handle* h, uint64_t* out, int max) {
   if (!h || !out) return PHIP_ERR_INVALID;
   std::lock_guard<std::mutex> g(h->mu);
@@ -2889,7 +3020,10 @@ int phip_table_stats(phip_handle* h, uint64_t* out, int max) {
   int rc;
   if ((rc = ensure(h, B_TSTATS, 2, &d))) return rc;
   HIPCHK(h, hipMemsetAsync(d, 0, 2 * sizeof(u64), h->stream));
-  k_table_stats<<<grid_for(h->cap), kBlock, 0, h->stream>>>(table(h), h->cap, d);
+  {
+    Launch l(h, "k_table_stats");
+    k_table_stats<<<grid_for(h->cap), kBlock, 0, h->stream>>>(table(h), h->cap, d);
+  }
   HIPCHK(h, hipGetLastError());
   u64 r[2] = {0, 0};
   HIPCHK(h, hipMemcpyAsync(r, d, sizeof r, hipMemcpyDeviceToHost, h->stream));

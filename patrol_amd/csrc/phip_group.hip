@@ -877,4 +877,17 @@ int phip_group_anti_entropy(phip_group* g, int64_t* const* replicas, uint32_t nr
   });
 }
 
+// Eviction is local per shard (a bucket lives on its owner alone): every
+// member sweeps its own table, with no exchange.
+int phip_group_evict_idle(phip_group* g, int64_t now, int64_t idle_ns, uint64_t min_evict,
+                          phip_evict_stats* out, uint32_t flags) {
+  if (!g) return PHIP_ERR_INVALID;
+  return for_members(g, [&](size_t i) {
+    Member& mb = g->m[i];
+    GHIP(mb, hipSetDevice(mb.device));
+    GPHIP(mb, phip_evict_idle(mb.h, now, idle_ns, min_evict, out ? out + i : nullptr, flags));
+    return (int)PHIP_OK;
+  });
+}
+
 }  // extern "C"

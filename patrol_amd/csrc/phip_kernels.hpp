@@ -4586,4 +4586,135 @@ __global__ void k_get_one(const u8* name, u32 len, Table T, Rec* out, int* found
   if (pr == kFound) *out = load_rec(&T.recs[s]);   // probe's copy may be the 48-byte view
 }
 
+// ------------------------------------------------------------ eviction ---
+// phip_evict_idle: a filtered rebuild.  Deleting in place from a linear-
+// probing table needs tombstones (taught to every lookup on the hot path) or
+// serial backward shifts; moving the survivors into a fresh table needs
+// neither and changes no other kernel.  Both kernels judge a record by
+// bucket_idle (phip_device.hpp), one thread per slot of the old table.  Every
+// occupied slot is a published record here: no claimed-but-unnamed slot and
+// no kRecNew flag lives between calls.
+//
+// Counters of the sweep (u64 words of one device buffer).
+constexpr u32 kEvIdle = 0;       // k_evict_count: buckets that met the rule
+constexpr u32 kEvKeep = 1;       // k_evict_count: survivors
+constexpr u32 kEvLongBytes = 2;  // k_evict_count: arena bytes of the survivors' long names
+constexpr u32 kEvCursor = 3;     // k_evict_move: the new arena's cursor
+constexpr u32 kEvWords = 4;
+
+// Count pass: one streaming read of the slots.  A wave's three sums first
+// (shuffle sums), then one atomic per counter and wave that has something to
+// add.  The grid is a few workgroups per compute unit striding over the
+// slots, not one thread per slot: with a wave per 64 slots the pass was bound
+// by its atomics on the three words (2^25 slots: 6.3 ms with one counter
+// live, 12.6 ms with two, ~12 ns an atomic, against the ~0.7 ms the read
+// takes; k_table_stats, built that way, takes 11 ms there).
+__global__ __launch_bounds__(kBlock) void k_evict_count(const Rec* __restrict__ recs, u64 cap,
+                                                        i64 now, i64 idle_ns, u64* out) {
+  u32 n_idle = 0, n_keep = 0;
+  u64 lb = 0;
+  const u64 stride = (u64)gridDim.x * kBlock;
+  for (u64 s = (u64)blockIdx.x * kBlock + threadIdx.x; s < cap; s += stride) {
+    // the four words the rule needs, loaded together (not behind the tag test)
+    const Rec* p = &recs[s];
+    const u64 tag = p->tag, name0 = p->name0;
+    const i64 elapsed = p->elapsed, created = p->created;
+    if (!tag) continue;
+    const bool idle = bucket_idle(created, elapsed, now, idle_ns);
+    const u32 len = (u32)(name0 & 0xFFu);
+    n_idle += idle;
+    n_keep += !idle;
+    if (!idle && len > kInlineName) lb += len;
+  }
+  // (a wave sees at most 64 * 2^31 / 256 = 2^29 slots: the u32 counts hold)
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    n_idle += __shfl_xor(n_idle, d);
+    n_keep += __shfl_xor(n_keep, d);
+    lb += __shfl_xor(lb, d);
+  }
+  if (__lane_id() == 0) {
+    if (n_idle) atomicAdd(&out[kEvIdle], (u64)n_idle);
+    if (n_keep) atomicAdd(&out[kEvKeep], (u64)n_keep);
+    if (lb) atomicAdd(&out[kEvLongBytes], lb);
+  }
+}
+
+// Move pass: k_rehash with the rule in front.  A survivor claims its home in
+// the new table T by a CAS on the tag (names are distinct: none is compared)
+// and moves as it is, aux word included.  A surviving long name is copied
+// into the new arena, byte-packed as k_publish leaves it, and the offset
+// bytes of name0 are rewritten (the 16 fast-reject bytes stay).  Room in the
+// new arena comes from one atomicAdd on its cursor per workgroup of 16 waves:
+// a wave prefix sum of the lengths, the waves' totals summed through LDS,
+// thread 0 adds, broadcast.  (One add per wave left the pass bound by that
+// word: with 1M long names among 10M buckets in 2^25 slots 5.5 ms, against
+// 1.0 ms with none, ~12 ns for each of the ~450k waves holding one.)  Every
+// index is checked before the write, so a count that was wrong ends as an
+// error code: ctr[8] a wrapped probe (as k_rehash), ctr[7] a long name that
+// does not fit the arenas.
+constexpr u32 kEvictBlock = 1024;
+__global__ __launch_bounds__(kEvictBlock) void k_evict_move(
+    const Rec* __restrict__ old, const u32* __restrict__ old_aux, u64 old_cap,
+    const u8* __restrict__ old_arena, u64 old_used, i64 now, i64 idle_ns, Table T, u64 new_cap,
+    u8* __restrict__ new_arena, u64 new_arena_cap, u64* ev, u32* ctr) {
+  __shared__ u32 wave_off[kEvictBlock / 64];
+  __shared__ u64 block_base;
+  const u64 s = (u64)blockIdx.x * kEvictBlock + threadIdx.x;
+  Rec r{};
+  bool keep = false;
+  if (s < old_cap) {
+    r = load_rec(&old[s]);
+    keep = r.tag && !bucket_idle(r.created, r.elapsed, now, idle_ns);
+  }
+  const u32 len = (u32)(r.name0 & 0xFFu);
+  const u32 lb = keep && len > kInlineName ? len : 0u;
+  // (no thread leaves before the workgroup's scan and broadcast)
+  const u32 sc = wave_incl_scan(lb);
+  const u32 wv = threadIdx.x >> 6;
+  if (__lane_id() == 63) wave_off[wv] = sc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u32 tot = 0;
+    for (u32 i = 0; i < kEvictBlock / 64; ++i) {
+      const u32 v = wave_off[i];
+      wave_off[i] = tot;
+      tot += v;
+    }
+    block_base = tot ? atomicAdd(&ev[kEvCursor], (u64)tot) : 0ull;
+  }
+  __syncthreads();
+  const u64 base = block_base + wave_off[wv];
+  if (!keep) return;
+  if (lb) {
+    const u64 a = base + sc - lb, oa = r.name0 >> 32;
+    if (!new_arena || a + len > new_arena_cap || a > 0xFFFFFFFFull || oa + len > old_used) {
+      atomicOr(&ctr[7], 1u);
+      return;
+    }
+    // eight bytes a step (the arenas are byte-packed, so neither side is
+    // aligned: the copies are left to the compiler's unaligned accesses)
+    u32 k = 0;
+    for (; k + 8 <= len; k += 8) {
+      u64 w;
+      __builtin_memcpy(&w, old_arena + oa + k, 8);
+      __builtin_memcpy(new_arena + a + k, &w, 8);
+    }
+    for (; k < len; ++k) new_arena[a + k] = old_arena[oa + k];
+    r.name0 = (r.name0 & 0xFFFFFFFFull) | (a << 32);
+  }
+  const u32 mask = T.mask();
+  u32 d = T.home(r.tag);
+  u32 k = 0;
+  for (; k <= mask; ++k, d = (d + 1) & mask) {
+    if (d >= new_cap) break;
+    if (atomicCAS(&T.recs[d].tag, 0ull, r.tag) == 0ull) break;
+  }
+  if (k > mask || d >= new_cap) { atomicOr(&ctr[8], 1u); return; }
+  Rec* q = &T.recs[d];
+  q->added = r.added; q->taken = r.taken; q->elapsed = r.elapsed;
+  q->name0 = r.name0; q->name1 = r.name1; q->created = r.created; q->name2 = r.name2;
+  T.aux[d] = old_aux[s];
+}
+
 }  // namespace phip

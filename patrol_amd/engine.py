@@ -72,6 +72,14 @@ def names_blob(names: Sequence[bytes]):
     return blob, offs
 
 
+def _evict_flags(shrink: bool, dry_run: bool) -> int:
+    return (_lib.EVICT_SHRINK if shrink else 0) | (_lib.EVICT_DRY_RUN if dry_run else 0)
+
+
+def _evict_dict(st) -> dict:
+    return {k: int(getattr(st, k)) for k, _ in _lib.phip_evict_stats._fields_}
+
+
 @dataclass
 class BucketState:
     """A Bucket's replicated fields plus its local `created` (bucket.go:20-32)."""
@@ -278,6 +286,23 @@ class GPURepo:
         buf = np.fromfile(src, np.uint8) if isinstance(src, (str, bytes, os.PathLike)) else \
             np.ascontiguousarray(src, np.uint8)
         self._check(self.L.phip_restore(self.h, buf.ctypes.data, buf.size))
+
+    def evict_idle(self, now: int, idle_ns: int, min_evict: int = 1, shrink: bool = False,
+                   dry_run: bool = False) -> dict:
+        """Evict every bucket idle for idle_ns or longer (phip_evict_idle):
+        idle = now - (created + elapsed), exact, 0 when negative.  An evicted
+        bucket is recreated by its next GetBucket (PHIP_ST_CREATED), as after
+        a node restart in the reference (repo.go:96-106); keep idle_ns >= per
+        of every rate served and its first Take answers as it would have.
+        Fewer than min_evict idle buckets, or dry_run, only counts.  shrink
+        also picks a smaller table.  -> dict(idle, evicted, buckets, slots,
+        arena_used, arena_freed)."""
+        st = _lib.phip_evict_stats()
+        rc = self.L.phip_evict_idle(self.h, int(now), int(idle_ns), int(min_evict), C.byref(st),
+                                    _evict_flags(shrink, dry_run))
+        self._queued = None   # a queued batch is finished (or failed)
+        self._check(rc)
+        return _evict_dict(st)
 
     def dump_arrays(self):
         """Every bucket as arrays (unordered): (names uint8, offs uint64[n+1],
@@ -562,6 +587,16 @@ class GPUGroup:
         R, three, B = replicas[0].shape
         ptrs = (C.c_void_p * len(replicas))(*[x.data_ptr() for x in replicas])
         self._check(self.L.phip_group_anti_entropy(self.g, ptrs, R, B, DEVICE_PTRS))
+
+    def evict_idle(self, now: int, idle_ns: int, min_evict: int = 1, shrink: bool = False,
+                   dry_run: bool = False) -> list:
+        """GPURepo.evict_idle on every local member, concurrently
+        (phip_group_evict_idle; eviction is local per shard) -> one dict per
+        member."""
+        st = (_lib.phip_evict_stats * len(self.repos))()
+        self._check(self.L.phip_group_evict_idle(self.g, int(now), int(idle_ns), int(min_evict),
+                                                 st, _evict_flags(shrink, dry_run)))
+        return [_evict_dict(s) for s in st]
 
     def close(self):
         if getattr(self, "g", None):
