@@ -549,6 +549,24 @@ int phip_route_pack(phip_handle* h, const phip_msgs* m, uint32_t world, uint8_t*
                     int64_t* send_elapsed, uint64_t* counts, uint64_t* name_bytes,
                     uint32_t flags);
 
+/* Stable owner partition of an op stream (device pointers only, world <= 64):
+ * op j of the send buffers is op send_src[j] of `ops`; owner-major, each owner's
+ * ops in their batch order.  x0/x1/x2 carry the op's three operands by kind:
+ * TAKE freq/per/count, RECEIVE and UPSERT added/taken/elapsed (bit patterns).
+ * A NULL operand column of `ops` reads as zeros.  counts / name_bytes as
+ * phip_route_pack.  No combining: ordered ops never combine.
+ * The send_* columns have ops->n entries, send_names holds every name byte.
+ * flags must be exactly PHIP_DEVICE_PTRS (PHIP_ROUTE_COMBINE included, any
+ * other bit is PHIP_ERR_INVALID).  A checked batch (ops->names_len != 0) with
+ * a malformed offset entry is PHIP_ERR_INVALID and nothing is packed.  The
+ * `kind` values of a device batch are the producer's to guarantee, as for
+ * phip_apply_mixed. */
+int phip_route_pack_ops(phip_handle* h, const phip_ops* ops, uint32_t world,
+                        uint8_t* send_names, uint32_t* send_lens, uint8_t* send_kind,
+                        int64_t* send_now, uint64_t* send_x0, uint64_t* send_x1,
+                        uint64_t* send_x2, uint32_t* send_src,
+                        uint64_t* counts, uint64_t* name_bytes, uint32_t flags);
+
 /* Anti-entropy over simulated replicas (BASELINE configs[4]).  `replicas`
  * holds nrep replicas of nbuckets buckets, each as three int64 planes
  * [r][0..2][i]: E codes (the order-preserving key of the engine, mirrored by
@@ -632,6 +650,54 @@ phip_handle* phip_group_handle(phip_group* g, uint32_t i);
  * is hashed or copied.  With names_len == 0 the offsets are trusted. */
 int phip_group_receive(phip_group* g, const phip_msgs* batches, int64_t now, uint64_t* sent,
                        uint64_t* merged, uint32_t flags);
+/* Owner-routed phip_apply_mixed: batches[i] / results[i] belong to local member i
+ * (device memory of its GPU; any results pointer may be NULL, results itself
+ * too).  The sharded form of POST /take (api.go:51-86): an op that arrived at
+ * member i for a bucket of member j is applied at j, in order, and its result
+ * comes back to i.
+ *
+ * Order rule.  The call runs K rounds, K the largest ceil(n / chunk) over the
+ * members of the group; chunk is 2^24, or 4096 with PHIP_GROUP_SMALL_CHUNKS
+ * (phip_group_receive's constants).  In round k every member packs ops
+ * [k * chunk, (k + 1) * chunk) of its batch by owner (phip_route_pack_ops; a
+ * member whose batch has ended sends an empty round), the segments travel to
+ * their owners, and every owner applies what it received with ONE
+ * phip_apply_mixed: sources in rank order, each source's round-k ops in their
+ * index order.  A bucket's ops therefore take effect in the order
+ *     (round, source rank, index in the source's batch);
+ * buckets are independent, so the whole call equals the Go code run over all
+ * ops sorted by that key.  Ordered ops never combine.
+ *
+ * Results.  results[i] entry j is the result of op j of batches[i]: status
+ * (with PHIP_ST_CREATED), remaining, have and reply, each exactly what
+ * phip_apply_mixed reports for that op at its owner.  All four columns always
+ * return over the exchange (49 bytes per op: the members of a multi-process
+ * group cannot see each other's NULL pointers); they come back in send order
+ * and the source scatters them to the ops' places, skipping a column the
+ * caller passed as NULL.  sent[i] / applied[i] (optional) receive the ops
+ * member i sent and the ops it applied as an owner.
+ *
+ * Flags.  PHIP_DEVICE_PTRS is required; PHIP_GROUP_RCCL_SELF and
+ * PHIP_GROUP_SMALL_CHUNKS as for phip_group_receive; any other bit
+ * (PHIP_ROUTE_COMBINE included) is PHIP_ERR_INVALID.  A world of one without
+ * PHIP_GROUP_RCCL_SELF has nothing to route: the batch goes straight to
+ * phip_apply_mixed and the results straight into the caller's buffers.
+ *
+ * Checked batches (phip_ops.names_len != 0): phip_group_receive's rule.
+ * Every local batch's offset column is checked in full before any pack; if
+ * any holds a malformed entry, none of this process's batches is applied, the
+ * process still runs every round with empty batches (so peers do not wait),
+ * the call returns PHIP_ERR_INVALID and phip_group_last_error names the
+ * member and the op.  A device batch's `kind` values are the producer's to
+ * guarantee, as for phip_apply_mixed.
+ *
+ * Errors follow phip_group_receive: a failing member releases the call's
+ * barriers and its error is the call's.  Every status column the caller
+ * passed is zeroed first, so an op that was not applied (a failed call, a
+ * rejected batch) reports status 0, which no applied op has. */
+int phip_group_apply_mixed(phip_group* g, const phip_ops* batches,
+                           const phip_results* results, uint64_t* sent,
+                           uint64_t* applied, uint32_t flags);
 /* Anti-entropy round over simulated replicas (BASELINE configs[4]):
  * replicas[i] holds member i's nrep replicas in phip_ae_local_max's layout
  * (device memory).  Local join (phip_ae_local_max), RCCL all-reduce(MAX) of
@@ -653,6 +719,9 @@ int phip_group_evict_idle(phip_group* g, int64_t now, int64_t idle_ns, uint64_t 
  * (the sum over its chunks): ms[0] pack (phip_route_pack; the local join of
  * an anti-entropy round), ms[1] exchange (split sizes and segments over RCCL
  * or device copies; the all-reduce), ms[2] the owner's merges (the apply).
+ * phip_group_apply_mixed: ms[0] the pack (phip_route_pack_ops), ms[1] both
+ * exchanges (ops out, results back), ms[2] the owner's phip_apply_mixed plus
+ * the results scatter.
  * The stages overlap, so their sum can exceed the call.  The read
  * synchronises on the events. */
 int phip_group_set_timing(phip_group* g, int on);

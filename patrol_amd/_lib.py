@@ -30,6 +30,7 @@ EXPORTS = [
     "phip_group_handle", "phip_group_receive", "phip_group_anti_entropy",
     "phip_group_set_timing", "phip_group_stage_ms", "phip_group_rccl_info",
     "phip_evict_idle", "phip_group_evict_idle",
+    "phip_route_pack_ops", "phip_group_apply_mixed",
 ]
 
 PHIP_OK = 0
@@ -218,5 +219,10 @@ def load(path: str = LIB_PATH):
     if hasattr(L, "phip_evict_idle"):
         L.phip_evict_idle.argtypes = [vp, i64, i64, u64, C.POINTER(phip_evict_stats), u32]
         L.phip_group_evict_idle.argtypes = [vp, i64, i64, u64, C.POINTER(phip_evict_stats), u32]
+    if hasattr(L, "phip_group_apply_mixed"):
+        L.phip_route_pack_ops.argtypes = [vp, C.POINTER(phip_ops), u32, vp, vp, vp, vp, vp, vp, vp,
+                                          vp, vp, vp, u32]
+        L.phip_group_apply_mixed.argtypes = [vp, C.POINTER(phip_ops), C.POINTER(phip_results),
+                                             C.POINTER(u64), C.POINTER(u64), u32]
     _lib = L
     return L

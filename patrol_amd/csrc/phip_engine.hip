@@ -1903,6 +1903,58 @@ static int route_pack_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32
   return PHIP_OK;
 }
 
+// Stable owner partition of an op stream (phip_route_pack_ops, and the chunks
+// of phip_group_apply_mixed) into owner-major send buffers, queued on `st`
+// with no host synchronisation.  route_pack_on's plan and scratch (B_ROUTE,
+// which nothing of ordered() touches); ordered ops never combine.
+static int route_pack_ops_on(phip_handle* h, hipStream_t st, const phip_ops& ops, u32 world,
+                             uint8_t* send_names, uint32_t* send_lens, uint8_t* send_kind,
+                             int64_t* send_now, uint64_t* send_x0, uint64_t* send_x1,
+                             uint64_t* send_x2, uint32_t* send_src, uint64_t* counts,
+                             uint64_t* nbytes) {
+  const u32 n = ops.n;
+  if (n == 0) {
+    HIPCHK(h, hipMemsetAsync(counts, 0, world * sizeof(uint64_t), st));
+    HIPCHK(h, hipMemsetAsync(nbytes, 0, world * sizeof(uint64_t), st));
+    return PHIP_OK;
+  }
+  const RoutePlan p = route_plan(h, n, world);
+  u8 *base, *temp;
+  u32* pctr;
+  size_t tb;
+  int rc;
+  if ((rc = route_scratch(h, n, world, &base, &pctr, &tb, &temp))) return rc;
+  u32* cnt = (u32*)base;
+  u32* bytes = cnt + p.cells;
+  u32* cbase = bytes + p.cells;
+  u32* bbase = cbase + p.cells;
+  u16* code = (u16*)(bbase + p.cells);
+  NamesOffs src{ops.names, ops.name_offs, ops.names_len};
+  const RouteOps ro{ops.kind, ops.now, ops.freq, ops.per, ops.count, ops.added, ops.taken,
+                    ops.elapsed};
+  {
+    Launch l(h, "k_route_ops_count", st);
+    k_route_ops_count<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(src, n, p.span, world, p.ntile,
+                                                                  code, cnt, bytes);
+  }
+  HIPCHK(h, hipGetLastError());
+  {
+    Launch l(h, "route_scan", st);
+    HIPCHK(h, rocprim::exclusive_scan(temp, tb, cnt, cbase, 0u, p.cells, rocprim::plus<u32>(), st));
+    HIPCHK(h, rocprim::exclusive_scan(temp, tb, bytes, bbase, 0u, p.cells, rocprim::plus<u32>(), st));
+  }
+  {
+    Launch l(h, "k_route_ops_scatter", st);
+    k_route_ops_scatter<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
+        src, ro, n, p.span, world, p.ntile, code, cbase, bbase, send_names, send_lens, send_kind,
+        send_now, send_x0, send_x1, send_x2, send_src);
+  }
+  k_route_totals<<<1, kRouteMaxWorld, 0, st>>>(cnt, bytes, cbase, bbase, p.ntile, world, counts,
+                                               nbytes);
+  HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
+}
+
 // A checked batch's offset column (names_len != 0) in one pass on `st`,
 // before anything of the batch is routed: *first_bad is its first malformed
 // entry (NamesOffs::bad), ~0 when there is none or the batch is unchecked.
@@ -2788,6 +2840,38 @@ int phip_route_pack(phip_handle* h, const phip_msgs* m, uint32_t world, uint8_t*
   return PHIP_OK;
 }
 
+int phip_route_pack_ops(phip_handle* h, const phip_ops* ops, uint32_t world, uint8_t* send_names,
+                        uint32_t* send_lens, uint8_t* send_kind, int64_t* send_now,
+                        uint64_t* send_x0, uint64_t* send_x1, uint64_t* send_x2,
+                        uint32_t* send_src, uint64_t* counts, uint64_t* name_bytes,
+                        uint32_t flags) {
+  if (!h || !ops || flags != PHIP_DEVICE_PTRS || world == 0 || world > kRouteMaxWorld ||
+      !counts || !name_bytes)
+    return PHIP_ERR_INVALID;
+  const u32 n = ops->n;
+  if (n && (!ops->kind || !ops->names || !ops->name_offs || !ops->now || !send_names ||
+            !send_lens || !send_kind || !send_now || !send_x0 || !send_x1 || !send_x2 || !send_src))
+    return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;
+  int rc;
+  phip_msgs view{};
+  view.n = n;
+  view.names_len = ops->names_len;
+  view.names = ops->names;
+  view.name_offs = ops->name_offs;
+  u32 first_bad;
+  if ((rc = check_offsets_on(h, h->stream, view, &first_bad))) return rc;
+  if (first_bad != ~0u)
+    return set_err(h, PHIP_ERR_INVALID,
+                   "malformed name offsets at op %u (names_len check): nothing packed", first_bad);
+  if ((rc = route_pack_ops_on(h, h->stream, *ops, world, send_names, send_lens, send_kind,
+                              send_now, send_x0, send_x1, send_x2, send_src, counts, name_bytes)))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PHIP_OK;
+}
+
 int phip_ae_local_max(phip_handle* h, const int64_t* replicas, uint32_t nrep, uint64_t nbuckets,
                       int64_t* out, uint32_t flags) {
   if (!h || !(flags & PHIP_DEVICE_PTRS) || (nbuckets && (!replicas || !out)) || nrep == 0)
@@ -3070,6 +3154,25 @@ int route_pack(phip_handle* h, void* stream, const phip_msgs* m, uint32_t world,
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = finish_queued(h)) return rc0;
   return route_pack_on(h, (hipStream_t)stream, *m, world, dir, names, lens, a, t, e, counts, nbytes);
+}
+int route_pack_ops(phip_handle* h, void* stream, const phip_ops* ops, uint32_t world,
+                   uint8_t* names, uint32_t* lens, uint8_t* kind, int64_t* now, uint64_t* x0,
+                   uint64_t* x1, uint64_t* x2, uint32_t* src, uint64_t* counts, uint64_t* nbytes) {
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = finish_queued(h)) return rc0;
+  return route_pack_ops_on(h, (hipStream_t)stream, *ops, world, names, lens, kind, now, x0, x1, x2,
+                           src, counts, nbytes);
+}
+int results_scatter(phip_handle* h, void* stream, const uint32_t* src, uint32_t n,
+                    const uint8_t* status, const uint64_t* remaining, const uint64_t* have,
+                    const phip_state* reply, const phip_results* out) {
+  if (!n || !out) return PHIP_OK;
+  const OutView ow{out->status, out->remaining, out->have, out->reply};
+  if (!ow.status && !ow.remaining && !ow.have && !ow.reply) return PHIP_OK;
+  k_route_results_scatter<<<grid_for(n), kBlock, 0, (hipStream_t)stream>>>(src, n, status, remaining,
+                                                                           have, reply, ow);
+  HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
 }
 int check_offsets(phip_handle* h, void* stream, const phip_msgs* m, uint32_t* first_bad) {
   std::lock_guard<std::mutex> g(h->mu);

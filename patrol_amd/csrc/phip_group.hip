@@ -137,7 +137,26 @@ struct StageTimer {
   }
 };
 
+// phip_group_apply_mixed's per-round buffers, apart from Receive's sets (its
+// path touches none of them).  The source side: one round's ops packed
+// owner-major (phip_route_pack_ops' columns; src stays here, it is the
+// results' way back), the split sizes in SendSet's layout, and the results
+// the owners returned, in send order.
+struct OpsSend {
+  Buf names, lens, kind, now, x0, x1, x2, src, sizes;
+  Buf r_status, r_rem, r_have, r_reply;
+  uint64_t* host = nullptr;   // pinned [6 * world]
+};
+// The owner side: one round's received ops (sources in rank order) and the
+// results of applying them, in that order.
+struct OpsRecv {
+  Buf names, lens, offs, kind, now, x0, x1, x2;
+  Buf status, rem, have, reply;
+};
+
 struct Member {
+  OpsSend osend;
+  OpsRecv orecv;
   phip_handle* h = nullptr;
   bool own = false;            // opened by the group (phip_group_open_all)
   int device = 0;
@@ -599,6 +618,321 @@ int member_receive(phip_group* g, Member& mb, const phip_msgs& in, int64_t now, 
   return PHIP_OK;
 }
 
+// Round k of an op batch: ops [k * chunk, ...) (empty past the batch).
+phip_ops ops_chunk_of(const phip_ops& in, u64 chunk, u64 k) {
+  phip_ops c = in;
+  const u64 lo = k * chunk;
+  c.n = lo < in.n ? (u32)std::min<u64>(chunk, in.n - lo) : 0u;
+  if (c.n) {
+    c.kind = in.kind + lo;
+    c.name_offs = in.name_offs + lo;   // absolute offsets into the same blob
+    c.now = in.now + lo;
+    if (in.freq) c.freq = in.freq + lo;
+    if (in.per) c.per = in.per + lo;
+    if (in.count) c.count = in.count + lo;
+    if (in.added) c.added = in.added + lo;
+    if (in.taken) c.taken = in.taken + lo;
+    if (in.elapsed) c.elapsed = in.elapsed + lo;
+  }
+  return c;
+}
+
+phip_results results_from(const phip_results& r, u64 lo) {
+  phip_results c = r;
+  if (c.status) c.status += lo;
+  if (c.remaining) c.remaining += lo;
+  if (c.have) c.have += lo;
+  if (c.reply) c.reply += lo;
+  return c;
+}
+
+// One segment of ops from a source's packed round (src) into the owner's
+// receive buffers, on stream st.
+int copy_ops_seg(Member& mb, const OpsSend& src, const Seg& s_, const Seg& d_, OpsRecv& rs,
+                 hipStream_t st) {
+  if (!d_.rc) return PHIP_OK;
+  GHIP(mb, hipMemcpyAsync((u32*)rs.lens.p + d_.ro, (const u32*)src.lens.p + s_.so, d_.rc * 4,
+                          hipMemcpyDeviceToDevice, st));
+  if (d_.rbytes)
+    GHIP(mb, hipMemcpyAsync((uint8_t*)rs.names.p + d_.rb, (const uint8_t*)src.names.p + s_.sb,
+                            d_.rbytes, hipMemcpyDeviceToDevice, st));
+  GHIP(mb, hipMemcpyAsync((uint8_t*)rs.kind.p + d_.ro, (const uint8_t*)src.kind.p + s_.so, d_.rc,
+                          hipMemcpyDeviceToDevice, st));
+  GHIP(mb, hipMemcpyAsync((int64_t*)rs.now.p + d_.ro, (const int64_t*)src.now.p + s_.so, d_.rc * 8,
+                          hipMemcpyDeviceToDevice, st));
+  GHIP(mb, hipMemcpyAsync((u64*)rs.x0.p + d_.ro, (const u64*)src.x0.p + s_.so, d_.rc * 8,
+                          hipMemcpyDeviceToDevice, st));
+  GHIP(mb, hipMemcpyAsync((u64*)rs.x1.p + d_.ro, (const u64*)src.x1.p + s_.so, d_.rc * 8,
+                          hipMemcpyDeviceToDevice, st));
+  GHIP(mb, hipMemcpyAsync((u64*)rs.x2.p + d_.ro, (const u64*)src.x2.p + s_.so, d_.rc * 8,
+                          hipMemcpyDeviceToDevice, st));
+  return PHIP_OK;
+}
+
+// The results of `cnt` ops at `from` of an owner's result buffers (own) into
+// a source's returned columns at `to`, on stream st.
+int copy_results_seg(Member& mb, const OpsRecv& own, u64 from, OpsSend& ss, u64 to, u64 cnt,
+                     hipStream_t st) {
+  if (!cnt) return PHIP_OK;
+  GHIP(mb, hipMemcpyAsync((uint8_t*)ss.r_status.p + to, (const uint8_t*)own.status.p + from, cnt,
+                          hipMemcpyDeviceToDevice, st));
+  GHIP(mb, hipMemcpyAsync((u64*)ss.r_rem.p + to, (const u64*)own.rem.p + from, cnt * 8,
+                          hipMemcpyDeviceToDevice, st));
+  GHIP(mb, hipMemcpyAsync((u64*)ss.r_have.p + to, (const u64*)own.have.p + from, cnt * 8,
+                          hipMemcpyDeviceToDevice, st));
+  GHIP(mb, hipMemcpyAsync((phip_state*)ss.r_reply.p + to, (const phip_state*)own.reply.p + from,
+                          cnt * sizeof(phip_state), hipMemcpyDeviceToDevice, st));
+  return PHIP_OK;
+}
+
+// Owner-routed phip_apply_mixed of one member (the order rule: patrolhip.h).
+// The rounds run one after another on the handle's stream: pack, split
+// sizes, the ops to their owners, the owner's phip_apply_mixed, the results
+// back to their sources, the scatter into the caller's columns.  An ordered
+// round cannot start before the one before it was applied, and a Take's
+// caller waits for its result, so there is nothing to overlap across rounds.
+int member_apply_mixed(phip_group* g, Member& mb, const phip_ops& in, const phip_results& res,
+                       uint64_t* sent, uint64_t* applied, uint32_t flags) {
+  const u32 W = g->world;
+  const u32 n = in.n;
+  GHIP(mb, hipSetDevice(mb.device));
+  hipStream_t st = (hipStream_t)phip_host::handle_stream(mb.h);
+  const bool rccl_self = (flags & PHIP_GROUP_RCCL_SELF) && !g->shared;
+  mb.tm.reset();
+  if (W == 1 && !rccl_self) {   // one owner: nothing to route
+    if (sent) *sent = n;
+    if (applied) *applied = n;
+    if (n == 0) return PHIP_OK;
+    GHIP(mb, mb.tm.mark(2, st));
+    GPHIP(mb, phip_apply_mixed(mb.h, &in, &res, PHIP_DEVICE_PTRS));
+    GHIP(mb, mb.tm.mark(2, st));
+    return PHIP_OK;
+  }
+  const u64 chunk = (flags & PHIP_GROUP_SMALL_CHUNKS) ? kSmallChunk : kChunk;
+  const u64 k_local = ((u64)n + chunk - 1) / chunk;
+  mb.k_local = k_local;
+  for (u32 p = 0; p < W; ++p) mb.host_k[p] = k_local;
+  const u64 cmax = std::max<u64>(1, std::min<u64>(n, chunk));
+  // name bytes of the largest round: the offsets at the chunk boundaries
+  u64 max_bytes = 0;
+  if (n) {
+    std::vector<u32> bnd(k_local + 1);
+    GHIP(mb, mb.bounds.ensure((k_local + 1) * 4));
+    k_chunk_bounds<<<(unsigned)((k_local + 1 + 255) / 256), 256, 0, st>>>(
+        in.name_offs, n, chunk, k_local, (u32*)mb.bounds.p);
+    GHIP(mb, hipGetLastError());
+    GHIP(mb, hipMemcpyAsync(bnd.data(), mb.bounds.p, (k_local + 1) * 4, hipMemcpyDeviceToHost, st));
+    GHIP(mb, hipStreamSynchronize(st));
+    for (u64 k = 0; k < k_local; ++k) max_bytes = std::max<u64>(max_bytes, (u64)(bnd[k + 1] - bnd[k]));
+  }
+  OpsSend& ss = mb.osend;
+  OpsRecv& rs = mb.orecv;
+  if (!ss.host) GHIP(mb, hipHostMalloc(&ss.host, 6 * (size_t)W * sizeof(u64), 0));
+  GHIP(mb, ss.names.ensure(max_bytes + 64));
+  GHIP(mb, ss.lens.ensure(cmax * 4 + 4));
+  GHIP(mb, ss.kind.ensure(cmax + 8));
+  for (Buf* b : {&ss.now, &ss.x0, &ss.x1, &ss.x2, &ss.r_rem, &ss.r_have}) GHIP(mb, b->ensure(cmax * 8 + 8));
+  GHIP(mb, ss.src.ensure(cmax * 4 + 4));
+  GHIP(mb, ss.r_status.ensure(cmax + 8));
+  GHIP(mb, ss.r_reply.ensure(cmax * sizeof(phip_state)));
+  GHIP(mb, ss.sizes.ensure((size_t)6 * W * 8));
+  u64* sz = (u64*)ss.sizes.p;
+  u64* hs = ss.host;
+  u64 K = 1, n_send = 0, n_recv = 0;
+  std::vector<Seg> plan;
+  int rc;
+  for (u64 k = 0; k < K; ++k) {
+    // 1. the pack of round k
+    const phip_ops c = ops_chunk_of(in, chunk, k);
+    GHIP(mb, mb.tm.mark(0, st));
+    if (phip_host::route_pack_ops(mb.h, st, &c, W, (uint8_t*)ss.names.p, (uint32_t*)ss.lens.p,
+                                  (uint8_t*)ss.kind.p, (int64_t*)ss.now.p, (uint64_t*)ss.x0.p,
+                                  (uint64_t*)ss.x1.p, (uint64_t*)ss.x2.p, (uint32_t*)ss.src.p, sz,
+                                  sz + W) != PHIP_OK)
+      return fail(mb, PHIP_ERR_HIP, "route pack ops: %s", phip_host::last_error(mb.h));
+    GHIP(mb, hipMemcpyAsync(sz + 2 * W, mb.host_k, W * 8, hipMemcpyHostToDevice, st));
+    GHIP(mb, mb.tm.mark(0, st));
+    // 2. the split sizes: every member learns what each source sends it
+    //    (RCCL; shared-device groups read each other's after a barrier)
+    GHIP(mb, mb.tm.mark(1, st));
+    if (!g->shared) {
+      GNCCL(mb, ncclGroupStart());
+      GNCCL(mb, ncclAllToAll(sz, sz + 3 * W, 1, ncclUint64, mb.comm, st));
+      GNCCL(mb, ncclAllToAll(sz + W, sz + 4 * W, 1, ncclUint64, mb.comm, st));
+      GNCCL(mb, ncclAllToAll(sz + 2 * W, sz + 5 * W, 1, ncclUint64, mb.comm, st));
+      GNCCL(mb, ncclGroupEnd());
+    }
+    GHIP(mb, hipMemcpyAsync(hs, sz, 6 * W * sizeof(u64), hipMemcpyDeviceToHost, st));
+    GHIP(mb, mb.tm.mark(1, st));
+    GHIP(mb, hipStreamSynchronize(st));
+    if (g->shared) {   // what member p packed for this one, after every member packed round k
+      if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
+      for (u32 p = 0; p < W; ++p) {
+        const OpsSend& ps = g->m[p].osend;
+        hs[3 * W + p] = ps.host[mb.rank];
+        hs[4 * W + p] = ps.host[W + mb.rank];
+        hs[5 * W + p] = g->m[p].k_local;
+      }
+    }
+    if (k == 0) {   // every member runs max(K) rounds (a shorter batch sends empty rounds)
+      for (u32 p = 0; p < W; ++p) K = std::max<u64>(K, hs[5 * W + p]);
+      K = std::max<u64>(K, 1);
+    }
+    segment_plan(hs, W, &plan);
+    u64 c_send = 0, c_recv = 0, b_recv = 0;
+    for (u32 p = 0; p < W; ++p) {
+      c_send += plan[p].sc;
+      c_recv += plan[p].rc;
+      b_recv += plan[p].rbytes;
+    }
+    if (c_send != c.n)
+      return fail(mb, PHIP_ERR_INVALID, "internal: packed %llu of %u ops", (unsigned long long)c_send,
+                  c.n);
+    if (c_recv > 0xFFFFFFFFull || b_recv > 0xFFFFFFFFull)
+      return fail(mb, PHIP_ERR_INVALID, "routed round of %llu ops / %llu name bytes exceeds 2^32",
+                  (unsigned long long)c_recv, (unsigned long long)b_recv);
+    GHIP(mb, rs.names.ensure(b_recv + 64));
+    GHIP(mb, rs.lens.ensure(c_recv * 4 + 4));
+    GHIP(mb, rs.offs.ensure(c_recv * 4 + 8));
+    GHIP(mb, rs.kind.ensure(c_recv + 8));
+    GHIP(mb, rs.status.ensure(c_recv + 8));
+    for (Buf* b : {&rs.now, &rs.x0, &rs.x1, &rs.x2, &rs.rem, &rs.have}) GHIP(mb, b->ensure(c_recv * 8 + 8));
+    GHIP(mb, rs.reply.ensure(std::max<u64>(c_recv, 1) * sizeof(phip_state)));
+    // 3. the ops to their owners: one send and one receive per peer and
+    //    column; this member's own segment is a device copy unless rccl_self
+    GHIP(mb, mb.tm.mark(1, st));
+    if (g->shared) {
+      for (u32 p = 0; p < W; ++p) {
+        const Member& src = g->m[p];
+        const Seg s_ = send_seg(src.osend.host, W, mb.rank);   // the source's send side
+        if (s_.sc != plan[p].rc || s_.sbytes != plan[p].rbytes)
+          return fail(mb, PHIP_ERR_INVALID, "internal: member %u sends %llu/%llu, %u expects %llu/%llu",
+                      p, (unsigned long long)s_.sc, (unsigned long long)s_.sbytes, mb.rank,
+                      (unsigned long long)plan[p].rc, (unsigned long long)plan[p].rbytes);
+        if ((rc = copy_ops_seg(mb, src.osend, s_, plan[p], rs, st))) return rc;
+      }
+    } else {
+      const Seg& own = plan[mb.rank];
+      if (own.sc != own.rc || own.sbytes != own.rbytes)
+        return fail(mb, PHIP_ERR_INVALID, "internal: own segment %llu/%llu vs %llu/%llu",
+                    (unsigned long long)own.sc, (unsigned long long)own.sbytes,
+                    (unsigned long long)own.rc, (unsigned long long)own.rbytes);
+      if (!rccl_self && (rc = copy_ops_seg(mb, ss, own, own, rs, st))) return rc;
+      GNCCL(mb, ncclGroupStart());
+      for (u32 p = 0; p < W; ++p) {
+        if (p == mb.rank && !rccl_self) continue;
+        const Seg& x = plan[p];
+        GNCCL(mb, ncclSend((u32*)ss.lens.p + x.so, x.sc, ncclUint32, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((u32*)rs.lens.p + x.ro, x.rc, ncclUint32, p, mb.comm, st));
+        GNCCL(mb, ncclSend((uint8_t*)ss.names.p + x.sb, x.sbytes, ncclUint8, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((uint8_t*)rs.names.p + x.rb, x.rbytes, ncclUint8, p, mb.comm, st));
+        GNCCL(mb, ncclSend((uint8_t*)ss.kind.p + x.so, x.sc, ncclUint8, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((uint8_t*)rs.kind.p + x.ro, x.rc, ncclUint8, p, mb.comm, st));
+        GNCCL(mb, ncclSend((int64_t*)ss.now.p + x.so, x.sc, ncclInt64, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((int64_t*)rs.now.p + x.ro, x.rc, ncclInt64, p, mb.comm, st));
+        GNCCL(mb, ncclSend((u64*)ss.x0.p + x.so, x.sc, ncclUint64, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((u64*)rs.x0.p + x.ro, x.rc, ncclUint64, p, mb.comm, st));
+        GNCCL(mb, ncclSend((u64*)ss.x1.p + x.so, x.sc, ncclUint64, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((u64*)rs.x1.p + x.ro, x.rc, ncclUint64, p, mb.comm, st));
+        GNCCL(mb, ncclSend((u64*)ss.x2.p + x.so, x.sc, ncclUint64, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((u64*)rs.x2.p + x.ro, x.rc, ncclUint64, p, mb.comm, st));
+      }
+      GNCCL(mb, ncclGroupEnd());
+    }
+    GHIP(mb, mb.tm.mark(1, st));
+    // 4. the owner's apply: name offsets by an inclusive scan of the lengths,
+    //    then one phip_apply_mixed over the round (sources in rank order,
+    //    each in its order).  The three operand words serve both kinds:
+    //    k_pack_ops reads freq/per/count under TAKE and added/taken/elapsed
+    //    otherwise.
+    if (c_recv) {
+      GHIP(mb, mb.tm.mark(2, st));
+      u32* offs = (u32*)rs.offs.p;
+      const u32* lens = (const u32*)rs.lens.p;
+      GHIP(mb, hipMemsetAsync(offs, 0, sizeof(u32), st));
+      size_t tb = 0;
+      GHIP(mb, rocprim::inclusive_scan(nullptr, tb, lens, offs + 1, (size_t)c_recv,
+                                       rocprim::plus<u32>(), st));
+      GHIP(mb, mb.scan_tmp.ensure(tb));
+      GHIP(mb, rocprim::inclusive_scan(mb.scan_tmp.p, tb, lens, offs + 1, (size_t)c_recv,
+                                       rocprim::plus<u32>(), st));
+      phip_ops ro{};
+      ro.n = (u32)c_recv;
+      ro.kind = (const uint8_t*)rs.kind.p;
+      ro.names = (const uint8_t*)rs.names.p;
+      ro.name_offs = offs;
+      ro.now = (const int64_t*)rs.now.p;
+      ro.freq = (const int64_t*)rs.x0.p;
+      ro.per = (const int64_t*)rs.x1.p;
+      ro.count = (const uint64_t*)rs.x2.p;
+      ro.added = (const uint64_t*)rs.x0.p;
+      ro.taken = (const uint64_t*)rs.x1.p;
+      ro.elapsed = (const int64_t*)rs.x2.p;
+      phip_results rr{};
+      rr.status = (uint8_t*)rs.status.p;
+      rr.remaining = (uint64_t*)rs.rem.p;
+      rr.have = (uint64_t*)rs.have.p;
+      rr.reply = (phip_state*)rs.reply.p;
+      GPHIP(mb, phip_apply_mixed(mb.h, &ro, &rr, PHIP_DEVICE_PTRS));
+      GHIP(mb, mb.tm.mark(2, st));
+    }
+    // 5. the results back to their sources: source p's segment [ro, ro + rc)
+    //    of the owner's result buffers lands at [so, so + sc) of p's returned
+    //    columns (the forward plan with its roles swapped)
+    if (g->shared) {
+      // every owner's results are complete before any source copies them,
+      // and every source has copied before an owner reuses its buffers
+      GHIP(mb, hipStreamSynchronize(st));
+      if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
+      GHIP(mb, mb.tm.mark(1, st));
+      for (u32 p = 0; p < W; ++p) {
+        u64 from = 0;   // where this member's segment lies at owner p: after the lower ranks'
+        for (u32 q = 0; q < mb.rank; ++q) from += g->m[q].osend.host[p];
+        if ((rc = copy_results_seg(mb, g->m[p].orecv, from, ss, plan[p].so, plan[p].sc, st))) return rc;
+      }
+      GHIP(mb, mb.tm.mark(1, st));
+      GHIP(mb, hipStreamSynchronize(st));
+      if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
+    } else {
+      GHIP(mb, mb.tm.mark(1, st));
+      const Seg& own = plan[mb.rank];
+      if (!rccl_self && (rc = copy_results_seg(mb, rs, own.ro, ss, own.so, own.sc, st))) return rc;
+      GNCCL(mb, ncclGroupStart());
+      for (u32 p = 0; p < W; ++p) {
+        if (p == mb.rank && !rccl_self) continue;
+        const Seg& x = plan[p];
+        GNCCL(mb, ncclSend((uint8_t*)rs.status.p + x.ro, x.rc, ncclUint8, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((uint8_t*)ss.r_status.p + x.so, x.sc, ncclUint8, p, mb.comm, st));
+        GNCCL(mb, ncclSend((u64*)rs.rem.p + x.ro, x.rc, ncclUint64, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((u64*)ss.r_rem.p + x.so, x.sc, ncclUint64, p, mb.comm, st));
+        GNCCL(mb, ncclSend((u64*)rs.have.p + x.ro, x.rc, ncclUint64, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((u64*)ss.r_have.p + x.so, x.sc, ncclUint64, p, mb.comm, st));
+        GNCCL(mb, ncclSend((u64*)rs.reply.p + 4 * x.ro, 4 * x.rc, ncclUint64, p, mb.comm, st));
+        GNCCL(mb, ncclRecv((u64*)ss.r_reply.p + 4 * x.so, 4 * x.sc, ncclUint64, p, mb.comm, st));
+      }
+      GNCCL(mb, ncclGroupEnd());
+      GHIP(mb, mb.tm.mark(1, st));
+    }
+    // 6. into the caller's columns, at the ops' places in the batch
+    if (c.n) {
+      const phip_results out = results_from(res, k * chunk);
+      GHIP(mb, mb.tm.mark(2, st));
+      if (phip_host::results_scatter(mb.h, st, (const uint32_t*)ss.src.p, c.n,
+                                     (const uint8_t*)ss.r_status.p, (const uint64_t*)ss.r_rem.p,
+                                     (const uint64_t*)ss.r_have.p, (const phip_state*)ss.r_reply.p,
+                                     &out) != PHIP_OK)
+        return fail(mb, PHIP_ERR_HIP, "results scatter: %s", phip_host::last_error(mb.h));
+      GHIP(mb, mb.tm.mark(2, st));
+    }
+    n_send += c_send;
+    n_recv += c_recv;
+  }
+  if (sent) *sent = n_send;
+  if (applied) *applied = n_recv;
+  GHIP(mb, hipStreamSynchronize(st));   // the results are the caller's to read
+  return PHIP_OK;
+}
+
 __global__ void k_max_into(int64_t* __restrict__ dst, const int64_t* __restrict__ src, u64 n) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && src[i] > dst[i]) dst[i] = src[i];
@@ -661,6 +995,16 @@ void destroy(phip_group* g) {
       for (Buf* b : {&rs.names, &rs.lens, &rs.offs, &rs.a, &rs.t, &rs.e}) b->release();
       for (hipEvent_t ev : {rs.ev_recv, rs.ev_merged})
         if (ev) (void)hipEventDestroy(ev);
+    }
+    {
+      OpsSend& os = mb.osend;
+      OpsRecv& orv = mb.orecv;
+      for (Buf* b : {&os.names, &os.lens, &os.kind, &os.now, &os.x0, &os.x1, &os.x2, &os.src,
+                     &os.sizes, &os.r_status, &os.r_rem, &os.r_have, &os.r_reply, &orv.names,
+                     &orv.lens, &orv.offs, &orv.kind, &orv.now, &orv.x0, &orv.x1, &orv.x2,
+                     &orv.status, &orv.rem, &orv.have, &orv.reply})
+        b->release();
+      if (os.host) (void)hipHostFree(os.host);
     }
     for (Buf* b : {&mb.scan_tmp, &mb.ae, &mb.bounds}) b->release();
     mb.tm.release();
@@ -832,6 +1176,57 @@ int phip_group_receive(phip_group* g, const phip_msgs* batches, int64_t now, uin
   return for_members(g, [&](size_t i) {
     return member_receive(g, g->m[i], batches[i], now, sent ? sent + i : nullptr,
                           merged ? merged + i : nullptr, flags);
+  });
+}
+
+int phip_group_apply_mixed(phip_group* g, const phip_ops* batches, const phip_results* results,
+                           uint64_t* sent, uint64_t* applied, uint32_t flags) {
+  constexpr uint32_t kAllowed = PHIP_DEVICE_PTRS | PHIP_GROUP_RCCL_SELF | PHIP_GROUP_SMALL_CHUNKS;
+  if (!g || !batches || !(flags & PHIP_DEVICE_PTRS) || (flags & ~kAllowed)) return PHIP_ERR_INVALID;
+  const size_t nl = g->m.size();
+  for (size_t i = 0; i < nl; ++i) {
+    const phip_ops& b = batches[i];
+    if (b.n && (!b.kind || !b.names || !b.name_offs || !b.now)) return PHIP_ERR_INVALID;
+  }
+  std::vector<phip_results> res(nl);   // (a NULL results: no column wanted)
+  for (size_t i = 0; i < nl; ++i) res[i] = results ? results[i] : phip_results{};
+  // Ops that are not applied report status 0: the status columns are zeroed
+  // first.  Then the checked batches (names_len): every local member's offset
+  // column in full before any round is packed, phip_group_receive's rule.
+  std::vector<uint32_t> bad(nl, ~0u);
+  if (int rc = for_members(g, [&](size_t i) {
+        Member& mb = g->m[i];
+        GHIP(mb, hipSetDevice(mb.device));
+        hipStream_t st = (hipStream_t)phip_host::handle_stream(mb.h);
+        if (res[i].status && batches[i].n)
+          GHIP(mb, hipMemsetAsync(res[i].status, 0, batches[i].n, st));
+        phip_msgs view{};
+        view.n = batches[i].n;
+        view.names_len = batches[i].names_len;
+        view.names = batches[i].names;
+        view.name_offs = batches[i].name_offs;
+        if (phip_host::check_offsets(mb.h, st, &view, &bad[i]) != PHIP_OK)
+          return fail(mb, PHIP_ERR_HIP, "name offsets check: %s", phip_host::last_error(mb.h));
+        return (int)PHIP_OK;
+      }))
+    return rc;
+  size_t ib = 0;
+  while (ib < nl && bad[ib] == ~0u) ++ib;
+  if (ib < nl) {
+    std::vector<phip_ops> none(batches, batches + nl);
+    for (phip_ops& b : none) b.n = 0;
+    const int rc = for_members(g, [&](size_t i) {
+      return member_apply_mixed(g, g->m[i], none[i], res[i], sent ? sent + i : nullptr,
+                                applied ? applied + i : nullptr, flags);
+    });
+    const std::string xerr = rc != PHIP_OK ? "; and the empty exchange failed: " + g->err : "";
+    g->err = "member " + std::to_string(ib) + ": malformed name offsets at op " +
+             std::to_string(bad[ib]) + " (names_len check): no local batch applied" + xerr;
+    return PHIP_ERR_INVALID;
+  }
+  return for_members(g, [&](size_t i) {
+    return member_apply_mixed(g, g->m[i], batches[i], res[i], sent ? sent + i : nullptr,
+                              applied ? applied + i : nullptr, flags);
   });
 }
 

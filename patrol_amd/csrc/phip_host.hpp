@@ -25,6 +25,16 @@ int route_dir(phip_handle* h, void* stream, const phip_msgs* m, uint32_t world, 
 int route_pack(phip_handle* h, void* stream, const phip_msgs* m, uint32_t world, const void* dir,
                uint8_t* names, uint32_t* lens, uint64_t* a, uint64_t* t, int64_t* e,
                uint64_t* counts, uint64_t* nbytes);
+// The same for an ordered op stream (phip_route_pack_ops' pack of one chunk,
+// no combine), and the results' way back: entry j of the returned columns
+// (send order) into out's columns at src[j]; a NULL column of out is skipped.
+// Both are queued on `stream` with no host synchronisation.
+int route_pack_ops(phip_handle* h, void* stream, const phip_ops* ops, uint32_t world,
+                   uint8_t* names, uint32_t* lens, uint8_t* kind, int64_t* now, uint64_t* x0,
+                   uint64_t* x1, uint64_t* x2, uint32_t* src, uint64_t* counts, uint64_t* nbytes);
+int results_scatter(phip_handle* h, void* stream, const uint32_t* src, uint32_t n,
+                    const uint8_t* status, const uint64_t* remaining, const uint64_t* have,
+                    const phip_state* reply, const phip_results* out);
 // The route kernels do not check a batch's name offsets as they go.
 // check_offsets: one pass over a checked batch's offset column (names_len !=
 // 0; NamesOffs::bad's rule) on `stream`, which it synchronises: *first_bad is

@@ -4397,6 +4397,225 @@ __global__ void k_route_totals(const u32* __restrict__ cnt, const u32* __restric
   nbytes[o] = b1 - b0;
 }
 
+// ------------------------------------------------- owner routing of ops ----
+// The stable owner partition of an ordered op stream (phip_route_pack_ops,
+// phip_group_apply_mixed): k_route_count / k_route_scatter's shape (one
+// workgroup per tile, per-owner ranks by ballots within a wave, one barrier a
+// step, one contiguous run per owner and column) with an op's columns in
+// place of a message's.  Ordered ops never combine, so there is no directory:
+// the count pass keeps each op's owner as its route code, the scatter reads
+// it back.  An op travels as kind, now and three operand words chosen by its
+// kind (TAKE: freq, per, count; RECEIVE / UPSERT: added, taken, elapsed; a
+// NULL column reads as zeros), and send_src keeps where it stood in the
+// batch, for the results' way back (k_route_results_scatter).
+struct RouteOps {
+  const u8* kind;
+  const int64_t* now;
+  const int64_t* freq; const int64_t* per; const uint64_t* count;
+  const uint64_t* a; const uint64_t* t; const int64_t* e;
+};
+
+template <class Src>
+__global__ __launch_bounds__(kRouteBlock) void k_route_ops_count(
+    Src src, u32 n, u32 span, u32 world, u32 ntile, u16* __restrict__ code,
+    u32* __restrict__ cnt, u32* __restrict__ bytes) {
+  __shared__ u32 wc[kRouteWaves][kRouteMaxWorld], wb[kRouteWaves][kRouteMaxWorld];
+  for (u32 j = threadIdx.x; j < kRouteWaves * kRouteMaxWorld; j += kRouteBlock) {
+    (&wc[0][0])[j] = 0; (&wb[0][0])[j] = 0;
+  }
+  __syncthreads();
+  const u32 wave = threadIdx.x / 64, lane = threadIdx.x & 63;
+  const u32 tile = blockIdx.x;
+  const u64 t0 = (u64)tile * span, t1 = min((u64)n, t0 + span);
+  for (u64 b0 = t0 + (u64)wave * 64 * kRUC; b0 < t1; b0 += (u64)kRouteWaves * 64 * kRUC) {
+    u32 len[kRUC];
+    bool valid[kRUC];
+    u64 off[kRUC], w0[kRUC], w1[kRUC], w2[kRUC];
+#pragma unroll
+    for (u32 u = 0; u < kRUC; ++u) {
+      const u64 i = b0 + u * 64 + lane;
+      valid[u] = i < t1;
+      src.template get<true>((u32)(valid[u] ? i : t0), off[u], len[u]);
+    }
+#pragma unroll
+    for (u32 u = 0; u < kRUC; ++u) load_words3<true>(src.blob, off[u], len[u], w0[u], w1[u], w2[u]);
+#pragma unroll
+    for (u32 u = 0; u < kRUC; ++u) {
+      const u64 i = b0 + u * 64 + lane;
+      Name nm;
+      if (len[u] <= kShortName) short_name(w0[u], w1[u], w2[u], off[u], len[u], nm);
+      else load_name_wide<true>(src.blob, off[u], len[u], nm);
+      const u32 o = owner_of_hash(nm.h, world);
+      if (valid[u]) {   // the wave's own row: LDS atomics, no cross-lane loop
+        code[i] = (u16)o;
+        atomicAdd(&wc[wave][o], 1u);
+        atomicAdd(&wb[wave][o], len[u]);
+      }
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {   // the workgroup's cells
+    for (u32 o = lane; o < world; o += 64) {
+      u32 c = 0, b = 0;
+#pragma unroll
+      for (u32 w = 0; w < kRouteWaves; ++w) { c += wc[w][o]; b += wb[w][o]; }
+      cnt[(u64)o * ntile + tile] = c;
+      bytes[(u64)o * ntile + tile] = b;
+    }
+  }
+}
+
+template <class Src>
+__global__ __launch_bounds__(kRouteBlock) void k_route_ops_scatter(
+    Src src, RouteOps op, u32 n, u32 span, u32 world, u32 ntile, const u16* __restrict__ code,
+    const u32* __restrict__ cbase, const u32* __restrict__ bbase, u8* __restrict__ out_names,
+    u32* __restrict__ out_lens, u8* __restrict__ out_kind, int64_t* __restrict__ out_now,
+    uint64_t* __restrict__ out_x0, uint64_t* __restrict__ out_x1, uint64_t* __restrict__ out_x2,
+    u32* __restrict__ out_src) {
+  // per step (two parities, so one barrier a step suffices): each wave's own
+  // running place per owner, and the workgroup's place before the step
+  __shared__ u32 lrun[2][kRouteWaves][kRouteMaxWorld], lrunb[2][kRouteWaves][kRouteMaxWorld];
+  __shared__ u32 run[2][kRouteMaxWorld], runb[2][kRouteMaxWorld];
+  __shared__ u32 nstage[kRouteWaves][kStageWords];
+  const u32 wave = threadIdx.x / 64, lane = threadIdx.x & 63;
+  const u32 tile = blockIdx.x;
+  if (wave == 0)
+    for (u32 o = lane; o < world; o += 64) {
+      run[0][o] = cbase[(u64)o * ntile + tile];
+      runb[0][o] = bbase[(u64)o * ntile + tile];
+    }
+  __syncthreads();
+  const u64 t0 = (u64)tile * span, t1 = min((u64)n, t0 + span);
+  u32* stg = nstage[wave];
+  u32 p = 0;
+  for (u64 s0 = t0; s0 < t1; s0 += kRouteStep, p ^= 1) {
+    u32* lr = lrun[p][wave];
+    u32* lrb = lrunb[p][wave];
+    for (u32 o = lane; o < world; o += 64) { lr[o] = 0; lrb[o] = 0; }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    u32 c[kRU], len[kRU], dst[kRU], dby[kRU], bo_l[kRU], be_l[kRU], kd[kRU], idx[kRU];
+    u64 off[kRU], x0[kRU], x1[kRU], x2[kRU], w0[kRU], w1[kRU], w2[kRU];
+    i64 nw[kRU];
+    bool valid[kRU];
+#pragma unroll
+    for (u32 u = 0; u < kRU; ++u) {   // every load unconditional (index clamped into the tile)
+      const u64 i = s0 + (u64)(wave * kRU + u) * 64 + lane;
+      valid[u] = i < t1;
+      const u32 ic = (u32)(valid[u] ? i : t0);
+      idx[u] = ic;
+      c[u] = code[ic];
+      src.get(ic, off[u], len[u]);
+      kd[u] = op.kind[ic];
+      nw[u] = op.now[ic];
+      // the operand words of the op's kind; a column the batch does not have
+      // reads as zeros
+      const bool take = kd[u] == PHIP_OP_TAKE;
+      const u64* p0 = take ? (const u64*)op.freq : (const u64*)op.a;
+      const u64* p1 = take ? (const u64*)op.per : (const u64*)op.t;
+      const u64* p2 = take ? (const u64*)op.count : (const u64*)op.e;
+      x0[u] = p0 ? p0[ic] : 0;
+      x1[u] = p1 ? p1[ic] : 0;
+      x2[u] = p2 ? p2[ic] : 0;
+    }
+    // the name as three aligned words (all of a name of <= 16 bytes)
+#pragma unroll
+    for (u32 u = 0; u < kRU; ++u) load_words3<false>(src.blob, off[u], len[u], w0[u], w1[u], w2[u]);
+    // 1. this wave's ranks per owner, chunk after chunk (lane o keeps owner
+    //    o's byte run of every chunk for the name staging)
+#pragma unroll
+    for (u32 u = 0; u < kRU; ++u) {
+      const bool plain = valid[u];
+      bo_l[u] = lane < world ? lrb[lane] : 0u;
+      const u32 pl = plain ? len[u] : 0u;
+      dst[u] = 0; dby[u] = 0;
+      if (world <= 8 && !__ballot(pl > 255))
+        route_place_packed<2, 4>(plain, c[u], pl, lr, lrb, dst[u], dby[u]);
+      else if (world <= 16 && !__ballot(pl > 255))
+        route_place_packed<4, 8>(plain, c[u], pl, lr, lrb, dst[u], dby[u]);
+      else
+        route_place(plain, c[u], pl, lr, lrb, dst[u], dby[u]);
+      be_l[u] = lane < world ? lrb[lane] : 0u;
+      c[u] = plain ? c[u] : 0xFFFFu;
+    }
+    __syncthreads();   // every wave's totals for this step are in LDS
+    // 2. this wave's base per owner: the workgroup's place before the step
+    //    plus the waves before this one (lane o: owner o); wave 0 also moves
+    //    the workgroup's place past the step (the other parity)
+    u32 pc = 0, pb = 0;
+    if (lane < world) {
+      pc = run[p][lane];
+      pb = runb[p][lane];
+      u32 tc = 0, tb = 0;
+#pragma unroll
+      for (u32 w = 0; w < kRouteWaves; ++w) {
+        const u32 xc = lrun[p][w][lane], xb = lrunb[p][w][lane];
+        if (w < wave) { pc += xc; pb += xb; }
+        tc += xc; tb += xb;
+      }
+      if (wave == 0) {
+        run[p ^ 1][lane] = run[p][lane] + tc;
+        runb[p ^ 1][lane] = runb[p][lane] + tb;
+      }
+    }
+    // 3. the columns and the names
+#pragma unroll
+    for (u32 u = 0; u < kRU; ++u) {
+      const bool plain = c[u] != 0xFFFFu;
+      const u32 oo = plain ? c[u] : 0u;
+      const u32 d = (u32)__shfl((int)pc, (int)oo) + dst[u];
+      const u32 db = (u32)__shfl((int)pb, (int)oo) + dby[u];
+      if (plain) {
+        out_lens[d] = len[u];
+        out_kind[d] = (u8)kd[u];
+        out_now[d] = nw[u];
+        out_x0[d] = x0[u];
+        out_x1[d] = x1[u];
+        out_x2[d] = x2[u];
+        out_src[d] = idx[u];
+      }
+      // owner runs of this chunk [bo, be) (lane o), in the send buffer
+      const u32 bo = pb + bo_l[u], be = pb + be_l[u];
+      const u32 sh = (u32)(off[u] & 7) * 8;
+      const u64 n0 = sh ? (w0[u] >> sh) | (w1[u] << (64 - sh)) : w0[u];
+      const u64 n1 = sh ? (w1[u] >> sh) | (w2[u] << (64 - sh)) : w1[u];
+      if (!__ballot(plain && len[u] > 16)) {
+        // a run's first and last dwords are shared with the runs of other
+        // waves or steps: stored byte by byte (t0 = bo, pend flushed)
+        u32 pend = 0;
+        route_names_staged(out_names, stg, world, plain, oo, plain ? len[u] : 0u, db, n0, n1, bo,
+                           be, bo, pend);
+        route_flush_pend(out_names, world, be, bo, pend);
+      } else if (plain) {   // a longer name in the chunk: every name byte by byte
+        if (len[u] <= 16) {
+#pragma unroll
+          for (u32 k = 0; k < 16; ++k)
+            if (k < len[u]) out_names[db + k] = (u8)((k < 8 ? n0 >> (8 * k) : n1 >> (8 * (k - 8))) & 0xFFu);
+        } else {
+          for (u32 k = 0; k < len[u]; ++k) out_names[db + k] = src.blob[off[u] + k];
+        }
+      }
+    }
+  }
+}
+
+// The owners' results, returned in send order (entry j answers the op that
+// stood at src[j] of the batch), into the caller's result columns; a column
+// the caller did not ask for is skipped.
+__global__ __launch_bounds__(kBlock) void k_route_results_scatter(
+    const u32* __restrict__ src, u32 n, const u8* __restrict__ status,
+    const uint64_t* __restrict__ remaining, const uint64_t* __restrict__ have,
+    const phip_state* __restrict__ reply, OutView ow) {
+  const u32 j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= n) return;
+  const u32 i = src[j];
+  if (ow.status) ow.status[i] = status[j];
+  if (ow.remaining) ow.remaining[i] = remaining[j];
+  if (ow.have) ow.have[i] = have[j];
+  if (ow.reply) ow.reply[i] = reply[j];
+}
+
 // ------------------------------------------------------------ shard layer --
 // Anti-entropy over simulated cluster replicas (BASELINE configs[4], SURVEY
 // §8e).  Replica r of a GPU is three planes of B int64 for the same B buckets:

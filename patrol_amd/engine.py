@@ -449,6 +449,37 @@ class GPURepo:
         res = phip_results(_ptr(status), _ptr(remaining), _ptr(have), None)
         self._check(self.L.phip_apply_mixed(self.h, C.byref(ops), C.byref(res), DEVICE_PTRS))
 
+    def route_pack_ops_device(self, n, world, kind, names, name_offs, now, freq=None, per=None,
+                              count=None, added=None, taken=None, elapsed=None, names_len=None):
+        """phip_route_pack_ops: the stable owner partition of an op stream given
+        as torch CUDA tensors (a missing operand column reads as zeros) ->
+        dict of CUDA tensors: names (uint8, packed back to back), lens, kind,
+        now, x0, x1, x2 (the operand words by kind), src (op j of the send
+        buffers is op src[j] of the batch), counts and name_bytes per owner."""
+        import torch
+        dev = names.device
+        nb = int(names.numel())
+        z = max(n, 1)
+        out = dict(names=torch.zeros(nb + 64, dtype=torch.uint8, device=dev),
+                   lens=torch.zeros(z, dtype=torch.int32, device=dev),
+                   kind=torch.zeros(z, dtype=torch.uint8, device=dev),
+                   now=torch.zeros(z, dtype=torch.int64, device=dev),
+                   x0=torch.zeros(z, dtype=torch.int64, device=dev),
+                   x1=torch.zeros(z, dtype=torch.int64, device=dev),
+                   x2=torch.zeros(z, dtype=torch.int64, device=dev),
+                   src=torch.zeros(z, dtype=torch.int32, device=dev),
+                   counts=torch.zeros(max(world, 1), dtype=torch.int64, device=dev),
+                   name_bytes=torch.zeros(max(world, 1), dtype=torch.int64, device=dev))
+        ops = phip_ops(n, _names_len(names, names_len), _ptr(kind), _ptr(names), _ptr(name_offs),
+                       _ptr(now), _ptr(freq), _ptr(per), _ptr(count), _ptr(added), _ptr(taken),
+                       _ptr(elapsed))
+        torch.cuda.synchronize(dev)
+        self._check(self.L.phip_route_pack_ops(
+            self.h, C.byref(ops), world, _ptr(out["names"]), _ptr(out["lens"]), _ptr(out["kind"]),
+            _ptr(out["now"]), _ptr(out["x0"]), _ptr(out["x1"]), _ptr(out["x2"]), _ptr(out["src"]),
+            _ptr(out["counts"]), _ptr(out["name_bytes"]), DEVICE_PTRS))
+        return out
+
     def take(self, names, now, freq, per, count):
         """Batched Bucket.Take via GetBucket (create) then Take: (remaining, ok)."""
         n = len(names)
@@ -549,6 +580,54 @@ class GPUGroup:
             (_lib.GROUP_SMALL_CHUNKS if small_chunks else 0)
         self._check(self.L.phip_group_receive(self.g, msgs, int(now), sent, merged, flags))
         return [int(x) for x in sent], [int(x) for x in merged]
+
+    _OPS_KEYS = ("kind", "names", "name_offs", "now", "freq", "per", "count", "added", "taken",
+                 "elapsed")
+
+    def apply_mixed(self, batches, rccl_self: bool = False, small_chunks: bool = False,
+                    want_reply: bool = True):
+        """Owner-routed phip_apply_mixed (phip_group_apply_mixed): batches holds,
+        per local member, the ops that arrived there as a dict (or a tuple in
+        this order) of CUDA tensors: kind uint8, names uint8 blob, name_offs
+        int32[n+1], now int64, and the operand columns freq, per, count
+        (TAKE), added, taken, elapsed (RECEIVE / UPSERT), any of which may be
+        None.  -> (results, sent, applied): results[i] is a dict of CUDA
+        tensors status uint8[n], remaining / have int64[n] (uint64 bit
+        patterns), reply int64[n, 4] (None without want_reply), entry j the
+        result of op j of batches[i] as its owner applied it; sent[i] /
+        applied[i] the ops member i sent and applied as an owner.
+
+        Order: a bucket's ops take effect in (round, source rank, index)
+        order, a round being 2^24 ops of every member's batch (4096 with
+        small_chunks).  The batches are checked (names_len = the names
+        tensor's length) as receive()'s are: a malformed name_offs entry
+        raises PatrolHipError (code -1, naming the member and the op) and no
+        batch is applied."""
+        import torch
+        k = len(batches)
+        ops = (phip_ops * k)()
+        res = (phip_results * k)()
+        out = []
+        for i, b in enumerate(batches):
+            if not isinstance(b, dict):
+                b = dict(zip(self._OPS_KEYS, b))
+            n = b["name_offs"].numel() - 1
+            ops[i] = phip_ops(n, _names_len(b["names"]), *[_ptr(b.get(key)) for key in self._OPS_KEYS])
+            dev, z = b["names"].device, max(n, 1)
+            r = dict(status=torch.zeros(z, dtype=torch.uint8, device=dev),
+                     remaining=torch.zeros(z, dtype=torch.int64, device=dev),
+                     have=torch.zeros(z, dtype=torch.int64, device=dev),
+                     reply=torch.zeros((z, 4), dtype=torch.int64, device=dev) if want_reply else None)
+            res[i] = phip_results(_ptr(r["status"]), _ptr(r["remaining"]), _ptr(r["have"]),
+                                  _ptr(r["reply"]))
+            out.append({key: (v[:n] if v is not None else None) for key, v in r.items()})
+        for r in self.repos:
+            torch.cuda.synchronize(r.device)
+        sent, applied = (C.c_uint64 * k)(), (C.c_uint64 * k)()
+        flags = DEVICE_PTRS | (_lib.GROUP_RCCL_SELF if rccl_self else 0) | \
+            (_lib.GROUP_SMALL_CHUNKS if small_chunks else 0)
+        self._check(self.L.phip_group_apply_mixed(self.g, ops, res, sent, applied, flags))
+        return out, [int(x) for x in sent], [int(x) for x in applied]
 
     def set_timing(self, on: bool = True):
         """phip_group_set_timing: per-stage event timing of later calls."""

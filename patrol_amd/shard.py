@@ -11,8 +11,9 @@ tensors for the CPU tests.
   stable-partitions its decoded replica messages by owner and one
   all_to_all_single per column moves them to their owners (per-source order
   kept, sources concatenated by rank: the merges are order-free in the clean
-  domain, and per-bucket Take order is preserved because a bucket's ops all
-  come from one source queue).
+  domain).  It routes replica messages only.  Takes and other ordered ops are
+  routed by the C library's phip_group_apply_mixed (GPUGroup.apply_mixed in
+  engine.py), whose order rule is (round, source rank, index in the batch).
 * anti_entropy(): the simulated cluster replicas of BASELINE configs[4].
   Replica states are E-encoded (the order-preserving key of
   phip_device.hpp, mirrored in torch by e_encode), so the CvRDT join of any
