@@ -1846,6 +1846,51 @@ static int route_dir_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32 
   return PHIP_OK;
 }
 
+// The skeleton of a stable owner partition of n entries, queued on `st` with
+// no host synchronisation: the plan and scratch (B_ROUTE), the per-(owner,
+// tile) cells, their two scans and the per-owner totals into counts / nbytes
+// (device).  `count` fills cnt / bytes / code and `scatter` writes the send
+// buffers from cbase / bbase; both launch on `st` with the plan and the
+// carved scratch.
+struct RouteCells {
+  u32 *cnt, *bytes, *cbase, *bbase, *pctr;
+  u16* code;
+};
+template <class Count, class Scatter>
+static int route_pack_with(phip_handle* h, hipStream_t st, u32 n, u32 world, uint64_t* counts,
+                           uint64_t* nbytes, Count count, Scatter scatter) {
+  if (n == 0) {
+    HIPCHK(h, hipMemsetAsync(counts, 0, world * sizeof(uint64_t), st));
+    HIPCHK(h, hipMemsetAsync(nbytes, 0, world * sizeof(uint64_t), st));
+    return PHIP_OK;
+  }
+  const RoutePlan p = route_plan(h, n, world);
+  u8 *base, *temp;
+  RouteCells c;
+  size_t tb;
+  int rc;
+  if ((rc = route_scratch(h, n, world, &base, &c.pctr, &tb, &temp))) return rc;
+  c.cnt = (u32*)base;
+  c.bytes = c.cnt + p.cells;
+  c.cbase = c.bytes + p.cells;
+  c.bbase = c.cbase + p.cells;
+  c.code = (u16*)(c.bbase + p.cells);
+  count(p, c);
+  HIPCHK(h, hipGetLastError());
+  {
+    Launch l(h, "route_scan", st);
+    HIPCHK(h, rocprim::exclusive_scan(temp, tb, c.cnt, c.cbase, 0u, p.cells, rocprim::plus<u32>(),
+                                      st));
+    HIPCHK(h, rocprim::exclusive_scan(temp, tb, c.bytes, c.bbase, 0u, p.cells, rocprim::plus<u32>(),
+                                      st));
+  }
+  scatter(p, c);
+  k_route_totals<<<1, kRouteMaxWorld, 0, st>>>(c.cnt, c.bytes, c.cbase, c.bbase, p.ntile, world,
+                                               counts, nbytes);
+  HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
+}
+
 // Stable owner partition of m's messages into owner-major send buffers, the
 // per-owner totals into counts / nbytes (device).  With a directory (dir) a
 // clean batch's hot names are max-combined (k_route_count classifies the
@@ -1855,121 +1900,73 @@ static int route_pack_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32
                   uint64_t* send_taken, int64_t* send_elapsed, uint64_t* counts,
                   uint64_t* nbytes) {
   const u32 n = m.n;
-  if (n == 0) {
-    HIPCHK(h, hipMemsetAsync(counts, 0, world * sizeof(uint64_t), st));
-    HIPCHK(h, hipMemsetAsync(nbytes, 0, world * sizeof(uint64_t), st));
-    return PHIP_OK;
-  }
-  const RoutePlan p = route_plan(h, n, world);
-  u8 *base, *temp;
-  u32* pctr;
-  size_t tb;
-  int rc;
-  if ((rc = route_scratch(h, n, world, &base, &pctr, &tb, &temp))) return rc;
-  u32* cnt = (u32*)base;
-  u32* bytes = cnt + p.cells;
-  u32* cbase = bytes + p.cells;
-  u32* bbase = cbase + p.cells;
-  u16* code = (u16*)(bbase + p.cells);
   const HotHdr* hot = (const HotHdr*)dir;
   const RouteHot* rdir = hot ? (const RouteHot*)(hot + 1) : nullptr;
   NamesOffs src{m.names, m.name_offs, m.names_len};
-  k_batch_reset<<<1, kShards, 0, st>>>(pctr, nullptr);
-  {
-    Launch l(h, "k_route_count", st);
-    k_route_count<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
-        src, m.added, m.taken, m.elapsed, n, p.span, world, p.ntile, hot, rdir, pctr, code, cnt,
-        bytes, hot ? kRouteCombine : kRoutePlain);
-    if (hot)
-      k_route_count<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
-          src, m.added, m.taken, m.elapsed, n, p.span, world, p.ntile, hot, rdir, pctr, code, cnt,
-          bytes, kRouteRecount);
-  }
-  HIPCHK(h, hipGetLastError());
-  {
-    Launch l(h, "route_scan", st);
-    HIPCHK(h, rocprim::exclusive_scan(temp, tb, cnt, cbase, 0u, p.cells, rocprim::plus<u32>(), st));
-    HIPCHK(h, rocprim::exclusive_scan(temp, tb, bytes, bbase, 0u, p.cells, rocprim::plus<u32>(), st));
-  }
-  {
-    Launch l(h, "k_route_scatter", st);
-    k_route_scatter<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
-        src, m.added, m.taken, m.elapsed, n, p.span, world, p.ntile, hot, rdir, pctr, code, cbase,
-        bbase, send_names, send_lens, send_added, send_taken, send_elapsed);
-  }
-  k_route_totals<<<1, kRouteMaxWorld, 0, st>>>(cnt, bytes, cbase, bbase, p.ntile, world, counts,
-                                               nbytes);
-  HIPCHK(h, hipGetLastError());
-  return PHIP_OK;
+  return route_pack_with(
+      h, st, n, world, counts, nbytes,
+      [&](const RoutePlan& p, const RouteCells& c) {
+        k_batch_reset<<<1, kShards, 0, st>>>(c.pctr, nullptr);
+        Launch l(h, "k_route_count", st);
+        k_route_count<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
+            src, m.added, m.taken, m.elapsed, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
+            c.cnt, c.bytes, hot ? kRouteCombine : kRoutePlain);
+        if (hot)
+          k_route_count<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
+              src, m.added, m.taken, m.elapsed, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
+              c.cnt, c.bytes, kRouteRecount);
+      },
+      [&](const RoutePlan& p, const RouteCells& c) {
+        Launch l(h, "k_route_scatter", st);
+        k_route_scatter<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
+            src, m.added, m.taken, m.elapsed, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
+            c.cbase, c.bbase, send_names, send_lens, send_added, send_taken, send_elapsed);
+      });
 }
 
 // Stable owner partition of an op stream (phip_route_pack_ops, and the chunks
-// of phip_group_apply_mixed) into owner-major send buffers, queued on `st`
-// with no host synchronisation.  route_pack_on's plan and scratch (B_ROUTE,
-// which nothing of ordered() touches); ordered ops never combine.
+// of phip_group_apply_mixed) into owner-major send buffers: route_pack_on's
+// skeleton (B_ROUTE, which nothing of ordered() touches); ordered ops never
+// combine.
 static int route_pack_ops_on(phip_handle* h, hipStream_t st, const phip_ops& ops, u32 world,
                              uint8_t* send_names, uint32_t* send_lens, uint8_t* send_kind,
                              int64_t* send_now, uint64_t* send_x0, uint64_t* send_x1,
                              uint64_t* send_x2, uint32_t* send_src, uint64_t* counts,
                              uint64_t* nbytes) {
   const u32 n = ops.n;
-  if (n == 0) {
-    HIPCHK(h, hipMemsetAsync(counts, 0, world * sizeof(uint64_t), st));
-    HIPCHK(h, hipMemsetAsync(nbytes, 0, world * sizeof(uint64_t), st));
-    return PHIP_OK;
-  }
-  const RoutePlan p = route_plan(h, n, world);
-  u8 *base, *temp;
-  u32* pctr;
-  size_t tb;
-  int rc;
-  if ((rc = route_scratch(h, n, world, &base, &pctr, &tb, &temp))) return rc;
-  u32* cnt = (u32*)base;
-  u32* bytes = cnt + p.cells;
-  u32* cbase = bytes + p.cells;
-  u32* bbase = cbase + p.cells;
-  u16* code = (u16*)(bbase + p.cells);
   NamesOffs src{ops.names, ops.name_offs, ops.names_len};
   const RouteOps ro{ops.kind, ops.now, ops.freq, ops.per, ops.count, ops.added, ops.taken,
                     ops.elapsed};
-  {
-    Launch l(h, "k_route_ops_count", st);
-    k_route_ops_count<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(src, n, p.span, world, p.ntile,
-                                                                  code, cnt, bytes);
-  }
-  HIPCHK(h, hipGetLastError());
-  {
-    Launch l(h, "route_scan", st);
-    HIPCHK(h, rocprim::exclusive_scan(temp, tb, cnt, cbase, 0u, p.cells, rocprim::plus<u32>(), st));
-    HIPCHK(h, rocprim::exclusive_scan(temp, tb, bytes, bbase, 0u, p.cells, rocprim::plus<u32>(), st));
-  }
-  {
-    Launch l(h, "k_route_ops_scatter", st);
-    k_route_ops_scatter<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
-        src, ro, n, p.span, world, p.ntile, code, cbase, bbase, send_names, send_lens, send_kind,
-        send_now, send_x0, send_x1, send_x2, send_src);
-  }
-  k_route_totals<<<1, kRouteMaxWorld, 0, st>>>(cnt, bytes, cbase, bbase, p.ntile, world, counts,
-                                               nbytes);
-  HIPCHK(h, hipGetLastError());
-  return PHIP_OK;
+  return route_pack_with(
+      h, st, n, world, counts, nbytes,
+      [&](const RoutePlan& p, const RouteCells& c) {
+        Launch l(h, "k_route_ops_count", st);
+        k_route_ops_count<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(src, n, p.span, world, p.ntile,
+                                                                      c.code, c.cnt, c.bytes);
+      },
+      [&](const RoutePlan& p, const RouteCells& c) {
+        Launch l(h, "k_route_ops_scatter", st);
+        k_route_ops_scatter<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
+            src, ro, n, p.span, world, p.ntile, c.code, c.cbase, c.bbase, send_names, send_lens,
+            send_kind, send_now, send_x0, send_x1, send_x2, send_src);
+      });
 }
 
 // A checked batch's offset column (names_len != 0) in one pass on `st`,
 // before anything of the batch is routed: *first_bad is its first malformed
 // entry (NamesOffs::bad), ~0 when there is none or the batch is unchecked.
 // Synchronises `st`.
-static int check_offsets_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32* first_bad) {
+static int check_offsets_on(phip_handle* h, hipStream_t st, const uint8_t* names,
+                            const uint32_t* name_offs, u32 names_len, u32 n, u32* first_bad) {
   *first_bad = ~0u;
-  if (m.n == 0 || m.names_len == 0) return PHIP_OK;
+  if (n == 0 || names_len == 0) return PHIP_OK;
   u32* d;
   int rc;
   if ((rc = ensure(h, B_NCHK, 1, &d))) return rc;
   HIPCHK(h, hipMemsetAsync(d, 0xFF, sizeof(u32), st));
   {
     Launch l(h, "k_offs_check", st);
-    k_offs_check<<<grid_for(m.n), kBlock, 0, st>>>(NamesOffs{m.names, m.name_offs, m.names_len},
-                                                   m.n, d);
+    k_offs_check<<<grid_for(n), kBlock, 0, st>>>(NamesOffs{names, name_offs, names_len}, n, d);
   }
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(first_bad, d, sizeof(u32), hipMemcpyDeviceToHost, st));
@@ -2826,7 +2823,8 @@ int phip_route_pack(phip_handle* h, const phip_msgs* m, uint32_t world, uint8_t*
   // (the route kernels do not check as they go: a checked batch's offsets
   // first, so that no malformed entry is ever hashed or copied)
   u32 first_bad;
-  if ((rc = check_offsets_on(h, h->stream, *m, &first_bad))) return rc;
+  if ((rc = check_offsets_on(h, h->stream, m->names, m->name_offs, m->names_len, n, &first_bad)))
+    return rc;
   if (first_bad != ~0u)
     return set_err(h, PHIP_ERR_INVALID,
                    "malformed name offsets at message %u (names_len check): nothing packed",
@@ -2855,13 +2853,10 @@ int phip_route_pack_ops(phip_handle* h, const phip_ops* ops, uint32_t world, uin
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = begin_call(h)) return rc0;
   int rc;
-  phip_msgs view{};
-  view.n = n;
-  view.names_len = ops->names_len;
-  view.names = ops->names;
-  view.name_offs = ops->name_offs;
   u32 first_bad;
-  if ((rc = check_offsets_on(h, h->stream, view, &first_bad))) return rc;
+  if ((rc = check_offsets_on(h, h->stream, ops->names, ops->name_offs, ops->names_len, n,
+                             &first_bad)))
+    return rc;
   if (first_bad != ~0u)
     return set_err(h, PHIP_ERR_INVALID,
                    "malformed name offsets at op %u (names_len check): nothing packed", first_bad);
@@ -3174,10 +3169,11 @@ int results_scatter(phip_handle* h, void* stream, const uint32_t* src, uint32_t 
   HIPCHK(h, hipGetLastError());
   return PHIP_OK;
 }
-int check_offsets(phip_handle* h, void* stream, const phip_msgs* m, uint32_t* first_bad) {
+int check_offsets(phip_handle* h, void* stream, const uint8_t* names, const uint32_t* name_offs,
+                  uint32_t names_len, uint32_t n, uint32_t* first_bad) {
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = finish_queued(h)) return rc0;
-  return check_offsets_on(h, (hipStream_t)stream, *m, first_bad);
+  return check_offsets_on(h, (hipStream_t)stream, names, name_offs, names_len, n, first_bad);
 }
 const char* last_error(phip_handle* h) { return h ? h->err.c_str() : ""; }
 int handle_device(const phip_handle* h) { return h ? h->device : -1; }

@@ -79,26 +79,79 @@ struct Buf {
 constexpr uint32_t kChunk = 1u << 24;
 constexpr uint32_t kSmallChunk = 1u << 12;   // PHIP_GROUP_SMALL_CHUNKS
 
-// One chunk's send buffers (owner-major, phip_route_pack's layout) and its
-// split sizes.  sizes (device) and host (pinned) hold [6 * world] u64:
+// One travelling column: its entry's size, whether a segment of it is
+// addressed by message (Seg's so/sc, ro/rc) or by name byte (sb/sbytes,
+// rb/rbytes), an entry on the wire (`per` elements of `type`) and the bytes
+// its buffer keeps past the last entry (the kernels' over-read slack).
+struct Col {
+  u32 elem;
+  bool by_bytes;
+  ncclDataType_t type;
+  u32 per;
+  u32 slack;
+};
+constexpr u32 kMaxCols = 7;
+struct Cols {
+  u32 n;
+  Col c[kMaxCols];
+};
+constexpr Col kLens = {4, false, ncclUint32, 1, 4}, kNames = {1, true, ncclUint8, 1, 64},
+              kByte = {1, false, ncclUint8, 1, 8}, kWord = {8, false, ncclUint64, 1, 8},
+              kReply = {sizeof(phip_state), false, ncclUint64, sizeof(phip_state) / 8, 0};
+// The three column sets that travel, and their columns' places in a ColSet:
+// messages (phip_route_pack's send columns), ops (phip_route_pack_ops'; the
+// three operand words serve both kinds) and the results of applied ops.
+constexpr Cols kMsgCols = {5, {kLens, kNames, kWord, kWord, kWord}};
+constexpr Cols kOpCols = {7, {kLens, kNames, kByte, kWord, kWord, kWord, kWord}};
+constexpr Cols kResCols = {4, {kByte, kWord, kWord, kReply}};
+enum { C_LENS, C_NAMES, MSG_A, MSG_T, MSG_E };
+enum { O_KIND = C_NAMES + 1, O_NOW, O_X0, O_X1, O_X2 };
+enum { R_STATUS, R_REM, R_HAVE, R_REPLY };
+
+// The buffers of one column set, sized and moved by its table.
+struct ColSet {
+  const Cols* cols;
+  Buf b[kMaxCols];
+  explicit ColSet(const Cols& c) : cols(&c) {}
+  // Room for n entries and nb name bytes, and never less than one entry (RCCL
+  // is handed every column's pointer, also for an empty segment).
+  hipError_t ensure(u64 n, u64 nb) {
+    for (u32 i = 0; i < cols->n; ++i) {
+      const Col& c = cols->c[i];
+      hipError_t e = b[i].ensure(std::max<u64>((c.by_bytes ? nb : n) * c.elem + c.slack, c.elem));
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  void release() {
+    for (Buf& x : b) x.release();
+  }
+  template <class T>
+  T* at(u32 i) const { return (T*)b[i].p; }
+};
+
+// One chunk's split sizes: dev (device) and host (pinned) hold [6 * world] u64:
 //   send counts | send name bytes | send chunk totals | recv counts | recv name bytes | recv chunk totals
 // (the chunk totals: every member's chunk count K, so that all members run
 // the same number of exchange rounds).
-struct SendSet {
-  Buf names, lens, a, t, e, sizes;
+struct Sizes {
+  Buf dev;
   uint64_t* host = nullptr;
-  hipEvent_t ev_pack = nullptr, ev_sz = nullptr, ev_x = nullptr;
-  bool x_pending = false;   // ev_x recorded for an exchange reading this set
 };
 
-// One chunk's received segments (sources in rank order), merged while the
-// next chunk travels.
-struct RecvSet {
-  Buf names, lens, offs, a, t, e;
-  u64 n = 0;                      // messages received into it
+// Receive's pipeline state for the chunks of one parity (chunk k uses lane
+// k & 1 and the member's sizes k & 1): the chunk's send buffers (owner-major,
+// phip_route_pack's layout) and its received segments (sources in rank
+// order), merged while the next chunk travels.
+struct Lane {
+  ColSet send{kMsgCols}, recv{kMsgCols};
+  Buf offs;                       // the received names' offsets
+  hipEvent_t ev_pack = nullptr, ev_sz = nullptr, ev_x = nullptr;
+  bool x_pending = false;         // ev_x recorded for an exchange reading `send`
+  u64 n = 0;                      // messages received into `recv`
   hipEvent_t ev_recv = nullptr;   // its exchange (exchange stream)
   hipEvent_t ev_merged = nullptr; // its merge (handle stream)
-  bool merge_pending = false;     // ev_merged recorded for a merge reading it
+  bool merge_pending = false;     // ev_merged recorded for a merge reading `recv`
 };
 
 // Busy spans of one group call per stage (0 pack, 1 exchange, 2 merge):
@@ -137,26 +190,9 @@ struct StageTimer {
   }
 };
 
-// phip_group_apply_mixed's per-round buffers, apart from Receive's sets (its
-// path touches none of them).  The source side: one round's ops packed
-// owner-major (phip_route_pack_ops' columns; src stays here, it is the
-// results' way back), the split sizes in SendSet's layout, and the results
-// the owners returned, in send order.
-struct OpsSend {
-  Buf names, lens, kind, now, x0, x1, x2, src, sizes;
-  Buf r_status, r_rem, r_have, r_reply;
-  uint64_t* host = nullptr;   // pinned [6 * world]
-};
-// The owner side: one round's received ops (sources in rank order) and the
-// results of applying them, in that order.
-struct OpsRecv {
-  Buf names, lens, offs, kind, now, x0, x1, x2;
-  Buf status, rem, have, reply;
-};
+constexpr u32 kOpsSizes = 2;   // Member::sz of the ops path (0, 1: Receive's lanes)
 
 struct Member {
-  OpsSend osend;
-  OpsRecv orecv;
   phip_handle* h = nullptr;
   bool own = false;            // opened by the group (phip_group_open_all)
   int device = 0;
@@ -164,8 +200,16 @@ struct Member {
   ncclComm_t comm = nullptr;
   hipStream_t sp = nullptr, sx = nullptr;   // pack stream, exchange stream
   hipEvent_t ev_done = nullptr;             // the call's last exchange
-  SendSet set[2];
-  RecvSet rset[2];             // chunk k is received into rset[k & 1]
+  Lane lane[2];
+  // phip_group_apply_mixed's per-round buffers, apart from Receive's lanes
+  // (its path touches none of them).  One round's ops packed owner-major
+  // (osrc, their places in the batch, stays here: it is the results' way
+  // back) and as the owner received them (sources in rank order, ooffs their
+  // names' offsets); the results of applying them, in that order, and the
+  // results the owners returned to this source, in send order.
+  ColSet osend{kOpCols}, orecv{kOpCols}, ores{kResCols}, oback{kResCols};
+  Buf osrc, ooffs;
+  Sizes sz[3];
   Buf scan_tmp, ae, bounds;
   u64* host_k = nullptr;       // pinned [world]: this member's chunk count, to every peer
   u64 k_local = 0;             // (shared-device groups read each other's)
@@ -282,7 +326,7 @@ int for_members(phip_group* g, F f) {
 }
 
 // The exchange plan of one chunk of one member, shared by the RCCL and the
-// shared-device paths: with hs = the chunk's split sizes (SendSet::host),
+// shared-device paths: with hs = the chunk's split sizes (Sizes::host),
 // peer p's entry gives
 //   send side: where the member's packed segment for owner p lies in its
 //              owner-major send buffers (so messages / sb name bytes in) and
@@ -305,50 +349,225 @@ void segment_plan(const u64* hs, u32 W, std::vector<Seg>* plan) {
   }
 }
 
-// The send side of one segment only (where a source's segment for owner p
-// lies in its send set): what a shared-device peer reads of another
-// member's sizes (their receive side is that member's own to write).
-Seg send_seg(const u64* hs, u32 W, u32 p) {
+// The plan with its roles swapped: the way back of what the plan brought
+// (each owner returns to source p what p sent it, to where p sent it from).
+Seg swapped(const Seg& s) { return Seg{s.ro, s.rb, s.rc, s.rbytes, s.so, s.sb, s.sc, s.sbytes}; }
+
+// Segment p of one side of another member's sizes alone (side = its host
+// block at 0: where its segment for owner p lies in its send buffers; at
+// 3 * W: where source p's segment lies in its receive buffers), as a send
+// side: what a shared-device peer reads of that member's sizes.
+Seg seg_at(const u64* side, u32 W, u32 p) {
   Seg g{};
   for (u32 q = 0; q < p; ++q) {
-    g.so += hs[q];
-    g.sb += hs[W + q];
+    g.so += side[q];
+    g.sb += side[W + q];
   }
-  g.sc = hs[p];
-  g.sbytes = hs[W + p];
+  g.sc = side[p];
+  g.sbytes = side[W + p];
   return g;
 }
 
+// A shared-device peer's part in a move: the set this member copies from and
+// where its segment lies in it.
+struct Peer {
+  const ColSet* from;
+  Seg at;
+};
+template <class F>
+std::vector<Peer> peers_of(const phip_group* g, const Member& mb, u32 si, u32 side, F set) {
+  std::vector<Peer> v;
+  if (g->shared)
+    for (const Member& m : g->m)
+      v.push_back({&set(m), seg_at(m.sz[si].host + side, g->world, mb.rank)});
+  return v;
+}
+
+// The part of a segment a column covers: by message or by name byte.
+struct Span {
+  u64 off, cnt;
+};
+Span send_span(const Col& c, const Seg& s) {
+  return c.by_bytes ? Span{s.sb, s.sbytes} : Span{s.so, s.sc};
+}
+Span recv_span(const Col& c, const Seg& s) {
+  return c.by_bytes ? Span{s.rb, s.rbytes} : Span{s.ro, s.rc};
+}
+
+// Moves a column set along a plan on stream st: for every peer p, the send
+// side of plan[p] out of `from` to p, and p's segment into the receive side
+// of plan[p] in `to`; one send and one receive per peer and column, this
+// member's own segment a device copy unless rccl_self.  In a shared-device
+// group (no RCCL) the member copies every segment out of its peers' sets
+// instead, after a barrier that the caller keeps.
+int move_segments(phip_group* g, Member& mb, const std::vector<Seg>& plan, const ColSet& from,
+                  ColSet& to, hipStream_t st, bool rccl_self, const std::vector<Peer>& peers) {
+  const u32 W = g->world;
+  const Cols& cols = *to.cols;
+  if (from.cols != to.cols) return fail(mb, PHIP_ERR_INVALID, "internal: column sets differ");
+  auto copy = [&](const ColSet& src, const Seg& s, const Seg& d) -> int {
+    for (u32 i = 0; i < cols.n; ++i) {
+      const Col& c = cols.c[i];
+      const Span f = send_span(c, s), t = recv_span(c, d);
+      if (t.cnt)
+        GHIP(mb, hipMemcpyAsync(to.at<uint8_t>(i) + t.off * c.elem, src.at<uint8_t>(i) + f.off * c.elem,
+                                t.cnt * c.elem, hipMemcpyDeviceToDevice, st));
+    }
+    return PHIP_OK;
+  };
+  int rc;
+  if (g->shared) {
+    for (u32 p = 0; p < W; ++p) {
+      const Seg& s = peers[p].at;   // the source's send side
+      if (s.sc != plan[p].rc || s.sbytes != plan[p].rbytes)
+        return fail(mb, PHIP_ERR_INVALID, "internal: member %u sends %llu/%llu, %u expects %llu/%llu",
+                    p, (unsigned long long)s.sc, (unsigned long long)s.sbytes, mb.rank,
+                    (unsigned long long)plan[p].rc, (unsigned long long)plan[p].rbytes);
+      if ((rc = copy(*peers[p].from, s, plan[p]))) return rc;
+    }
+    return PHIP_OK;
+  }
+  const Seg& own = plan[mb.rank];
+  if (own.sc != own.rc || own.sbytes != own.rbytes)
+    return fail(mb, PHIP_ERR_INVALID, "internal: own segment %llu/%llu vs %llu/%llu",
+                (unsigned long long)own.sc, (unsigned long long)own.sbytes,
+                (unsigned long long)own.rc, (unsigned long long)own.rbytes);
+  if (!rccl_self && (rc = copy(from, own, own))) return rc;
+  GNCCL(mb, ncclGroupStart());
+  for (u32 p = 0; p < W; ++p) {
+    if (p == mb.rank && !rccl_self) continue;
+    for (u32 i = 0; i < cols.n; ++i) {
+      const Col& c = cols.c[i];
+      const Span f = send_span(c, plan[p]), t = recv_span(c, plan[p]);
+      GNCCL(mb, ncclSend(from.at<uint8_t>(i) + f.off * c.elem, f.cnt * c.per, c.type, p, mb.comm, st));
+      GNCCL(mb, ncclRecv(to.at<uint8_t>(i) + t.off * c.elem, t.cnt * c.per, c.type, p, mb.comm, st));
+    }
+  }
+  GNCCL(mb, ncclGroupEnd());
+  return PHIP_OK;
+}
+
+// A chunk's split sizes (stage 1) on stream st: every member learns what each
+// source sends it (RCCL; shared-device groups read each other's after a
+// barrier, adopt_sizes), and the block goes to its pinned mirror.
+int exchange_sizes(phip_group* g, Member& mb, Sizes& s, hipStream_t st) {
+  const u32 W = g->world;
+  u64* sz = (u64*)s.dev.p;
+  GHIP(mb, mb.tm.mark(1, st));
+  if (!g->shared) {
+    GNCCL(mb, ncclGroupStart());
+    GNCCL(mb, ncclAllToAll(sz, sz + 3 * W, 1, ncclUint64, mb.comm, st));
+    GNCCL(mb, ncclAllToAll(sz + W, sz + 4 * W, 1, ncclUint64, mb.comm, st));
+    GNCCL(mb, ncclAllToAll(sz + 2 * W, sz + 5 * W, 1, ncclUint64, mb.comm, st));
+    GNCCL(mb, ncclGroupEnd());
+  }
+  GHIP(mb, hipMemcpyAsync(s.host, sz, 6 * W * sizeof(u64), hipMemcpyDeviceToHost, st));
+  GHIP(mb, mb.tm.mark(1, st));
+  return PHIP_OK;
+}
+
+// Once sizes si are in the member's pinned mirror: a shared-device member
+// waits until every member's are and takes what member p packed for it from
+// p's.  The first chunk's totals give the call's round count *K: every member
+// runs max(K) rounds (a shorter batch sends empty chunks).
+int adopt_sizes(phip_group* g, Member& mb, u32 si, bool first, u64* K) {
+  const u32 W = g->world;
+  u64* hs = mb.sz[si].host;
+  if (g->shared) {
+    if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
+    for (u32 p = 0; p < W; ++p) {
+      const u64* ps = g->m[p].sz[si].host;
+      hs[3 * W + p] = ps[mb.rank];
+      hs[4 * W + p] = ps[W + mb.rank];
+      hs[5 * W + p] = g->m[p].k_local;
+    }
+  }
+  if (first) {
+    for (u32 p = 0; p < W; ++p) *K = std::max<u64>(*K, hs[5 * W + p]);
+    *K = std::max<u64>(*K, 1);
+  }
+  return PHIP_OK;
+}
+
+// What one round sends and receives; a receive side past 2^32 is refused.
+struct Totals {
+  u64 c_send = 0, c_recv = 0, b_recv = 0;
+};
+int round_totals(Member& mb, const std::vector<Seg>& plan, const char* round, const char* items,
+                 Totals* t) {
+  *t = Totals{};
+  for (const Seg& s : plan) {
+    t->c_send += s.sc;
+    t->c_recv += s.rc;
+    t->b_recv += s.rbytes;
+  }
+  if (t->c_recv > 0xFFFFFFFFull || t->b_recv > 0xFFFFFFFFull)
+    return fail(mb, PHIP_ERR_INVALID, "routed %s of %llu %s / %llu name bytes exceeds 2^32", round,
+                (unsigned long long)t->c_recv, items, (unsigned long long)t->b_recv);
+  return PHIP_OK;
+}
+
+// name_offs at the chunk boundaries: out[k] = offs[min(k * chunk, n)].
+__global__ void k_chunk_bounds(const uint32_t* __restrict__ offs, u32 n, u64 chunk, u64 kc,
+                               u32* __restrict__ out) {
+  const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k <= kc) out[k] = offs[k * chunk < n ? k * chunk : n];
+}
+
+// A batch of n entries in rounds of `chunk`: the member's round count, where
+// the split sizes carry it to the peers, and the name offsets at the round
+// boundaries ((*bnd)[k + 1] - (*bnd)[k]: the name bytes of round k), read
+// back on stream st, which it synchronises.
+int chunk_bounds(phip_group* g, Member& mb, hipStream_t st, const u32* offs, u32 n, u64 chunk,
+                 std::vector<u32>* bnd) {
+  const u64 kc = ((u64)n + chunk - 1) / chunk;
+  mb.k_local = kc;
+  for (u32 p = 0; p < g->world; ++p) mb.host_k[p] = kc;
+  bnd->assign(kc + 1, 0);
+  if (n == 0) return PHIP_OK;
+  GHIP(mb, mb.bounds.ensure((kc + 1) * 4));
+  k_chunk_bounds<<<(unsigned)((kc + 1 + 255) / 256), 256, 0, st>>>(offs, n, chunk, kc,
+                                                                   (u32*)mb.bounds.p);
+  GHIP(mb, hipGetLastError());
+  GHIP(mb, hipMemcpyAsync(bnd->data(), mb.bounds.p, (kc + 1) * 4, hipMemcpyDeviceToHost, st));
+  GHIP(mb, hipStreamSynchronize(st));
+  return PHIP_OK;
+}
+
+// Name offsets of n received entries from their lengths: offs[0] = 0 and an
+// inclusive scan into offs[1..n], on stream st.
+int offsets_from_lens(Member& mb, const u32* lens, u64 n, u32* offs, hipStream_t st) {
+  GHIP(mb, hipMemsetAsync(offs, 0, sizeof(u32), st));
+  size_t tb = 0;
+  GHIP(mb, rocprim::inclusive_scan(nullptr, tb, lens, offs + 1, (size_t)n, rocprim::plus<u32>(), st));
+  GHIP(mb, mb.scan_tmp.ensure(tb));
+  GHIP(mb, rocprim::inclusive_scan(mb.scan_tmp.p, tb, lens, offs + 1, (size_t)n,
+                                   rocprim::plus<u32>(), st));
+  return PHIP_OK;
+}
+
 // The owner's merge of one received chunk (lengths, packed names, states):
-// name offsets by an inclusive scan of the lengths, then phip_receive_soa
-// (sources in rank order, each in its order), on the handle's stream behind
-// the chunk's exchange.
-int merge_chunk(Member& mb, RecvSet& rs, hipStream_t st, int64_t now) {
-  if (rs.n) {
-    const u64 n = rs.n;
-    GHIP(mb, hipStreamWaitEvent(st, rs.ev_recv, 0));
+// the names' offsets, then phip_receive_soa (sources in rank order, each in
+// its order), on the handle's stream behind the chunk's exchange.
+int merge_chunk(Member& mb, Lane& ln, hipStream_t st, int64_t now) {
+  if (ln.n) {
+    GHIP(mb, hipStreamWaitEvent(st, ln.ev_recv, 0));
     GHIP(mb, mb.tm.mark(2, st));
-    GHIP(mb, rs.offs.ensure(n * 4 + 8));
-    u32* offs = (u32*)rs.offs.p;
-    const u32* lens = (const u32*)rs.lens.p;
-    GHIP(mb, hipMemsetAsync(offs, 0, sizeof(u32), st));
-    size_t tb = 0;
-    GHIP(mb, rocprim::inclusive_scan(nullptr, tb, lens, offs + 1, (size_t)n, rocprim::plus<u32>(), st));
-    GHIP(mb, mb.scan_tmp.ensure(tb));
-    GHIP(mb, rocprim::inclusive_scan(mb.scan_tmp.p, tb, lens, offs + 1, (size_t)n,
-                                     rocprim::plus<u32>(), st));
+    GHIP(mb, ln.offs.ensure(ln.n * 4 + 8));
+    int rc;
+    if ((rc = offsets_from_lens(mb, ln.recv.at<u32>(C_LENS), ln.n, (u32*)ln.offs.p, st))) return rc;
     phip_msgs rm{};
-    rm.n = (u32)n;
-    rm.names = (const uint8_t*)rs.names.p;
-    rm.name_offs = offs;
-    rm.added = (const u64*)rs.a.p;
-    rm.taken = (const u64*)rs.t.p;
-    rm.elapsed = (const int64_t*)rs.e.p;
+    rm.n = (u32)ln.n;
+    rm.names = ln.recv.at<uint8_t>(C_NAMES);
+    rm.name_offs = (const u32*)ln.offs.p;
+    rm.added = ln.recv.at<u64>(MSG_A);
+    rm.taken = ln.recv.at<u64>(MSG_T);
+    rm.elapsed = ln.recv.at<int64_t>(MSG_E);
     GPHIP(mb, phip_receive_soa(mb.h, &rm, now, nullptr, PHIP_DEVICE_PTRS));
     GHIP(mb, mb.tm.mark(2, st));
   }
-  GHIP(mb, hipEventRecord(rs.ev_merged, st));
-  rs.merge_pending = true;
+  GHIP(mb, hipEventRecord(ln.ev_merged, st));
+  ln.merge_pending = true;
   return PHIP_OK;
 }
 
@@ -364,45 +583,6 @@ phip_msgs chunk_of(const phip_msgs& in, u64 chunk, u64 k) {
     c.elapsed = in.elapsed + lo;
   }
   return c;
-}
-
-// Room in a receive set for n messages and nb name bytes, once the merge
-// of the chunk it held before is done.
-int recv_room(Member& mb, RecvSet& rs, u64 n, u64 nb) {
-  if (rs.merge_pending) GHIP(mb, hipEventSynchronize(rs.ev_merged));
-  rs.merge_pending = false;
-  GHIP(mb, rs.lens.ensure(n * 4 + 4));
-  GHIP(mb, rs.a.ensure(n * 8 + 8));
-  GHIP(mb, rs.t.ensure(n * 8 + 8));
-  GHIP(mb, rs.e.ensure(n * 8 + 8));
-  GHIP(mb, rs.names.ensure(nb + 64));
-  return PHIP_OK;
-}
-
-// One segment from a source's send set (src) into receive set rs, on
-// stream st.
-int copy_seg(Member& mb, const SendSet& src, const Seg& s_, const Seg& d_, RecvSet& rs,
-             hipStream_t st) {
-  if (!d_.rc) return PHIP_OK;
-  GHIP(mb, hipMemcpyAsync((u32*)rs.lens.p + d_.ro, (const u32*)src.lens.p + s_.so, d_.rc * 4,
-                          hipMemcpyDeviceToDevice, st));
-  if (d_.rbytes)
-    GHIP(mb, hipMemcpyAsync((uint8_t*)rs.names.p + d_.rb, (const uint8_t*)src.names.p + s_.sb,
-                            d_.rbytes, hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((u64*)rs.a.p + d_.ro, (const u64*)src.a.p + s_.so, d_.rc * 8,
-                          hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((u64*)rs.t.p + d_.ro, (const u64*)src.t.p + s_.so, d_.rc * 8,
-                          hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((int64_t*)rs.e.p + d_.ro, (const int64_t*)src.e.p + s_.so, d_.rc * 8,
-                          hipMemcpyDeviceToDevice, st));
-  return PHIP_OK;
-}
-
-// name_offs at the chunk boundaries: out[k] = offs[min(k * chunk, n)].
-__global__ void k_chunk_bounds(const uint32_t* __restrict__ offs, u32 n, u64 chunk, u64 kc,
-                               u32* __restrict__ out) {
-  const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k <= kc) out[k] = offs[k * chunk < n ? k * chunk : n];
 }
 
 int member_receive(phip_group* g, Member& mb, const phip_msgs& in, int64_t now, uint64_t* sent,
@@ -435,165 +615,95 @@ int member_receive(phip_group* g, Member& mb, const phip_msgs& in, int64_t now, 
   GHIP(mb, hipStreamWaitEvent(mb.sx, mb.ev_done, 0));
   // (PHIP_GROUP_SMALL_CHUNKS, testing: many rounds on small batches)
   const u64 chunk = (flags & PHIP_GROUP_SMALL_CHUNKS) ? kSmallChunk : kChunk;
-  const u64 k_local = ((u64)n + chunk - 1) / chunk;
-  mb.k_local = k_local;
-  for (u32 p = 0; p < W; ++p) mb.host_k[p] = k_local;
   const u64 cmax = std::max<u64>(1, std::min<u64>(n, chunk));
-  // name bytes per chunk: the offsets at the chunk boundaries
+  int rc;
+  // name bytes per chunk and lane: the offsets at the chunk boundaries
+  std::vector<u32> bnd;
+  if ((rc = chunk_bounds(g, mb, st, in.name_offs, n, chunk, &bnd))) return rc;
+  const u64 k_local = mb.k_local;
   u64 set_bytes[2] = {0, 0};
-  if (n) {
-    std::vector<u32> bnd(k_local + 1);
-    GHIP(mb, mb.bounds.ensure((k_local + 1) * 4));
-    k_chunk_bounds<<<(unsigned)((k_local + 1 + 255) / 256), 256, 0, st>>>(
-        in.name_offs, n, chunk, k_local, (u32*)mb.bounds.p);
-    GHIP(mb, hipGetLastError());
-    GHIP(mb, hipMemcpyAsync(bnd.data(), mb.bounds.p, (k_local + 1) * 4, hipMemcpyDeviceToHost, st));
-    GHIP(mb, hipStreamSynchronize(st));
-    for (u64 k = 0; k < k_local; ++k)
-      set_bytes[k & 1] = std::max<u64>(set_bytes[k & 1], (u64)(bnd[k + 1] - bnd[k]));
-  }
+  for (u64 k = 0; k < k_local; ++k)
+    set_bytes[k & 1] = std::max<u64>(set_bytes[k & 1], (u64)(bnd[k + 1] - bnd[k]));
   for (u32 si = 0; si < 2; ++si) {
-    SendSet& ss = mb.set[si];
-    GHIP(mb, ss.names.ensure(set_bytes[si] + 64));
-    GHIP(mb, ss.lens.ensure(cmax * 4 + 4));
-    GHIP(mb, ss.a.ensure(cmax * 8 + 8));
-    GHIP(mb, ss.t.ensure(cmax * 8 + 8));
-    GHIP(mb, ss.e.ensure(cmax * 8 + 8));
-    GHIP(mb, ss.sizes.ensure((size_t)6 * W * 8));
-    ss.x_pending = false;
+    GHIP(mb, mb.lane[si].send.ensure(cmax, set_bytes[si]));
+    GHIP(mb, mb.sz[si].dev.ensure((size_t)6 * W * 8));
+    mb.lane[si].x_pending = false;
   }
   // 1. the combine's directory, from a sample of the whole batch
   const void* dir = nullptr;
   if ((flags & PHIP_ROUTE_COMBINE) && n &&
       phip_host::route_dir(mb.h, mb.sp, &in, W, &dir) != PHIP_OK)
     return fail(mb, PHIP_ERR_HIP, "route directory: %s", phip_host::last_error(mb.h));
-  // 2. pack chunk k into set k & 1 (pack stream), once no exchange reads it
+  // 2. pack chunk k into lane k & 1 (pack stream), once no exchange reads it
   auto pack = [&](u64 k) -> int {
-    SendSet& ss = mb.set[k & 1];
-    if (ss.x_pending) GHIP(mb, hipStreamWaitEvent(mb.sp, ss.ev_x, 0));
+    Lane& ln = mb.lane[k & 1];
+    const ColSet& ss = ln.send;
+    if (ln.x_pending) GHIP(mb, hipStreamWaitEvent(mb.sp, ln.ev_x, 0));
     const phip_msgs c = chunk_of(in, chunk, k);
-    u64* sz = (u64*)ss.sizes.p;
+    u64* sz = (u64*)mb.sz[k & 1].dev.p;
     GHIP(mb, mb.tm.mark(0, mb.sp));
-    if (phip_host::route_pack(mb.h, mb.sp, &c, W, dir, (uint8_t*)ss.names.p, (uint32_t*)ss.lens.p,
-                              (uint64_t*)ss.a.p, (uint64_t*)ss.t.p, (int64_t*)ss.e.p, sz, sz + W) !=
-        PHIP_OK)
+    if (phip_host::route_pack(mb.h, mb.sp, &c, W, dir, ss.at<uint8_t>(C_NAMES), ss.at<uint32_t>(C_LENS),
+                              ss.at<uint64_t>(MSG_A), ss.at<uint64_t>(MSG_T), ss.at<int64_t>(MSG_E), sz,
+                              sz + W) != PHIP_OK)
       return fail(mb, PHIP_ERR_HIP, "route pack: %s", phip_host::last_error(mb.h));
     GHIP(mb, hipMemcpyAsync(sz + 2 * W, mb.host_k, W * 8, hipMemcpyHostToDevice, mb.sp));
     GHIP(mb, mb.tm.mark(0, mb.sp));
-    GHIP(mb, hipEventRecord(ss.ev_pack, mb.sp));
+    GHIP(mb, hipEventRecord(ln.ev_pack, mb.sp));
     return PHIP_OK;
   };
-  // 3. chunk k's split sizes: every member learns what each source sends it
-  //    (RCCL; shared-device groups read each other's after a barrier)
+  // 3. chunk k's split sizes, behind its pack (exchange stream)
   auto sizes = [&](u64 k) -> int {
-    SendSet& ss = mb.set[k & 1];
-    u64* sz = (u64*)ss.sizes.p;
-    GHIP(mb, hipStreamWaitEvent(mb.sx, ss.ev_pack, 0));
-    GHIP(mb, mb.tm.mark(1, mb.sx));
-    if (!g->shared) {
-      GNCCL(mb, ncclGroupStart());
-      GNCCL(mb, ncclAllToAll(sz, sz + 3 * W, 1, ncclUint64, mb.comm, mb.sx));
-      GNCCL(mb, ncclAllToAll(sz + W, sz + 4 * W, 1, ncclUint64, mb.comm, mb.sx));
-      GNCCL(mb, ncclAllToAll(sz + 2 * W, sz + 5 * W, 1, ncclUint64, mb.comm, mb.sx));
-      GNCCL(mb, ncclGroupEnd());
-    }
-    GHIP(mb, hipMemcpyAsync(ss.host, sz, 6 * W * sizeof(u64), hipMemcpyDeviceToHost, mb.sx));
-    GHIP(mb, mb.tm.mark(1, mb.sx));
-    GHIP(mb, hipEventRecord(ss.ev_sz, mb.sx));
+    Lane& ln = mb.lane[k & 1];
+    GHIP(mb, hipStreamWaitEvent(mb.sx, ln.ev_pack, 0));
+    if (int r = exchange_sizes(g, mb, mb.sz[k & 1], mb.sx)) return r;
+    GHIP(mb, hipEventRecord(ln.ev_sz, mb.sx));
     return PHIP_OK;
   };
-  int rc;
   if ((rc = pack(0)) || (rc = sizes(0))) return rc;
   if (k_local > 1 && (rc = pack(1))) return rc;
   u64 K = 1, n_send = 0, recv_msgs = 0;
   u64 packed = k_local > 1 ? 2 : 1;   // chunks whose pack is queued
   std::vector<Seg> plan;
   for (u64 k = 0; k < K; ++k) {
-    SendSet& ss = mb.set[k & 1];
-    GHIP(mb, hipEventSynchronize(ss.ev_sz));
-    u64* hs = ss.host;
-    if (g->shared) {   // what member p packed for this one, after every member packed chunk k
-      if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
-      for (u32 p = 0; p < W; ++p) {
-        const SendSet& ps = g->m[p].set[k & 1];
-        hs[3 * W + p] = ps.host[mb.rank];
-        hs[4 * W + p] = ps.host[W + mb.rank];
-        hs[5 * W + p] = g->m[p].k_local;
-      }
-    }
-    if (k == 0) {   // every member runs max(K) rounds (a shorter batch sends empty chunks)
-      for (u32 p = 0; p < W; ++p) K = std::max<u64>(K, hs[5 * W + p]);
-      K = std::max<u64>(K, 1);
-    }
-    segment_plan(hs, W, &plan);
-    u64 c_send = 0, c_recv = 0, b_recv = 0;
-    for (u32 p = 0; p < W; ++p) {
-      c_send += plan[p].sc;
-      c_recv += plan[p].rc;
-      b_recv += plan[p].rbytes;
-    }
-    if (c_recv > 0xFFFFFFFFull || b_recv > 0xFFFFFFFFull)
-      return fail(mb, PHIP_ERR_INVALID, "routed chunk of %llu messages / %llu name bytes exceeds 2^32",
-                  (unsigned long long)c_recv, (unsigned long long)b_recv);
-    RecvSet& rs = mb.rset[k & 1];
-    if ((rc = recv_room(mb, rs, c_recv, b_recv))) return rc;
-    // 4. the segments: one send and one receive per peer and column; this
-    //    member's own segment is a device copy unless rccl_self
+    const u32 si = k & 1;
+    Lane& ln = mb.lane[si];
+    GHIP(mb, hipEventSynchronize(ln.ev_sz));
+    if ((rc = adopt_sizes(g, mb, si, k == 0, &K))) return rc;
+    segment_plan(mb.sz[si].host, W, &plan);
+    Totals t;
+    if ((rc = round_totals(mb, plan, "chunk", "messages", &t))) return rc;
+    // room in the lane's receive set, once the merge of the chunk it held
+    // before is done
+    if (ln.merge_pending) GHIP(mb, hipEventSynchronize(ln.ev_merged));
+    ln.merge_pending = false;
+    GHIP(mb, ln.recv.ensure(t.c_recv, t.b_recv));
+    // 4. the segments
     GHIP(mb, mb.tm.mark(1, mb.sx));
-    if (g->shared) {
-      for (u32 p = 0; p < W; ++p) {
-        const Member& src = g->m[p];
-        const Seg s_ = send_seg(src.set[k & 1].host, W, mb.rank);   // the source's send side
-        if (s_.sc != plan[p].rc || s_.sbytes != plan[p].rbytes)
-          return fail(mb, PHIP_ERR_INVALID, "internal: member %u sends %llu/%llu, %u expects %llu/%llu",
-                      p, (unsigned long long)s_.sc, (unsigned long long)s_.sbytes, mb.rank,
-                      (unsigned long long)plan[p].rc, (unsigned long long)plan[p].rbytes);
-        if ((rc = copy_seg(mb, src.set[k & 1], s_, plan[p], rs, mb.sx))) return rc;
-      }
-    } else {
-      const Seg& own = plan[mb.rank];
-      if (own.sc != own.rc || own.sbytes != own.rbytes)
-        return fail(mb, PHIP_ERR_INVALID, "internal: own segment %llu/%llu vs %llu/%llu",
-                    (unsigned long long)own.sc, (unsigned long long)own.sbytes,
-                    (unsigned long long)own.rc, (unsigned long long)own.rbytes);
-      if (!rccl_self && (rc = copy_seg(mb, ss, own, own, rs, mb.sx))) return rc;
-      GNCCL(mb, ncclGroupStart());
-      for (u32 p = 0; p < W; ++p) {
-        if (p == mb.rank && !rccl_self) continue;
-        const Seg& x = plan[p];
-        GNCCL(mb, ncclSend((u32*)ss.lens.p + x.so, x.sc, ncclUint32, p, mb.comm, mb.sx));
-        GNCCL(mb, ncclRecv((u32*)rs.lens.p + x.ro, x.rc, ncclUint32, p, mb.comm, mb.sx));
-        GNCCL(mb, ncclSend((uint8_t*)ss.names.p + x.sb, x.sbytes, ncclUint8, p, mb.comm, mb.sx));
-        GNCCL(mb, ncclRecv((uint8_t*)rs.names.p + x.rb, x.rbytes, ncclUint8, p, mb.comm, mb.sx));
-        GNCCL(mb, ncclSend((u64*)ss.a.p + x.so, x.sc, ncclUint64, p, mb.comm, mb.sx));
-        GNCCL(mb, ncclRecv((u64*)rs.a.p + x.ro, x.rc, ncclUint64, p, mb.comm, mb.sx));
-        GNCCL(mb, ncclSend((u64*)ss.t.p + x.so, x.sc, ncclUint64, p, mb.comm, mb.sx));
-        GNCCL(mb, ncclRecv((u64*)rs.t.p + x.ro, x.rc, ncclUint64, p, mb.comm, mb.sx));
-        GNCCL(mb, ncclSend((u64*)ss.e.p + x.so, x.sc, ncclUint64, p, mb.comm, mb.sx));
-        GNCCL(mb, ncclRecv((int64_t*)rs.e.p + x.ro, x.rc, ncclUint64, p, mb.comm, mb.sx));
-      }
-      GNCCL(mb, ncclGroupEnd());
-    }
+    if ((rc = move_segments(g, mb, plan, ln.send, ln.recv, mb.sx, rccl_self,
+                            peers_of(g, mb, si, 0, [&](const Member& m) -> const ColSet& {
+                              return m.lane[si].send;
+                            }))))
+      return rc;
     GHIP(mb, mb.tm.mark(1, mb.sx));
-    GHIP(mb, hipEventRecord(ss.ev_x, mb.sx));
-    GHIP(mb, hipEventRecord(rs.ev_recv, mb.sx));
-    ss.x_pending = true;
-    rs.n = c_recv;
-    n_send += c_send;
-    recv_msgs += c_recv;
+    GHIP(mb, hipEventRecord(ln.ev_x, mb.sx));
+    GHIP(mb, hipEventRecord(ln.ev_recv, mb.sx));
+    ln.x_pending = true;
+    ln.n = t.c_recv;
+    n_send += t.c_send;
+    recv_msgs += t.c_recv;
     // 6. the owner's merge of chunk k-1 beside chunk k's exchange (chunk
     //    order: the merges queue on the handle's stream; a shared-device
     //    member merges before it waits for its copies)
     const bool merge_prev = k >= 1;
     if (g->shared) {
-      if (merge_prev && (rc = merge_chunk(mb, mb.rset[(k - 1) & 1], st, now))) return rc;
-      // every member has copied chunk k out of every set k & 1 before any
+      if (merge_prev && (rc = merge_chunk(mb, mb.lane[(k - 1) & 1], st, now))) return rc;
+      // every member has copied chunk k out of every lane k & 1 before any
       // packs chunk k + 2 into it
-      GHIP(mb, hipEventSynchronize(ss.ev_x));
+      GHIP(mb, hipEventSynchronize(ln.ev_x));
       if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
     }
     // 5. next: chunk k+1's sizes behind chunk k's exchange (RCCL keeps one
-    //    order per communicator), chunk k+2's pack into the set just sent
+    //    order per communicator), chunk k+2's pack into the lane just sent
     if (k + 1 < K) {
       if (packed < k + 2) {   // a chunk past this member's batch: an empty pack
         if ((rc = pack(k + 1))) return rc;
@@ -605,14 +715,14 @@ int member_receive(phip_group* g, Member& mb, const phip_msgs& in, int64_t now, 
         packed = k + 3;
       }
     }
-    if (!g->shared && merge_prev && (rc = merge_chunk(mb, mb.rset[(k - 1) & 1], st, now)))
+    if (!g->shared && merge_prev && (rc = merge_chunk(mb, mb.lane[(k - 1) & 1], st, now)))
       return rc;
   }
   if (sent) *sent = n_send;
   if (merged) *merged = recv_msgs;
   // the last chunk's merge; the handle's stream ends behind every exchange
   // (the next call's packs reuse the send sets)
-  if ((rc = merge_chunk(mb, mb.rset[(K - 1) & 1], st, now))) return rc;
+  if ((rc = merge_chunk(mb, mb.lane[(K - 1) & 1], st, now))) return rc;
   GHIP(mb, hipEventRecord(mb.ev_done, mb.sx));
   GHIP(mb, hipStreamWaitEvent(st, mb.ev_done, 0));
   return PHIP_OK;
@@ -646,45 +756,6 @@ phip_results results_from(const phip_results& r, u64 lo) {
   return c;
 }
 
-// One segment of ops from a source's packed round (src) into the owner's
-// receive buffers, on stream st.
-int copy_ops_seg(Member& mb, const OpsSend& src, const Seg& s_, const Seg& d_, OpsRecv& rs,
-                 hipStream_t st) {
-  if (!d_.rc) return PHIP_OK;
-  GHIP(mb, hipMemcpyAsync((u32*)rs.lens.p + d_.ro, (const u32*)src.lens.p + s_.so, d_.rc * 4,
-                          hipMemcpyDeviceToDevice, st));
-  if (d_.rbytes)
-    GHIP(mb, hipMemcpyAsync((uint8_t*)rs.names.p + d_.rb, (const uint8_t*)src.names.p + s_.sb,
-                            d_.rbytes, hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((uint8_t*)rs.kind.p + d_.ro, (const uint8_t*)src.kind.p + s_.so, d_.rc,
-                          hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((int64_t*)rs.now.p + d_.ro, (const int64_t*)src.now.p + s_.so, d_.rc * 8,
-                          hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((u64*)rs.x0.p + d_.ro, (const u64*)src.x0.p + s_.so, d_.rc * 8,
-                          hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((u64*)rs.x1.p + d_.ro, (const u64*)src.x1.p + s_.so, d_.rc * 8,
-                          hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((u64*)rs.x2.p + d_.ro, (const u64*)src.x2.p + s_.so, d_.rc * 8,
-                          hipMemcpyDeviceToDevice, st));
-  return PHIP_OK;
-}
-
-// The results of `cnt` ops at `from` of an owner's result buffers (own) into
-// a source's returned columns at `to`, on stream st.
-int copy_results_seg(Member& mb, const OpsRecv& own, u64 from, OpsSend& ss, u64 to, u64 cnt,
-                     hipStream_t st) {
-  if (!cnt) return PHIP_OK;
-  GHIP(mb, hipMemcpyAsync((uint8_t*)ss.r_status.p + to, (const uint8_t*)own.status.p + from, cnt,
-                          hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((u64*)ss.r_rem.p + to, (const u64*)own.rem.p + from, cnt * 8,
-                          hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((u64*)ss.r_have.p + to, (const u64*)own.have.p + from, cnt * 8,
-                          hipMemcpyDeviceToDevice, st));
-  GHIP(mb, hipMemcpyAsync((phip_state*)ss.r_reply.p + to, (const phip_state*)own.reply.p + from,
-                          cnt * sizeof(phip_state), hipMemcpyDeviceToDevice, st));
-  return PHIP_OK;
-}
-
 // Owner-routed phip_apply_mixed of one member (the order rule: patrolhip.h).
 // The rounds run one after another on the handle's stream: pack, split
 // sizes, the ops to their owners, the owner's phip_apply_mixed, the results
@@ -709,223 +780,116 @@ int member_apply_mixed(phip_group* g, Member& mb, const phip_ops& in, const phip
     return PHIP_OK;
   }
   const u64 chunk = (flags & PHIP_GROUP_SMALL_CHUNKS) ? kSmallChunk : kChunk;
-  const u64 k_local = ((u64)n + chunk - 1) / chunk;
-  mb.k_local = k_local;
-  for (u32 p = 0; p < W; ++p) mb.host_k[p] = k_local;
   const u64 cmax = std::max<u64>(1, std::min<u64>(n, chunk));
-  // name bytes of the largest round: the offsets at the chunk boundaries
-  u64 max_bytes = 0;
-  if (n) {
-    std::vector<u32> bnd(k_local + 1);
-    GHIP(mb, mb.bounds.ensure((k_local + 1) * 4));
-    k_chunk_bounds<<<(unsigned)((k_local + 1 + 255) / 256), 256, 0, st>>>(
-        in.name_offs, n, chunk, k_local, (u32*)mb.bounds.p);
-    GHIP(mb, hipGetLastError());
-    GHIP(mb, hipMemcpyAsync(bnd.data(), mb.bounds.p, (k_local + 1) * 4, hipMemcpyDeviceToHost, st));
-    GHIP(mb, hipStreamSynchronize(st));
-    for (u64 k = 0; k < k_local; ++k) max_bytes = std::max<u64>(max_bytes, (u64)(bnd[k + 1] - bnd[k]));
-  }
-  OpsSend& ss = mb.osend;
-  OpsRecv& rs = mb.orecv;
-  if (!ss.host) GHIP(mb, hipHostMalloc(&ss.host, 6 * (size_t)W * sizeof(u64), 0));
-  GHIP(mb, ss.names.ensure(max_bytes + 64));
-  GHIP(mb, ss.lens.ensure(cmax * 4 + 4));
-  GHIP(mb, ss.kind.ensure(cmax + 8));
-  for (Buf* b : {&ss.now, &ss.x0, &ss.x1, &ss.x2, &ss.r_rem, &ss.r_have}) GHIP(mb, b->ensure(cmax * 8 + 8));
-  GHIP(mb, ss.src.ensure(cmax * 4 + 4));
-  GHIP(mb, ss.r_status.ensure(cmax + 8));
-  GHIP(mb, ss.r_reply.ensure(cmax * sizeof(phip_state)));
-  GHIP(mb, ss.sizes.ensure((size_t)6 * W * 8));
-  u64* sz = (u64*)ss.sizes.p;
-  u64* hs = ss.host;
-  u64 K = 1, n_send = 0, n_recv = 0;
-  std::vector<Seg> plan;
   int rc;
+  // name bytes of the largest round: the offsets at the chunk boundaries
+  std::vector<u32> bnd;
+  if ((rc = chunk_bounds(g, mb, st, in.name_offs, n, chunk, &bnd))) return rc;
+  u64 max_bytes = 0;
+  for (u64 k = 0; k < mb.k_local; ++k) max_bytes = std::max<u64>(max_bytes, (u64)(bnd[k + 1] - bnd[k]));
+  Sizes& zs = mb.sz[kOpsSizes];
+  const ColSet& ss = mb.osend;
+  ColSet& rs = mb.orecv;
+  GHIP(mb, mb.osend.ensure(cmax, max_bytes));
+  GHIP(mb, mb.osrc.ensure(cmax * 4 + 4));
+  GHIP(mb, mb.oback.ensure(cmax, 0));
+  GHIP(mb, zs.dev.ensure((size_t)6 * W * 8));
+  u64* sz = (u64*)zs.dev.p;
+  u64 K = 1, n_send = 0, n_recv = 0;
+  std::vector<Seg> plan, back(W);
   for (u64 k = 0; k < K; ++k) {
     // 1. the pack of round k
     const phip_ops c = ops_chunk_of(in, chunk, k);
     GHIP(mb, mb.tm.mark(0, st));
-    if (phip_host::route_pack_ops(mb.h, st, &c, W, (uint8_t*)ss.names.p, (uint32_t*)ss.lens.p,
-                                  (uint8_t*)ss.kind.p, (int64_t*)ss.now.p, (uint64_t*)ss.x0.p,
-                                  (uint64_t*)ss.x1.p, (uint64_t*)ss.x2.p, (uint32_t*)ss.src.p, sz,
-                                  sz + W) != PHIP_OK)
+    if (phip_host::route_pack_ops(mb.h, st, &c, W, ss.at<uint8_t>(C_NAMES), ss.at<uint32_t>(C_LENS),
+                                  ss.at<uint8_t>(O_KIND), ss.at<int64_t>(O_NOW), ss.at<uint64_t>(O_X0),
+                                  ss.at<uint64_t>(O_X1), ss.at<uint64_t>(O_X2), (uint32_t*)mb.osrc.p,
+                                  sz, sz + W) != PHIP_OK)
       return fail(mb, PHIP_ERR_HIP, "route pack ops: %s", phip_host::last_error(mb.h));
     GHIP(mb, hipMemcpyAsync(sz + 2 * W, mb.host_k, W * 8, hipMemcpyHostToDevice, st));
     GHIP(mb, mb.tm.mark(0, st));
-    // 2. the split sizes: every member learns what each source sends it
-    //    (RCCL; shared-device groups read each other's after a barrier)
-    GHIP(mb, mb.tm.mark(1, st));
-    if (!g->shared) {
-      GNCCL(mb, ncclGroupStart());
-      GNCCL(mb, ncclAllToAll(sz, sz + 3 * W, 1, ncclUint64, mb.comm, st));
-      GNCCL(mb, ncclAllToAll(sz + W, sz + 4 * W, 1, ncclUint64, mb.comm, st));
-      GNCCL(mb, ncclAllToAll(sz + 2 * W, sz + 5 * W, 1, ncclUint64, mb.comm, st));
-      GNCCL(mb, ncclGroupEnd());
-    }
-    GHIP(mb, hipMemcpyAsync(hs, sz, 6 * W * sizeof(u64), hipMemcpyDeviceToHost, st));
-    GHIP(mb, mb.tm.mark(1, st));
+    // 2. the split sizes
+    if ((rc = exchange_sizes(g, mb, zs, st))) return rc;
     GHIP(mb, hipStreamSynchronize(st));
-    if (g->shared) {   // what member p packed for this one, after every member packed round k
-      if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
-      for (u32 p = 0; p < W; ++p) {
-        const OpsSend& ps = g->m[p].osend;
-        hs[3 * W + p] = ps.host[mb.rank];
-        hs[4 * W + p] = ps.host[W + mb.rank];
-        hs[5 * W + p] = g->m[p].k_local;
-      }
-    }
-    if (k == 0) {   // every member runs max(K) rounds (a shorter batch sends empty rounds)
-      for (u32 p = 0; p < W; ++p) K = std::max<u64>(K, hs[5 * W + p]);
-      K = std::max<u64>(K, 1);
-    }
-    segment_plan(hs, W, &plan);
-    u64 c_send = 0, c_recv = 0, b_recv = 0;
-    for (u32 p = 0; p < W; ++p) {
-      c_send += plan[p].sc;
-      c_recv += plan[p].rc;
-      b_recv += plan[p].rbytes;
-    }
-    if (c_send != c.n)
-      return fail(mb, PHIP_ERR_INVALID, "internal: packed %llu of %u ops", (unsigned long long)c_send,
+    if ((rc = adopt_sizes(g, mb, kOpsSizes, k == 0, &K))) return rc;
+    segment_plan(zs.host, W, &plan);
+    Totals t;
+    if ((rc = round_totals(mb, plan, "round", "ops", &t))) return rc;
+    if (t.c_send != c.n)
+      return fail(mb, PHIP_ERR_INVALID, "internal: packed %llu of %u ops", (unsigned long long)t.c_send,
                   c.n);
-    if (c_recv > 0xFFFFFFFFull || b_recv > 0xFFFFFFFFull)
-      return fail(mb, PHIP_ERR_INVALID, "routed round of %llu ops / %llu name bytes exceeds 2^32",
-                  (unsigned long long)c_recv, (unsigned long long)b_recv);
-    GHIP(mb, rs.names.ensure(b_recv + 64));
-    GHIP(mb, rs.lens.ensure(c_recv * 4 + 4));
-    GHIP(mb, rs.offs.ensure(c_recv * 4 + 8));
-    GHIP(mb, rs.kind.ensure(c_recv + 8));
-    GHIP(mb, rs.status.ensure(c_recv + 8));
-    for (Buf* b : {&rs.now, &rs.x0, &rs.x1, &rs.x2, &rs.rem, &rs.have}) GHIP(mb, b->ensure(c_recv * 8 + 8));
-    GHIP(mb, rs.reply.ensure(std::max<u64>(c_recv, 1) * sizeof(phip_state)));
-    // 3. the ops to their owners: one send and one receive per peer and
-    //    column; this member's own segment is a device copy unless rccl_self
+    GHIP(mb, rs.ensure(t.c_recv, t.b_recv));
+    GHIP(mb, mb.ooffs.ensure(t.c_recv * 4 + 8));
+    GHIP(mb, mb.ores.ensure(t.c_recv, 0));
+    // 3. the ops to their owners
     GHIP(mb, mb.tm.mark(1, st));
-    if (g->shared) {
-      for (u32 p = 0; p < W; ++p) {
-        const Member& src = g->m[p];
-        const Seg s_ = send_seg(src.osend.host, W, mb.rank);   // the source's send side
-        if (s_.sc != plan[p].rc || s_.sbytes != plan[p].rbytes)
-          return fail(mb, PHIP_ERR_INVALID, "internal: member %u sends %llu/%llu, %u expects %llu/%llu",
-                      p, (unsigned long long)s_.sc, (unsigned long long)s_.sbytes, mb.rank,
-                      (unsigned long long)plan[p].rc, (unsigned long long)plan[p].rbytes);
-        if ((rc = copy_ops_seg(mb, src.osend, s_, plan[p], rs, st))) return rc;
-      }
-    } else {
-      const Seg& own = plan[mb.rank];
-      if (own.sc != own.rc || own.sbytes != own.rbytes)
-        return fail(mb, PHIP_ERR_INVALID, "internal: own segment %llu/%llu vs %llu/%llu",
-                    (unsigned long long)own.sc, (unsigned long long)own.sbytes,
-                    (unsigned long long)own.rc, (unsigned long long)own.rbytes);
-      if (!rccl_self && (rc = copy_ops_seg(mb, ss, own, own, rs, st))) return rc;
-      GNCCL(mb, ncclGroupStart());
-      for (u32 p = 0; p < W; ++p) {
-        if (p == mb.rank && !rccl_self) continue;
-        const Seg& x = plan[p];
-        GNCCL(mb, ncclSend((u32*)ss.lens.p + x.so, x.sc, ncclUint32, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((u32*)rs.lens.p + x.ro, x.rc, ncclUint32, p, mb.comm, st));
-        GNCCL(mb, ncclSend((uint8_t*)ss.names.p + x.sb, x.sbytes, ncclUint8, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((uint8_t*)rs.names.p + x.rb, x.rbytes, ncclUint8, p, mb.comm, st));
-        GNCCL(mb, ncclSend((uint8_t*)ss.kind.p + x.so, x.sc, ncclUint8, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((uint8_t*)rs.kind.p + x.ro, x.rc, ncclUint8, p, mb.comm, st));
-        GNCCL(mb, ncclSend((int64_t*)ss.now.p + x.so, x.sc, ncclInt64, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((int64_t*)rs.now.p + x.ro, x.rc, ncclInt64, p, mb.comm, st));
-        GNCCL(mb, ncclSend((u64*)ss.x0.p + x.so, x.sc, ncclUint64, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((u64*)rs.x0.p + x.ro, x.rc, ncclUint64, p, mb.comm, st));
-        GNCCL(mb, ncclSend((u64*)ss.x1.p + x.so, x.sc, ncclUint64, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((u64*)rs.x1.p + x.ro, x.rc, ncclUint64, p, mb.comm, st));
-        GNCCL(mb, ncclSend((u64*)ss.x2.p + x.so, x.sc, ncclUint64, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((u64*)rs.x2.p + x.ro, x.rc, ncclUint64, p, mb.comm, st));
-      }
-      GNCCL(mb, ncclGroupEnd());
-    }
+    if ((rc = move_segments(g, mb, plan, ss, rs, st, rccl_self,
+                            peers_of(g, mb, kOpsSizes, 0, [](const Member& m) -> const ColSet& {
+                              return m.osend;
+                            }))))
+      return rc;
     GHIP(mb, mb.tm.mark(1, st));
-    // 4. the owner's apply: name offsets by an inclusive scan of the lengths,
-    //    then one phip_apply_mixed over the round (sources in rank order,
-    //    each in its order).  The three operand words serve both kinds:
-    //    k_pack_ops reads freq/per/count under TAKE and added/taken/elapsed
-    //    otherwise.
-    if (c_recv) {
+    // 4. the owner's apply: the names' offsets, then one phip_apply_mixed over
+    //    the round (sources in rank order, each in its order).  The three
+    //    operand words serve both kinds: k_pack_ops reads freq/per/count under
+    //    TAKE and added/taken/elapsed otherwise.
+    if (t.c_recv) {
       GHIP(mb, mb.tm.mark(2, st));
-      u32* offs = (u32*)rs.offs.p;
-      const u32* lens = (const u32*)rs.lens.p;
-      GHIP(mb, hipMemsetAsync(offs, 0, sizeof(u32), st));
-      size_t tb = 0;
-      GHIP(mb, rocprim::inclusive_scan(nullptr, tb, lens, offs + 1, (size_t)c_recv,
-                                       rocprim::plus<u32>(), st));
-      GHIP(mb, mb.scan_tmp.ensure(tb));
-      GHIP(mb, rocprim::inclusive_scan(mb.scan_tmp.p, tb, lens, offs + 1, (size_t)c_recv,
-                                       rocprim::plus<u32>(), st));
+      if ((rc = offsets_from_lens(mb, rs.at<u32>(C_LENS), t.c_recv, (u32*)mb.ooffs.p, st))) return rc;
       phip_ops ro{};
-      ro.n = (u32)c_recv;
-      ro.kind = (const uint8_t*)rs.kind.p;
-      ro.names = (const uint8_t*)rs.names.p;
-      ro.name_offs = offs;
-      ro.now = (const int64_t*)rs.now.p;
-      ro.freq = (const int64_t*)rs.x0.p;
-      ro.per = (const int64_t*)rs.x1.p;
-      ro.count = (const uint64_t*)rs.x2.p;
-      ro.added = (const uint64_t*)rs.x0.p;
-      ro.taken = (const uint64_t*)rs.x1.p;
-      ro.elapsed = (const int64_t*)rs.x2.p;
+      ro.n = (u32)t.c_recv;
+      ro.kind = rs.at<uint8_t>(O_KIND);
+      ro.names = rs.at<uint8_t>(C_NAMES);
+      ro.name_offs = (const u32*)mb.ooffs.p;
+      ro.now = rs.at<int64_t>(O_NOW);
+      ro.freq = rs.at<int64_t>(O_X0);
+      ro.per = rs.at<int64_t>(O_X1);
+      ro.count = rs.at<uint64_t>(O_X2);
+      ro.added = rs.at<uint64_t>(O_X0);
+      ro.taken = rs.at<uint64_t>(O_X1);
+      ro.elapsed = rs.at<int64_t>(O_X2);
       phip_results rr{};
-      rr.status = (uint8_t*)rs.status.p;
-      rr.remaining = (uint64_t*)rs.rem.p;
-      rr.have = (uint64_t*)rs.have.p;
-      rr.reply = (phip_state*)rs.reply.p;
+      rr.status = mb.ores.at<uint8_t>(R_STATUS);
+      rr.remaining = mb.ores.at<uint64_t>(R_REM);
+      rr.have = mb.ores.at<uint64_t>(R_HAVE);
+      rr.reply = mb.ores.at<phip_state>(R_REPLY);
       GPHIP(mb, phip_apply_mixed(mb.h, &ro, &rr, PHIP_DEVICE_PTRS));
       GHIP(mb, mb.tm.mark(2, st));
     }
     // 5. the results back to their sources: source p's segment [ro, ro + rc)
     //    of the owner's result buffers lands at [so, so + sc) of p's returned
-    //    columns (the forward plan with its roles swapped)
+    //    columns (the forward plan with its roles swapped).  In a shared-device
+    //    group every owner's results are complete before any source copies
+    //    them, and every source has copied before an owner reuses its buffers.
     if (g->shared) {
-      // every owner's results are complete before any source copies them,
-      // and every source has copied before an owner reuses its buffers
       GHIP(mb, hipStreamSynchronize(st));
       if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
-      GHIP(mb, mb.tm.mark(1, st));
-      for (u32 p = 0; p < W; ++p) {
-        u64 from = 0;   // where this member's segment lies at owner p: after the lower ranks'
-        for (u32 q = 0; q < mb.rank; ++q) from += g->m[q].osend.host[p];
-        if ((rc = copy_results_seg(mb, g->m[p].orecv, from, ss, plan[p].so, plan[p].sc, st))) return rc;
-      }
-      GHIP(mb, mb.tm.mark(1, st));
+    }
+    for (u32 p = 0; p < W; ++p) back[p] = swapped(plan[p]);
+    GHIP(mb, mb.tm.mark(1, st));
+    if ((rc = move_segments(g, mb, back, mb.ores, mb.oback, st, rccl_self,
+                            peers_of(g, mb, kOpsSizes, 3 * W, [](const Member& m) -> const ColSet& {
+                              return m.ores;
+                            }))))
+      return rc;
+    GHIP(mb, mb.tm.mark(1, st));
+    if (g->shared) {
       GHIP(mb, hipStreamSynchronize(st));
       if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
-    } else {
-      GHIP(mb, mb.tm.mark(1, st));
-      const Seg& own = plan[mb.rank];
-      if (!rccl_self && (rc = copy_results_seg(mb, rs, own.ro, ss, own.so, own.sc, st))) return rc;
-      GNCCL(mb, ncclGroupStart());
-      for (u32 p = 0; p < W; ++p) {
-        if (p == mb.rank && !rccl_self) continue;
-        const Seg& x = plan[p];
-        GNCCL(mb, ncclSend((uint8_t*)rs.status.p + x.ro, x.rc, ncclUint8, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((uint8_t*)ss.r_status.p + x.so, x.sc, ncclUint8, p, mb.comm, st));
-        GNCCL(mb, ncclSend((u64*)rs.rem.p + x.ro, x.rc, ncclUint64, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((u64*)ss.r_rem.p + x.so, x.sc, ncclUint64, p, mb.comm, st));
-        GNCCL(mb, ncclSend((u64*)rs.have.p + x.ro, x.rc, ncclUint64, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((u64*)ss.r_have.p + x.so, x.sc, ncclUint64, p, mb.comm, st));
-        GNCCL(mb, ncclSend((u64*)rs.reply.p + 4 * x.ro, 4 * x.rc, ncclUint64, p, mb.comm, st));
-        GNCCL(mb, ncclRecv((u64*)ss.r_reply.p + 4 * x.so, 4 * x.sc, ncclUint64, p, mb.comm, st));
-      }
-      GNCCL(mb, ncclGroupEnd());
-      GHIP(mb, mb.tm.mark(1, st));
     }
     // 6. into the caller's columns, at the ops' places in the batch
     if (c.n) {
       const phip_results out = results_from(res, k * chunk);
       GHIP(mb, mb.tm.mark(2, st));
-      if (phip_host::results_scatter(mb.h, st, (const uint32_t*)ss.src.p, c.n,
-                                     (const uint8_t*)ss.r_status.p, (const uint64_t*)ss.r_rem.p,
-                                     (const uint64_t*)ss.r_have.p, (const phip_state*)ss.r_reply.p,
+      if (phip_host::results_scatter(mb.h, st, (const uint32_t*)mb.osrc.p, c.n,
+                                     mb.oback.at<uint8_t>(R_STATUS), mb.oback.at<uint64_t>(R_REM),
+                                     mb.oback.at<uint64_t>(R_HAVE), mb.oback.at<phip_state>(R_REPLY),
                                      &out) != PHIP_OK)
         return fail(mb, PHIP_ERR_HIP, "results scatter: %s", phip_host::last_error(mb.h));
       GHIP(mb, mb.tm.mark(2, st));
     }
-    n_send += c_send;
-    n_recv += c_recv;
+    n_send += t.c_send;
+    n_recv += t.c_recv;
   }
   if (sent) *sent = n_send;
   if (applied) *applied = n_recv;
@@ -985,28 +949,19 @@ void destroy(phip_group* g) {
     if (mb.sp) (void)hipStreamSynchronize(mb.sp);
     if (mb.sx) (void)hipStreamSynchronize(mb.sx);
     if (mb.comm) (void)ncclCommDestroy(mb.comm);
-    for (SendSet& ss : mb.set) {
-      for (Buf* b : {&ss.names, &ss.lens, &ss.a, &ss.t, &ss.e, &ss.sizes}) b->release();
-      if (ss.host) (void)hipHostFree(ss.host);
-      for (hipEvent_t ev : {ss.ev_pack, ss.ev_sz, ss.ev_x})
+    for (Lane& ln : mb.lane) {
+      ln.send.release();
+      ln.recv.release();
+      ln.offs.release();
+      for (hipEvent_t ev : {ln.ev_pack, ln.ev_sz, ln.ev_x, ln.ev_recv, ln.ev_merged})
         if (ev) (void)hipEventDestroy(ev);
     }
-    for (RecvSet& rs : mb.rset) {
-      for (Buf* b : {&rs.names, &rs.lens, &rs.offs, &rs.a, &rs.t, &rs.e}) b->release();
-      for (hipEvent_t ev : {rs.ev_recv, rs.ev_merged})
-        if (ev) (void)hipEventDestroy(ev);
+    for (ColSet* s : {&mb.osend, &mb.orecv, &mb.ores, &mb.oback}) s->release();
+    for (Sizes& s : mb.sz) {
+      s.dev.release();
+      if (s.host) (void)hipHostFree(s.host);
     }
-    {
-      OpsSend& os = mb.osend;
-      OpsRecv& orv = mb.orecv;
-      for (Buf* b : {&os.names, &os.lens, &os.kind, &os.now, &os.x0, &os.x1, &os.x2, &os.src,
-                     &os.sizes, &os.r_status, &os.r_rem, &os.r_have, &os.r_reply, &orv.names,
-                     &orv.lens, &orv.offs, &orv.kind, &orv.now, &orv.x0, &orv.x1, &orv.x2,
-                     &orv.status, &orv.rem, &orv.have, &orv.reply})
-        b->release();
-      if (os.host) (void)hipHostFree(os.host);
-    }
-    for (Buf* b : {&mb.scan_tmp, &mb.ae, &mb.bounds}) b->release();
+    for (Buf* b : {&mb.osrc, &mb.ooffs, &mb.scan_tmp, &mb.ae, &mb.bounds}) b->release();
     mb.tm.release();
     if (mb.host_k) (void)hipHostFree(mb.host_k);
     if (mb.ev_done) (void)hipEventDestroy(mb.ev_done);
@@ -1017,8 +972,8 @@ void destroy(phip_group* g) {
   delete g;
 }
 
-// Per member: the pipeline's two streams, the send sets' pinned size mirrors
-// and events.
+// Per member: the pipeline's two streams, the pinned mirrors of the split
+// sizes and the lanes' events.
 int alloc_member_state(phip_group* g) {
   for (auto& mb : g->m) {
     if (hipSetDevice(mb.device) != hipSuccess ||
@@ -1027,20 +982,51 @@ int alloc_member_state(phip_group* g) {
         hipEventCreateWithFlags(&mb.ev_done, hipEventDisableTiming) != hipSuccess ||
         hipHostMalloc(&mb.host_k, (size_t)g->world * sizeof(u64), 0) != hipSuccess)
       return PHIP_ERR_HIP;
-    for (SendSet& ss : mb.set)
-      if (hipHostMalloc(&ss.host, 6 * (size_t)g->world * sizeof(u64), 0) != hipSuccess ||
-          hipEventCreateWithFlags(&ss.ev_pack, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&ss.ev_sz, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&ss.ev_x, hipEventDisableTiming) != hipSuccess)
+    for (Sizes& s : mb.sz)
+      if (hipHostMalloc(&s.host, 6 * (size_t)g->world * sizeof(u64), 0) != hipSuccess)
         return PHIP_ERR_HIP;
-    for (RecvSet& rs : mb.rset) {
-      rs.merge_pending = false;
-      if (hipEventCreateWithFlags(&rs.ev_recv, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&rs.ev_merged, hipEventDisableTiming) != hipSuccess)
-        return PHIP_ERR_HIP;
-    }
+    for (Lane& ln : mb.lane)
+      for (hipEvent_t* ev : {&ln.ev_pack, &ln.ev_sz, &ln.ev_x, &ln.ev_recv, &ln.ev_merged})
+        if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) return PHIP_ERR_HIP;
   }
   return PHIP_OK;
+}
+
+// A group call over checked batches (names_len; phip_msgs or phip_ops): every
+// local member's offset column in full before any chunk is packed (the route
+// kernels do not check as they go), behind pre(member, its stream, i).  One
+// malformed entry anywhere and none of this process's batches is applied; the
+// members still run the exchange, with empty batches, so that the peers of a
+// multi-rank group never wait for a rank that left early.  run(i, batch) is
+// the member's call; `what` names an entry in the error text.
+template <class Batch, class Pre, class Run>
+int checked_call(phip_group* g, const Batch* batches, const char* what, Pre pre, Run run) {
+  const size_t nl = g->m.size();
+  std::vector<uint32_t> bad(nl, ~0u);
+  if (int rc = for_members(g, [&](size_t i) {
+        Member& mb = g->m[i];
+        GHIP(mb, hipSetDevice(mb.device));
+        hipStream_t st = (hipStream_t)phip_host::handle_stream(mb.h);
+        if (int r = pre(mb, st, i)) return r;
+        const Batch& b = batches[i];
+        if (phip_host::check_offsets(mb.h, st, b.names, b.name_offs, b.names_len, b.n, &bad[i]) !=
+            PHIP_OK)
+          return fail(mb, PHIP_ERR_HIP, "name offsets check: %s", phip_host::last_error(mb.h));
+        return (int)PHIP_OK;
+      }))
+    return rc;
+  size_t ib = 0;
+  while (ib < nl && bad[ib] == ~0u) ++ib;
+  if (ib < nl) {
+    std::vector<Batch> none(batches, batches + nl);
+    for (Batch& b : none) b.n = 0;
+    const int rc = for_members(g, [&](size_t i) { return run(i, none[i]); });
+    const std::string xerr = rc != PHIP_OK ? "; and the empty exchange failed: " + g->err : "";
+    g->err = "member " + std::to_string(ib) + ": malformed name offsets at " + what + " " +
+             std::to_string(bad[ib]) + " (names_len check): no local batch applied" + xerr;
+    return PHIP_ERR_INVALID;
+  }
+  return for_members(g, [&](size_t i) { return run(i, batches[i]); });
 }
 
 }  // namespace
@@ -1143,40 +1129,12 @@ phip_handle* phip_group_handle(phip_group* g, uint32_t i) {
 int phip_group_receive(phip_group* g, const phip_msgs* batches, int64_t now, uint64_t* sent,
                        uint64_t* merged, uint32_t flags) {
   if (!g || !batches || !(flags & PHIP_DEVICE_PTRS)) return PHIP_ERR_INVALID;
-  // Checked batches (names_len): every local member's offset column in full
-  // before any chunk is packed (the route kernels do not check as they go).
-  // One malformed entry anywhere and none of this process's batches is
-  // applied; the members still run the exchange, with empty batches, so that
-  // the peers of a multi-rank group never wait for a rank that left early.
-  const size_t nl = g->m.size();
-  std::vector<uint32_t> bad(nl, ~0u);
-  if (int rc = for_members(g, [&](size_t i) {
-        Member& mb = g->m[i];
-        GHIP(mb, hipSetDevice(mb.device));
-        if (phip_host::check_offsets(mb.h, phip_host::handle_stream(mb.h), &batches[i], &bad[i]) !=
-            PHIP_OK)
-          return fail(mb, PHIP_ERR_HIP, "name offsets check: %s", phip_host::last_error(mb.h));
-        return (int)PHIP_OK;
-      }))
-    return rc;
-  size_t ib = 0;
-  while (ib < nl && bad[ib] == ~0u) ++ib;
-  if (ib < nl) {
-    std::vector<phip_msgs> none(batches, batches + nl);
-    for (phip_msgs& m : none) m.n = 0;
-    const int rc = for_members(g, [&](size_t i) {
-      return member_receive(g, g->m[i], none[i], now, sent ? sent + i : nullptr,
-                            merged ? merged + i : nullptr, flags);
-    });
-    const std::string xerr = rc != PHIP_OK ? "; and the empty exchange failed: " + g->err : "";
-    g->err = "member " + std::to_string(ib) + ": malformed name offsets at message " +
-             std::to_string(bad[ib]) + " (names_len check): no local batch applied" + xerr;
-    return PHIP_ERR_INVALID;
-  }
-  return for_members(g, [&](size_t i) {
-    return member_receive(g, g->m[i], batches[i], now, sent ? sent + i : nullptr,
-                          merged ? merged + i : nullptr, flags);
-  });
+  return checked_call(
+      g, batches, "message", [](Member&, hipStream_t, size_t) { return (int)PHIP_OK; },
+      [&](size_t i, const phip_msgs& b) {
+        return member_receive(g, g->m[i], b, now, sent ? sent + i : nullptr,
+                              merged ? merged + i : nullptr, flags);
+      });
 }
 
 int phip_group_apply_mixed(phip_group* g, const phip_ops* batches, const phip_results* results,
@@ -1191,43 +1149,18 @@ int phip_group_apply_mixed(phip_group* g, const phip_ops* batches, const phip_re
   std::vector<phip_results> res(nl);   // (a NULL results: no column wanted)
   for (size_t i = 0; i < nl; ++i) res[i] = results ? results[i] : phip_results{};
   // Ops that are not applied report status 0: the status columns are zeroed
-  // first.  Then the checked batches (names_len): every local member's offset
-  // column in full before any round is packed, phip_group_receive's rule.
-  std::vector<uint32_t> bad(nl, ~0u);
-  if (int rc = for_members(g, [&](size_t i) {
-        Member& mb = g->m[i];
-        GHIP(mb, hipSetDevice(mb.device));
-        hipStream_t st = (hipStream_t)phip_host::handle_stream(mb.h);
+  // first, then the batches checked by phip_group_receive's rule.
+  return checked_call(
+      g, batches, "op",
+      [&](Member& mb, hipStream_t st, size_t i) {
         if (res[i].status && batches[i].n)
           GHIP(mb, hipMemsetAsync(res[i].status, 0, batches[i].n, st));
-        phip_msgs view{};
-        view.n = batches[i].n;
-        view.names_len = batches[i].names_len;
-        view.names = batches[i].names;
-        view.name_offs = batches[i].name_offs;
-        if (phip_host::check_offsets(mb.h, st, &view, &bad[i]) != PHIP_OK)
-          return fail(mb, PHIP_ERR_HIP, "name offsets check: %s", phip_host::last_error(mb.h));
         return (int)PHIP_OK;
-      }))
-    return rc;
-  size_t ib = 0;
-  while (ib < nl && bad[ib] == ~0u) ++ib;
-  if (ib < nl) {
-    std::vector<phip_ops> none(batches, batches + nl);
-    for (phip_ops& b : none) b.n = 0;
-    const int rc = for_members(g, [&](size_t i) {
-      return member_apply_mixed(g, g->m[i], none[i], res[i], sent ? sent + i : nullptr,
-                                applied ? applied + i : nullptr, flags);
-    });
-    const std::string xerr = rc != PHIP_OK ? "; and the empty exchange failed: " + g->err : "";
-    g->err = "member " + std::to_string(ib) + ": malformed name offsets at op " +
-             std::to_string(bad[ib]) + " (names_len check): no local batch applied" + xerr;
-    return PHIP_ERR_INVALID;
-  }
-  return for_members(g, [&](size_t i) {
-    return member_apply_mixed(g, g->m[i], batches[i], res[i], sent ? sent + i : nullptr,
-                              applied ? applied + i : nullptr, flags);
-  });
+      },
+      [&](size_t i, const phip_ops& b) {
+        return member_apply_mixed(g, g->m[i], b, res[i], sent ? sent + i : nullptr,
+                                  applied ? applied + i : nullptr, flags);
+      });
 }
 
 int phip_group_set_timing(phip_group* g, int on) {

@@ -38,9 +38,12 @@ int results_scatter(phip_handle* h, void* stream, const uint32_t* src, uint32_t 
 // The route kernels do not check a batch's name offsets as they go.
 // check_offsets: one pass over a checked batch's offset column (names_len !=
 // 0; NamesOffs::bad's rule) on `stream`, which it synchronises: *first_bad is
-// the first malformed message, ~0 when there is none (or names_len == 0).
-// phip_group_receive runs it over every local batch before any pack.
-int check_offsets(phip_handle* h, void* stream, const phip_msgs* m, uint32_t* first_bad);
+// the first malformed entry, ~0 when there is none (or names_len == 0).  It
+// takes the names view of a batch (a phip_msgs' or a phip_ops' names,
+// name_offs, names_len and n): phip_group_receive and phip_group_apply_mixed
+// run it over every local batch before any pack.
+int check_offsets(phip_handle* h, void* stream, const uint8_t* names, const uint32_t* name_offs,
+                  uint32_t names_len, uint32_t n, uint32_t* first_bad);
 const char* last_error(phip_handle* h);
 
 // The request parsing of API.takeBucket (api.go:55-65): the name-length check

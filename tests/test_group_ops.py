@@ -3,8 +3,8 @@ phip_group_apply_mixed) on one GPU, bit-exact against the oracle run over
 all ops in (round, source rank, index) order (tests/_group_ops.py): the
 stable owner partition itself, world 1 in both group forms with and without
 the RCCL self-exchange, shared-device groups of world 2 and 3, the order of
-sources on one hot bucket, many small rounds, a corrupted offset column and
-the flag checks.
+sources on one hot bucket, many small rounds, Receive and apply_mixed taking
+turns on one group, a corrupted offset column and the flag checks.
 """
 import ctypes as C
 
@@ -256,6 +256,64 @@ def test_group_apply_mixed_small_chunks_round_order(pa, world):
     for i in range(world):
         _check(out[i], want[i], bs[i], "member %d" % i)
     assert sent == list(sizes) and sum(applied) == sum(sizes)
+    assert _union(g.repos, world) == o.dump()
+    g.close()
+
+
+def _msgs(rng, n):
+    """n clean Receive messages over POOL: host columns and the tuple of CUDA
+    tensors GPUGroup.receive takes (an empty batch keeps one-entry columns)."""
+    from patrol_amd.engine import names_blob
+    names = [POOL[int(i)] for i in _gen.zipf_ids(rng, n, len(POOL))] if n else []
+    a, t, e = _gen.clean_states(rng, n)
+    blob, offs = names_blob(names)
+    cols = [blob if blob.size else np.zeros(8, np.uint8), offs.view(np.int32)]
+    cols += [x.view(np.int64) if x.size else np.zeros(1, np.int64) for x in (a, t, e)]
+    return names, a, t, e, tuple(torch.from_numpy(np.ascontiguousarray(x)).to(DEV) for x in cols)
+
+
+@pytest.mark.parametrize("world", [2, 1])
+def test_group_receive_and_apply_mixed_interleaved(pa, world):
+    """Receive, apply_mixed, Receive, apply_mixed on one group, in rounds of
+    4096: both calls run the same exchange steps over the member's scan and
+    bounds scratch, each over its own column sets.  Two shards on one GPU
+    (9000 / 0 then 0 / 5000 messages, 9000 / 5000 ops: an empty member, both
+    set parities, uneven round counts) and world 1 through the RCCL exchange
+    to itself.  Every result column, the totals and the tables equal the
+    oracle's under each call's order rule, and the stage timer of an
+    apply_mixed call reads back for every member."""
+    rng = np.random.default_rng(5800 + world)
+    g = pa.GPUGroup.open_all([0] * world, log2_slots=12)
+    kw = dict(small_chunks=True, rccl_self=world == 1)
+    g.set_timing(True)
+    o = O.Repo()
+    chunk = GO.SMALL_CHUNK
+
+    def receive(sizes, now):
+        per = [_msgs(rng, n) for n in sizes]
+        sent, merged = g.receive([b[4] for b in per], now, **kw)
+        assert sent == list(sizes) and sum(merged) == sum(sizes)
+        # chunk by chunk, sources in rank order within a chunk
+        for c in range(max((n + chunk - 1) // chunk for n in sizes)):
+            for b, n in zip(per, sizes):
+                if c * chunk < n:
+                    sl = slice(c * chunk, min(n, (c + 1) * chunk))
+                    o.receive_soa(b[0][sl], b[1][sl], b[2][sl], b[3][sl], now)
+
+    def apply(sizes, t0, tag):
+        bs = [GO.gen_ops(rng, n, POOL, t0=t0 + 1000 * i) for i, n in enumerate(sizes)]
+        want = GO.oracle_results(o, bs, GO.apply_order(sizes, chunk))
+        out, sent, applied = g.apply_mixed([_dev(b) for b in bs], **kw)
+        for i in range(world):
+            _check(out[i], want[i], bs[i], "%s, member %d" % (tag, i))
+            ms = g.stage_ms(i)
+            assert len(ms) == 3 and all(np.isfinite(v) and v >= 0 for v in ms.values()), (tag, i, ms)
+        assert sent == list(sizes) and sum(applied) == sum(sizes)
+
+    receive((9000, 0)[:world], _gen.T0)
+    apply((9000, 5000)[:world], _gen.T0 + _gen.SEC, "first")
+    receive((0, 5000)[-world:], _gen.T0 + 10**12)
+    apply((9000, 5000)[:world], _gen.T0 + 10**12 + _gen.SEC, "second")
     assert _union(g.repos, world) == o.dump()
     g.close()
 
