@@ -122,6 +122,10 @@ enum {
                                  classification and hot directory behind the batch before
                                  it, so the host's read-back of that batch overlaps them. */
 
+#define PHIP_RECV_CLASSIFY 0x100u /* phip_receive_soa: classify this batch before it is merged,
+                                     as PHIP_CFG_CLASSIFY_FIRST does for every batch of a
+                                     handle (the shard group's merges pass it) */
+
 /* phip_config.flags */
 #define PHIP_CFG_NO_GROW 0x1u   /* refuse (PHIP_ERR_FULL / PHIP_ERR_ARENA) instead of growing */
 #define PHIP_CFG_NO_SMALL 0x2u  /* ordered batches of <= 1024 host ops also take the large,
@@ -132,6 +136,12 @@ enum {
                                    "Order"); by default a handle does so from the first batch
                                    after one that held an incast or -0.0 field until 256
                                    clean batches in a row (a clean batch pays ~30 us for it) */
+#define PHIP_CFG_CLASSIFY_FIRST 0x10u /* classify every decoded Receive batch before it is merged.
+                                   By default a batch of a handle that does not set dirty
+                                   buckets apart is merged optimistically, with an undo log:
+                                   a batch that turns out to hold an incast, a -0.0 field or
+                                   a malformed name entry is undone and run again classified,
+                                   with the same results.  For A/B measurements and tests. */
 
 typedef struct phip_config {
   int32_t device;        /* HIP device ordinal                                          */
@@ -749,12 +759,23 @@ void phip_set_timing(phip_handle* h, int on);
  * that missed the table (inserted); out[3] table growths (rehashes) since
  * phip_open; out[4] messages of the batch that went through the ordered path
  * (the dirty buckets' sub-batch, or the suffix from the first dirty
- * message: phip_receive_soa).  Returns the number written (<= 5).
+ * message: phip_receive_soa); out[5] undo-log entries of the handle's last
+ * optimistic pass and out[6] the messages of that pass that found their
+ * wave's log full (such a pass is undone and the batch run again classified,
+ * as one that met a dirty message; the handle then classifies its next 256
+ * fast passes first).  Returns the number written (<= 7).
  * Not a plain counter read: a batch queued with PHIP_RECV_ASYNC is finished
  * first (the call waits for it), so that the counters are that batch's.  The
  * call has no status to return an error in: if finishing the batch fails, its
  * error is kept and returned by the handle's next call that returns one. */
 int phip_last_stats(phip_handle* h, uint64_t* out, int max);
+/* The undo log an optimistic Receive pass over n messages keeps on a device
+ * with `compute_units` compute units (host arithmetic only, no device call):
+ * out[0] workgroups of the pass, out[1] its waves (one log region each),
+ * out[2] entries of a region (32 bytes each: half the messages of the busiest
+ * wave, 24 more, and 64 kept for the hot directory's flush), out[3] bytes of
+ * the whole log.  Returns the number written (<= 4). */
+int phip_undo_log_layout(uint32_t n, uint32_t compute_units, uint64_t* out, int max);
 /* Placement quality of the table (one scan of the slots): out[0] buckets,
  * out[1] slots, out[2] the longest probe distance of a bucket from its home
  * slot, out[3] the sum of those distances.  Returns the number written

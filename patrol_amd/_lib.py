@@ -31,6 +31,7 @@ EXPORTS = [
     "phip_group_set_timing", "phip_group_stage_ms", "phip_group_rccl_info",
     "phip_evict_idle", "phip_group_evict_idle",
     "phip_route_pack_ops", "phip_group_apply_mixed",
+    "phip_undo_log_layout",
 ]
 
 PHIP_OK = 0
@@ -46,10 +47,12 @@ CFG_NO_GROW = 0x1
 CFG_NO_SMALL = 0x2
 CFG_FIXED_SEED = 0x4
 CFG_ISOLATE = 0x8
+CFG_CLASSIFY_FIRST = 0x10
 ROUTE_COMBINE = 0x2
 GROUP_RCCL_SELF = 0x4
 GROUP_SMALL_CHUNKS = 0x8
 RECV_ASYNC = 0x20
+RECV_CLASSIFY = 0x100
 EVICT_SHRINK = 0x40
 EVICT_DRY_RUN = 0x80
 PACKET_SIZE = 256
@@ -224,5 +227,7 @@ def load(path: str = LIB_PATH):
                                           vp, vp, vp, u32]
         L.phip_group_apply_mixed.argtypes = [vp, C.POINTER(phip_ops), C.POINTER(phip_results),
                                              C.POINTER(u64), C.POINTER(u64), u32]
+    if hasattr(L, "phip_undo_log_layout"):
+        L.phip_undo_log_layout.argtypes = [u32, u32, C.POINTER(u64), C.c_int]
     _lib = L
     return L

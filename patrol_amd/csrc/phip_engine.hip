@@ -62,7 +62,7 @@ enum BufId {
   B_WING, B_SEGXF, B_FOLDDBG, B_SMALL, B_HUGE2, B_LONG2,
   B_STATES, B_NAME1, B_HOT, B_ROUTE, B_EXPORT, B_MSHARD, B_MSCNT, B_FSCNT, B_DEDUP, B_DSET, B_TSTATS, B_SEGT, B_RHOT,
   B_DLIST, B_DTAB, B_DMARK, B_SMAP, B_SOFF, B_SLEN, B_SA, B_ST, B_SE, B_SSTAT, B_SREP, B_NCHK,
-  B_EVICT,
+  B_EVICT, B_ULOG, B_ULCNT,
   B_COUNT_
 };
 
@@ -89,8 +89,16 @@ struct phip_handle {
   bool iso_always = false;
   u32 iso_left = 0;
   bool coll_iso = false;
-  uint64_t stats[4] = {0, 0, 0, 0};   // last fast batch: hot entries, hot hits, misses,
-                                      // messages it sent through the ordered path
+  // The optimistic pass (phip_kernels.hpp "The optimistic pass"): a decoded
+  // batch of a pass that does not isolate runs without classification, unless
+  // the handle was opened with PHIP_CFG_CLASSIFY_FIRST or one of its last
+  // kOptBackoff fast passes overflowed its undo log (opt_left counts down).
+  bool classify_first = false;
+  u32 opt_left = 0;
+  uint64_t stats[6] = {0, 0, 0, 0, 0, 0};   // last fast batch: hot entries, hot hits, misses,
+                                            // messages it sent through the ordered path; last
+                                            // optimistic pass: log entries, messages that
+                                            // found the log full
   hipStream_t stream = nullptr;      // the stream every call runs on (own_stream or the caller's)
   hipStream_t own_stream = nullptr;  // created by phip_open
   hipStream_t stream2 = nullptr;   // second stream: the hot-bucket fold overlaps the others
@@ -149,6 +157,8 @@ struct phip_handle {
     u32 n = 0;
     u32 par = 0;
     bool iso = false;
+    bool opt = false;   // an optimistic pass: `log` is what undoes it
+    UndoLog log{};
     i64 now = 0;
     OutView ow{};
   } pend;
@@ -590,10 +600,11 @@ int build_hot(phip_handle* h, Src src, u32 n, hipStream_t st, const HotHdr** hdr
   return PHIP_OK;
 }
 
-inline unsigned fast_grid(phip_handle* h, u32 n) {
-  const u64 tiles = (n + kFastBlock - 1) / kFastBlock;
-  return (unsigned)std::max<u64>(1, std::min<u64>(tiles, (u64)h->ncu * kFastPerCU));
+inline unsigned fast_grid_on(u32 ncu, u32 n) {
+  const u64 tiles = ((u64)n + kFastBlock - 1) / kFastBlock;
+  return (unsigned)std::max<u64>(1, std::min<u64>(tiles, (u64)ncu * kFastPerCU));
 }
+inline unsigned fast_grid(phip_handle* h, u32 n) { return fast_grid_on((u32)h->ncu, n); }
 
 int join_hot(phip_handle* h, const HotHdr* hot);
 
@@ -656,7 +667,37 @@ struct FastFront {
   bool iso = false;     // this pass sets its dirty buckets apart (the isolation kernels run)
   u32* c = nullptr;     // the pass's counter set (fctr)
   u8* mark = nullptr;   // decoded batches: the status column, or a cleared one (k_dirty_pass)
+  bool opt = false;     // an optimistic pass: no classification, the kernel keeps an undo log
+  UndoLog log{};        // its log (cnt: set by the front; base, cap: by the back)
 };
+
+// Whether the handle's policy lets a decoded batch run optimistically.
+inline bool opt_allowed(const phip_handle* h) {
+  return !h->classify_first && h->opt_left == 0 && !h->iso_always && h->iso_left == 0;
+}
+
+// The per-wave entry counts of an optimistic pass's log, sized for the
+// largest grid.  No reset: every wave of the pass stores its count, and a
+// queued batch's kernel runs only after the batch before is collected (and,
+// if it failed, undone).
+inline size_t undo_counts(const phip_handle* h) { return (size_t)h->ncu * kFastPerCU * (kFastBlock / 64); }
+
+// The undo log of an optimistic pass over n messages on `ncu` compute units:
+// the fast kernel's grid, its waves, the entries of a wave's region
+// (undo_wave_cap) and the 16-byte halves the whole log takes (the ensure()
+// count).
+struct UndoLayout {
+  u32 grid, waves, cap;
+  u64 halves;
+};
+inline UndoLayout undo_layout(u32 n, u32 ncu) {
+  UndoLayout l;
+  l.grid = fast_grid_on(ncu, n);
+  l.waves = l.grid * (kFastBlock / 64);
+  l.cap = undo_wave_cap(n, l.grid);
+  l.halves = (u64)l.waves * l.cap * 2;
+  return l;
+}
 
 // A fast pass's device counters: one of two sets by batch parity, apart
 // from the general set every other path uses (ordered batches, inserts, the
@@ -715,15 +756,45 @@ int fast_shards(phip_handle* h, u32 n, u32 par, Sharded* out) {
 // counters in its last launch.
 // iso: whether the pass sets its dirty buckets apart (-1: the handle's
 // policy, phip_handle::iso_left).
+// opt: the caller can undo the pass and run the batch again (a decoded
+// batch's first pass), so the handle's policy may make it optimistic; its
+// front is the counter reset, the status fill and the directory chain.
 template <class In, class HotSrc>
 int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront* ff,
-               bool reset = true, int iso = -1) {
+               bool reset = true, int iso = -1, bool opt = false) {
   int rc;
   *ff = FastFront{};
   ff->iso = iso >= 0 ? iso != 0 : (h->iso_always || h->iso_left > 0);
   u32 *c, *dlist = nullptr;
   DirtySet dset;
   if ((rc = ensure(h, B_FSCNT, 4 * kShards, &c))) return rc;
+  if constexpr (In::kSoa) {
+    if (opt && iso < 0 && opt_allowed(h)) {
+      u32* lc;
+      const size_t nw = undo_counts(h);
+      if ((rc = ensure(h, B_ULCNT, nw, &lc))) return rc;
+      ff->opt = true;
+      ff->par = h->fpar ^= 1u;
+      ff->c = fctr(h, ff->par);
+      ff->log.cnt = lc;
+      ++h->nfast;
+      if (reset) {
+        k_batch_reset<<<1, kShards, 0, h->stream>>>(ff->c, fast_counts(h, ff->par));
+        HIPCHK(h, hipGetLastError());
+      }
+      // (the directory chain waits for the batch's producers only, not for
+      // the fills)
+      if (n >= kHotMinBatch) HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
+      // Statuses: a fill here, not byte stores from the kernel's lanes (2% of
+      // the kernel when measured, below): a queued batch's fill runs while
+      // the host reads the batch before back, when the GPU has nothing else
+      // to do.
+      if (kOptStatus) ff->mark = status;   // (a tuning build: the kernel's lanes fill it)
+      else if (status) HIPCHK(h, hipMemsetAsync(status, PHIP_ST_MERGED, n, h->stream));
+      if (n >= kHotMinBatch && (rc = fork_hot(h, hsrc, n, &ff->hot, &ff->dir))) return rc;
+      return PHIP_OK;
+    }
+  }
   // (the classification lists the dirty messages either way: the policy
   // learns of them, and an isolating pass builds its set from the list)
   if ((rc = dirty_set(h, &dset, &dlist))) return rc;
@@ -784,7 +855,7 @@ int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront*
 // The fast kernel is enqueued behind the classification without a host
 // round trip; it reads the counters itself.
 template <class In>
-int fast_back(phip_handle* h, In in, u32 n, const FastFront& ff, bool queued) {
+int fast_back(phip_handle* h, In in, u32 n, FastFront& ff, bool queued) {
   u32* miss;
   int rc;
   Sharded msh;
@@ -801,10 +872,22 @@ int fast_back(phip_handle* h, In in, u32 n, const FastFront& ff, bool queued) {
     HIPCHK(h, hipGetLastError());
   }
   if ((rc = join_hot(h, ff.hot))) return rc;
-  {
+  if (ff.opt) {
+    if constexpr (In::kSoa) {
+      // (the log is sized here, not in the front: a queued front runs before
+      // the batch before is collected, and that batch's undo reads the log)
+      const UndoLayout ul = undo_layout(n, (u32)h->ncu);
+      ff.log.cap = ul.cap;
+      if ((rc = ensure(h, B_ULOG, (size_t)ul.halves, &ff.log.base))) return rc;
+      Launch l(h, "k_receive_fast");
+      k_receive_fast<In, true><<<ul.grid, kFastBlock, 0, h->stream>>>(
+          in, 0, n, table(h), msh, ff.c, ff.hot, ff.dir, nullptr, ff.mark, ff.log);
+    }
+  } else {
     Launch l(h, "k_receive_fast");
     k_receive_fast<In><<<fast_grid(h, n), kFastBlock, 0, h->stream>>>(
-        in, 0, n, table(h), msh, ff.c, ff.hot, ff.dir, ff.iso ? dset.key : nullptr, ff.mark);
+        in, 0, n, table(h), msh, ff.c, ff.hot, ff.dir, ff.iso ? dset.key : nullptr, ff.mark,
+        UndoLog{});
   }
   HIPCHK(h, hipGetLastError());
   if (ff.iso) {
@@ -838,9 +921,42 @@ int fast_back(phip_handle* h, In in, u32 n, const FastFront& ff, bool queued) {
 // message (the prefix rule).  Updates the isolation policy: kIsoKeep passes
 // after one that met a dirty message.
 constexpr u32 kIsoKeep = 256;
-int fast_collect(phip_handle* h, u32 n, u32 par, u32* first_dirty, u32* nmiss, bool iso_ran) {
+// An optimistic pass whose undo log overflowed (a batch that grows a field
+// with most of its cold messages: uniform keys) left the overflowing
+// messages unmerged.  They are on its miss list, but that list is not used
+// for them: the insert pipeline may refuse a batch (PHIP_CFG_NO_GROW) before
+// it merges anything, and a message naming an existing bucket must be merged
+// even then.  Such a pass counts as failed, like one that met a dirty
+// message, and the handle's next kOptBackoff fast passes classify first.
+constexpr u32 kOptBackoff = 256;
+
+// The counters of an optimistic pass (mirrored to the host): its log's
+// statistics and the back-off.  True when the speculation failed: the pass
+// met a dirty message or a malformed name entry, or its log overflowed, and
+// it has to be undone.
+bool opt_failed(phip_handle* h, u32 n) {
+  h->stats[4] = h->ctr_host[kCtrLogCount];
+  h->stats[5] = h->ctr_host[kCtrLogOver];
+  if (h->stats[5]) h->opt_left = kOptBackoff;
+  return h->ctr_host[kCtrDirty] < n || h->ctr_host[5] < n || h->stats[5] != 0;
+}
+
+// A failed optimistic pass undone: every record it touched back to its state
+// before the batch (k_undo).  Its miss list is dropped with its counters;
+// nothing was created, and the classified pass that follows fills the status
+// column again.
+int undo_pass(phip_handle* h, u32 n, const UndoLog& log) {
+  Launch l(h, "k_undo");
+  k_undo<<<fast_grid(h, n) * (kFastBlock / 64), 256, 0, h->stream>>>(log, table(h));
+  HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
+}
+
+int fast_collect(phip_handle* h, u32 n, u32 par, u32* first_dirty, u32* nmiss, bool iso_ran,
+                 bool opt_ran = false) {
   int rc;
   if ((rc = check_flags(h))) return rc;
+  if (!opt_ran && h->opt_left) --h->opt_left;
   *nmiss = h->ctr_host[2];
   if (*nmiss) {
     Sharded msh;
@@ -871,15 +987,22 @@ int fast_collect(phip_handle* h, u32 n, u32 par, u32* first_dirty, u32* nmiss, b
 // clean prefix: the messages before the first dirty one (*first_dirty; n if
 // none) and before the first malformed datagram (ctr[5]).  The prefix's
 // misses (*nmiss of them) are listed in B_MISS.
+// opt: the pass may be optimistic (fast_front); one that fails is undone here
+// and the batch run again, classified, under the policy as it stood.
 template <class In, class HotSrc>
 int fast_apply(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, u32* first_dirty,
-               u32* nmiss, int iso = -1) {
+               u32* nmiss, int iso = -1, bool opt = false) {
   int rc;
   FastFront ff;
-  if ((rc = fast_front(h, in, hsrc, n, status, &ff, true, iso)) ||
+  if ((rc = fast_front(h, in, hsrc, n, status, &ff, true, iso, opt)) ||
       (rc = fast_back(h, in, n, ff, false)))
     return rc;
-  return fast_collect(h, n, ff.par, first_dirty, nmiss, ff.iso);
+  if (ff.opt && opt_failed(h, n)) {
+    if ((rc = undo_pass(h, n, ff.log)) || (rc = fast_front(h, in, hsrc, n, status, &ff, true, iso)) ||
+        (rc = fast_back(h, in, n, ff, false)))
+      return rc;
+  }
+  return fast_collect(h, n, ff.par, first_dirty, nmiss, ff.iso, ff.opt);
 }
 
 template <class Src>
@@ -1525,12 +1648,14 @@ int stopped_at_bad_name(phip_handle* h, const OutView& ow, u32 n, u32 stop) {
 // ordered path from its first incast or -0.0 on.
 template <class Src>
 int receive_decoded(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t,
-                    const int64_t* e, u32 n, i64 now, const OutView& ow) {
+                    const int64_t* e, u32 n, i64 now, const OutView& ow, bool opt = true) {
   int rc;
   // The hot directory (read-only on the table and the batch) is built on
   // stream2 while the batch is classified.
+  // (opt = false: the batch of a failed optimistic pass, run again)
   u32 fd = n, nmiss = 0;
-  if ((rc = fast_apply(h, SoaIn<Src>{src, a, t, e}, src, n, ow.status, &fd, &nmiss))) return rc;
+  if ((rc = fast_apply(h, SoaIn<Src>{src, a, t, e}, src, n, ow.status, &fd, &nmiss, -1, opt)))
+    return rc;
   const u32 stop = std::min<u32>(h->ctr_host[5], n);   // (a checked batch's malformed entry)
   if ((rc = finish_receive(h, src, a, t, e, stop, fd, nmiss, now, ow, n, h->ndef != 0)))
     return rc;
@@ -1548,7 +1673,18 @@ int finish_pending(phip_handle* h, bool* worked) {
   HIPCHK(h, hipEventSynchronize(h->ev_ctr));
   u32 fd = p.n, nmiss = 0;
   int rc;
-  if ((rc = fast_collect(h, p.n, p.par, &fd, &nmiss, p.iso))) return rc;
+  if (p.opt && opt_failed(h, p.n)) {
+    // A failed speculation: undone, and the batch run again through the
+    // classified path as a synchronous call would (a fast pass of its own,
+    // so the caller queues the next batch's front again).
+    if (worked) *worked = true;
+    if ((rc = undo_pass(h, p.n, p.log)) ||
+        (rc = receive_decoded(h, p.src, p.a, p.t, p.e, p.n, p.now, p.ow, false)))
+      return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PHIP_OK;
+  }
+  if ((rc = fast_collect(h, p.n, p.par, &fd, &nmiss, p.iso, p.opt))) return rc;
   const u32 stop = std::min<u32>(h->ctr_host[5], p.n);   // (a checked batch's malformed entry)
   const bool deferred = h->ndef != 0;
   if (nmiss == 0 && fd >= stop && !deferred) return stopped_at_bad_name(h, p.ow, p.n, stop);
@@ -2001,6 +2137,7 @@ int phip_open(const phip_config* cfg, phip_handle** out) {
   h->max_load = load_limit(h->cap, h->load_pct);
   h->grow = !(cfg->flags & PHIP_CFG_NO_GROW);
   h->iso_always = cfg->flags & PHIP_CFG_ISOLATE;
+  h->classify_first = cfg->flags & PHIP_CFG_CLASSIFY_FIRST;
   h->small = !(cfg->flags & PHIP_CFG_NO_SMALL);
   h->arena_cap = h->arena_open = cfg->arena_bytes ? cfg->arena_bytes : (1ull << 20);
   if (cfg->debug_tag_bits && cfg->debug_tag_bits < 64) h->tag_mask = (1ull << cfg->debug_tag_bits) - 1;
@@ -2397,15 +2534,19 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
     bool worked = false;
     if ((rc = outputs(h, res, n, true, &ow))) return rc;
     const bool prev = h->pend.active;
-    if ((rc = fast_front(h, in, src, n, ow.status, &ff, !prev))) return after_error(h, rc);
+    const bool opt = !(flags & PHIP_RECV_CLASSIFY);
+    if ((rc = fast_front(h, in, src, n, ow.status, &ff, !prev, -1, opt)))
+      return after_error(h, rc);
     const u64 nfast = h->nfast, grows = h->grows;
     if (prev && (rc = finish_pending(h, &worked))) return after_error(h, rc);
     // The leftover work of the batch before (its misses, its dirty buckets)
     // runs on the general counters and leaves this front standing, unless it
     // ran a fast pass of its own (the directory and dirty list buffers) or
     // grew the table (the directory's slots).
+    // (a failed optimistic pass ran the batch again, a fast pass of its own:
+    // the front queued again follows the policy as that batch left it)
     if (worked && (h->nfast != nfast || h->grows != grows) &&
-        (rc = fast_front(h, in, src, n, ow.status, &ff)))
+        (rc = fast_front(h, in, src, n, ow.status, &ff, true, -1, opt)))
       return after_error(h, rc);
     if ((rc = fast_back(h, in, n, ff, true))) return after_error(h, rc);
     h->pend.active = true;
@@ -2416,6 +2557,8 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
     h->pend.n = n;
     h->pend.par = ff.par;
     h->pend.iso = ff.iso;
+    h->pend.opt = ff.opt;
+    h->pend.log = ff.log;
     h->pend.now = now;
     h->pend.ow = ow;
     return PHIP_OK;
@@ -2438,7 +2581,8 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
       (rc = stage(h, B_A, m->added, n, dev, &a)) || (rc = stage(h, B_T, m->taken, n, dev, &t)) ||
       (rc = stage(h, B_E, m->elapsed, n, dev, &e)) || (rc = outputs(h, res, n, dev, &ow)))
     return rc;
-  if ((rc = receive_decoded(h, src, a, t, e, n, now, ow))) return after_error(h, rc);
+  if ((rc = receive_decoded(h, src, a, t, e, n, now, ow, !(flags & PHIP_RECV_CLASSIFY))))
+    return after_error(h, rc);
   return copy_outputs(h, res, n, dev, ow);
 }
 
@@ -3119,9 +3263,19 @@ int phip_last_stats(phip_handle* h, uint64_t* out, int max) {
   // a queued PHIP_RECV_ASYNC batch is finished first, so the stats are its
   // own (its error, if any, is kept for the next call that returns one)
   if (h->pend.active && !h->deferred_rc) h->deferred_rc = begin_call(h);
-  const uint64_t v[5] = {h->stats[0], h->stats[1], h->stats[2], h->grows, h->stats[3]};
+  const uint64_t v[7] = {h->stats[0], h->stats[1], h->stats[2], h->grows, h->stats[3],
+                         h->stats[4], h->stats[5]};
   int k = 0;
-  for (; k < max && k < 5; ++k) out[k] = v[k];
+  for (; k < max && k < 7; ++k) out[k] = v[k];
+  return k;
+}
+
+int phip_undo_log_layout(uint32_t n, uint32_t compute_units, uint64_t* out, int max) {
+  if (!out || !compute_units) return 0;
+  const UndoLayout l = undo_layout(n, compute_units);
+  const uint64_t v[4] = {l.grid, l.waves, l.cap, l.halves * sizeof(u64x2)};
+  int k = 0;
+  for (; k < max && k < 4; ++k) out[k] = v[k];
   return k;
 }
 

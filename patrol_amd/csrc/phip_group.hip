@@ -563,7 +563,7 @@ int merge_chunk(Member& mb, Lane& ln, hipStream_t st, int64_t now) {
     rm.added = ln.recv.at<u64>(MSG_A);
     rm.taken = ln.recv.at<u64>(MSG_T);
     rm.elapsed = ln.recv.at<int64_t>(MSG_E);
-    GPHIP(mb, phip_receive_soa(mb.h, &rm, now, nullptr, PHIP_DEVICE_PTRS));
+    GPHIP(mb, phip_receive_soa(mb.h, &rm, now, nullptr, PHIP_DEVICE_PTRS | PHIP_RECV_CLASSIFY));
     GHIP(mb, mb.tm.mark(2, st));
   }
   GHIP(mb, hipEventRecord(ln.ev_merged, st));
@@ -604,7 +604,7 @@ int member_receive(phip_group* g, Member& mb, const phip_msgs& in, int64_t now, 
     if (merged) *merged = n;
     if (n == 0) return PHIP_OK;
     GHIP(mb, mb.tm.mark(2, st));
-    GPHIP(mb, phip_receive_soa(mb.h, &in, now, nullptr, PHIP_DEVICE_PTRS));
+    GPHIP(mb, phip_receive_soa(mb.h, &in, now, nullptr, PHIP_DEVICE_PTRS | PHIP_RECV_CLASSIFY));
     GHIP(mb, mb.tm.mark(2, st));
     return PHIP_OK;
   }

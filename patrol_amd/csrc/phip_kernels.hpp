@@ -1166,19 +1166,103 @@ __device__ inline bool tail_match(const u64 (&htail)[kHotTailWords][kHotMax], u3
 // whose statuses are < 0x40 or carry 0x80).
 constexpr u8 kMarkDirty = 0x40;
 
+// ---- The optimistic pass (Opt) and its undo log ----
+// A clean batch needs no classification: every field the fast path writes
+// is a monotone max, and the kernel loads a record's fields before every
+// atomicMax on them.  Let P be a field's value when the kernel starts.  Every
+// value a lane loads is >= P (a load returns something the word held since
+// the kernel began; the stream orders earlier kernels' writes before it), and
+// if the field changed at all, the lane that issued the first atomic on it
+// loaded exactly P.  So when every lane that issues an atomic on a record
+// first logs (slot, loaded added, loaded taken, loaded elapsed), an atomicMin
+// of every logged value into its record (k_undo) puts every touched record
+// back to its state before the batch: an unchanged field only ever logged
+// values >= P = its value, a changed one has P among its entries.
+// The Opt instantiation therefore runs without k_classify: it looks at the
+// replica fields it holds anyway, does not merge a dirty message (an incast,
+// a -0.0 field) or one with a malformed name entry (checked names), and
+// min-reduces their indices into ctr[kCtrDirty] / ctr[5].  A pass that found
+// one is a failed speculation: the host undoes it and runs the batch again
+// through the classified path.  The status column is filled by the host
+// before the pass.
+// The log: a region of `cap` 32-byte entries {slot, 0 | added | taken |
+// elapsed} per wave, the cursor a wave-uniform register, no atomic counter;
+// the lanes that log in an iteration store their entries side by side (mbcnt).
+// A lane that finds the region full issues no atomic (nothing is ever changed
+// without an entry) and the pass counts it in ctr[kCtrLogOver]: the host
+// treats such a pass as failed too.  The last kUndoFlushReserve entries of a
+// region are kept for the directory flush, which logs (slot, ca, ct, ce) as
+// it issues its atomics.  Every wave stores its count once, at the end (so
+// the counts need no reset).
+// (PHIP_UNDO_NT / PHIP_OPT_STATUS: tuning builds, tools/build_variants.sh --
+// plain instead of non-temporal log stores; the status column filled by the
+// kernel's lanes instead of the host's fill before the pass.  DESIGN.md §4
+// round 7 has the measurements behind the defaults.)
+#ifndef PHIP_UNDO_NT
+#define PHIP_UNDO_NT 1
+#endif
+#ifndef PHIP_OPT_STATUS
+#define PHIP_OPT_STATUS 0
+#endif
+constexpr bool kOptStatus = PHIP_OPT_STATUS != 0;
+constexpr u32 kCtrLogOver = 6;    // fast-pass counter set: messages that found their wave's log full
+constexpr u32 kCtrLogCount = 9;   //   and the pass's log entries
+constexpr u32 kUndoFlushReserve = 64 * ((kHotMax + kFastBlock - 1) / kFastBlock);
+struct UndoLog {
+  u64x2* base = nullptr;   // waves * cap entries of two 16-byte halves
+  u32* cnt = nullptr;      // entries per wave
+  u32 cap = 0;             // entries per wave region
+};
+// The chunks of 64 messages the busiest wave of the fast kernel walks (its
+// chunk order: the batch in eighths when the grid is a multiple of 8).
+__host__ __device__ inline u32 fast_wave_chunks(u32 n, u32 grid) {
+  const u32 nchunks = (n + 63) / 64, kw = kFastBlock / 64;
+  if (grid % 8 == 0) {
+    const u32 per = (nchunks + 7) / 8, waves = grid / 8 * kw;
+    return (per + waves - 1) / waves;
+  }
+  return (nchunks + grid * kw - 1) / (grid * kw);
+}
+// Entries of a wave's region: one for every second message of the busiest
+// wave (the C2 headline logs 0.09 entries per message, DESIGN.md §4 round 7;
+// a batch whose every cold message grows a field overflows and sends the
+// handle back to the classified path), kUndoSlack for the waves of a small
+// batch, and the flush's reserve.  The slack: a wave that walks one chunk
+// logs about Binomial(64, p) entries; at p = 1/2 (a batch that raises half
+// of what its cold messages name) 32 + 24 lies 6 standard deviations out.
+// With 16, about one wave in 10^5 overflowed, and a clean 2^17-message batch
+// went back through the classified path now and then.
+constexpr u32 kUndoSlack = 24;
+__host__ __device__ inline u32 undo_wave_cap(u32 n, u32 grid) {
+  return fast_wave_chunks(n, grid) * 32 + kUndoSlack + kUndoFlushReserve;
+}
+__device__ inline u32 lane_rank(u64 m) {   // set bits of m below this lane
+  return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
+}
+__device__ inline void undo_store(u64x2* p, u32 slot, u64 a, u64 t, i64 e) {
+#if PHIP_UNDO_NT
+  __builtin_nontemporal_store(u64x2{(u64)slot, a}, p);
+  __builtin_nontemporal_store(u64x2{t, (u64)e}, p + 1);
+#else
+  p[0] = u64x2{(u64)slot, a};
+  p[1] = u64x2{t, (u64)e};
+#endif
+}
+
 // Messages [lo, n) of the batch (lo a multiple of 64: a segment of a batch
 // classified segment by segment, or 0).
-template <class In>
+template <class In, bool Opt = false>
 __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_receive_fast(
     In in, u32 lo, u32 n, Table T, Sharded miss, u32* ctr,
     const HotHdr* __restrict__ hot, const HotEntry* __restrict__ hot_dir, const u64* dtab,
-    u8* __restrict__ mark) {
+    u8* __restrict__ mark, UndoLog ulog) {
   __shared__ u32 hslot[kHotLds];        // directory index + 1 (0 = empty)
   __shared__ u64 htag[kHotMax], hw0[kHotMax], hw1[kHotMax], hw2[kHotMax];
   __shared__ u32 hrec[kHotMax], haoff[kHotMax];
   __shared__ u64 htail[kHotTailWords][kHotMax];
   __shared__ u64 hmax[3][kHotMax];      // per-workgroup maxima (elapsed biased by 2^63)
   __shared__ u32 hhits;
+  __shared__ u32 hlog[2];               // Opt: the workgroup's log entries, overflowed messages
 
   // Gate (k_classify ran before, over every message up to n): only the clean
   // prefix is applied, the messages before the first dirty one
@@ -1187,9 +1271,11 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   // (dirty buckets, decoded batches: with a dirty set, the whole batch up to
   // the first malformed message; the messages that may name a dirty bucket
   // are marked for k_dirty_pass)
-  const u32 ndr = dtab ? ctr[kCtrNDirty] : 0u;
-  const bool iso = ndr != 0 && ndr <= kDirtyCap;
-  n = min(n, iso ? ctr[5] : min(ctr[5], ctr[kCtrDirty]));
+  // (Opt: no classification ran and there is no gate; the kernel finds the
+  // dirty and malformed messages itself and leaves them alone)
+  const u32 ndr = !Opt && dtab ? ctr[kCtrNDirty] : 0u;
+  const bool iso = !Opt && ndr != 0 && ndr <= kDirtyCap;
+  if constexpr (!Opt) n = min(n, iso ? ctr[5] : min(ctr[5], ctr[kCtrDirty]));
   if (n <= lo) return;
   const u32 nh = hot ? min(hot->n, kHotMax) : 0u;
   for (u32 j = threadIdx.x; j < kHotLds; j += kFastBlock) hslot[j] = 0;
@@ -1197,6 +1283,7 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     hmax[0][j] = 0; hmax[1][j] = 0; hmax[2][j] = 0;
   }
   if (threadIdx.x == 0) hhits = 0;
+  if (Opt && threadIdx.x < 2) hlog[threadIdx.x] = 0;
   __syncthreads();
   for (u32 j = threadIdx.x; j < nh; j += kFastBlock) {
     const HotEntry d = hot_dir[j];
@@ -1234,17 +1321,50 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     cstride = gridDim.x * kWaves;
     chunk = lo / 64 + blockIdx.x * kWaves + wave;
   }
+  // Opt: the wave's log region, its cursor and the messages it found no
+  // room for (wave-uniform)
+  u64x2* lbase = nullptr;
+  u32 lcur = 0, lover = 0;
+  const u32 lcap = Opt ? ulog.cap - kUndoFlushReserve : 0u;
+  if constexpr (Opt) lbase = ulog.base + (size_t)(blockIdx.x * kWaves + wave) * ulog.cap * 2;
   typename In::Pre pre{};
   if (chunk < nchunks) pre = in.pre(min(chunk * 64 + lane, n - 1));
   for (; chunk < nchunks; chunk += cstride) {
     const u32 tid = chunk * 64 + lane;
-    const bool valid = tid < n;
+    bool valid = tid < n;
     const u32 i = tid < n ? tid : n - 1;
+    if constexpr (Opt && kOptStatus) {
+      if (mark && tid < n) mark[tid] = PHIP_ST_MERGED;
+    }
+    if constexpr (Opt && In::kSoa) {
+      // checked names: a malformed entry reads as the empty name at offset 0
+      // (NamesOffs::get) and ends the speculation
+      if constexpr (In::kOffs) {
+        if (in.src.lim) {   // (uniform)
+          const bool bad = in.src.bad(pre.a, pre.b);
+          note_min(valid && bad, i, &ctr[5]);
+          if (bad) { pre.a = 0; pre.b = 0; valid = false; }
+        }
+      }
+    }
     // round 2: the name words and replica fields
     u64 off, w0, w1, w2, ra, rt;
     u32 len;
     i64 re;
     in.load(i, pre, off, len, w0, w1, w2, ra, rt, re);
+    if constexpr (Opt) {
+      // a dirty message is not merged: its index (the lowest of the wave)
+      // and the wave's count, only in waves that hold one (note_dirty)
+      const bool d = valid && replica_dirty(ra, rt, re);
+      const u64 dm = __ballot(d);
+      if (dm) {
+        if (__lane_id() == (u32)(__ffsll((long long)dm) - 1)) {
+          atomicMin(&ctr[kCtrDirty], i);
+          atomicAdd(&ctr[kCtrNDirty], (u32)__popcll(dm));
+        }
+        valid = valid && !d;
+      }
+    }
     if (chunk + cstride < nchunks) pre = in.pre(min((chunk + cstride) * 64 + lane, n - 1));
     Name nm;
     short_name(w0, w1, w2, off, len, nm);
@@ -1271,6 +1391,12 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     const u64 ea = enc_replica_nz(ra), et = enc_replica_nz(rt), ee = (u64)re ^ kSign;
 
     bool missed = false;
+    // Opt: the cold lane's merge waits for its log entry (below, where the
+    // wave is whole again): its slot and the fields it loaded
+    bool grows = false;
+    u32 gs = 0;
+    u64 ga = 0, gt = 0;
+    i64 ge = 0;
     if (valid) {
       int hidx = -1;
       if (nh) {
@@ -1318,6 +1444,9 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
         if (pr == kFound) {
           if (iso && (rec_flags(cur) & kRecDirty)) {
             mark[i] = kMarkDirty;
+          } else if constexpr (Opt) {
+            grows = ea > cur.added || et > cur.taken || ee > ((u64)cur.elapsed ^ kSign);
+            gs = s; ga = cur.added; gt = cur.taken; ge = cur.elapsed;
           } else {
             Rec* r = &T.recs[s];
             if (ea > cur.added) atomicMax(&r->added, ea);
@@ -1332,6 +1461,24 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
         }
       }
     }
+    if constexpr (Opt) {
+      const u64 gm = __ballot(grows);
+      if (gm) {
+        if (grows) {
+          const u32 pos = lcur + lane_rank(gm);
+          if (pos < lcap) {   // (no room: not merged, the pass fails -- lover)
+            undo_store(lbase + 2 * (size_t)pos, gs, ga, gt, ge);
+            Rec* r = &T.recs[gs];
+            if (ea > ga) atomicMax(&r->added, ea);
+            if (et > gt) atomicMax(&r->taken, et);
+            if (ee > ((u64)ge ^ kSign)) atomicMax(&r->elapsed, (i64)(ee ^ kSign));
+          }
+        }
+        const u32 want = lcur + (u32)__popcll(gm);
+        lover += want > lcap ? want - lcap : 0u;
+        lcur = min(want, lcap);
+      }
+    }
     miss.append(chunk, missed, i);
   }
   if (hits) atomicAdd(&hhits, hits);
@@ -1342,6 +1489,47 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   }
 
   // Directory flush: the workgroup's maxima, skipping fields already beaten.
+  // (Opt: logged like a cold merge, in the region's reserve -- at most 64
+  // entries per wave and round, so the flush always finds room)
+  if constexpr (Opt) {
+    for (u32 jb = wave * 64; jb < nh; jb += kFastBlock) {   // (wave-uniform bounds)
+      const u32 j = jb + lane;
+      bool lg = false;
+      u64 xa = 0, xt = 0, xe = 0, ca = 0, ct = 0, ce = 0;
+      Rec* r = nullptr;
+      if (j < nh) {
+        xa = hmax[0][j]; xt = hmax[1][j]; xe = hmax[2][j];
+        if (xa | xt | xe) {
+          r = &T.recs[hrec[j] & 0x7FFFFFFFu];
+          ca = r->added; ct = r->taken; ce = (u64)r->elapsed ^ kSign;
+          lg = xa > ca || xt > ct || xe > ce;
+        }
+      }
+      const u64 gm = __ballot(lg);
+      if (lg) {
+        undo_store(lbase + 2 * (size_t)(lcur + lane_rank(gm)), hrec[j] & 0x7FFFFFFFu, ca, ct,
+                   (i64)(ce ^ kSign));
+        if (xa > ca) atomicMax(&r->added, xa);
+        if (xt > ct) atomicMax(&r->taken, xt);
+        if (xe > ce) atomicMax(&r->elapsed, (i64)(xe ^ kSign));
+      }
+      lcur += (u32)__popcll(gm);
+    }
+    // (the statistics summed per workgroup first: one atomic per wave on one
+    // word serialises at the memory side, 8192 of them took 80 us of a
+    // 1M-message batch's kernel)
+    if (lane == 0) {
+      ulog.cnt[blockIdx.x * kWaves + wave] = lcur;
+      if (lcur) atomicAdd(&hlog[0], lcur);
+      if (lover) atomicAdd(&hlog[1], lover);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      if (hlog[0]) atomicAdd(&ctr[kCtrLogCount], hlog[0]);
+      if (hlog[1]) atomicAdd(&ctr[kCtrLogOver], hlog[1]);
+    }
+    return;
+  }
   for (u32 j = threadIdx.x; j < nh; j += kFastBlock) {
     const u64 xa = hmax[0][j], xt = hmax[1][j], xe = hmax[2][j];
     if (!(xa | xt | xe)) continue;
@@ -1350,6 +1538,23 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     if (xa > ca) atomicMax(&r->added, xa);
     if (xt > ct) atomicMax(&r->taken, xt);
     if (xe > ce) atomicMax(&r->elapsed, (i64)(xe ^ kSign));
+  }
+}
+
+// A failed optimistic pass undone (one workgroup per wave region): every
+// logged field value min-reduced into its record, unsigned for the E-coded
+// floats, signed for elapsed.  The plain load first only saves atomics:
+// fields only fall here, so a stale value is too high and the atomic is
+// issued all the same.
+__global__ __launch_bounds__(256) void k_undo(UndoLog L, Table T) {
+  const u32 c = min(L.cnt[blockIdx.x], L.cap);
+  const u64x2* p = L.base + (size_t)blockIdx.x * L.cap * 2;
+  for (u32 k = threadIdx.x; k < c; k += 256) {
+    const u64x2 x = p[2 * (size_t)k], y = p[2 * (size_t)k + 1];
+    Rec* r = &T.recs[(u32)x.x & T.mask()];
+    if (r->added > x.y) atomicMin(&r->added, x.y);
+    if (r->taken > y.x) atomicMin(&r->taken, y.x);
+    if (r->elapsed > (i64)y.y) atomicMin(&r->elapsed, (i64)y.y);
   }
 }
 

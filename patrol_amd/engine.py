@@ -102,16 +102,21 @@ class GPURepo:
 
     def __init__(self, device: int = 0, log2_slots: int = 20, arena_bytes: int = 1 << 24,
                  max_load_pct: int = 90, debug_tag_bits: int = 0, grow: bool = True,
-                 small: bool = True, hash_seed: int | None = None, isolate: bool = False):
+                 small: bool = True, hash_seed: int | None = None, isolate: bool = False,
+                 classify_first: bool = False):
         """hash_seed: None = a random placement seed per handle (the default,
         as Go's map seeds its hash per process); an int pins it
         (PHIP_CFG_FIXED_SEED; 0 = the unseeded placement).  isolate: set every
         Receive batch's dirty buckets apart (PHIP_CFG_ISOLATE; by default only
-        after a dirty batch)."""
+        after a dirty batch).  classify_first: classify every decoded Receive
+        batch before merging it instead of merging optimistically
+        (PHIP_CFG_CLASSIFY_FIRST; same results)."""
         self.L = _lib.load()
         flags = (0 if grow else _lib.CFG_NO_GROW) | (0 if small else _lib.CFG_NO_SMALL)
         if isolate:
             flags |= _lib.CFG_ISOLATE
+        if classify_first:
+            flags |= _lib.CFG_CLASSIFY_FIRST
         if hash_seed is not None:
             flags |= _lib.CFG_FIXED_SEED
         cfg = phip_config(device, log2_slots, arena_bytes, max_load_pct, debug_tag_bits, flags, 0,
@@ -187,9 +192,11 @@ class GPURepo:
     def last_stats(self):
         """(hot-directory entries, messages folded through it, misses) of the
         last fast-path Receive batch, the table's growths since open, and the
-        batch's messages that went through the ordered path."""
-        out = (C.c_uint64 * 5)()
-        k = self.L.phip_last_stats(self.h, out, 5)
+        batch's messages that went through the ordered path; then the undo-log
+        entries of the last optimistic pass and its messages that found the
+        log full."""
+        out = (C.c_uint64 * 7)()
+        k = self.L.phip_last_stats(self.h, out, 7)
         return tuple(int(out[i]) for i in range(k))
 
     def table_stats(self):
