@@ -359,6 +359,90 @@ int phip_evict_idle(phip_handle* h, int64_t now, int64_t idle_ns, uint64_t min_e
 int phip_dump(phip_handle* h, uint8_t* names, uint64_t names_cap, uint64_t* name_offs,
               phip_state* states, uint64_t max_n, uint64_t* n_out, uint64_t* names_bytes_out);
 
+/* Anti-entropy sweep: the live table as wire datagrams, a bounded piece per
+ * call (the reference has no counterpart: a Patrol node gets state one bucket
+ * at a time, by a zero-state incast request per bucket it touches,
+ * repo.go:96-106, and never pushes its state anywhere).  A caller loops
+ *     phip_export_sweep -> phip_udp_send_batch (or a peer handle's
+ *     phip_receive_datagrams)
+ * until st->done, and the peer has merged everything this table knows.
+ *
+ * Output.  Datagram i is out[offs[i] .. offs[i+1]), offs[0] = 0: the bucket's
+ * byte-identical MarshalBinary (bucket.go:51-68: added, taken, elapsed
+ * big-endian, one length byte, the name), back to back -- the layout
+ * phip_udp_send_batch and phip_receive_datagrams take, offs uint64 as theirs.
+ * Within a call the buckets appear in slot order.
+ *
+ * Which buckets.  Every published record of the slots the call covers, except:
+ *  - a record whose state is zero (Bucket.IsZero, bucket.go:165-170): its
+ *    datagram would be an incast request to the receiver (repo.go:78,86-90),
+ *    not a merge, and carries nothing a merge could use;
+ *  - with idle_ns > 0, a record phip_evict_idle's rule calls idle at `now`
+ *    (idle = now - (created + elapsed) >= idle_ns, the same arithmetic).  This
+ *    keeps the buckets whose last successful Take or merged `elapsed` lies
+ *    within idle_ns of `now`.  It is not a change log: a denied Take and a
+ *    merge that raises only added / taken do not move `elapsed`, and such a
+ *    bucket is filtered as if untouched.  idle_ns == 0: no filter; idle_ns < 0
+ *    is PHIP_ERR_INVALID;
+ *  - a record whose name is longer than PHIP_MAX_NAME_LEN (only a datagram
+ *    can bring one in): MarshalBinary refuses it (bucket.go:48).
+ * NaN, -0.0 and negative fields are exported as they are (the receiver's
+ * ordered path handles -0.0).
+ *
+ * Bounds and progress.  A call writes at most max_msgs datagrams and at most
+ * out_cap bytes, cut at a record (never at a tile or window), and sets *cur to
+ * the slot of the first record it did not write, or to the end of the slots
+ * it covered.  max_msgs == 0 or out_cap < PHIP_BUCKET_PACKET_SIZE (one
+ * datagram of a PHIP_MAX_NAME_LEN-byte name) is PHIP_ERR_INVALID, so every
+ * valid call makes progress.
+ *
+ * Window.  A call reads the slots [cur->slot, cur->slot + W) clipped to the
+ * table, W = max(4 * max_msgs, PHIP_SWEEP_TILE) rounded up to a multiple of
+ * PHIP_SWEEP_TILE, and never the rest of the table: a sweep in small batches
+ * stays linear in the table size.  A call may write fewer than max_msgs
+ * datagrams, or none, with done == 0: loop until done.
+ *
+ * Rebuilds.  The handle counts its table layouts: growth, the move of
+ * phip_evict_idle and phip_restore each begin a new one, and slot numbers
+ * mean nothing across them.  The cursor carries the count it was made under;
+ * a cursor of another layout starts again at slot 0 and the call reports
+ * restarted = 1.  That is no error: merges are idempotent, so a bucket sent
+ * twice is harmless.  A zeroed cursor (the start) never reports it.  A cursor
+ * belongs to the handle that filled it.
+ *
+ * Count mode.  PHIP_SWEEP_COUNT with out == NULL (offs, out_cap and max_msgs
+ * are ignored): one count pass over the whole table under the same filter;
+ * st->n and st->bytes receive what a whole sweep would write, to size
+ * buffers by, and *cur is left untouched.
+ *
+ * Pointers and flags.  Host pointers, or PHIP_DEVICE_PTRS: `out` must then be
+ * 8-byte aligned and out_cap a multiple of 8 and at least
+ * PHIP_BUCKET_PACKET_SIZE + 8, else PHIP_ERR_INVALID; the byte budget is
+ * out_cap - 8, so the next 8-byte boundary past offs[n] lies inside the buffer
+ * and out / offs can go unchanged into another handle's
+ * phip_receive_datagrams(..., PHIP_DEVICE_PTRS), which reads aligned words.
+ * With host pointers only the bytes and offsets written are copied back.
+ * cur and st are host memory either way.  Unknown flag bits are
+ * PHIP_ERR_INVALID.  The call is serialised with the handle's other calls, as
+ * phip_evict_idle is; a batch queued with PHIP_RECV_ASYNC is finished first,
+ * and its error is this call's. */
+#define PHIP_SWEEP_TILE 4096      /* slots: the window's granule (see "Window") */
+#define PHIP_SWEEP_COUNT 0x200u   /* count only (see "Count mode")              */
+typedef struct phip_sweep_cursor {
+  uint64_t slot;   /* next slot to read                              */
+  uint64_t layout; /* the table layout the slot number belongs to    */
+} phip_sweep_cursor; /* all zero = start */
+typedef struct phip_sweep_stats {
+  uint64_t n;             /* datagrams written (count mode: datagrams the whole table would give) */
+  uint64_t bytes;         /* = offs[n]                                                            */
+  uint64_t slots_scanned; /* slots this call read (one pass's worth)                              */
+  uint32_t done;          /* 1: the cursor reached the end of the table                           */
+  uint32_t restarted;     /* 1: the table was rebuilt since the cursor was made; began at slot 0  */
+} phip_sweep_stats;
+int phip_export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64_t idle_ns,
+                      uint8_t* out, uint64_t out_cap, uint64_t* offs /* max_msgs+1 */,
+                      uint32_t max_msgs, phip_sweep_stats* st, uint32_t flags);
+
 /* ---- hot path ---- */
 /* ReplicatedRepo.Receive over n raw datagrams (byte-identical wire format,
  * bucket.go:59-64): bytes[offs[i] .. offs[i+1]).  `now` is the clock reading

@@ -32,6 +32,7 @@ EXPORTS = [
     "phip_evict_idle", "phip_group_evict_idle",
     "phip_route_pack_ops", "phip_group_apply_mixed",
     "phip_undo_log_layout",
+    "phip_export_sweep",
 ]
 
 PHIP_OK = 0
@@ -55,6 +56,8 @@ RECV_ASYNC = 0x20
 RECV_CLASSIFY = 0x100
 EVICT_SHRINK = 0x40
 EVICT_DRY_RUN = 0x80
+SWEEP_COUNT = 0x200
+SWEEP_TILE = 4096        # PHIP_SWEEP_TILE: the sweep window's granule, slots
 PACKET_SIZE = 256
 BUCKET_FIXED_SIZE = 25   # PHIP_BUCKET_FIXED_SIZE: added, taken, elapsed, name length
 
@@ -97,6 +100,15 @@ class phip_take_reply(C.Structure):
 class phip_evict_stats(C.Structure):
     _fields_ = [("idle", C.c_uint64), ("evicted", C.c_uint64), ("buckets", C.c_uint64),
                 ("slots", C.c_uint64), ("arena_used", C.c_uint64), ("arena_freed", C.c_uint64)]
+
+
+class phip_sweep_cursor(C.Structure):
+    _fields_ = [("slot", C.c_uint64), ("layout", C.c_uint64)]
+
+
+class phip_sweep_stats(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("bytes", C.c_uint64), ("slots_scanned", C.c_uint64),
+                ("done", C.c_uint32), ("restarted", C.c_uint32)]
 
 
 class phip_results(C.Structure):
@@ -229,5 +241,8 @@ def load(path: str = LIB_PATH):
                                              C.POINTER(u64), C.POINTER(u64), u32]
     if hasattr(L, "phip_undo_log_layout"):
         L.phip_undo_log_layout.argtypes = [u32, u32, C.POINTER(u64), C.c_int]
+    if hasattr(L, "phip_export_sweep"):
+        L.phip_export_sweep.argtypes = [vp, C.POINTER(phip_sweep_cursor), i64, i64, vp, u64, vp,
+                                        u32, C.POINTER(phip_sweep_stats), u32]
     _lib = L
     return L

@@ -62,7 +62,7 @@ enum BufId {
   B_WING, B_SEGXF, B_FOLDDBG, B_SMALL, B_HUGE2, B_LONG2,
   B_STATES, B_NAME1, B_HOT, B_ROUTE, B_EXPORT, B_MSHARD, B_MSCNT, B_FSCNT, B_DEDUP, B_DSET, B_TSTATS, B_SEGT, B_RHOT,
   B_DLIST, B_DTAB, B_DMARK, B_SMAP, B_SOFF, B_SLEN, B_SA, B_ST, B_SE, B_SSTAT, B_SREP, B_NCHK,
-  B_EVICT, B_ULOG, B_ULCNT,
+  B_EVICT, B_ULOG, B_ULCNT, B_SWEEP,
   B_COUNT_
 };
 
@@ -123,6 +123,11 @@ struct phip_handle {
   bool grow = true;          // !PHIP_CFG_NO_GROW
   bool small = true;         // !PHIP_CFG_NO_SMALL
   u64 grows = 0;             // table rehashes so far
+  // layout generation: bumped wherever the slot array is replaced or reloaded
+  // (grow_table, the move of phip_evict_idle, phip_restore); a sweep cursor
+  // (phip_export_sweep) made under another value starts over.  Never 0, the
+  // value of a zeroed cursor.
+  u64 layout_gen = 1;
   u64 long_need = 0;         // arena bytes the last reserve() counted
   Rec* recs = nullptr;
   u32* aux = nullptr;
@@ -380,6 +385,7 @@ int grow_table(phip_handle* h, u32 newL) {
   h->cap = ncap;
   h->max_load = load_limit(ncap, h->load_pct);
   ++h->grows;
+  ++h->layout_gen;
   return PHIP_OK;
 }
 
@@ -2407,6 +2413,7 @@ int phip_restore(phip_handle* h, const uint8_t* in, uint64_t len) {
     h->cap = scap;
     h->max_load = load_limit(scap, h->load_pct);
   }
+  ++h->layout_gen;   // (replaced above or reloaded below: the slots' contents change either way)
   const u8* p = in + sizeof hd;
   HIPCHK(h, hipMemcpyAsync(h->recs, p, h->cap * sizeof(Rec), hipMemcpyHostToDevice, h->stream));
   if (hd.arena_used)
@@ -3208,6 +3215,7 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
   h->cap = ncap;
   h->max_load = load_limit(ncap, h->load_pct);
   h->n_buckets = keep;
+  ++h->layout_gen;
   if (narena) {
     h->arena = narena;
     h->arena_cap = narena_cap;
@@ -3233,6 +3241,134 @@ int phip_evict_idle(phip_handle* h, int64_t now, int64_t idle_ns, uint64_t min_e
   if (flags & ~(PHIP_EVICT_SHRINK | PHIP_EVICT_DRY_RUN))
     return set_err(h, PHIP_ERR_INVALID, "evict: unknown flag bits 0x%x", flags);
   return evict_idle(h, now, idle_ns, min_evict, out, flags);
+}
+
+// Export sweep (patrolhip.h "Anti-entropy sweep"; kernels in phip_kernels.hpp
+// "export sweep").  One window of slots per call: count per tile, scan, write.
+// A device-pointer call reads the four counters back once, at its end; a
+// host-pointer call also reads the window's totals after the scan, to size
+// its staging buffers by what the window holds instead of by the caller's caps.
+int phip_export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64_t idle_ns,
+                      uint8_t* out, uint64_t out_cap, uint64_t* offs, uint32_t max_msgs,
+                      phip_sweep_stats* st, uint32_t flags) {
+  if (!h || !cur || !st) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;   // (finishes a queued PHIP_RECV_ASYNC batch)
+  if (flags & ~(PHIP_DEVICE_PTRS | PHIP_SWEEP_COUNT))
+    return set_err(h, PHIP_ERR_INVALID, "sweep: unknown flag bits 0x%x", flags);
+  if (idle_ns < 0) return set_err(h, PHIP_ERR_INVALID, "sweep: idle_ns must not be negative");
+  const bool dev = flags & PHIP_DEVICE_PTRS;
+  int rc;
+  u64 c[kSwWords] = {};
+  phip_sweep_stats s{};
+  if (flags & PHIP_SWEEP_COUNT) {
+    if (out) return set_err(h, PHIP_ERR_INVALID, "sweep: count mode takes no output buffer");
+    u64* ctr;
+    if ((rc = ensure(h, B_SWEEP, kSwWords, &ctr))) return rc;
+    HIPCHK(h, hipMemsetAsync(ctr, 0, kSwWords * sizeof(u64), h->stream));
+    {
+      Launch l(h, "k_sweep_count");
+      k_sweep_count<false><<<std::min<unsigned>(grid_for(h->cap), 8u * (unsigned)h->ncu), kBlock,
+                             0, h->stream>>>(h->recs, 0, h->cap, now, idle_ns, nullptr, nullptr,
+                                             ctr);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    s.n = c[kSwN];
+    s.bytes = c[kSwBytes];
+    s.slots_scanned = h->cap;
+    *st = s;
+    return PHIP_OK;
+  }
+  if (!out || !offs) return set_err(h, PHIP_ERR_INVALID, "sweep: out and offs are required");
+  if (!max_msgs) return set_err(h, PHIP_ERR_INVALID, "sweep: max_msgs must be positive");
+  if (out_cap < PHIP_BUCKET_PACKET_SIZE)
+    return set_err(h, PHIP_ERR_INVALID, "sweep: out_cap below one datagram (%d bytes)",
+                   PHIP_BUCKET_PACKET_SIZE);
+  if (dev && ((reinterpret_cast<uintptr_t>(out) & 7) || (out_cap & 7) ||
+              out_cap < PHIP_BUCKET_PACKET_SIZE + 8))
+    return set_err(h, PHIP_ERR_INVALID,
+                   "sweep: a device buffer is 8-byte aligned, a multiple of 8 and >= %d bytes",
+                   PHIP_BUCKET_PACKET_SIZE + 8);
+  const u64 budget = dev ? out_cap - 8 : out_cap;
+
+  u64 s0 = cur->slot;
+  if (cur->slot || cur->layout) {
+    if (cur->layout != h->layout_gen) {
+      s0 = 0;
+      s.restarted = 1;
+    }
+  }
+  s0 = std::min<u64>(s0, h->cap);
+  u64 W = std::max<u64>(4ull * max_msgs, PHIP_SWEEP_TILE);
+  W = (W + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE * PHIP_SWEEP_TILE;
+  const u64 s_end = std::min<u64>(s0 + W, h->cap);
+  s.slots_scanned = s_end - s0;
+  const u32 ntiles = (u32)((s_end - s0 + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE);
+  u64 next = s_end;
+  if (ntiles) {
+    // one buffer: the counters, the tiles' byte sums, the tiles' counts
+    u64* ctr;
+    if ((rc = ensure(h, B_SWEEP, kSwWords + (size_t)ntiles + ((size_t)ntiles + 1) / 2, &ctr)))
+      return rc;
+    u64* tile_bytes = ctr + kSwWords;
+    u32* tile_cnt = (u32*)(tile_bytes + ntiles);
+    {
+      Launch l(h, "k_sweep_count");
+      k_sweep_count<true><<<ntiles, kBlock, 0, h->stream>>>(h->recs, s0, s_end, now, idle_ns,
+                                                            tile_cnt, tile_bytes, ctr);
+    }
+    {
+      Launch l(h, "k_sweep_scan");
+      k_sweep_scan<<<1, kSweepBlock, 0, h->stream>>>(tile_cnt, tile_bytes, ntiles, ctr);
+    }
+    HIPCHK(h, hipGetLastError());
+    u8* d_out = out;
+    u64* d_offs = reinterpret_cast<u64*>(offs);
+    if (!dev) {
+      HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      if ((rc = ensure(h, B_EXPORT, (size_t)std::min<u64>(out_cap, c[kSwBytes]), &d_out)) ||
+          (rc = ensure(h, B_OFFS, (size_t)std::min<u64>(max_msgs, c[kSwN]) + 1, &d_offs)))
+        return rc;
+    }
+    {
+      // (long names are bounded by the arena's size, not its cursor: reading
+      // the cursor would cost a device-pointer call a second round trip)
+      Launch l(h, "k_sweep_write");
+      k_sweep_write<<<ntiles, kSweepBlock, 0, h->stream>>>(h->recs, h->arena, h->arena_cap, s0, s_end, now,
+                                                           idle_ns, tile_cnt, tile_bytes, max_msgs,
+                                                           budget, d_out, d_offs, ctr);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (c[kSwErr]) return set_err(h, PHIP_ERR_INVALID, "internal: sweep met a long name outside the arena");
+    if (c[kSwN] > max_msgs || c[kSwBytes] > budget)
+      return set_err(h, PHIP_ERR_INVALID, "internal: sweep wrote %llu datagrams, %llu bytes",
+                     (unsigned long long)c[kSwN], (unsigned long long)c[kSwBytes]);
+    s.n = c[kSwN];
+    s.bytes = c[kSwBytes];
+    if (c[kSwNext] != ~0ull) next = c[kSwNext];
+    if (!dev) {
+      // only what was written travels back
+      if (s.bytes) HIPCHK(h, hipMemcpyAsync(out, d_out, s.bytes, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(offs, d_offs, (s.n + 1) * sizeof(u64), hipMemcpyDeviceToHost,
+                               h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+  } else if (dev) {
+    HIPCHK(h, hipMemsetAsync(offs, 0, sizeof(u64), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  } else {
+    offs[0] = 0;
+  }
+  cur->slot = next;
+  cur->layout = h->layout_gen;
+  s.done = next >= h->cap;
+  *st = s;
+  return PHIP_OK;
 }
 
 int phip_table_stats(phip_handle* h, uint64_t* out, int max) {

@@ -5141,4 +5141,259 @@ __global__ __launch_bounds__(kEvictBlock) void k_evict_move(
   T.aux[d] = old_aux[s];
 }
 
+// ------------------------------------------------------ export sweep -----
+// phip_export_sweep: the table itself as MarshalBinary datagrams (bucket.go:
+// 51-68), back to back in slot order, a window of slots per call.  Three
+// launches over the window's tiles of PHIP_SWEEP_TILE slots:
+//   k_sweep_count  per tile, the qualifying records and their datagram bytes;
+//   k_sweep_scan   exclusive scans of the two tile arrays (one workgroup);
+//   k_sweep_write  one workgroup per tile ranks its records again, in slot
+//                  order, and writes those that fit both caps.
+// A record qualifies by sweep_size: published, not a zero state (its datagram
+// would be an incast request, repo.go:78,86-90), a name MarshalBinary takes
+// (bucket.go:48: a name of 232..255 bytes, which only a datagram can bring in,
+// has no datagram) and, with idle_ns > 0, not bucket_idle.  Ranks and byte
+// offsets are monotone in slot order, so the written records are a prefix of
+// the qualifying ones, cut at a record.
+//
+// Counters (u64 words of the sweep's device buffer).
+constexpr u32 kSwN = 0;      // datagrams written
+constexpr u32 kSwBytes = 1;  // their bytes (= offs[n])
+constexpr u32 kSwNext = 2;   // slot of the first qualifying record not written (~0: none)
+constexpr u32 kSwErr = 3;    // a long name outside the arena (internal)
+constexpr u32 kSwWords = 8;
+constexpr u32 kSweepTile = PHIP_SWEEP_TILE;
+// (k_sweep_write's workgroup: 512 threads 0.525 ms over C2's table, 256
+// 0.528 ms, 1024 0.609 ms -- one 16-wave workgroup fills a compute unit at
+// the kernel's register count, and its barriers then stall all of it)
+#ifndef PHIP_SWEEP_BLOCK
+#define PHIP_SWEEP_BLOCK 512
+#endif
+constexpr u32 kSweepBlock = PHIP_SWEEP_BLOCK;
+static_assert(kSweepTile % kSweepBlock == 0 && kSweepTile % kBlock == 0 && kSweepBlock <= 1024,
+              "sweep tile");
+
+// Datagram bytes of a record the sweep exports, 0 for one it skips.
+__device__ inline u32 sweep_size(const Rec& r, i64 now, i64 idle_ns) {
+  if (!r.tag || !(rec_flags(r) & kRecPublished)) return 0;
+  const u32 len = (u32)(r.name0 & 0xFFu);
+  if (len > PHIP_MAX_NAME_LEN) return 0;
+  if (state_is_zero(dec_f64(r.added), dec_f64(r.taken), r.elapsed)) return 0;
+  if (idle_ns > 0 && bucket_idle(r.created, r.elapsed, now, idle_ns)) return 0;
+  return PHIP_BUCKET_FIXED_SIZE + len;
+}
+
+// Count pass.  kTiles: workgroup t sums tile t of the window [s0, s_end) into
+// tile_cnt[t] / tile_bytes[t] (plain stores, no atomics).  Otherwise (count
+// mode over the whole table) k_evict_count's grid: a few workgroups per
+// compute unit striding, sums in registers, one add per wave and counter.
+template <bool kTiles>
+__global__ __launch_bounds__(kBlock) void k_sweep_count(const Rec* __restrict__ recs, u64 s0,
+                                                        u64 s_end, i64 now, i64 idle_ns,
+                                                        u32* __restrict__ tile_cnt,
+                                                        u64* __restrict__ tile_bytes, u64* ctr) {
+  u32 n = 0;
+  u64 b = 0;
+  if (kTiles) {
+    const u64 t0 = s0 + (u64)blockIdx.x * kSweepTile;
+#pragma unroll 4
+    for (u32 k = 0; k < kSweepTile / kBlock; ++k) {
+      const u64 s = t0 + (u64)k * kBlock + threadIdx.x;
+      if (s >= s_end) break;
+      const u32 sz = sweep_size(load_rec(&recs[s]), now, idle_ns);
+      n += sz != 0;
+      b += sz;
+    }
+  } else {
+    const u64 stride = (u64)gridDim.x * kBlock;
+    for (u64 s = s0 + (u64)blockIdx.x * kBlock + threadIdx.x; s < s_end; s += stride) {
+      const u32 sz = sweep_size(load_rec(&recs[s]), now, idle_ns);
+      n += sz != 0;
+      b += sz;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    n += __shfl_xor(n, d);
+    b += __shfl_xor(b, d);
+  }
+  if (kTiles) {
+    __shared__ u32 wn[kBlock / 64];
+    __shared__ u64 wb[kBlock / 64];
+    if (__lane_id() == 0) { wn[threadIdx.x >> 6] = n; wb[threadIdx.x >> 6] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      u32 tn = 0;
+      u64 tb = 0;
+      for (u32 i = 0; i < kBlock / 64; ++i) { tn += wn[i]; tb += wb[i]; }
+      tile_cnt[blockIdx.x] = tn;
+      tile_bytes[blockIdx.x] = tb;
+    }
+  } else if (__lane_id() == 0) {
+    if (n) atomicAdd(&ctr[kSwN], (u64)n);
+    if (b) atomicAdd(&ctr[kSwBytes], b);
+  }
+}
+
+__device__ inline u64 wave_incl_scan64(u64 v) {
+  const u32 lane = __lane_id();
+#pragma unroll
+  for (u32 d = 1; d < 64; d <<= 1) {
+    const u64 o = __shfl_up(v, d);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+// Exclusive scans of tile_cnt / tile_bytes in place, one workgroup walking
+// the tiles in chunks of its size with a running carry.  The totals are what
+// k_sweep_write leaves standing when every record fits: n, bytes, no next slot.
+__global__ __launch_bounds__(kSweepBlock) void k_sweep_scan(u32* __restrict__ tile_cnt,
+                                                            u64* __restrict__ tile_bytes,
+                                                            u32 ntiles, u64* ctr) {
+  __shared__ u32 wn[kSweepBlock / 64];
+  __shared__ u64 wb[kSweepBlock / 64];
+  const u32 wv = threadIdx.x >> 6;
+  u64 carry_n = 0, carry_b = 0;
+  for (u32 base = 0; base < ntiles; base += kSweepBlock) {
+    const u32 i = base + threadIdx.x;
+    const u32 c = i < ntiles ? tile_cnt[i] : 0u;
+    const u64 b = i < ntiles ? tile_bytes[i] : 0ull;
+    const u32 sc = wave_incl_scan(c);
+    const u64 sb = wave_incl_scan64(b);
+    if (__lane_id() == 63) { wn[wv] = sc; wb[wv] = sb; }
+    __syncthreads();
+    u64 pn = 0, pb = 0, tn = 0, tb = 0;
+    for (u32 w = 0; w < kSweepBlock / 64; ++w) {
+      if (w < wv) { pn += wn[w]; pb += wb[w]; }
+      tn += wn[w];
+      tb += wb[w];
+    }
+    if (i < ntiles) {
+      tile_cnt[i] = (u32)(carry_n + pn + sc - c);   // (at most 2^31 slots: the u32 holds)
+      tile_bytes[i] = carry_b + pb + sb - b;
+    }
+    carry_n += tn;
+    carry_b += tb;
+    __syncthreads();   // (the totals are read before the next chunk overwrites them)
+  }
+  if (threadIdx.x == 0) {
+    ctr[kSwN] = carry_n;
+    ctr[kSwBytes] = carry_b;
+    ctr[kSwNext] = ~0ull;
+    ctr[kSwErr] = 0;
+  }
+}
+
+// Stores: whole 8-byte words wherever eight bytes of the datagram are left
+// (neither side aligned: the datagrams are byte-packed; the compiler's
+// unaligned accesses, as in k_evict_move), single bytes for the rest, so no
+// lane writes outside its own datagram.  PHIP_SWEEP_BYTE_STORES=1 builds the
+// per-byte form k_export has (DESIGN.md §3.9 has both numbers).
+#ifndef PHIP_SWEEP_BYTE_STORES
+#define PHIP_SWEEP_BYTE_STORES 0
+#endif
+__device__ inline void sweep_put8(u8* d, u64 w) {
+#if PHIP_SWEEP_BYTE_STORES
+#pragma unroll
+  for (u32 k = 0; k < 8; ++k) d[k] = (u8)(w >> (8 * k));
+#else
+  __builtin_memcpy(d, &w, 8);
+#endif
+}
+
+// Write pass, one workgroup per tile, its 4096 slots in eight steps of 512
+// consecutive slots.  A step packs (qualifies << 19 | bytes) per lane (a step
+// holds at most 1024 * 256 = 2^18 bytes), scans it per wave and adds the
+// totals of the waves before it through LDS (two buffers by step parity: one
+// barrier a step); the running totals of the steps stay in registers.  With
+// the tile's bases that is every record's rank and start byte.  Record `rank`
+// is written iff rank < max_msgs and its end <= budget; it stores its
+// datagram and offs[rank + 1] = its end (thread 0 of tile 0 stores offs[0]),
+// so offs[n] is the last written record's.  The first record not written is
+// the one whose predecessor was (or rank 0): it alone stores n, bytes and its
+// slot over the totals k_sweep_scan left -- no atomics.  A tile whose base
+// rank is above max_msgs holds neither a written record nor that one, and
+// returns at once.
+__global__ __launch_bounds__(kSweepBlock) void k_sweep_write(
+    const Rec* __restrict__ recs, const u8* __restrict__ arena, u64 arena_used, u64 s0, u64 s_end,
+    i64 now, i64 idle_ns, const u32* __restrict__ tile_cnt, const u64* __restrict__ tile_bytes,
+    u32 max_msgs, u64 budget, u8* __restrict__ out, u64* __restrict__ offs, u64* ctr) {
+  __shared__ u32 wtot[2][kSweepBlock / 64];
+  u64 rank0 = tile_cnt[blockIdx.x];
+  u64 byte0 = tile_bytes[blockIdx.x];
+  if (blockIdx.x == 0 && threadIdx.x == 0) offs[0] = 0;
+  if (rank0 > max_msgs) return;
+  const u32 wv = threadIdx.x >> 6;
+  const u64 t0 = s0 + (u64)blockIdx.x * kSweepTile;
+  for (u32 k = 0; k < kSweepTile / kSweepBlock; ++k) {
+    const u64 s = t0 + (u64)k * kSweepBlock + threadIdx.x;
+    Rec r{};
+    u32 sz = 0;
+    if (s < s_end) {
+      r = load_rec(&recs[s]);
+      sz = sweep_size(r, now, idle_ns);
+    }
+    const u32 v = sz ? (1u << 19) | sz : 0u;
+    const u32 sc = wave_incl_scan(v);
+    if (__lane_id() == 63) wtot[k & 1][wv] = sc;
+    __syncthreads();   // (no thread leaves the loop early: every step has its barrier)
+    u32 pre = 0, tot = 0;
+#pragma unroll
+    for (u32 w = 0; w < kSweepBlock / 64; ++w) {
+      const u32 x = wtot[k & 1][w];
+      if (w < wv) pre += x;
+      tot += x;
+    }
+    const u32 ex = pre + sc - v;
+    const u64 rank = rank0 + (ex >> 19);
+    const u64 start = byte0 + (ex & 0x7FFFFu);
+    rank0 += tot >> 19;
+    byte0 += tot & 0x7FFFFu;
+    if (!sz) continue;
+    const u64 end = start + sz;
+    if (rank >= max_msgs || end > budget) {
+      if (rank == 0 || (rank - 1 < max_msgs && start <= budget)) {
+        ctr[kSwN] = rank;
+        ctr[kSwBytes] = start;
+        ctr[kSwNext] = s;
+      }
+      continue;
+    }
+    offs[rank + 1] = end;
+    u8* d = out + start;
+    sweep_put8(d, __builtin_bswap64(dec_f64(r.added)));
+    sweep_put8(d + 8, __builtin_bswap64(dec_f64(r.taken)));
+    sweep_put8(d + 16, __builtin_bswap64((u64)r.elapsed));
+    const u32 len = sz - PHIP_BUCKET_FIXED_SIZE;
+    d[24] = (u8)len;
+    d += PHIP_BUCKET_FIXED_SIZE;
+    if (len <= kInlineName) {
+      // name byte j is byte j + 2 of the canonical words
+      const u64 w[4] = {r.name0, r.name1, r.name2, 0};
+      u32 j = 0;
+#pragma unroll
+      for (u32 q = 0; q < 3; ++q)
+        if (j + 8 <= len) {
+          sweep_put8(d + j, (w[q] >> 16) | (w[q + 1] << 48));
+          j += 8;
+        }
+      for (; j < len; ++j) d[j] = (u8)(w[(j + 2) >> 3] >> (((j + 2) & 7) * 8));
+    } else {
+      const u64 oa = r.name0 >> 32;
+      if (oa + len > arena_used) {
+        ctr[kSwErr] = 1;
+        continue;
+      }
+      u32 j = 0;
+      for (; j + 8 <= len; j += 8) {
+        u64 x;
+        __builtin_memcpy(&x, arena + oa + j, 8);
+        sweep_put8(d + j, x);
+      }
+      for (; j < len; ++j) d[j] = arena[oa + j];
+    }
+  }
+}
+
 }  // namespace phip

@@ -311,6 +311,76 @@ class GPURepo:
         self._check(rc)
         return _evict_dict(st)
 
+    # ------------------------------------------------------------- sweep --
+    @staticmethod
+    def _sweep_cursor(cursor):
+        return _lib.phip_sweep_cursor(*(cursor or (0, 0)))
+
+    @staticmethod
+    def _sweep_dict(st) -> dict:
+        return {k: int(getattr(st, k)) for k, _ in _lib.phip_sweep_stats._fields_}
+
+    def export_sweep(self, cursor=None, max_msgs: int = 1 << 16, out_cap: int | None = None,
+                     now: int = 0, idle_ns: int = 0):
+        """One call of the anti-entropy sweep (phip_export_sweep): the next
+        window of the table as MarshalBinary datagrams (bucket.go:51-68), at
+        most max_msgs of them in at most out_cap bytes (default 256 each).
+        Zero states are skipped; idle_ns > 0 also skips the buckets
+        evict_idle(now, idle_ns) would evict.  cursor: None to start, then
+        the one the last call returned.  -> (datagrams, cursor, stats dict(n,
+        bytes, slots_scanned, done, restarted)); loop until stats["done"]."""
+        if out_cap is None:
+            out_cap = _lib.PACKET_SIZE * max_msgs
+        cur, st = self._sweep_cursor(cursor), _lib.phip_sweep_stats()
+        out = np.zeros(max(int(out_cap), 1), np.uint8)
+        offs = np.zeros(int(max_msgs) + 1, np.uint64)
+        rc = self.L.phip_export_sweep(self.h, C.byref(cur), int(now), int(idle_ns),
+                                      out.ctypes.data, int(out_cap), offs.ctypes.data,
+                                      int(max_msgs), C.byref(st), 0)
+        self._queued = None   # a queued batch is finished (or failed)
+        self._check(rc)
+        raw = out[:int(st.bytes)].tobytes()
+        dgs = [raw[int(offs[i]):int(offs[i + 1])] for i in range(int(st.n))]
+        d = self._sweep_dict(st)
+        d["offs"] = offs[:int(st.n) + 1]
+        return dgs, (int(cur.slot), int(cur.layout)), d
+
+    def export_sweep_device(self, out, offs, cursor, max_msgs: int, now: int = 0,
+                            idle_ns: int = 0):
+        """phip_export_sweep with device pointers: out (uint8 CUDA tensor, 8-byte
+        aligned, a multiple of 8 bytes; the byte budget is its size - 8), offs
+        (int64[max_msgs + 1]).  Both can go unchanged into another repo's
+        receive_datagrams_device.  -> (n, cursor, stats dict)."""
+        cur, st = self._sweep_cursor(cursor), _lib.phip_sweep_stats()
+        cap = int(out.numel() * out.element_size())
+        rc = self.L.phip_export_sweep(self.h, C.byref(cur), int(now), int(idle_ns), _ptr(out), cap,
+                                      _ptr(offs), int(max_msgs), C.byref(st), DEVICE_PTRS)
+        self._queued = None
+        self._check(rc)
+        return int(st.n), (int(cur.slot), int(cur.layout)), self._sweep_dict(st)
+
+    def sweep_count(self, now: int = 0, idle_ns: int = 0) -> dict:
+        """What a whole sweep under this filter would write (PHIP_SWEEP_COUNT):
+        dict(n, bytes, ...), to size buffers by."""
+        cur, st = _lib.phip_sweep_cursor(), _lib.phip_sweep_stats()
+        rc = self.L.phip_export_sweep(self.h, C.byref(cur), int(now), int(idle_ns), None, 0, None,
+                                      0, C.byref(st), _lib.SWEEP_COUNT)
+        self._queued = None
+        self._check(rc)
+        return self._sweep_dict(st)
+
+    def sweep(self, max_msgs: int = 1 << 16, out_cap: int | None = None, now: int = 0,
+              idle_ns: int = 0):
+        """Generator over a whole sweep: yields (datagrams, stats) per call
+        until the cursor reaches the end of the table (a rebuild in between
+        starts it over, stats["restarted"])."""
+        cursor = None
+        while True:
+            dgs, cursor, st = self.export_sweep(cursor, max_msgs, out_cap, now, idle_ns)
+            yield dgs, st
+            if st["done"]:
+                return
+
     def dump_arrays(self):
         """Every bucket as arrays (unordered): (names uint8, offs uint64[n+1],
         added bits, taken bits, elapsed, created) -- for tables too large for
