@@ -8,7 +8,7 @@
 //                 -> run-length segments
 //                 -> k_fold_thread / k_fold_wave / k_fold_block (stream2)
 // Everything runs on the handle's own HIP stream; host synchronisation only
-// reads back small counters (miss count, segment count) between stages.
+// reads back small counters (phip_kernels.hpp "counter words") between stages.
 #include <sys/random.h>
 
 #include <chrono>
@@ -95,10 +95,12 @@ struct phip_handle {
   // kOptBackoff fast passes overflowed its undo log (opt_left counts down).
   bool classify_first = false;
   u32 opt_left = 0;
-  uint64_t stats[6] = {0, 0, 0, 0, 0, 0};   // last fast batch: hot entries, hot hits, misses,
-                                            // messages it sent through the ordered path; last
-                                            // optimistic pass: log entries, messages that
-                                            // found the log full
+  struct LastStats {   // phip_last_stats lays them out
+    uint64_t hot_entries = 0, hot_hits = 0, misses = 0;   // last fast batch
+    uint64_t ordered = 0;    // messages it sent through the ordered path
+    uint64_t log_count = 0, log_over = 0;   // last optimistic pass: log entries, messages
+                                            // that found the log full
+  } stats;
   hipStream_t stream = nullptr;      // the stream every call runs on (own_stream or the caller's)
   hipStream_t own_stream = nullptr;  // created by phip_open
   hipStream_t stream2 = nullptr;   // second stream: the hot-bucket fold overlaps the others
@@ -253,11 +255,8 @@ struct Launch {
   }
 };
 
-// Device counters: ctr[0..15] u32 per batch (k_batch_reset), ctr[16..17] one
-// u64 scratch sum (k_list_long_bytes).
-constexpr u32 kCtrWords = 32;
-constexpr u32 kCtrLongBytes = 16;
-
+// Device counters (phip_kernels.hpp "counter words"): the general set to the
+// host's mirror.
 int read_ctr(phip_handle* h) {
   HIPCHK(h, hipMemcpyAsync(h->ctr_host, h->ctr, kCtrWords * sizeof(u32), hipMemcpyDeviceToHost,
                            h->stream));
@@ -266,9 +265,6 @@ int read_ctr(phip_handle* h) {
 }
 
 int reset_ctr(phip_handle* h) {
-  // ctr[5] = first short datagram, ctr[kCtrDirty] = first dirty message
-  // (phip_kernels.hpp): both start at "none", the rest at zero.
-  static_assert(kCtrDirty == 12, "k_batch_reset");
   k_batch_reset<<<1, kShards, 0, h->stream>>>(h->ctr, nullptr);
   HIPCHK(h, hipGetLastError());
   return PHIP_OK;
@@ -277,9 +273,17 @@ int reset_ctr(phip_handle* h) {
 int check_flags(phip_handle* h) {
   if (h->ctr_host[kCtrBadName])
     return set_err(h, PHIP_ERR_INVALID, "malformed name offsets (names_len check): nothing applied");
-  if (h->ctr_host[8]) return set_err(h, PHIP_ERR_FULL, "hash table full (probe wrapped)");
-  if (h->ctr_host[7]) return set_err(h, PHIP_ERR_ARENA, "long-name arena exhausted");
+  if (h->ctr_host[kCtrTableFull]) return set_err(h, PHIP_ERR_FULL, "hash table full (probe wrapped)");
+  if (h->ctr_host[kCtrArenaFull]) return set_err(h, PHIP_ERR_ARENA, "long-name arena exhausted");
   return PHIP_OK;
+}
+
+// A stats call's words into the caller's array of `max`; returns how many.
+template <int N>
+int copy_words(const uint64_t (&v)[N], uint64_t* out, int max) {
+  int k = 0;
+  for (; k < max && k < N; ++k) out[k] = v[k];
+  return k;
 }
 
 // Every entry point binds the handle's device first: Go goroutines migrate
@@ -362,7 +366,7 @@ int grow_table(phip_handle* h, u32 newL) {
   };
   if (hipMemsetAsync(nrecs, 0, ncap * sizeof(Rec), h->stream) != hipSuccess ||
       hipMemsetAsync(naux, 0, ncap * sizeof(u32), h->stream) != hipSuccess ||
-      hipMemsetAsync(h->ctr + 8, 0, sizeof(u32), h->stream) != hipSuccess)
+      hipMemsetAsync(h->ctr + kCtrTableFull, 0, sizeof(u32), h->stream) != hipSuccess)
     return drop_new(set_err(h, PHIP_ERR_HIP, "table growth: clearing the new table failed"));
   Table nt = table(h);
   nt.recs = nrecs;
@@ -376,7 +380,8 @@ int grow_table(phip_handle* h, u32 newL) {
     return drop_new(set_err(h, PHIP_ERR_HIP, "k_rehash launch failed"));
   int rc;
   if ((rc = read_ctr(h))) return drop_new(rc);   // synchronises: the old table is no longer read
-  if (h->ctr_host[8]) return drop_new(set_err(h, PHIP_ERR_INVALID, "internal: rehash probe wrapped"));
+  if (h->ctr_host[kCtrTableFull])
+    return drop_new(set_err(h, PHIP_ERR_INVALID, "internal: rehash probe wrapped"));
   HIPCHK(h, hipFree(h->recs));
   HIPCHK(h, hipFree(h->aux));
   h->recs = nrecs;
@@ -487,10 +492,10 @@ int insert_names(phip_handle* h, Src src, u32* list, u32 nlist, const int64_t* n
       (rc = ensure(h, B_RETRY, nlist, &retry)))
     return rc;
   u32 total = 0, ncur = nlist;
-  // ctr[3] counts this call's claims (B_CSLOT/B_CMSG positions): a batch can
-  // run the pipeline twice (finish_many_misses, resolve_all), so it starts
+  // kCtrClaimed counts this call's claims (B_CSLOT/B_CMSG positions): a batch
+  // can run the pipeline twice (finish_many_misses, resolve_all), so it starts
   // from zero here, not at the batch's reset_ctr.
-  HIPCHK(h, hipMemsetAsync(h->ctr + 3, 0, sizeof(u32), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->ctr + kCtrClaimed, 0, sizeof(u32), h->stream));
   // Swap buffers between rounds: round k reads `cur`, writes retries to `nxt`.
   u32* nxt = retry;
   u32* spare = nullptr;
@@ -499,8 +504,7 @@ int insert_names(phip_handle* h, Src src, u32* list, u32 nlist, const int64_t* n
   // name met a slot claimed in that same round), so this terminates; with a
   // 64-bit tag a second round is already rare.
   while (ncur > 0) {
-    // ctr[3] is the running claimed count (cumulative), ctr[4] the retry count.
-    HIPCHK(h, hipMemsetAsync(h->ctr + 4, 0, sizeof(u32), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->ctr + kCtrRetry, 0, sizeof(u32), h->stream));
     {
       Launch l(h, "k_claim");
       k_claim<Src><<<grid_for(ncur), kBlock, 0, h->stream>>>(src, ncur, cur, table(h), cslot, cmsg,
@@ -508,7 +512,7 @@ int insert_names(phip_handle* h, Src src, u32* list, u32 nlist, const int64_t* n
     }
     HIPCHK(h, hipGetLastError());
     if ((rc = read_ctr(h))) return rc;
-    u32 claimed_total = h->ctr_host[3];
+    u32 claimed_total = h->ctr_host[kCtrClaimed];   // (cumulative over the rounds)
     u32 fresh = claimed_total - total;
     // The round's claims are published before any error is reported.
     if (fresh) {
@@ -521,7 +525,7 @@ int insert_names(phip_handle* h, Src src, u32* list, u32 nlist, const int64_t* n
     h->n_buckets += fresh;
     total = claimed_total;
     *n_claimed = total;
-    ncur = h->ctr_host[4];
+    ncur = h->ctr_host[kCtrRetry];
     if ((rc = check_flags(h))) return rc;
     if (fresh == 0 && ncur != 0)
       return set_err(h, PHIP_ERR_INVALID, "internal: insert round made no progress");
@@ -614,12 +618,6 @@ inline unsigned fast_grid(phip_handle* h, u32 n) { return fast_grid_on((u32)h->n
 
 int join_hot(phip_handle* h, const HotHdr* hot);
 
-// The fast path over a batch input (SoaIn or WireIn; hsrc: its names for the
-// hot-directory sample).  Resets the batch's counters, classifies, builds the
-// hot directory on stream2 and applies the batch's clean prefix: the messages
-// before the first dirty one (*first_dirty; n if none) and before the first
-// malformed datagram (ctr[5]).  The prefix's misses (*nmiss of them) are
-// listed in B_MISS.
 // A sharded append list over `units` units of up to `per_unit` entries
 // (counters zeroed on the stream).
 int sharded(phip_handle* h, BufId base_id, u32 units, u32 per_unit, Sharded* out,
@@ -644,7 +642,7 @@ int pack_sharded(phip_handle* h, const Sharded& sh, u32 total_slot, u32* out, u3
   *total = h->ctr_host[total_slot];
   if (*total) {
     Launch l(h, "k_shard_compact");
-    dim3 grid(grid_for(h->ctr_host[13]), kShards);
+    dim3 grid(grid_for(h->ctr_host[kCtrShardMax]), kShards);
     k_shard_compact<<<grid, 256, 0, h->stream>>>(sh.base, sh.cap, sh.cnt, out);
     HIPCHK(h, hipGetLastError());
   }
@@ -774,20 +772,22 @@ int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront*
   u32 *c, *dlist = nullptr;
   DirtySet dset;
   if ((rc = ensure(h, B_FSCNT, 4 * kShards, &c))) return rc;
+  // the pass's counter set and shard counters (the other parity's); their
+  // reset is the first thing either kind of pass puts on the stream
+  ff->par = h->fpar ^= 1u;
+  ff->c = fctr(h, ff->par);
+  ++h->nfast;
+  if (reset) {
+    k_batch_reset<<<1, kShards, 0, h->stream>>>(ff->c, fast_counts(h, ff->par));
+    HIPCHK(h, hipGetLastError());
+  }
   if constexpr (In::kSoa) {
     if (opt && iso < 0 && opt_allowed(h)) {
       u32* lc;
       const size_t nw = undo_counts(h);
       if ((rc = ensure(h, B_ULCNT, nw, &lc))) return rc;
       ff->opt = true;
-      ff->par = h->fpar ^= 1u;
-      ff->c = fctr(h, ff->par);
       ff->log.cnt = lc;
-      ++h->nfast;
-      if (reset) {
-        k_batch_reset<<<1, kShards, 0, h->stream>>>(ff->c, fast_counts(h, ff->par));
-        HIPCHK(h, hipGetLastError());
-      }
       // (the directory chain waits for the batch's producers only, not for
       // the fills)
       if (n >= kHotMinBatch) HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
@@ -810,13 +810,6 @@ int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront*
       if ((rc = ensure(h, B_DMARK, n, &ff->mark))) return rc;
       HIPCHK(h, hipMemsetAsync(ff->mark, 0, n, h->stream));
     }
-  }
-  ff->par = h->fpar ^= 1u;
-  ff->c = fctr(h, ff->par);
-  ++h->nfast;
-  if (reset) {
-    k_batch_reset<<<1, kShards, 0, h->stream>>>(ff->c, fast_counts(h, ff->par));
-    HIPCHK(h, hipGetLastError());
   }
   const bool with_hot = n >= kHotMinBatch;
   // A small batch classifies in a few µs, less than the directory chain
@@ -912,7 +905,7 @@ int fast_back(phip_handle* h, In in, u32 n, FastFront& ff, bool queued) {
         SubOut{sb.off, sb.len, sb.a, sb.t, sb.e, sb.map, kSubBatchCap}, msh.cnt, h->ctr_map,
         kCtrWords, queued ? fast_counts(h, ff.par ^ 1u) : nullptr, fctr(h, ff.par ^ 1u));
   } else {
-    k_shard_scan<<<1, kShards, 0, h->stream>>>(msh.cnt, ff.c, 2, h->ctr_map, kCtrWords,
+    k_shard_scan<<<1, kShards, 0, h->stream>>>(msh.cnt, ff.c, kCtrMiss, h->ctr_map, kCtrWords,
                                                queued ? fast_counts(h, ff.par ^ 1u) : nullptr,
                                                fctr(h, ff.par ^ 1u));
   }
@@ -941,10 +934,10 @@ constexpr u32 kOptBackoff = 256;
 // met a dirty message or a malformed name entry, or its log overflowed, and
 // it has to be undone.
 bool opt_failed(phip_handle* h, u32 n) {
-  h->stats[4] = h->ctr_host[kCtrLogCount];
-  h->stats[5] = h->ctr_host[kCtrLogOver];
-  if (h->stats[5]) h->opt_left = kOptBackoff;
-  return h->ctr_host[kCtrDirty] < n || h->ctr_host[5] < n || h->stats[5] != 0;
+  h->stats.log_count = h->ctr_host[kCtrLogCount];
+  h->stats.log_over = h->ctr_host[kCtrLogOver];
+  if (h->stats.log_over) h->opt_left = kOptBackoff;
+  return h->ctr_host[kCtrDirty] < n || h->ctr_host[kCtrStop] < n || h->stats.log_over != 0;
 }
 
 // A failed optimistic pass undone: every record it touched back to its state
@@ -963,12 +956,12 @@ int fast_collect(phip_handle* h, u32 n, u32 par, u32* first_dirty, u32* nmiss, b
   int rc;
   if ((rc = check_flags(h))) return rc;
   if (!opt_ran && h->opt_left) --h->opt_left;
-  *nmiss = h->ctr_host[2];
+  *nmiss = h->ctr_host[kCtrMiss];
   if (*nmiss) {
     Sharded msh;
     if ((rc = fast_shards(h, n, par, &msh))) return rc;
     Launch l(h, "k_shard_compact");
-    dim3 grid(grid_for(h->ctr_host[13]), kShards);
+    dim3 grid(grid_for(h->ctr_host[kCtrShardMax]), kShards);
     k_shard_compact<<<grid, 256, 0, h->stream>>>(msh.base, msh.cap, msh.cnt,
                                                  (u32*)h->buf[B_MISS].p);
     HIPCHK(h, hipGetLastError());
@@ -980,10 +973,10 @@ int fast_collect(phip_handle* h, u32 n, u32 par, u32* first_dirty, u32* nmiss, b
   else if (h->iso_left) --h->iso_left;
   h->coll_iso = iso_ran;
   h->ndef = iso ? h->ctr_host[kCtrNDefer] : 0;   // (the ordered sub-batch, run_deferred)
-  h->stats[3] = 0;   // (finish_receive: the messages it sends through the ordered path)
-  h->stats[0] = h->ctr_host[11];
-  h->stats[1] = h->ctr_host[10];
-  h->stats[2] = *nmiss;
+  h->stats.ordered = 0;   // (finish_receive: the messages it sends through the ordered path)
+  h->stats.hot_entries = h->ctr_host[kCtrHotEntries];
+  h->stats.hot_hits = h->ctr_host[kCtrHotHits];
+  h->stats.misses = *nmiss;
   return PHIP_OK;
 }
 
@@ -991,7 +984,7 @@ int fast_collect(phip_handle* h, u32 n, u32 par, u32* first_dirty, u32* nmiss, b
 // hot-directory sample), synchronously: resets the batch's counters,
 // classifies, builds the hot directory on stream2 and applies the batch's
 // clean prefix: the messages before the first dirty one (*first_dirty; n if
-// none) and before the first malformed datagram (ctr[5]).  The prefix's
+// none) and before the first malformed datagram (kCtrStop).  The prefix's
 // misses (*nmiss of them) are listed in B_MISS.
 // opt: the pass may be optimistic (fast_front); one that fails is undone here
 // and the batch run again, classified, under the policy as it stood.
@@ -1032,7 +1025,7 @@ int dedupe_names(phip_handle* h, Src src, const u32* list, u32 n, u32** out, u32
     k_dedupe<Src><<<grid_for(n), kBlock, 0, h->stream>>>(src, n, list, table(h), set, setbits, dsh);
     HIPCHK(h, hipGetLastError());
   }
-  return pack_sharded(h, dsh, 14, *out, nout);
+  return pack_sharded(h, dsh, kCtrAux, *out, nout);
 }
 
 // Many misses (an insert-heavy batch: a node starting empty, a fresh key
@@ -1093,7 +1086,7 @@ int finish_misses(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t,
   u32* miss = (u32*)h->buf[B_MISS].p;
   u32 n_claimed = 0;
   if ((rc = insert_names(h, src, miss, nmiss, nullptr, now, &n_claimed))) return rc;
-  HIPCHK(h, hipMemsetAsync(h->ctr + 2, 0, sizeof(u32), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->ctr + kCtrMiss, 0, sizeof(u32), h->stream));
   u32* miss2;
   if ((rc = ensure(h, B_MISS2, nmiss, &miss2))) return rc;
   {
@@ -1109,7 +1102,8 @@ int finish_misses(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t,
   }
   HIPCHK(h, hipGetLastError());
   if ((rc = read_ctr(h))) return rc;
-  if (h->ctr_host[2]) return set_err(h, PHIP_ERR_INVALID, "internal: %u names missing after insert", h->ctr_host[2]);
+  if (const u32 left = h->ctr_host[kCtrMiss])
+    return set_err(h, PHIP_ERR_INVALID, "internal: %u names missing after insert", left);
   return clear_new(h, n_claimed);
 }
 
@@ -1177,7 +1171,7 @@ int resolve_all(phip_handle* h, Src src, u32 n, const int64_t* now_arr, i64 now0
   }
   HIPCHK(h, hipGetLastError());
   u32 nmiss = 0;
-  if ((rc = pack_sharded(h, rsh, 2, miss, &nmiss))) return rc;
+  if ((rc = pack_sharded(h, rsh, kCtrMiss, miss, &nmiss))) return rc;
   if ((rc = check_flags(h))) return rc;
   *n_claimed = 0;
   bool grew = false;
@@ -1197,7 +1191,7 @@ int resolve_all(phip_handle* h, Src src, u32 n, const int64_t* now_arr, i64 now0
                                                                  r2, h->ctr, SortVals{});
     }
     HIPCHK(h, hipGetLastError());
-    if ((rc = pack_sharded(h, r2, 2, miss, &nmiss))) return rc;
+    if ((rc = pack_sharded(h, r2, kCtrMiss, miss, &nmiss))) return rc;
   }
   if (nmiss) {
     u32 more = 0;
@@ -1307,7 +1301,7 @@ int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow)
     if ((rc = read_ctr(h))) return rc;
     nseg = h->ctr_host[kCtrSegs];
   }
-  u32 nlong = h->ctr_host[6], nhuge = h->ctr_host[9];
+  u32 nlong = h->ctr_host[kCtrLongSegs], nhuge = h->ctr_host[kCtrHugeSegs];
   if ((rc = pack_join.join())) return rc;
   // Different segments touch different slots, so the folds may overlap: the
   // hot-bucket workgroups run on stream2 beside the wave and thread folds.
@@ -1460,10 +1454,10 @@ int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow)
       u32* lng2;
       if ((rc = ensure(h, B_LONG2, nlong, &lng2))) return rc;
       size_t tb7 = 0;
-      HIPCHK(h, rocprim::partition(nullptr, tb7, lng, lng2, h->ctr + 14, (size_t)nlong,
+      HIPCHK(h, rocprim::partition(nullptr, tb7, lng, lng2, h->ctr + kCtrAux, (size_t)nlong,
                                    BigLongSeg{scnt}, h->stream));
       if ((rc = ensure(h, B_TEMP, tb7, &temp))) return rc;
-      HIPCHK(h, rocprim::partition(temp, tb7, lng, lng2, h->ctr + 14, (size_t)nlong,
+      HIPCHK(h, rocprim::partition(temp, tb7, lng, lng2, h->ctr + kCtrAux, (size_t)nlong,
                                    BigLongSeg{scnt}, h->stream));
       lng = lng2;
     }
@@ -1584,10 +1578,10 @@ int run_deferred(phip_handle* h, Src src, i64 now, const OutView& ow) {
   // (kSubBatchOver included: dirty_finish counted more entries than the
   // sub-batch holds and wrote none)
   if (nd > kSubBatchCap) {
-    h->stats[3] = 0;
+    h->stats.ordered = 0;
     return set_err(h, PHIP_ERR_HIP, "ordered sub-batch over its %u entries", kSubBatchCap);
   }
-  h->stats[3] = nd;
+  h->stats.ordered = nd;
   if (nd == 0) return PHIP_OK;
   int rc;
   SubBatch sb;
@@ -1624,7 +1618,7 @@ int finish_receive(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t
   if ((rc = finish_misses(h, src, a, t, e, nmiss, std::min(stop, first_dirty), now, ow.status)))
     return rc;
   if (deferred) return run_deferred(h, src, now, ow);
-  h->stats[3] = first_dirty < stop ? stop - first_dirty : 0;
+  h->stats.ordered = first_dirty < stop ? stop - first_dirty : 0;
   if (first_dirty >= stop) return PHIP_OK;
   const u32 k = first_dirty;
   OpView ov{};
@@ -1634,17 +1628,23 @@ int finish_receive(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t
   return ordered(h, shifted(src, k), stop - k, ov, shifted(ow, k));
 }
 
+// Statuses of a batch that stopped at message `stop` (kCtrStop), as the Go
+// loop exits at a short datagram (repo.go:70-74): that message reads
+// PHIP_ST_SHORT, every later one PHIP_ST_NOT_PROCESSED.
+int fill_stopped(phip_handle* h, u8* status, u32 n, u32 stop) {
+  if (!status || stop >= n) return PHIP_OK;
+  HIPCHK(h, hipMemsetAsync(status + stop, PHIP_ST_NOT_PROCESSED, n - stop, h->stream));
+  HIPCHK(h, hipMemsetAsync(status + stop, PHIP_ST_SHORT, 1, h->stream));
+  return PHIP_OK;
+}
+
 // A checked batch (names_len) whose first malformed name entry is message
-// `stop` < n (k_classify_soa2, ctr[5]) stopped there, as the Go loop stops at
-// a short datagram (repo.go:70-74): that message reads PHIP_ST_SHORT, every
-// later one PHIP_ST_NOT_PROCESSED, and the call returns PHIP_ERR_INVALID.
+// `stop` < n (k_classify_soa2) stopped there: the call returns
+// PHIP_ERR_INVALID.
 int stopped_at_bad_name(phip_handle* h, const OutView& ow, u32 n, u32 stop) {
   if (stop >= n) return PHIP_OK;
-  if (ow.status) {
-    HIPCHK(h, hipMemsetAsync(ow.status + stop, PHIP_ST_NOT_PROCESSED, n - stop, h->stream));
-    HIPCHK(h, hipMemsetAsync(ow.status + stop, PHIP_ST_SHORT, 1, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
+  if (int rc = fill_stopped(h, ow.status, n, stop)) return rc;
+  if (ow.status) HIPCHK(h, hipStreamSynchronize(h->stream));
   return set_err(h, PHIP_ERR_INVALID,
                  "malformed name offsets at message %u (names_len check): the batch stopped there",
                  stop);
@@ -1662,7 +1662,7 @@ int receive_decoded(phip_handle* h, Src src, const uint64_t* a, const uint64_t* 
   u32 fd = n, nmiss = 0;
   if ((rc = fast_apply(h, SoaIn<Src>{src, a, t, e}, src, n, ow.status, &fd, &nmiss, -1, opt)))
     return rc;
-  const u32 stop = std::min<u32>(h->ctr_host[5], n);   // (a checked batch's malformed entry)
+  const u32 stop = std::min<u32>(h->ctr_host[kCtrStop], n);   // (a checked batch's malformed entry)
   if ((rc = finish_receive(h, src, a, t, e, stop, fd, nmiss, now, ow, n, h->ndef != 0)))
     return rc;
   return stopped_at_bad_name(h, ow, n, stop);
@@ -1691,7 +1691,7 @@ int finish_pending(phip_handle* h, bool* worked) {
     return PHIP_OK;
   }
   if ((rc = fast_collect(h, p.n, p.par, &fd, &nmiss, p.iso, p.opt))) return rc;
-  const u32 stop = std::min<u32>(h->ctr_host[5], p.n);   // (a checked batch's malformed entry)
+  const u32 stop = std::min<u32>(h->ctr_host[kCtrStop], p.n);   // (a checked batch's malformed entry)
   const bool deferred = h->ndef != 0;
   if (nmiss == 0 && fd >= stop && !deferred) return stopped_at_bad_name(h, p.ow, p.n, stop);
   if (worked) *worked = true;
@@ -2465,13 +2465,13 @@ int phip_dump(phip_handle* h, uint8_t* names, uint64_t names_cap, uint64_t* name
   k_dump_collect<<<grid_for(h->cap), kBlock, 0, h->stream>>>(h->recs, h->cap, nullptr, h->ctr);
   HIPCHK(h, hipGetLastError());
   if ((rc = read_ctr(h))) return rc;
-  const u32 occupied = h->ctr_host[2];
+  const u32 occupied = h->ctr_host[kCtrOccupied];
   if ((rc = ensure(h, B_DUMP, (size_t)occupied + 1, &list))) return rc;
   if ((rc = reset_ctr(h))) return rc;
   k_dump_collect<<<grid_for(h->cap), kBlock, 0, h->stream>>>(h->recs, h->cap, list, h->ctr);
   HIPCHK(h, hipGetLastError());
   if ((rc = read_ctr(h))) return rc;
-  u32 n = h->ctr_host[2];
+  u32 n = h->ctr_host[kCtrOccupied];
   if (n != occupied) return set_err(h, PHIP_ERR_INVALID, "internal: table changed during dump");
   Rec* d_out;
   if ((rc = ensure(h, B_TEMP, (size_t)n * sizeof(Rec), (u8**)&d_out))) return rc;
@@ -2616,12 +2616,8 @@ int receive_datagrams_dev(phip_handle* h, const u8* d_bytes, const uint64_t* d_o
   if ((rc = fast_apply(h, WireIn{d_bytes, d_offs}, Datagrams{d_bytes, d_offs}, n, ow.status, &fd,
                        &nmiss)))
     return after_error(h, rc);
-  const u32 stop = std::min<u32>(h->ctr_host[5], n);
-  // Statuses of the short datagram and everything after it (the Go loop exits).
-  if (ow.status && stop < n) {
-    HIPCHK(h, hipMemsetAsync(ow.status + stop, PHIP_ST_NOT_PROCESSED, n - stop, h->stream));
-    HIPCHK(h, hipMemsetAsync(ow.status + stop, PHIP_ST_SHORT, 1, h->stream));
-  }
+  const u32 stop = std::min<u32>(h->ctr_host[kCtrStop], n);   // (the first short datagram)
+  if ((rc = fill_stopped(h, ow.status, n, stop))) return rc;
   if (fd < stop || nmiss || h->ndef) {
     uint64_t *a, *t, *no;
     int64_t* e;
@@ -3178,7 +3174,8 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
   };
   if (hipMemsetAsync(nrecs, 0, ncap * sizeof(Rec), h->stream) != hipSuccess ||
       hipMemsetAsync(naux, 0, ncap * sizeof(u32), h->stream) != hipSuccess ||
-      hipMemsetAsync(h->ctr + 7, 0, 2 * sizeof(u32), h->stream) != hipSuccess)
+      // (both flags: kCtrTableFull is the next word)
+      hipMemsetAsync(h->ctr + kCtrArenaFull, 0, 2 * sizeof(u32), h->stream) != hipSuccess)
     return drop_new(set_err(h, PHIP_ERR_HIP, "evict: clearing the new table failed"));
   Table nt = table(h);
   nt.recs = nrecs;
@@ -3196,8 +3193,9 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
   if (hipMemcpyAsync(c, ev, sizeof c, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
     return drop_new(set_err(h, PHIP_ERR_HIP, "evict: counter read failed"));
   if ((rc = read_ctr(h))) return drop_new(rc);   // synchronises: the old table is no longer read
-  if (h->ctr_host[8]) return drop_new(set_err(h, PHIP_ERR_INVALID, "internal: evict probe wrapped"));
-  if (h->ctr_host[7] || c[kEvCursor] != long_bytes)
+  if (h->ctr_host[kCtrTableFull])
+    return drop_new(set_err(h, PHIP_ERR_INVALID, "internal: evict probe wrapped"));
+  if (h->ctr_host[kCtrArenaFull] || c[kEvCursor] != long_bytes)
     return drop_new(set_err(h, PHIP_ERR_INVALID,
                             "internal: evict moved %llu long-name bytes, counted %llu",
                             (unsigned long long)c[kEvCursor], (unsigned long long)long_bytes));
@@ -3387,10 +3385,8 @@ int phip_table_stats(phip_handle* h, uint64_t* out, int max) {
   u64 r[2] = {0, 0};
   HIPCHK(h, hipMemcpyAsync(r, d, sizeof r, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const u64 v[4] = {h->n_buckets, h->cap, r[0], r[1]};
-  int k = 0;
-  for (; k < max && k < 4; ++k) out[k] = v[k];
-  return k;
+  const uint64_t v[4] = {h->n_buckets, h->cap, r[0], r[1]};
+  return copy_words(v, out, max);
 }
 
 int phip_last_stats(phip_handle* h, uint64_t* out, int max) {
@@ -3399,20 +3395,17 @@ int phip_last_stats(phip_handle* h, uint64_t* out, int max) {
   // a queued PHIP_RECV_ASYNC batch is finished first, so the stats are its
   // own (its error, if any, is kept for the next call that returns one)
   if (h->pend.active && !h->deferred_rc) h->deferred_rc = begin_call(h);
-  const uint64_t v[7] = {h->stats[0], h->stats[1], h->stats[2], h->grows, h->stats[3],
-                         h->stats[4], h->stats[5]};
-  int k = 0;
-  for (; k < max && k < 7; ++k) out[k] = v[k];
-  return k;
+  const phip_handle::LastStats& s = h->stats;
+  const uint64_t v[7] = {s.hot_entries, s.hot_hits,  s.misses,  h->grows,
+                         s.ordered,     s.log_count, s.log_over};   // (patrolhip.h's order)
+  return copy_words(v, out, max);
 }
 
 int phip_undo_log_layout(uint32_t n, uint32_t compute_units, uint64_t* out, int max) {
   if (!out || !compute_units) return 0;
   const UndoLayout l = undo_layout(n, compute_units);
   const uint64_t v[4] = {l.grid, l.waves, l.cap, l.halves * sizeof(u64x2)};
-  int k = 0;
-  for (; k < max && k < 4; ++k) out[k] = v[k];
-  return k;
+  return copy_words(v, out, max);
 }
 
 }  // extern "C"

@@ -217,20 +217,123 @@ struct Sharded {
   }
 };
 
-// A batch's counters in one launch: ctr[16] zero except ctr[5] (first
-// malformed datagram) and ctr[kCtrDirty] (first dirty message), which start
-// at "none"; and, when given, a sharded list's kShards counters.
+// ------------------------------------------------------- counter words ----
+// Kernels and host talk through sets of kCtrWords u32 counters, all with this
+// layout:
+//   G  the general set (phip_handle::ctr): ordered batches, inserts, the miss
+//      path, rehash, evict, dump; the host copies it back (read_ctr);
+//   F  the two fast-pass sets behind it (fctr, one per batch parity): a
+//      pass's last launch (shard_scan) stores its set into the host's mirror;
+//   P  the block of a route pack (B_ROUTE), which the host never reads.
+// ctr_host mirrors G or F, whichever was stored last; every host reader reads
+// right after its own set's store.  Per word: what it holds; W its writers;
+// R its readers; the sets it is used in.
+
+// Dirty messages listed (F); above kDirtyCap, the last of them unlisted, the
+// batch keeps the prefix rule.  W: k_classify*, k_receive_fast<Opt> (counts),
+// k_dirty_build (~0: the prefix rule after all, 0: none before the stop).
+// R: k_dirty_build, k_receive_fast, k_dirty_pass, dirty_finish, fast_collect.
+constexpr u32 kCtrNDirty = 0;
+// An ordered batch's malformed name entry (G; F keeps its 0).
+// W: k_resolve_batch.  R: check_flags.
+constexpr u32 kCtrBadName = 1;
+// Misses listed (F, G).  W: shard_scan (a miss list's total, `tot`),
+// k_receive_list (names still missing).  R: fast_collect, pack_sharded's
+// callers, finish_misses.
+constexpr u32 kCtrMiss = 2;
+// Occupied slots (G).  W: k_dump_collect.  R: phip_dump, which resets G,
+// counts and reads back in one call under the handle's lock: no batch's
+// misses are counted in between.
+constexpr u32 kCtrOccupied = kCtrMiss;
+// Slots claimed by the running insert_names call, cumulative over its rounds
+// (it zeroes the word itself: a batch may insert twice), and the round's
+// names to try again (zeroed per round) (G).  W: k_claim.  R: insert_names.
+constexpr u32 kCtrClaimed = 3;
+constexpr u32 kCtrRetry = 4;
+// Min-reduced: the first malformed datagram or name entry; the batch stops
+// there (F).  W: k_classify*, k_receive_fast<Opt>; k_decode on G, where nobody
+// reads it (it decodes below a stop already known).  R: k_dirty_build,
+// k_receive_fast, k_dirty_pass, opt_failed and the receive paths' `stop`.
+constexpr u32 kCtrStop = 5;
+// The ordered path's long and huge segments (G).  W: k_seg_count (zeroes),
+// k_seg_finish (appends).  R: ordered().
+constexpr u32 kCtrLongSegs = 6;
+constexpr u32 kCtrHugeSegs = 9;
+// An optimistic pass's undo log: messages that found their wave's region
+// full, and the pass's entries (F).  W: k_receive_fast<Opt>.  R: opt_failed.
+// They share the segment words: those kernels run on G only, this one on F
+// only.
+constexpr u32 kCtrLogOver = kCtrLongSegs;
+constexpr u32 kCtrLogCount = kCtrHugeSegs;
+// Flags: a long name past the arena's end (G; F keeps its 0), a probe that
+// wrapped round the table (F, G).  W: k_publish, k_evict_move (arena);
+// k_receive_fast, k_receive_list, k_resolve*, k_claim, k_rehash, k_evict_move
+// (table).  R: check_flags, grow_table, evict_idle.
+constexpr u32 kCtrArenaFull = 7;
+constexpr u32 kCtrTableFull = 8;
+// Messages folded in the hot directory, and the directory's entries (F).
+// W: k_receive_fast.  R: fast_collect.
+constexpr u32 kCtrHotHits = 10;
+constexpr u32 kCtrHotEntries = 11;
+// Min-reduced: the first dirty message (F, P).  W: k_classify*,
+// k_receive_fast<Opt>; k_route_count (P).  R: k_receive_fast, fast_collect,
+// opt_failed; k_route_count's recount, route_hot_n (P).
+constexpr u32 kCtrDirty = 12;
+// A sharded list's largest shard (F, G).  W: shard_scan.  R: the host's
+// k_shard_compact grids.
+constexpr u32 kCtrShardMax = 13;
+// Scratch totals (G).  W: shard_scan (the k_dedupe list's total, `tot`),
+// rocprim::partition in ordered()'s folds (its selected count, unread).
+// R: dedupe_names, which reads its total back before it returns: the
+// partition, later on the same stream, cannot reach it.
+constexpr u32 kCtrAux = 14;
+// The ordered path's segments (G).  W: k_seg_finish.  R: ordered().
+constexpr u32 kCtrSegs = 15;
+// Words [0, kCtrResetWords) start a batch at ctr_reset_value (k_batch_reset,
+// shard_scan's `next`); the words above are stored before every read.
+constexpr u32 kCtrResetWords = 16;
+// One u64: arena bytes of a list's long names (G).  W: reserve() (zeroes),
+// k_list_long_bytes.  R: reserve().
+constexpr u32 kCtrLongBytes = 16;
+// Entries of the ordered sub-batch (F).  W: dirty_finish, in every isolating
+// pass.  R: fast_collect, after such a pass.
+constexpr u32 kCtrNDefer = 18;
+// Dirty messages in the set, before the batch's stop (F).  W: k_dirty_build,
+// whenever it leaves kCtrNDirty in 1..kDirtyCap.  R: k_dirty_pass,
+// dirty_finish, only then.
+constexpr u32 kCtrNSorted = 19;
+constexpr u32 kCtrWords = 32;
+// The two min-reduced words start at "none", the rest at zero.
+__host__ __device__ constexpr u32 ctr_reset_value(u32 w) {
+  return (w == kCtrStop || w == kCtrDirty) ? ~0u : 0u;
+}
+static_assert(kCtrNDirty < kCtrResetWords && kCtrBadName < kCtrResetWords &&
+                  kCtrOccupied < kCtrResetWords && kCtrStop < kCtrResetWords &&
+                  kCtrLogOver < kCtrResetWords && kCtrLogCount < kCtrResetWords &&
+                  kCtrArenaFull < kCtrResetWords && kCtrTableFull < kCtrResetWords &&
+                  kCtrHotHits < kCtrResetWords && kCtrDirty < kCtrResetWords,
+              "the words kernels accumulate into from the batch's reset value");
+static_assert(kCtrTableFull == kCtrArenaFull + 1, "evict_idle clears both flags in one memset");
+static_assert(kCtrLongBytes % 2 == 0 && kCtrLongBytes >= kCtrResetWords &&
+              kCtrLongBytes + 2 <= kCtrWords, "an aligned u64 outside the reset");
+static_assert(kCtrNDefer >= kCtrResetWords && kCtrNDefer < kCtrWords &&
+              kCtrNSorted >= kCtrResetWords && kCtrNSorted < kCtrWords, "outside the reset");
+static_assert(kCtrResetWords <= kShards && kCtrWords <= kShards,
+              "k_batch_reset and shard_scan's host mirror: one lane per word");
+
+// A batch's counters in one launch: the first kCtrResetWords at their reset
+// values; and, when given, a sharded list's kShards counters.
 __global__ __launch_bounds__(kShards) void k_batch_reset(u32* ctr, u32* shard_cnt) {
   const u32 t = threadIdx.x;
-  if (t < 16) ctr[t] = (t == 5 || t == 12) ? ~0u : 0u;
+  if (t < kCtrResetWords) ctr[t] = ctr_reset_value(t);
   if (shard_cnt) shard_cnt[t] = 0;
 }
 
 // One workgroup of kShards lanes over a sharded list's counters: exclusive
 // offsets of the shards (into cnt[kShards + s]), the total into ctr[tot] and
-// the largest shard into ctr[13].  With `host` (the handle's pinned counter
-// mirror, mapped into the device's address space), the first `words` counter
-// words are then stored there, which ends a fast batch without a copy; with
+// the largest shard into ctr[kCtrShardMax].  With `host` (the handle's pinned
+// counter mirror, mapped into the device's address space), the first `words`
+// counter words are then stored there, which ends a fast batch without a copy; with
 // `next`, the next batch's counters (next_ctr: the other fast set) and its
 // shard counters are reset as k_batch_reset does, so a queued batch's
 // successor needs no reset launch.
@@ -262,14 +365,14 @@ __device__ inline void shard_scan(u32* cnt, u32* ctr, u32 tot, u32* host, u32 wo
   for (u32 w = 0; w < kShards / 64; ++w) mx = max(mx, wmax[w]);
   if (t == 0) {
     ctr[tot] = total;
-    ctr[13] = mx;
+    ctr[kCtrShardMax] = mx;
   }
   if (host && t < words) {
-    const u32 w = t == tot ? total : t == 13 ? mx : ctr[t];
+    const u32 w = t == tot ? total : t == kCtrShardMax ? mx : ctr[t];
     __hip_atomic_store(&host[t], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   if (next) {
-    if (t < 16) next_ctr[t] = (t == 5 || t == 12) ? ~0u : 0u;
+    if (t < kCtrResetWords) next_ctr[t] = ctr_reset_value(t);
     next[t] = 0;
   }
 }
@@ -396,13 +499,11 @@ __device__ inline int probe(const Table& T, const Name& nm, const u8* src, u32* 
 }
 
 // ----------------------------------------------------------- classify ----
-// Counter slot of the first dirty message of a Receive batch: an incast
+// kCtrDirty holds the first dirty message of a Receive batch: an incast
 // (an all-zero state asks for a reply, repo.go:78,86-90) or a -0.0 field (Go's
 // `>` and the E order disagree on +-0), the two things only the ordered path
 // handles.  The fast path applies the clean prefix before it (merges commute),
 // the ordered path the rest.
-constexpr u32 kCtrDirty = 12;
-constexpr u32 kCtrBadName = 1;   // an ordered batch's malformed name entry (k_resolve_batch)
 
 // Min-reduce the index of a wave's first dirty lane (lanes hold increasing
 // indices, so the lowest set lane has the lowest index).
@@ -434,9 +535,6 @@ __device__ inline void note_dirty(bool d, u32 i, u32* ctr) { note_min(d, i, &ctr
 // its dirty messages.  Up to kDirtyCap dirty messages with names of at most
 // kShortName bytes (the names the set compares exactly); otherwise the batch
 // keeps the prefix rule.
-constexpr u32 kCtrNDirty = 0;        // dirty messages listed (> kDirtyCap: the prefix rule)
-constexpr u32 kCtrNDefer = 18;       // entries of the ordered sub-batch (dirty_finish)
-constexpr u32 kCtrNSorted = 19;      // dirty messages in the set (before the batch's stop)
 constexpr u32 kDirtyCap = 4096;
 constexpr u32 kDirtySlots = 2 * kDirtyCap;
 // Capacity of the ordered sub-batch.  dirty_finish emits, per dirty message,
@@ -851,11 +949,11 @@ struct SoaIn {   // decoded messages (phip_receive_soa / decoded datagrams)
   // Classification (elapsed matters only when both floats are zero, so it is
   // read only then: a third of the pass's bytes on a clean batch).  A
   // malformed name entry (NamesOffs::bad, checked names only) min-reduces its
-  // index into ctr[5], as a short datagram does: the batch stops there.
+  // index into ctr[kCtrStop], as a short datagram does: the batch stops there.
   __device__ inline bool dirty(u32 i, u32* ctr) const {
     if constexpr (kOffs) {
       if (src.lim && src.bad(src.offs[i], src.offs[i + 1])) {
-        atomicMin(&ctr[5], i);
+        atomicMin(&ctr[kCtrStop], i);
         return false;
       }
     }
@@ -908,7 +1006,7 @@ struct WireIn {
     len = (u32)(h[3] >> (8 * sb)) & 0xFFu;
   }
   // Classification from the header words: a malformed datagram
-  // (io.ErrShortBuffer, bucket.go:72,84) min-reduces its index into ctr[5]
+  // (io.ErrShortBuffer, bucket.go:72,84) min-reduces its index into ctr[kCtrStop]
   // (the Go loop stops there); otherwise incast / -0.0 as SoaIn::dirty.
   __device__ inline bool dirty(u32 i, u32* ctr) const {
     const u64 o = offs[i], end = offs[i + 1], sz = end - o;
@@ -920,7 +1018,7 @@ struct WireIn {
     const u32 sb = (u32)(o & 7);
     const u32 len = (u32)(h[3] >> (8 * sb)) & 0xFFu;
     if (sz < PHIP_BUCKET_FIXED_SIZE || sz - PHIP_BUCKET_FIXED_SIZE < len) {
-      atomicMin(&ctr[5], i);
+      atomicMin(&ctr[kCtrStop], i);
       return false;
     }
     return replica_dirty(__builtin_bswap64(funnel8(h[0], h[1], sb)),
@@ -930,7 +1028,7 @@ struct WireIn {
 };
 
 // Classification of a fast batch: the first dirty message into
-// ctr[kCtrDirty], the first malformed datagram into ctr[5].  One atomic per
+// ctr[kCtrDirty], the first malformed datagram into ctr[kCtrStop].  One atomic per
 // wave that finds one, none on a clean batch.
 template <class In>
 __global__ __launch_bounds__(kBlock) void k_classify(In in, u32 n, u32* ctr, u32* dlist) {
@@ -964,7 +1062,7 @@ __global__ __launch_bounds__(1024) void k_dirty_build(In in, u32 n, u32* ctr, co
   }
   if (tid == 0) { longname = 0; nvalid = 0; }
   __syncthreads();
-  const u32 stop = min(n, ctr[5]);
+  const u32 stop = min(n, ctr[kCtrStop]);
   u32 valid = 0;
   for (u32 j = tid; j < nd; j += 1024) {
     const u32 i = dlist[j];
@@ -1081,7 +1179,7 @@ __global__ __launch_bounds__(1024) void k_dirty_build(In in, u32 n, u32* ctr, co
 // relies on: it writes no status for the messages it merges.
 // With names.lim (a caller-given blob length), the pass also checks the name
 // offsets (two more 4-byte loads per lane) and min-reduces the first
-// malformed entry into ctr[5]: the fast kernel stops there (its gate), and so
+// malformed entry into ctr[kCtrStop]: the fast kernel stops there (its gate), and so
 // does the batch (PHIP_ERR_INVALID).  Unchecked batches read no offsets (the
 // check costs the C2 step ~0.1 ms per 100M messages: a 0.4 GB stream).
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
@@ -1099,7 +1197,7 @@ __global__ __launch_bounds__(kBlock) void k_classify_soa2(const uint64_t* __rest
       b0 = names.bad(o0, o1);
       b1 = i0 + 1 < n && names.bad(o1, o2);
     }
-    note_min(b0 || b1, b0 ? i0 : i0 + 1, &ctr[5]);
+    note_min(b0 || b1, b0 ? i0 : i0 + 1, &ctr[kCtrStop]);
   }
   if (status) {   // every status starts as merged (the fast pass writes none)
     if (i0 + 1 < n && ((uintptr_t)status & 1) == 0)
@@ -1181,7 +1279,7 @@ constexpr u8 kMarkDirty = 0x40;
 // The Opt instantiation therefore runs without k_classify: it looks at the
 // replica fields it holds anyway, does not merge a dirty message (an incast,
 // a -0.0 field) or one with a malformed name entry (checked names), and
-// min-reduces their indices into ctr[kCtrDirty] / ctr[5].  A pass that found
+// min-reduces their indices into ctr[kCtrDirty] / ctr[kCtrStop].  A pass that found
 // one is a failed speculation: the host undoes it and runs the batch again
 // through the classified path.  The status column is filled by the host
 // before the pass.
@@ -1205,8 +1303,6 @@ constexpr u8 kMarkDirty = 0x40;
 #define PHIP_OPT_STATUS 0
 #endif
 constexpr bool kOptStatus = PHIP_OPT_STATUS != 0;
-constexpr u32 kCtrLogOver = 6;    // fast-pass counter set: messages that found their wave's log full
-constexpr u32 kCtrLogCount = 9;   //   and the pass's log entries
 constexpr u32 kUndoFlushReserve = 64 * ((kHotMax + kFastBlock - 1) / kFastBlock);
 struct UndoLog {
   u64x2* base = nullptr;   // waves * cap entries of two 16-byte halves
@@ -1266,7 +1362,7 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
 
   // Gate (k_classify ran before, over every message up to n): only the clean
   // prefix is applied, the messages before the first dirty one
-  // (ctr[kCtrDirty]) and before the first malformed datagram (ctr[5]); none:
+  // (ctr[kCtrDirty]) and before the first malformed datagram (ctr[kCtrStop]); none:
   // ~0.
   // (dirty buckets, decoded batches: with a dirty set, the whole batch up to
   // the first malformed message; the messages that may name a dirty bucket
@@ -1275,7 +1371,7 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   // dirty and malformed messages itself and leaves them alone)
   const u32 ndr = !Opt && dtab ? ctr[kCtrNDirty] : 0u;
   const bool iso = !Opt && ndr != 0 && ndr <= kDirtyCap;
-  if constexpr (!Opt) n = min(n, iso ? ctr[5] : min(ctr[5], ctr[kCtrDirty]));
+  if constexpr (!Opt) n = min(n, iso ? ctr[kCtrStop] : min(ctr[kCtrStop], ctr[kCtrDirty]));
   if (n <= lo) return;
   const u32 nh = hot ? min(hot->n, kHotMax) : 0u;
   for (u32 j = threadIdx.x; j < kHotLds; j += kFastBlock) hslot[j] = 0;
@@ -1342,7 +1438,7 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
       if constexpr (In::kOffs) {
         if (in.src.lim) {   // (uniform)
           const bool bad = in.src.bad(pre.a, pre.b);
-          note_min(valid && bad, i, &ctr[5]);
+          note_min(valid && bad, i, &ctr[kCtrStop]);
           if (bad) { pre.a = 0; pre.b = 0; valid = false; }
         }
       }
@@ -1457,7 +1553,7 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
           mark[i] = kMarkDirty;
         } else {
           missed = true;
-          if (pr == kFull) atomicOr(&ctr[8], 1u);
+          if (pr == kFull) atomicOr(&ctr[kCtrTableFull], 1u);
         }
       }
     }
@@ -1484,8 +1580,8 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   if (hits) atomicAdd(&hhits, hits);
   __syncthreads();
   if (threadIdx.x == 0) {
-    if (hhits) atomicAdd(&ctr[10], hhits);
-    if (blockIdx.x == 0) ctr[11] = nh;
+    if (hhits) atomicAdd(&ctr[kCtrHotHits], hhits);
+    if (blockIdx.x == 0) ctr[kCtrHotEntries] = nh;
   }
 
   // Directory flush: the workgroup's maxima, skipping fields already beaten.
@@ -1585,7 +1681,7 @@ __global__ __launch_bounds__(1024) void k_dirty_pass(In in, u32 n, u32* ctr, u8*
   __shared__ u32 queue[16][128];   // per wave: marked messages waiting for a full wave
   const u32 ndr = ctr[kCtrNDirty];
   if (ndr == 0 || ndr > kDirtyCap) return;
-  n = min(n, ctr[5]);
+  n = min(n, ctr[kCtrStop]);
   const DirtySet D = DirtySet::at(const_cast<u64*>(dtab));
   const u32 nv = ctr[kCtrNSorted];
   for (u32 j = threadIdx.x; j < nv; j += 1024) sidx[j] = D.idx[j];
@@ -1719,10 +1815,10 @@ __global__ __launch_bounds__(kBlock) void k_receive_list(
       if (status) status[i] = PHIP_ST_MERGED;
     } else {
       missed = true;
-      if (pr == kFull) atomicOr(&ctr[8], 1u);
+      if (pr == kFull) atomicOr(&ctr[kCtrTableFull], 1u);
     }
   }
-  const u32 pos = wave_append(&ctr[2], missed);
+  const u32 pos = wave_append(&ctr[kCtrMiss], missed);
   if (missed) miss[pos] = i;
 }
 
@@ -1835,7 +1931,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve(Src src, u32 n, const u32* _
     if (pr == kFound) slot_out[i] = s;
     else {
       missed = true;
-      if (pr == kFull) atomicOr(&ctr[8], 1u);
+      if (pr == kFull) atomicOr(&ctr[kCtrTableFull], 1u);
     }
   }
   if (miss.base) miss.append(blockIdx.x, missed, i);
@@ -1900,7 +1996,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve_batch(Src src, u32 n, Table 
         slot_out[i] = sk;
       } else {
         missed = true;
-        if (pr == kFull) atomicOr(&ctr[8], 1u);
+        if (pr == kFull) atomicOr(&ctr[kCtrTableFull], 1u);
       }
     }
     if (miss.base) miss.append(blockIdx.x * kResPer + k, missed, i);
@@ -1942,11 +2038,11 @@ __global__ __launch_bounds__(kBlock) void k_claim(Src src, u32 n, const u32* __r
       }
       s = (s + 1) & mask;
     }
-    if (k > mask) atomicOr(&ctr[8], 1u);
+    if (k > mask) atomicOr(&ctr[kCtrTableFull], 1u);
   }
-  u32 p = wave_append(&ctr[3], won);
+  u32 p = wave_append(&ctr[kCtrClaimed], won);
   if (won) { claimed_slot[p] = s; claimed_msg[p] = i; }
-  u32 q = wave_append(&ctr[4], again);
+  u32 q = wave_append(&ctr[kCtrRetry], again);
   if (again) retry[q] = i;
 }
 
@@ -1973,7 +2069,7 @@ __global__ void k_publish(Src src, u32 base, u32 n, const u32* __restrict__ clai
   r.name0 = nm.w0; r.name1 = nm.w1; r.name2 = nm.w2;
   if (len > kInlineName) {
     u64 a = atomicAdd(arena_cursor, (u64)len);
-    if (a + len > arena_cap) { atomicOr(&ctr[7], 1u); a = 0; }
+    if (a + len > arena_cap) { atomicOr(&ctr[kCtrArenaFull], 1u); a = 0; }
     else for (u32 k = 0; k < len; ++k) arena[a + k] = src.blob[off + k];
     r.name0 = (nm.w0 & 0xFFu) | (a << 32);
   }
@@ -2036,7 +2132,7 @@ __global__ __launch_bounds__(kBlock) void k_rehash(const Rec* __restrict__ old,
   u32 k = 0;
   for (; k <= mask; ++k, d = (d + 1) & mask)
     if (atomicCAS(&T.recs[d].tag, 0ull, r.tag) == 0ull) break;
-  if (k > mask) { atomicOr(&ctr[8], 1u); return; }
+  if (k > mask) { atomicOr(&ctr[kCtrTableFull], 1u); return; }
   Rec* q = &T.recs[d];
   q->added = r.added; q->taken = r.taken; q->elapsed = r.elapsed;
   q->name0 = r.name0; q->name1 = r.name1; q->created = r.created; q->name2 = r.name2;
@@ -2069,7 +2165,7 @@ __global__ __launch_bounds__(kBlock) void k_table_stats(Table T, u64 cap, u64* o
 // UnmarshalBinary (bucket.go:71-91) for a batch of raw datagrams: big-endian
 // fields, name length byte, io.ErrShortBuffer when < 25 bytes or the name is
 // truncated; trailing bytes are ignored.  The first short datagram index is
-// min-reduced into ctr[5] (the Go loop stops there, repo.go:72-73).
+// min-reduced into ctr[kCtrStop] (the Go loop stops there, repo.go:72-73).
 
 __global__ void k_decode(const u8* __restrict__ bytes, const uint64_t* __restrict__ offs, u32 n,
                          uint64_t* __restrict__ a, uint64_t* __restrict__ t,
@@ -2091,7 +2187,7 @@ __global__ void k_decode(const u8* __restrict__ bytes, const uint64_t* __restric
     }
     if (bad) {
       nlen[i] = 0; noff[i] = o;
-      atomicMin(&ctr[5], i);
+      atomicMin(&ctr[kCtrStop], i);
     }
   }
 }
@@ -2216,7 +2312,7 @@ __global__ __launch_bounds__(kShards) void k_batch_end(In in, u32* ctr, const u6
   dirty_finish(in, ctr, DirtySet::at(const_cast<u64*>(dtab)), T, so);
   __threadfence_block();
   __syncthreads();
-  shard_scan(cnt, ctr, 2, host, words, next, next_ctr);
+  shard_scan(cnt, ctr, kCtrMiss, host, words, next, next_ctr);
 }
 
 // ------------------------------------------------------------ ordered ----
@@ -3775,12 +3871,12 @@ struct BigLongSeg {
 // host round trip on C3): k_seg_count counts the segment heads of every tile
 // of kSegTile sorted ops, a scan of the tile counts places them, k_seg_write
 // writes each head's slot and start, and k_seg_finish derives the counts and
-// appends the long (ctr[6]) and huge (ctr[9]) segments; ctr[15] = segments.
+// appends the long (kCtrLongSegs) and huge (kCtrHugeSegs) segments and stores
+// the segment count (kCtrSegs).
 // The long / huge lists come out in no particular order: every segment is
 // folded on its own, so the order only schedules.
 constexpr u32 kSegTile = 4096;
 constexpr u32 kSegPer = kSegTile / 256;
-constexpr u32 kCtrSegs = 15;
 
 __device__ inline bool seg_head(const u32* __restrict__ key, u64 k) {
   return k == 0 || key[k] != key[k - 1];
@@ -3801,7 +3897,7 @@ __global__ __launch_bounds__(256) void k_seg_count(const u32* __restrict__ key, 
   __syncthreads();
   if (threadIdx.x == 0) {
     tile_cnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
-    if (blockIdx.x == 0) { ctr[6] = 0; ctr[9] = 0; tile_cnt[gridDim.x] = 0; }
+    if (blockIdx.x == 0) { ctr[kCtrLongSegs] = 0; ctr[kCtrHugeSegs] = 0; tile_cnt[gridDim.x] = 0; }
   }
 }
 
@@ -3839,7 +3935,7 @@ __global__ __launch_bounds__(256) void k_seg_write(const u32* __restrict__ key, 
 
 // Each workgroup takes a contiguous range of the segments (their number is on
 // the device only) and appends its long / huge ones through LDS lists, with
-// one global atomic per list and flush: a wave-level atomic on ctr[6] per
+// one global atomic per list and flush: a wave-level atomic on ctr[kCtrLongSegs] per
 // 64 segments serialised ~10^5 same-address atomics (0.41 ms on C3).
 constexpr u32 kSegListCap = 1024;
 __device__ inline void seg_flush(u32* lst, u32& cnt, u32* gcnt, u32* out, u32* base_sh) {
@@ -3880,11 +3976,11 @@ __global__ __launch_bounds__(256) void k_seg_finish(const u32* __restrict__ tile
     const u32 lc = lcnt, hc = hcnt;   // the same in every thread: read between barriers
     __syncthreads();
     // room for the next 256 in both lists
-    if (lc > kSegListCap - 256) seg_flush(llist, lcnt, &ctr[6], lng, &base_sh);
-    if (hc > kSegListCap - 256) seg_flush(hlist, hcnt, &ctr[9], huge, &base_sh);
+    if (lc > kSegListCap - 256) seg_flush(llist, lcnt, &ctr[kCtrLongSegs], lng, &base_sh);
+    if (hc > kSegListCap - 256) seg_flush(hlist, hcnt, &ctr[kCtrHugeSegs], huge, &base_sh);
   }
-  seg_flush(llist, lcnt, &ctr[6], lng, &base_sh);
-  seg_flush(hlist, hcnt, &ctr[9], huge, &base_sh);
+  seg_flush(llist, lcnt, &ctr[kCtrLongSegs], lng, &base_sh);
+  seg_flush(hlist, hcnt, &ctr[kCtrHugeSegs], huge, &base_sh);
 }
 
 // Sorted-slot segments from run-length output (counts -> starts is a scan).
@@ -3919,11 +4015,11 @@ __global__ void k_seed_finish(const u32* __restrict__ slot_of, u32 n, Table T) {
   T.recs[s].name0 = with_flags(T.recs[s].name0, kRecPublished);
 }
 
-// Occupied slots into list (list == nullptr: count only, into ctr[2]).
+// Occupied slots into list (list == nullptr: count only, into ctr[kCtrOccupied]).
 __global__ void k_dump_collect(const Rec* __restrict__ recs, u64 cap, u32* list, u32* ctr) {
   u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   bool occ = s < cap && recs[s].tag != 0;
-  u32 p = wave_append(&ctr[2], occ);
+  u32 p = wave_append(&ctr[kCtrOccupied], occ);
   if (occ && list) list[p] = (u32)s;
 }
 __global__ void k_dump_gather(const u32* __restrict__ list, u32 n, const Rec* __restrict__ recs,
@@ -5075,7 +5171,7 @@ __global__ __launch_bounds__(kBlock) void k_evict_count(const Rec* __restrict__ 
 // word: with 1M long names among 10M buckets in 2^25 slots 5.5 ms, against
 // 1.0 ms with none, ~12 ns for each of the ~450k waves holding one.)  Every
 // index is checked before the write, so a count that was wrong ends as an
-// error code: ctr[8] a wrapped probe (as k_rehash), ctr[7] a long name that
+// error code: ctr[kCtrTableFull] a wrapped probe (as k_rehash), ctr[kCtrArenaFull] a long name that
 // does not fit the arenas.
 constexpr u32 kEvictBlock = 1024;
 __global__ __launch_bounds__(kEvictBlock) void k_evict_move(
@@ -5113,7 +5209,7 @@ __global__ __launch_bounds__(kEvictBlock) void k_evict_move(
   if (lb) {
     const u64 a = base + sc - lb, oa = r.name0 >> 32;
     if (!new_arena || a + len > new_arena_cap || a > 0xFFFFFFFFull || oa + len > old_used) {
-      atomicOr(&ctr[7], 1u);
+      atomicOr(&ctr[kCtrArenaFull], 1u);
       return;
     }
     // eight bytes a step (the arenas are byte-packed, so neither side is
@@ -5134,7 +5230,7 @@ __global__ __launch_bounds__(kEvictBlock) void k_evict_move(
     if (d >= new_cap) break;
     if (atomicCAS(&T.recs[d].tag, 0ull, r.tag) == 0ull) break;
   }
-  if (k > mask || d >= new_cap) { atomicOr(&ctr[8], 1u); return; }
+  if (k > mask || d >= new_cap) { atomicOr(&ctr[kCtrTableFull], 1u); return; }
   Rec* q = &T.recs[d];
   q->added = r.added; q->taken = r.taken; q->elapsed = r.elapsed;
   q->name0 = r.name0; q->name1 = r.name1; q->created = r.created; q->name2 = r.name2;
