@@ -112,6 +112,9 @@ struct phip_handle {
   hipStream_t stream4 = nullptr;
   hipEvent_t ev_t4a = nullptr, ev_t4b = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // The B_HOT allocation whose count tables are zero, or will be when the
+  // launches queued so far have run (build_hot, fast_back); nullptr: not so.
+  void* hot_clean = nullptr;
   hipEvent_t ev_fork3 = nullptr, ev_join3 = nullptr;
   hipEvent_t ev_gather = nullptr, ev_gather3 = nullptr;   // huge-segment gathers done
   hipEvent_t ev_pack = nullptr;   // ordered path: op records packed (stream2)
@@ -557,7 +560,7 @@ int clear_new(phip_handle* h, u32 n_claimed) {
 int after_error(phip_handle* h, int rc) {
   if (rc == PHIP_OK) return rc;
   // Nothing of the failed call may still run when it returns: the side
-  // streams (the hot-directory chain of a batch whose front was queued, the
+  // streams (the hot directory of a batch whose front was queued, the
   // ordered path's folds) may still read the caller's inputs.
   if (h->stream2) (void)hipStreamSynchronize(h->stream2);
   if (h->stream3) (void)hipStreamSynchronize(h->stream3);
@@ -571,42 +574,59 @@ int after_error(phip_handle* h, int rc) {
 }
 
 // ------------------------------------------------------- fast receive ----
-// Hot directory of a fast batch (phip_kernels.hpp): sample -> count ->
-// threshold -> directory, all on the stream (no host round trip).  Returns
-// the header/directory to hand to k_receive_fast (nullptr: none).
+// Hot directory of a fast batch (phip_kernels.hpp k_hot_dir): one launch on
+// `st`, no host round trip.  Returns the header/directory to hand to
+// k_receive_fast (nullptr: none) and, in *zero_out, the kernel's count tables
+// and sync words, which have to be zero at its next launch: the fast kernel
+// that takes the directory clears them (fast_back).  Only a buffer just
+// created, or one whose directory no fast kernel took, is cleared in front.
+// status: nothing runs beside the kernel (an optimistic batch): one sample
+// per lane, and further workgroups fill the batch's status column; nullptr:
+// it shares the chip with k_classify, which writes the statuses.
 template <class Src>
-int build_hot(phip_handle* h, Src src, u32 n, hipStream_t st, const HotHdr** hdr_out,
-              const HotEntry** dir_out) {
+int build_hot(phip_handle* h, Src src, u32 n, hipStream_t st, u8* status, const HotHdr** hdr_out,
+              const HotEntry** dir_out, void** zero_out) {
   *hdr_out = nullptr;
   *dir_out = nullptr;
+  *zero_out = nullptr;
   if (n < kHotMinBatch) return PHIP_OK;
   constexpr size_t kCnt = size_t(1) << kHotCntBits;
-  const size_t zero_bytes = 2 * kCnt * sizeof(u32) + kHotHist * sizeof(u32) + sizeof(HotHdr);
   u8* base;
   int rc;
-  if ((rc = ensure(h, B_HOT, zero_bytes + kHotMax * sizeof(HotEntry), &base))) return rc;
+  if ((rc = ensure(h, B_HOT, kHotZeroBytes + kHotCandMax * sizeof(u32) + sizeof(HotHdr) +
+                                 kHotMax * sizeof(HotEntry), &base)))
+    return rc;
   u32* ckeys = (u32*)base;
   u32* ccnt = ckeys + kCnt;
-  u32* hist = ccnt + kCnt;
-  HotHdr* hdr = (HotHdr*)(hist + kHotHist);
+  u32* sync = ccnt + kCnt;
+  u32* cand = sync + kHotSyncWords;
+  HotHdr* hdr = (HotHdr*)(cand + kHotCandMax);
   HotEntry* dir = (HotEntry*)(hdr + 1);
-  HIPCHK(h, hipMemsetAsync(base, 0, zero_bytes, st));
+  if (h->hot_clean != base) HIPCHK(h, hipMemsetAsync(base, 0, kHotZeroBytes, st));
+  h->hot_clean = nullptr;
   const u32 stride = std::max<u32>(64, (n + kHotSampleMax - 1) / kHotSampleMax);
   const u32 nsample = (n + stride - 1) / stride;
   {
-    Launch l(h, "k_hot_sample", st);
-    k_hot_sample<Src><<<grid_for(nsample, kHotSamplePerBlock), 256, 0, st>>>(
-        src, n, stride, nsample, table(h), ckeys, ccnt);
-  }
-  {
-    Launch l(h, "k_hot_select", st);
-    k_hot_hist<<<grid_for(kCnt), kBlock, 0, st>>>(ccnt, hist);
-    k_hot_select<<<1, 256, 0, st>>>(hist, hdr, kHotMax);
-    k_hot_build<<<grid_for(kCnt), kBlock, 0, st>>>(ckeys, ccnt, hdr, table(h), dir);
+    Launch l(h, "k_hot_dir", st);
+    if (status) {
+      // (fill workgroups: 64 bytes of statuses a lane and pass, 1024 lanes
+      // resident a compute unit)
+      constexpr unsigned kT = kHotAloneThreads;
+      const unsigned nblk = grid_for(nsample, kT);
+      const unsigned fill =
+          std::min<unsigned>(grid_for(n, kT * 64), 1024 / kT * (unsigned)h->ncu);
+      k_hot_dir<Src, kT, 1><<<nblk + fill, kT, 0, st>>>(
+          src, n, stride, nsample, table(h), ckeys, ccnt, sync, cand, hdr, dir, nblk, status);
+    } else {
+      const unsigned nblk = grid_for(nsample, kHotSamplePerBlock);
+      k_hot_dir<Src, 256, 4><<<nblk, 256, 0, st>>>(
+          src, n, stride, nsample, table(h), ckeys, ccnt, sync, cand, hdr, dir, nblk, nullptr);
+    }
   }
   HIPCHK(h, hipGetLastError());
   *hdr_out = hdr;
   *dir_out = dir;
+  *zero_out = base;
   return PHIP_OK;
 }
 
@@ -616,7 +636,6 @@ inline unsigned fast_grid_on(u32 ncu, u32 n) {
 }
 inline unsigned fast_grid(phip_handle* h, u32 n) { return fast_grid_on((u32)h->ncu, n); }
 
-int join_hot(phip_handle* h, const HotHdr* hot);
 
 // A sharded append list over `units` units of up to `per_unit` entries
 // (counters zeroed on the stream).
@@ -649,14 +668,14 @@ int pack_sharded(phip_handle* h, const Sharded& sh, u32 total_slot, u32* out, u3
   return PHIP_OK;
 }
 
-template <class Src>
-int fork_hot(phip_handle* h, Src src, u32 n, const HotHdr** hot, const HotEntry** hot_dir);
-
 // A fast batch in three parts, so that a queued batch (PHIP_RECV_ASYNC) can
 // put the next batch's front in front of its own read-back:
-//   front    counter reset, hot directory (stream2), k_classify (which also
-//            fills the status column);
-//   back     k_receive_fast (after the directory), then one k_shard_scan
+//   front    counter reset, then either the hot directory alone (an
+//            optimistic batch: k_hot_dir on the main stream, its launch also
+//            filling the status column) or k_classify (which fills the
+//            column) with the directory beside it on stream2;
+//   back     k_receive_fast (after the directory, whose count tables it
+//            clears for the next batch), then one k_shard_scan
 //            that packs the miss shards' offsets and stores the counters in
 //            the host's mapped mirror (queued: and resets them for the next
 //            batch), ev_ctr behind it;
@@ -667,6 +686,8 @@ int fork_hot(phip_handle* h, Src src, u32 n, const HotHdr** hot, const HotEntry*
 struct FastFront {
   const HotHdr* hot = nullptr;
   const HotEntry* dir = nullptr;
+  void* hot_zero = nullptr;   // the directory kernel's count tables, for the fast kernel to clear
+  bool hot_join = false;      // the directory was built on stream2 (join_hot)
   u32 par = 0;
   bool iso = false;     // this pass sets its dirty buckets apart (the isolation kernels run)
   u32* c = nullptr;     // the pass's counter set (fctr)
@@ -674,6 +695,9 @@ struct FastFront {
   bool opt = false;     // an optimistic pass: no classification, the kernel keeps an undo log
   UndoLog log{};        // its log (cnt: set by the front; base, cap: by the back)
 };
+template <class Src>
+int fork_hot(phip_handle* h, Src src, u32 n, FastFront* ff);
+int join_hot(phip_handle* h, const FastFront& ff);
 
 // Whether the handle's policy lets a decoded batch run optimistically.
 inline bool opt_allowed(const phip_handle* h) {
@@ -754,15 +778,15 @@ int fast_shards(phip_handle* h, u32 n, u32 par, Sharded* out) {
 
 // Enqueue order matters at this size (2 ms per 100M messages): the counter
 // reset and the classification go first, so the GPU starts reading the batch
-// while the host still enqueues the hot-directory chain on stream2 (about
-// 0.1 ms of API calls that used to sit in front of k_classify).
+// while the host still enqueues the directory on stream2.
 // reset = false: the batch queued just before (nothing since) reset the
 // counters in its last launch.
 // iso: whether the pass sets its dirty buckets apart (-1: the handle's
 // policy, phip_handle::iso_left).
 // opt: the caller can undo the pass and run the batch again (a decoded
 // batch's first pass), so the handle's policy may make it optimistic; its
-// front is the counter reset, the status fill and the directory chain.
+// front is the counter reset and one launch, the directory with the status
+// fill.
 template <class In, class HotSrc>
 int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront* ff,
                bool reset = true, int iso = -1, bool opt = false) {
@@ -788,16 +812,20 @@ int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront*
       if ((rc = ensure(h, B_ULCNT, nw, &lc))) return rc;
       ff->opt = true;
       ff->log.cnt = lc;
-      // (the directory chain waits for the batch's producers only, not for
-      // the fills)
-      if (n >= kHotMinBatch) HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-      // Statuses: a fill here, not byte stores from the kernel's lanes (2% of
-      // the kernel when measured, below): a queued batch's fill runs while
-      // the host reads the batch before back, when the GPU has nothing else
-      // to do.
+      // Statuses: filled up front, not by byte stores from the fast kernel's
+      // lanes (2% of the kernel when measured, below).  Nothing runs beside
+      // an optimistic batch's directory, so it is built on the main stream,
+      // with no hop, and the fill is part of its launch (k_hot_dir's fill
+      // workgroups); a batch too small for a directory gets a fill.
       if (kOptStatus) ff->mark = status;   // (a tuning build: the kernel's lanes fill it)
-      else if (status) HIPCHK(h, hipMemsetAsync(status, PHIP_ST_MERGED, n, h->stream));
-      if (n >= kHotMinBatch && (rc = fork_hot(h, hsrc, n, &ff->hot, &ff->dir))) return rc;
+      u8* fill = kOptStatus ? nullptr : status;
+      if (n >= kHotMinBatch && fill)
+        return build_hot(h, hsrc, n, h->stream, fill, &ff->hot, &ff->dir, &ff->hot_zero);
+      if (fill) HIPCHK(h, hipMemsetAsync(fill, PHIP_ST_MERGED, n, h->stream));
+      if (n >= kHotMinBatch) {   // (no status column: the directory as a classified batch builds it)
+        HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
+        return fork_hot(h, hsrc, n, ff);
+      }
       return PHIP_OK;
     }
   }
@@ -812,7 +840,7 @@ int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront*
     }
   }
   const bool with_hot = n >= kHotMinBatch;
-  // A small batch classifies in a few µs, less than the directory chain
+  // A small batch classifies in a few µs, less than the directory kernel
   // takes: that chain goes first then.
   const bool hot_first = n < (1u << 23);
   // Statuses: the fast kernel merges most of the batch and writes none; the
@@ -824,7 +852,7 @@ int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront*
   // the classification slowed the classification more than it cost here
   // (DESIGN.md §4).
   if (with_hot) HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-  if (with_hot && hot_first && (rc = fork_hot(h, hsrc, n, &ff->hot, &ff->dir))) return rc;
+  if (with_hot && hot_first && (rc = fork_hot(h, hsrc, n, ff))) return rc;
   {
     bool done = false;
     if constexpr (In::kSoa) {
@@ -847,7 +875,7 @@ int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront*
     }
   }
   HIPCHK(h, hipGetLastError());
-  if (with_hot && !hot_first && (rc = fork_hot(h, hsrc, n, &ff->hot, &ff->dir))) return rc;
+  if (with_hot && !hot_first && (rc = fork_hot(h, hsrc, n, ff))) return rc;
   return PHIP_OK;
 }
 
@@ -870,7 +898,7 @@ int fast_back(phip_handle* h, In in, u32 n, FastFront& ff, bool queued) {
     k_dirty_build<In><<<1, 1024, 0, h->stream>>>(in, n, ff.c, dlist, dset, table(h));
     HIPCHK(h, hipGetLastError());
   }
-  if ((rc = join_hot(h, ff.hot))) return rc;
+  if ((rc = join_hot(h, ff))) return rc;
   if (ff.opt) {
     if constexpr (In::kSoa) {
       // (the log is sized here, not in the front: a queued front runs before
@@ -880,15 +908,17 @@ int fast_back(phip_handle* h, In in, u32 n, FastFront& ff, bool queued) {
       if ((rc = ensure(h, B_ULOG, (size_t)ul.halves, &ff.log.base))) return rc;
       Launch l(h, "k_receive_fast");
       k_receive_fast<In, true><<<ul.grid, kFastBlock, 0, h->stream>>>(
-          in, 0, n, table(h), msh, ff.c, ff.hot, ff.dir, nullptr, ff.mark, ff.log);
+          in, 0, n, table(h), msh, ff.c, ff.hot, ff.dir, nullptr, ff.mark, ff.log,
+          (uint4*)ff.hot_zero);
     }
   } else {
     Launch l(h, "k_receive_fast");
     k_receive_fast<In><<<fast_grid(h, n), kFastBlock, 0, h->stream>>>(
         in, 0, n, table(h), msh, ff.c, ff.hot, ff.dir, ff.iso ? dset.key : nullptr, ff.mark,
-        UndoLog{});
+        UndoLog{}, (uint4*)ff.hot_zero);
   }
   HIPCHK(h, hipGetLastError());
+  if (ff.hot_zero) h->hot_clean = ff.hot_zero;   // (queued behind every user of the tables)
   if (ff.iso) {
     // the messages the fast kernel marked (an isolated batch's only: others
     // return at once), then the dirty buckets' records unmarked and their
@@ -1004,9 +1034,6 @@ int fast_apply(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, u32* first
   return fast_collect(h, n, ff.par, first_dirty, nmiss, ff.iso, ff.opt);
 }
 
-template <class Src>
-int fork_hot(phip_handle* h, Src src, u32 n, const HotHdr** hot, const HotEntry** hot_dir);
-
 // One message per distinct name of list[0..n) (k_dedupe) into B_DEDUP.
 template <class Src>
 int dedupe_names(phip_handle* h, Src src, const u32* list, u32 n, u32** out, u32* nout) {
@@ -1107,23 +1134,23 @@ int finish_misses(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t,
   return clear_new(h, n_claimed);
 }
 
-// Start the hot directory of a fast batch on stream2 (joined by join_hot).
+// Start the hot directory of a classified fast batch on stream2, beside
+// k_classify (joined by join_hot).
 template <class Src>
-int fork_hot(phip_handle* h, Src src, u32 n, const HotHdr** hot, const HotEntry** hot_dir) {
-  *hot = nullptr;
-  *hot_dir = nullptr;
+int fork_hot(phip_handle* h, Src src, u32 n, FastFront* ff) {
   if (n < kHotMinBatch) return PHIP_OK;
-  // ev_fork: recorded by fast_apply before the classification (stream2 waits
+  // ev_fork: recorded by fast_front before the classification (stream2 waits
   // only for the batch's producers, not for k_classify)
   HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
   int rc;
-  if ((rc = build_hot(h, src, n, h->stream2, hot, hot_dir))) return rc;
+  if ((rc = build_hot(h, src, n, h->stream2, nullptr, &ff->hot, &ff->dir, &ff->hot_zero))) return rc;
   HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
+  ff->hot_join = true;
   return PHIP_OK;
 }
 
-int join_hot(phip_handle* h, const HotHdr* hot) {
-  if (hot) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
+int join_hot(phip_handle* h, const FastFront& ff) {
+  if (ff.hot_join) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
   return PHIP_OK;
 }
 
@@ -2526,8 +2553,8 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
   u32 n = m->n;
   if ((flags & PHIP_RECV_ASYNC) && dev && n >= kHotMinBatch && m->names && m->name_offs &&
       m->added && m->taken && m->elapsed) {
-    // Queue this batch's front (reset, directory, status fill,
-    // classification) behind the batch queued before, read that batch's
+    // Queue this batch's front (reset, directory with the status fill, or
+    // classification and directory) behind the batch queued before, read that batch's
     // counters meanwhile and finish it, then queue this batch's fast pass
     // and return.  The front's counters are a fast-pass set of their own
     // (fctr), so the previous batch's leftover work leaves it standing

@@ -739,9 +739,23 @@ constexpr u32 kRouteHotMax = 512;
 static_assert(kHotLds * 2 >= kRouteHotMax * 3 && kHotLds * 2 >= kHotMax * 3, "LDS lookup load");
 constexpr u32 kHotCntBits = 18;       // sample count table: 2^18 (slot+1, count) pairs
 constexpr u32 kHotSampleMax = 1u << 17;   // samples per batch (half the count table)
-constexpr u32 kHotSamplePerBlock = 1024;   // 128 workgroups: the chain runs beside k_classify on stream2 (512 one-sample workgroups queued behind its blocks and delayed the join)
+// Samples per workgroup, of the directory's and the route pack's sample (how
+// k_hot_dir's lanes share them: there).
+constexpr u32 kHotSamplePerBlock = 1024;
+// Lanes of a k_hot_dir workgroup with nothing beside it (PHIP_HOT_ALONE
+// overrides it for tuning builds: 1024 ran the step 20 us slower, DESIGN.md
+// §4 round 8).
+#ifndef PHIP_HOT_ALONE
+#define PHIP_HOT_ALONE 256
+#endif
+constexpr u32 kHotAloneThreads = PHIP_HOT_ALONE;
 constexpr u32 kHotHist = 4096;        // histogram bins of sample counts
 constexpr u32 kHotMinCount = 8;       // sample hits for a bucket to qualify
+constexpr u32 kHotCandMax = kHotSampleMax / kHotMinCount;   // count-table entries that can qualify
+// k_hot_dir's words that must be zero at launch: the two count tables, then
+// its sync words {ticket, candidates} on a line of their own.
+constexpr u32 kHotSyncWords = 16;
+constexpr size_t kHotZeroBytes = (2 * (size_t(1) << kHotCntBits) + kHotSyncWords) * sizeof(u32);
 // Smaller batches skip the directory.  2^16, not larger: a skewed batch of a
 // few 100k messages (C1: 1M into 100k buckets, 13% of them on one bucket)
 // otherwise sends every message of its hottest bucket to one record as a
@@ -773,19 +787,104 @@ struct HotHdr {
 
 __device__ inline u32 hot_home(u64 tag) { return (u32)(tag ^ (tag >> 29)) & (kHotLds - 1); }
 
-// Sample j = message j*stride: resolve it and count its
-// slot, aggregated per workgroup in LDS first (a hot slot is sampled by most
-// lanes; one global atomic per workgroup and slot keeps it off one address).
-template <class Src>
-__global__ __launch_bounds__(256) void k_hot_sample(Src src, u32 n, u32 stride, u32 nsample, Table T,
-                                                    u32* __restrict__ ckeys, u32* __restrict__ ccnt) {
-  constexpr u32 kPer = kHotSamplePerBlock / 256;
-  constexpr u32 kL = 2 * kHotSamplePerBlock;
-  __shared__ u32 lkey[kL], lcnt[kL];
-  for (u32 e = threadIdx.x; e < kL; e += 256) { lkey[e] = 0; lcnt[e] = 0; }
+// One record as a directory entry (tail words of a short arena name included).
+__device__ inline HotEntry hot_entry(const Table& T, u32 s) {
+  const Rec r = load_rec(&T.recs[s]);
+  HotEntry d;
+  const bool arena = (r.name0 & 0xFFu) > kInlineName;
+  d.tag = r.tag;
+  d.w0 = arena ? (r.name0 & 0xFFu) : (r.name0 & ~0xFF00ull);
+  d.w1 = r.name1;
+  d.w2 = r.name2;
+  d.slot = s;
+  d.aoff = arena ? (u32)(r.name0 >> 32) : 0u;
+  const u32 len = (u32)(r.name0 & 0xFFu);
+  for (u32 k = 0; k < kHotTailWords; ++k) d.tail[k] = 0;
+  if (arena && len <= kHotTailName) {
+    const u64 a0 = (r.name0 >> 32) + 16;
+    const u64* p = reinterpret_cast<const u64*>(T.arena + (a0 & ~7ull));
+    const u32 sh = (u32)(a0 & 7) * 8, lastw = ((u32)(a0 & 7) + len - 17) >> 3;
+    for (u32 k = 0; 8 * k < len - 16; ++k) {
+      const u32 m = len - 16 - 8 * k;
+      d.tail[k] = low_bytes(str_word(p, sh, k, lastw), m);
+    }
+  }
+  return d;
+}
+
+// Words other workgroups of the same launch wrote: agent-scope accesses, past
+// the CU's L1 and written through the XCD's L2.
+__device__ inline u32 ld_co32(const u32* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline void st_co32(u32* p, u32 v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The whole directory in one launch.
+// Every workgroup: sample j = message j*stride is resolved and its slot
+// counted, aggregated per workgroup in LDS first (a hot slot is sampled by
+// most lanes; one global atomic per workgroup and slot keeps it off one
+// address).  The add on the global count returns the count before it: the one
+// workgroup whose add takes an entry across kHotMinCount appends the entry to
+// the candidate list, so the list holds exactly the entries a directory can
+// take (at most nsample / kHotMinCount).
+// Then a ticket: every wave waits for its memory operations, the workgroup
+// meets at a barrier and one lane adds 1.  The workgroup whose add came last
+// finishes alone -- the candidates' final counts into an LDS histogram, the
+// lowest threshold t >= kHotMinCount with at most kHotMax candidates counted t
+// or more times, the header and the entries -- and resets the ticket and the
+// list's counter.  Nobody waits for anybody, so residency does not matter.
+// Per-XCD L2s are not coherent: the list is stored, and the list, the counts
+// and the keys are read back, at agent scope (the counts and keys are written
+// by device-scope atomics), behind one agent-scope acquire of the last
+// workgroup.  sync: {ticket, candidates}, zero before the launch; ckeys and
+// ccnt zero too (the fast kernel that takes the directory clears all three
+// for the next batch, k_receive_fast's hot_zero).
+// A workgroup takes kThreads * kRounds samples.  Where nothing runs beside
+// the kernel every lane takes one (kHotAloneThreads lanes a workgroup): the
+// three dependent loads of a probe are paid once.  Beside k_classify it is
+// 256 lanes and four rounds, 128 workgroups: 512 one-sample workgroups queued
+// behind k_classify's blocks and delayed the join.
+template <class Src, u32 kThreads, u32 kRounds>
+__global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride, u32 nsample,
+                                                      Table T, u32* ckeys, u32* ccnt, u32* sync,
+                                                      u32* cand, HotHdr* hdr,
+                                                      HotEntry* __restrict__ dir, u32 nblk,
+                                                      u8* __restrict__ status) {
+  constexpr u32 kPerBlock = kThreads * kRounds;
+  constexpr u32 kL = 2 * kPerBlock;
+  static_assert(kHotHist % kThreads == 0 && 4096 % kThreads == 0, "the last workgroup's shares");
+  constexpr u32 kWords = 2 * kL > kHotHist ? 2 * kL : kHotHist;
+  __shared__ u32 lds[kWords];
+  __shared__ u32 part[kThreads];
+  __shared__ u32 sel[kHotMax];
+  __shared__ u32 best, nsel, last;
+  if (blockIdx.x >= nblk) {
+    // The workgroups behind the nblk sampling ones fill the batch's status
+    // column with PHIP_ST_MERGED (an optimistic batch: fast_front), in the
+    // launch the sample's dependent loads leave idle: 16-byte stores over the
+    // aligned middle, bytes at both ends.
+    constexpr u32 b4 = PHIP_ST_MERGED * 0x01010101u;
+    const u64 head = min((u64)n, (u64)(-(uintptr_t)status & 15));
+    const u64 n16 = (n - head) / 16;
+    uint4* body = reinterpret_cast<uint4*>(status + head);
+    const u64 step = (u64)(gridDim.x - nblk) * kThreads;
+    for (u64 k = (u64)(blockIdx.x - nblk) * kThreads + threadIdx.x; k < n16; k += step)
+      body[k] = uint4{b4, b4, b4, b4};
+    if (blockIdx.x == nblk) {
+      if (threadIdx.x < head) status[threadIdx.x] = PHIP_ST_MERGED;
+      const u64 done = head + n16 * 16;
+      if (done + threadIdx.x < n) status[done + threadIdx.x] = PHIP_ST_MERGED;
+    }
+    return;
+  }
+  u32* lkey = lds;
+  u32* lcnt = lds + kL;
+  for (u32 e = threadIdx.x; e < 2 * kL; e += kThreads) lds[e] = 0;
   __syncthreads();
-  for (u32 r = 0; r < kPer; ++r) {
-    const u32 j = blockIdx.x * kHotSamplePerBlock + r * 256 + threadIdx.x;
+  for (u32 r = 0; r < kRounds; ++r) {
+    const u32 j = blockIdx.x * kPerBlock + r * kThreads + threadIdx.x;
     const u64 i = (u64)j * stride;
     if (j >= nsample || i >= n) continue;
     u64 off; u32 len;
@@ -796,7 +895,7 @@ __global__ __launch_bounds__(256) void k_hot_sample(Src src, u32 n, u32 stride, 
     Rec rec;
     if (probe(T, nm, src.blob, &s, &rec) != kFound) continue;
     u32 h = (s * 2654435761u) & (kL - 1);
-    for (;;) {   // at most kHotSamplePerBlock distinct keys in 2x as many entries
+    for (;;) {   // at most kPerBlock distinct keys in 2x as many entries
       const u32 old = atomicCAS(&lkey[h], 0u, s + 1);
       if (old == 0 || old == s + 1) { atomicAdd(&lcnt[h], 1u); break; }
       h = (h + 1) & (kL - 1);
@@ -804,15 +903,155 @@ __global__ __launch_bounds__(256) void k_hot_sample(Src src, u32 n, u32 stride, 
   }
   __syncthreads();
   constexpr u32 mask = (1u << kHotCntBits) - 1;
-  for (u32 e = threadIdx.x; e < kL; e += 256) {
-    const u32 key = lkey[e];
-    if (!key) continue;
-    u32 h = ((key - 1) * 2654435761u) >> (32 - kHotCntBits);
-    for (u32 k = 0; k <= mask; ++k) {
-      const u32 old = atomicCAS(&ckeys[h], 0u, key);
-      if (old == 0 || old == key) { atomicAdd(&ccnt[h], lcnt[e]); break; }
-      h = (h + 1) & mask;
+  // A lane's LDS entries to the global table with their atomics in flight
+  // together (each is a round trip to memory: a CAS on the key, the add on
+  // the count, and for the entries that cross kHotMinCount one add on the
+  // list's counter for all of them).
+  constexpr u32 kE = kL / kThreads;
+  u32 key[kE], cnt[kE], hh[kE], before[kE];
+#pragma unroll
+  for (u32 k = 0; k < kE; ++k) {
+    key[k] = lkey[k * kThreads + threadIdx.x];
+    cnt[k] = lcnt[k * kThreads + threadIdx.x];
+    hh[k] = ((key[k] - 1) * 2654435761u) >> (32 - kHotCntBits);
+    before[k] = ~0u;   // (not counted yet)
+  }
+  for (u32 tries = 0; tries <= mask; ++tries) {
+    u32 old[kE];
+#pragma unroll
+    for (u32 k = 0; k < kE; ++k)
+      if (key[k] && before[k] == ~0u) old[k] = atomicCAS(&ckeys[hh[k]], 0u, key[k]);
+    bool again = false;
+#pragma unroll
+    for (u32 k = 0; k < kE; ++k) {
+      if (!key[k] || before[k] != ~0u) continue;
+      if (old[k] == 0 || old[k] == key[k]) before[k] = atomicAdd(&ccnt[hh[k]], cnt[k]);
+      else { hh[k] = (hh[k] + 1) & mask; again = true; }
     }
+    if (!again) break;
+  }
+  u32 ncross = 0;
+#pragma unroll
+  for (u32 k = 0; k < kE; ++k) {
+    // (an entry the table had no room for keeps before = ~0)
+    const bool cross = key[k] && before[k] < kHotMinCount && before[k] + cnt[k] >= kHotMinCount;
+    if (!cross) key[k] = 0;
+    ncross += cross;
+  }
+  if (ncross) {
+    u32 at = atomicAdd(&sync[1], ncross);
+#pragma unroll
+    for (u32 k = 0; k < kE; ++k)
+      if (key[k] && at < kHotCandMax) st_co32(&cand[at++], hh[k]);
+  }
+  // the ticket, behind every wave's stores and atomics
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const u32 t = __hip_atomic_fetch_add(&sync[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = t == nblk - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  __syncthreads();
+  if (!last) return;
+
+  // ---- the last workgroup: threshold and directory ----
+  // A candidate costs two dependent loads (the list, then its count and key
+  // together); a lane keeps kU of them in flight, and the first 4096
+  // candidates (the headline has a few thousand) stay in registers from the
+  // histogram to the selection.  Any beyond are read again.  The first 4096
+  // list entries are read along with the list's length, not behind it.
+  constexpr u32 kU = 4096 / kThreads;
+  static_assert(4096 <= kHotCandMax, "the list entries read before its length");
+  u32 hh0[kU];
+#pragma unroll
+  for (u32 k = 0; k < kU; ++k) hh0[k] = ld_co32(&cand[k * kThreads + threadIdx.x]);
+  const u32 ncand = min(ld_co32(&sync[1]), kHotCandMax);
+#pragma unroll
+  for (u32 k = 0; k < kU; ++k) hh0[k] = k * kThreads + threadIdx.x < ncand ? hh0[k] & mask : ~0u;
+  u32* hist = lds;
+  for (u32 e = threadIdx.x; e < kHotHist; e += kThreads) hist[e] = 0;
+  if (threadIdx.x == 0) { best = kHotHist; nsel = 0; }
+  __syncthreads();
+  auto counts = [&](const u32 (&hh)[kU], u32 (&cc)[kU], u32 (&kk)[kU]) {
+#pragma unroll
+    for (u32 k = 0; k < kU; ++k) {
+      cc[k] = hh[k] != ~0u ? ld_co32(&ccnt[hh[k]]) : 0u;
+      kk[k] = hh[k] != ~0u ? ld_co32(&ckeys[hh[k]]) : 0u;
+    }
+  };
+  auto load = [&](u32 base, u32 (&cc)[kU], u32 (&kk)[kU]) {
+    u32 hh[kU];
+#pragma unroll
+    for (u32 k = 0; k < kU; ++k) {
+      const u32 c = base + k * kThreads + threadIdx.x;
+      hh[k] = c < ncand ? ld_co32(&cand[c]) & mask : ~0u;
+    }
+    counts(hh, cc, kk);
+  };
+  auto count = [&](const u32 (&cc)[kU]) {
+#pragma unroll
+    for (u32 k = 0; k < kU; ++k)
+      if (cc[k] >= kHotMinCount) atomicAdd(&hist[cc[k] < kHotHist ? cc[k] : kHotHist - 1], 1u);
+  };
+  u32 cc0[kU], kk0[kU];
+  counts(hh0, cc0, kk0);
+  count(cc0);
+  for (u32 base = kThreads * kU; base < ncand; base += kThreads * kU) {
+    u32 cc[kU], kk[kU];
+    load(base, cc, kk);
+    count(cc);
+  }
+  __syncthreads();
+  {   // (k_hot_select's rule, on the LDS histogram)
+    constexpr u32 kBins = kHotHist / kThreads;
+    const u32 t = threadIdx.x;
+    u32 s = 0;
+    for (u32 k = 0; k < kBins; ++k) s += hist[t * kBins + k];
+    part[t] = s;
+    __syncthreads();
+    u32 run = 0;   // slots counted in later chunks
+    for (u32 u = t + 1; u < kThreads; ++u) run += part[u];
+    u32 lo = kHotHist;
+    for (int b = (int)kBins - 1; b >= 0; --b) {
+      run += hist[t * kBins + b];
+      if (run <= kHotMax) lo = t * kBins + b;
+    }
+    atomicMin(&best, lo);
+    __syncthreads();
+  }
+  const u32 thresh = best > kHotMinCount ? best : kHotMinCount;
+  // the selected slots, packed in LDS: every lane then builds its share of
+  // the entries, their record reads in flight together
+  auto pick = [&](const u32 (&cc)[kU], const u32 (&kk)[kU]) {
+#pragma unroll
+    for (u32 k = 0; k < kU; ++k) {
+      if (cc[k] < thresh) continue;
+      const u32 idx = atomicAdd(&nsel, 1u);
+      if (idx < kHotMax) sel[idx] = kk[k] - 1;   // (always: the threshold bounds the count)
+    }
+  };
+  pick(cc0, kk0);
+  for (u32 base = kThreads * kU; base < ncand; base += kThreads * kU) {
+    u32 cc[kU], kk[kU];
+    load(base, cc, kk);
+    pick(cc, kk);
+  }
+  __syncthreads();
+  const u32 ns = min(nsel, kHotMax);
+#pragma unroll
+  for (u32 k = 0; k < (kHotMax + kThreads - 1) / kThreads; ++k) {
+    const u32 j = k * kThreads + threadIdx.x;
+    if (j < ns) dir[j] = hot_entry(T, sel[j]);
+  }
+  if (threadIdx.x == 0) {
+    hdr->n = nsel;
+    hdr->thresh = thresh;
+    st_co32(&sync[0], 0u);
+    st_co32(&sync[1], 0u);
   }
 }
 
@@ -851,41 +1090,10 @@ __global__ __launch_bounds__(256) void k_hot_select(const u32* __restrict__ hist
   }
 }
 
-__global__ void k_hot_build(const u32* __restrict__ ckeys, const u32* __restrict__ ccnt, HotHdr* hdr,
-                            Table T, HotEntry* __restrict__ dir) {
-  const u32 e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= (1u << kHotCntBits)) return;
-  const u32 c = ccnt[e];
-  if (c < kHotMinCount || c < hdr->thresh) return;
-  const u32 idx = atomicAdd(&hdr->n, 1u);
-  if (idx >= kHotMax) return;   // cannot happen: the threshold bounds the count
-  const u32 s = ckeys[e] - 1;
-  const Rec r = load_rec(&T.recs[s]);
-  HotEntry d;
-  const bool arena = (r.name0 & 0xFFu) > kInlineName;
-  d.tag = r.tag;
-  d.w0 = arena ? (r.name0 & 0xFFu) : (r.name0 & ~0xFF00ull);
-  d.w1 = r.name1;
-  d.w2 = r.name2;
-  d.slot = s;
-  d.aoff = arena ? (u32)(r.name0 >> 32) : 0u;
-  const u32 len = (u32)(r.name0 & 0xFFu);
-  for (u32 k = 0; k < kHotTailWords; ++k) d.tail[k] = 0;
-  if (arena && len <= kHotTailName) {
-    const u64 a0 = (r.name0 >> 32) + 16;
-    const u64* p = reinterpret_cast<const u64*>(T.arena + (a0 & ~7ull));
-    const u32 sh = (u32)(a0 & 7) * 8, lastw = ((u32)(a0 & 7) + len - 17) >> 3;
-    for (u32 k = 0; 8 * k < len - 16; ++k) {
-      const u32 m = len - 16 - 8 * k;
-      d.tail[k] = low_bytes(str_word(p, sh, k, lastw), m);
-    }
-  }
-  dir[idx] = d;
-}
-
 // ----------------------------------------------------- fast receive --------
 // Statuses: the caller's status column is filled with PHIP_ST_MERGED
-// before the kernel (by k_classify_soa2, or a fill beside k_classify); every
+// before the kernel (by k_classify_soa2, a fill beside k_classify, or an
+// optimistic batch's k_hot_dir); every
 // message the kernel does not merge is written again later (misses by the
 // miss path, dirty buckets by the ordered path).
 // Persistent workgroups; every wave walks its own 64-message chunks
@@ -1351,7 +1559,7 @@ template <class In, bool Opt = false>
 __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_receive_fast(
     In in, u32 lo, u32 n, Table T, Sharded miss, u32* ctr,
     const HotHdr* __restrict__ hot, const HotEntry* __restrict__ hot_dir, const u64* dtab,
-    u8* __restrict__ mark, UndoLog ulog) {
+    u8* __restrict__ mark, UndoLog ulog, uint4* __restrict__ hot_zero) {
   __shared__ u32 hslot[kHotLds];        // directory index + 1 (0 = empty)
   __shared__ u64 htag[kHotMax], hw0[kHotMax], hw1[kHotMax], hw2[kHotMax];
   __shared__ u32 hrec[kHotMax], haoff[kHotMax];
@@ -1369,6 +1577,13 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   // are marked for k_dirty_pass)
   // (Opt: no classification ran and there is no gate; the kernel finds the
   // dirty and malformed messages itself and leaves them alone)
+  // The directory kernel's count tables and sync words (kHotZeroBytes at
+  // hot_zero), cleared for the next batch's k_hot_dir: a store or two per
+  // lane here, where a fill of its own would stand between two launches.
+  if (hot_zero)
+    for (u32 k = blockIdx.x * kFastBlock + threadIdx.x; k < kHotZeroBytes / sizeof(uint4);
+         k += gridDim.x * kFastBlock)
+      hot_zero[k] = uint4{0, 0, 0, 0};
   const u32 ndr = !Opt && dtab ? ctr[kCtrNDirty] : 0u;
   const bool iso = !Opt && ndr != 0 && ndr <= kDirtyCap;
   if constexpr (!Opt) n = min(n, iso ? ctr[kCtrStop] : min(ctr[kCtrStop], ctr[kCtrDirty]));
