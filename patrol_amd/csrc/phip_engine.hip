@@ -76,19 +76,32 @@ struct Timing {
   hipEvent_t a, b;
 };
 
+// A fast Receive pass ("fast receive" below: what each kind enqueues).
+enum class PassKind { kOptimistic, kClassified, kIsolating };
+struct FastPass {
+  PassKind kind = PassKind::kClassified;
+  u32 n = 0;
+  u32 par = 0;          // batch parity: its shard counters (fast_counts) and
+  u32* c = nullptr;     // its counter set (fctr)
+  const HotHdr* hot = nullptr;   // the hot directory (nullptr: none)
+  const HotEntry* dir = nullptr;
+  void* hot_zero = nullptr;   // the directory kernel's count tables, for the fast kernel to clear
+  bool hot_join = false;      // the directory was built on stream2 (fast_back joins it)
+  u8* mark = nullptr;   // isolating: the status column, or a cleared one (k_dirty_pass)
+  UndoLog log{};        // optimistic: the undo log (cnt: set by the front; base, cap: by the back)
+};
+
 }  // namespace
 
 struct phip_handle {
   int device = 0;
   int ncu = 256;             // compute units (persistent grid size)
-  u32 ndef = 0;   // the last fast pass's ordered sub-batch (dirty buckets), entries
+  // The fast-pass policy: read by pass_kind alone, moved by apply_policy alone.
   // Dirty-bucket isolation (phip_kernels.hpp "Dirty buckets"): always
   // (PHIP_CFG_ISOLATE), or while iso_left > 0 -- kIsoKeep fast passes after
-  // the last one that met a dirty message.  coll_iso: whether the pass whose
-  // counters were collected last ran with it (its nested pass must too).
+  // the last one that met a dirty message.
   bool iso_always = false;
   u32 iso_left = 0;
-  bool coll_iso = false;
   // The optimistic pass (phip_kernels.hpp "The optimistic pass"): a decoded
   // batch of a pass that does not isolate runs without classification, unless
   // the handle was opened with PHIP_CFG_CLASSIFY_FIRST or one of its last
@@ -161,16 +174,10 @@ struct phip_handle {
   // call (or phip_flush)
   struct Pending {
     bool active = false;
-    NamesOffs src{};
-    const uint64_t *a = nullptr, *t = nullptr;
-    const int64_t* e = nullptr;
-    u32 n = 0;
-    u32 par = 0;
-    bool iso = false;
-    bool opt = false;   // an optimistic pass: `log` is what undoes it
-    UndoLog log{};
+    SoaIn<NamesOffs> in{};
     i64 now = 0;
     OutView ow{};
+    FastPass pass{};   // its queued pass (front and back enqueued)
   } pend;
   hipEvent_t ev_ctr = nullptr;   // a queued batch's counters reached ctr_host
   int deferred_rc = 0;   // a queued batch's error met by a call that returns no status
@@ -670,38 +677,36 @@ int pack_sharded(phip_handle* h, const Sharded& sh, u32 total_slot, u32* out, u3
 
 // A fast batch in three parts, so that a queued batch (PHIP_RECV_ASYNC) can
 // put the next batch's front in front of its own read-back:
-//   front    counter reset, then either the hot directory alone (an
-//            optimistic batch: k_hot_dir on the main stream, its launch also
-//            filling the status column) or k_classify (which fills the
-//            column) with the directory beside it on stream2;
-//   back     k_receive_fast (after the directory, whose count tables it
-//            clears for the next batch), then one k_shard_scan
-//            that packs the miss shards' offsets and stores the counters in
-//            the host's mapped mirror (queued: and resets them for the next
-//            batch), ev_ctr behind it;
-//   collect  the miss list packed from the host's counters, flags, stats.
+// fast_begin (the front: parity, counter set, k_batch_reset, then by kind),
+// fast_back (the fast kernel, which clears the directory's count tables for
+// the next batch, then the launch that packs the miss shards' offsets and
+// stores the counters in the host's mapped mirror -- queued: and resets the
+// next batch's -- with ev_ctr behind it) and fast_settle (the counters read:
+// a failed speculation run again, the policy moved, the pass collected).
+//   kind        front, main stream but marked    back, main stream
+//   optimistic  k_hot_dir with the status fill   k_receive_fast<Opt>, k_shard_scan
+//   classified  k_classify (fills the column),   k_receive_fast, k_shard_scan
+//               k_hot_dir on stream2
+//   isolating   as classified                    k_dirty_build, k_receive_fast,
+//                                                k_dirty_pass, k_batch_end
 // The miss list's shard counters alternate between two sets by batch parity
 // (B_FSCNT): the next batch's front resets its own set while the batch
 // before still has to pack its list from the other.
-struct FastFront {
-  const HotHdr* hot = nullptr;
-  const HotEntry* dir = nullptr;
-  void* hot_zero = nullptr;   // the directory kernel's count tables, for the fast kernel to clear
-  bool hot_join = false;      // the directory was built on stream2 (join_hot)
-  u32 par = 0;
-  bool iso = false;     // this pass sets its dirty buckets apart (the isolation kernels run)
-  u32* c = nullptr;     // the pass's counter set (fctr)
-  u8* mark = nullptr;   // decoded batches: the status column, or a cleared one (k_dirty_pass)
-  bool opt = false;     // an optimistic pass: no classification, the kernel keeps an undo log
-  UndoLog log{};        // its log (cnt: set by the front; base, cap: by the back)
-};
-template <class Src>
-int fork_hot(phip_handle* h, Src src, u32 n, FastFront* ff);
-int join_hot(phip_handle* h, const FastFront& ff);
 
-// Whether the handle's policy lets a decoded batch run optimistically.
-inline bool opt_allowed(const phip_handle* h) {
-  return !h->classify_first && h->opt_left == 0 && !h->iso_always && h->iso_left == 0;
+// What a caller asks of a pass: the handle's policy; the policy, and it may be
+// optimistic (the caller can undo it: a decoded batch's first pass); or isolation
+// forced on or off (finish_many_misses' nested pass, as the pass it finishes ran).
+enum class PassAsk { kPolicy, kMayUndo, kIsolate, kNoIsolate };
+
+// The one place that decides what a pass is.  Wire input is never optimistic.
+template <class In>
+PassKind pass_kind(const phip_handle* h, PassAsk ask) {
+  if (ask == PassAsk::kIsolate) return PassKind::kIsolating;
+  if (ask == PassAsk::kNoIsolate) return PassKind::kClassified;
+  if (h->iso_always || h->iso_left > 0) return PassKind::kIsolating;
+  if (ask == PassAsk::kMayUndo && In::kSoa && !h->classify_first && h->opt_left == 0)
+    return PassKind::kOptimistic;
+  return PassKind::kClassified;
 }
 
 // The per-wave entry counts of an optimistic pass's log, sized for the
@@ -776,70 +781,57 @@ int fast_shards(phip_handle* h, u32 n, u32 par, Sharded* out) {
   return PHIP_OK;
 }
 
-// Enqueue order matters at this size (2 ms per 100M messages): the counter
-// reset and the classification go first, so the GPU starts reading the batch
-// while the host still enqueues the directory on stream2.
-// reset = false: the batch queued just before (nothing since) reset the
-// counters in its last launch.
-// iso: whether the pass sets its dirty buckets apart (-1: the handle's
-// policy, phip_handle::iso_left).
-// opt: the caller can undo the pass and run the batch again (a decoded
-// batch's first pass), so the handle's policy may make it optimistic; its
-// front is the counter reset and one launch, the directory with the status
-// fill.
-template <class In, class HotSrc>
-int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront* ff,
-               bool reset = true, int iso = -1, bool opt = false) {
+// Start the hot directory of a classified fast batch on stream2, beside
+// k_classify (fast_back joins it).
+template <class Src>
+int fork_hot(phip_handle* h, Src src, FastPass* p) {
+  if (p->n < kHotMinBatch) return PHIP_OK;
+  // ev_fork: recorded by the front before the classification (stream2 waits
+  // only for the batch's producers, not for k_classify)
+  HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
   int rc;
-  *ff = FastFront{};
-  ff->iso = iso >= 0 ? iso != 0 : (h->iso_always || h->iso_left > 0);
-  u32 *c, *dlist = nullptr;
+  if ((rc = build_hot(h, src, p->n, h->stream2, nullptr, &p->hot, &p->dir, &p->hot_zero))) return rc;
+  HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
+  p->hot_join = true;
+  return PHIP_OK;
+}
+
+// An optimistic pass's front: no classification, and nothing runs beside the
+// directory, so it is built on the main stream with no hop, its launch also
+// filling the status column (k_hot_dir's fill workgroups; why a fill:
+// front_classified).  A batch too small for a directory gets a plain fill,
+// one without a status column the directory a classified batch builds.
+template <class HotSrc>
+int front_optimistic(phip_handle* h, HotSrc hsrc, u8* status, FastPass* p) {
+  int rc;
+  if ((rc = ensure(h, B_ULCNT, undo_counts(h), &p->log.cnt))) return rc;
+  if (p->n >= kHotMinBatch && status)
+    return build_hot(h, hsrc, p->n, h->stream, status, &p->hot, &p->dir, &p->hot_zero);
+  if (status) HIPCHK(h, hipMemsetAsync(status, PHIP_ST_MERGED, p->n, h->stream));
+  if (p->n >= kHotMinBatch) HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
+  return fork_hot(h, hsrc, p);
+}
+
+// A classified or isolating pass's front.  Enqueue order matters at this
+// size (2 ms per 100M messages): the classification goes right behind the
+// counter reset, so the GPU starts reading the batch while the host still
+// enqueues the directory on stream2.
+template <class In, class HotSrc>
+int front_classified(phip_handle* h, In in, HotSrc hsrc, u8* status, FastPass* p) {
+  int rc;
+  const u32 n = p->n;
+  u32* dlist = nullptr;
   DirtySet dset;
-  if ((rc = ensure(h, B_FSCNT, 4 * kShards, &c))) return rc;
-  // the pass's counter set and shard counters (the other parity's); their
-  // reset is the first thing either kind of pass puts on the stream
-  ff->par = h->fpar ^= 1u;
-  ff->c = fctr(h, ff->par);
-  ++h->nfast;
-  if (reset) {
-    k_batch_reset<<<1, kShards, 0, h->stream>>>(ff->c, fast_counts(h, ff->par));
-    HIPCHK(h, hipGetLastError());
-  }
-  if constexpr (In::kSoa) {
-    if (opt && iso < 0 && opt_allowed(h)) {
-      u32* lc;
-      const size_t nw = undo_counts(h);
-      if ((rc = ensure(h, B_ULCNT, nw, &lc))) return rc;
-      ff->opt = true;
-      ff->log.cnt = lc;
-      // Statuses: filled up front, not by byte stores from the fast kernel's
-      // lanes (2% of the kernel when measured, below).  Nothing runs beside
-      // an optimistic batch's directory, so it is built on the main stream,
-      // with no hop, and the fill is part of its launch (k_hot_dir's fill
-      // workgroups); a batch too small for a directory gets a fill.
-      if (kOptStatus) ff->mark = status;   // (a tuning build: the kernel's lanes fill it)
-      u8* fill = kOptStatus ? nullptr : status;
-      if (n >= kHotMinBatch && fill)
-        return build_hot(h, hsrc, n, h->stream, fill, &ff->hot, &ff->dir, &ff->hot_zero);
-      if (fill) HIPCHK(h, hipMemsetAsync(fill, PHIP_ST_MERGED, n, h->stream));
-      if (n >= kHotMinBatch) {   // (no status column: the directory as a classified batch builds it)
-        HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-        return fork_hot(h, hsrc, n, ff);
-      }
-      return PHIP_OK;
-    }
-  }
   // (the classification lists the dirty messages either way: the policy
   // learns of them, and an isolating pass builds its set from the list)
   if ((rc = dirty_set(h, &dset, &dlist))) return rc;
-  if (ff->iso) {
-    ff->mark = status;
+  if (p->kind == PassKind::kIsolating) {
+    p->mark = status;
     if (!status) {   // (marks need a column: a cleared one)
-      if ((rc = ensure(h, B_DMARK, n, &ff->mark))) return rc;
-      HIPCHK(h, hipMemsetAsync(ff->mark, 0, n, h->stream));
+      if ((rc = ensure(h, B_DMARK, n, &p->mark))) return rc;
+      HIPCHK(h, hipMemsetAsync(p->mark, 0, n, h->stream));
     }
   }
-  const bool with_hot = n >= kHotMinBatch;
   // A small batch classifies in a few µs, less than the directory kernel
   // takes: that chain goes first then.
   const bool hot_first = n < (1u << 23);
@@ -851,8 +843,8 @@ int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront*
   // stores from the fast kernel's lanes cost it 2%; a fill on stream2 beside
   // the classification slowed the classification more than it cost here
   // (DESIGN.md §4).
-  if (with_hot) HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-  if (with_hot && hot_first && (rc = fork_hot(h, hsrc, n, ff))) return rc;
+  if (n >= kHotMinBatch) HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
+  if (hot_first && (rc = fork_hot(h, hsrc, p))) return rc;
   {
     bool done = false;
     if constexpr (In::kSoa) {
@@ -863,63 +855,92 @@ int fast_front(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, FastFront*
         NamesOffs chk{};
         if constexpr (In::kOffs) chk = in.src;
         k_classify_soa2<<<grid_for((n + 1) / 2), kBlock, 0, h->stream>>>(in.ma, in.mt, in.me, n,
-                                                                          ff->c, status, chk,
-                                                                          dlist);
+                                                                          p->c, status, chk, dlist);
         done = true;
       }
     }
     if (!done) {
       if (status) HIPCHK(h, hipMemsetAsync(status, PHIP_ST_MERGED, n, h->stream));
       Launch l(h, "k_classify");
-      k_classify<In><<<grid_for(n), kBlock, 0, h->stream>>>(in, n, ff->c, dlist);
+      k_classify<In><<<grid_for(n), kBlock, 0, h->stream>>>(in, n, p->c, dlist);
     }
   }
   HIPCHK(h, hipGetLastError());
-  if (with_hot && !hot_first && (rc = fork_hot(h, hsrc, n, ff))) return rc;
-  return PHIP_OK;
+  return hot_first ? PHIP_OK : fork_hot(h, hsrc, p);
+}
+
+// A pass's front: what it is (pass_kind), its parity and counter set, the
+// counter reset (reset = false: the batch queued just before, nothing
+// since, reset the counters in its last launch), then the kind's front.
+template <class In, class HotSrc>
+int fast_begin(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, PassAsk ask, bool reset,
+               FastPass* p) {
+  int rc;
+  u32* c;
+  *p = FastPass{};
+  p->kind = pass_kind<In>(h, ask);
+  p->n = n;
+  if ((rc = ensure(h, B_FSCNT, 4 * kShards, &c))) return rc;
+  // the pass's counter set and shard counters (the other parity's); their
+  // reset is the first thing any kind of pass puts on the stream
+  p->par = h->fpar ^= 1u;
+  p->c = fctr(h, p->par);
+  ++h->nfast;
+  if (reset) {
+    k_batch_reset<<<1, kShards, 0, h->stream>>>(p->c, fast_counts(h, p->par));
+    HIPCHK(h, hipGetLastError());
+  }
+  if (p->kind == PassKind::kOptimistic) return front_optimistic(h, hsrc, status, p);
+  return front_classified(h, in, hsrc, status, p);
 }
 
 // The fast kernel is enqueued behind the classification without a host
 // round trip; it reads the counters itself.
 template <class In>
-int fast_back(phip_handle* h, In in, u32 n, FastFront& ff, bool queued) {
+int fast_back(phip_handle* h, In in, FastPass& p, bool queued) {
+  const u32 n = p.n;
+  const bool iso = p.kind == PassKind::kIsolating;
   u32* miss;
   int rc;
   Sharded msh;
   DirtySet dset{};
   SubBatch sb{};
   u32* dlist = nullptr;
-  if ((rc = ensure(h, B_MISS, n, &miss)) || (rc = fast_shards(h, n, ff.par, &msh))) return rc;
-  if (ff.iso) {
+  if ((rc = ensure(h, B_MISS, n, &miss)) || (rc = fast_shards(h, n, p.par, &msh))) return rc;
+  if (iso) {
     // the dirty set behind the classification (a batch without a dirty
     // message returns at once: one launch of ~3 us)
     if ((rc = dirty_set(h, &dset, &dlist)) || (rc = sub_batch(h, &sb))) return rc;
     Launch l(h, "k_dirty_build");
-    k_dirty_build<In><<<1, 1024, 0, h->stream>>>(in, n, ff.c, dlist, dset, table(h));
+    k_dirty_build<In><<<1, 1024, 0, h->stream>>>(in, n, p.c, dlist, dset, table(h));
     HIPCHK(h, hipGetLastError());
   }
-  if ((rc = join_hot(h, ff))) return rc;
-  if (ff.opt) {
-    if constexpr (In::kSoa) {
-      // (the log is sized here, not in the front: a queued front runs before
-      // the batch before is collected, and that batch's undo reads the log)
-      const UndoLayout ul = undo_layout(n, (u32)h->ncu);
-      ff.log.cap = ul.cap;
-      if ((rc = ensure(h, B_ULOG, (size_t)ul.halves, &ff.log.base))) return rc;
+  if (p.hot_join) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
+  switch (p.kind) {
+    case PassKind::kOptimistic:
+      if constexpr (In::kSoa) {   // (pass_kind: no other input is optimistic)
+        // (the log is sized here, not in the front: a queued front runs before
+        // the batch before is collected, and that batch's undo reads the log)
+        const UndoLayout ul = undo_layout(n, (u32)h->ncu);
+        p.log.cap = ul.cap;
+        if ((rc = ensure(h, B_ULOG, (size_t)ul.halves, &p.log.base))) return rc;
+        Launch l(h, "k_receive_fast");
+        k_receive_fast<In, true><<<ul.grid, kFastBlock, 0, h->stream>>>(
+            in, 0, n, table(h), msh, p.c, p.hot, p.dir, nullptr, nullptr, p.log,
+            (uint4*)p.hot_zero);
+      }
+      break;
+    case PassKind::kClassified:
+    case PassKind::kIsolating: {
       Launch l(h, "k_receive_fast");
-      k_receive_fast<In, true><<<ul.grid, kFastBlock, 0, h->stream>>>(
-          in, 0, n, table(h), msh, ff.c, ff.hot, ff.dir, nullptr, ff.mark, ff.log,
-          (uint4*)ff.hot_zero);
+      k_receive_fast<In><<<fast_grid(h, n), kFastBlock, 0, h->stream>>>(
+          in, 0, n, table(h), msh, p.c, p.hot, p.dir, iso ? dset.key : nullptr, p.mark,
+          UndoLog{}, (uint4*)p.hot_zero);
     }
-  } else {
-    Launch l(h, "k_receive_fast");
-    k_receive_fast<In><<<fast_grid(h, n), kFastBlock, 0, h->stream>>>(
-        in, 0, n, table(h), msh, ff.c, ff.hot, ff.dir, ff.iso ? dset.key : nullptr, ff.mark,
-        UndoLog{}, (uint4*)ff.hot_zero);
   }
   HIPCHK(h, hipGetLastError());
-  if (ff.hot_zero) h->hot_clean = ff.hot_zero;   // (queued behind every user of the tables)
-  if (ff.iso) {
+  if (p.hot_zero) h->hot_clean = p.hot_zero;   // (queued behind every user of the tables)
+  if (iso) {
     // the messages the fast kernel marked (an isolated batch's only: others
     // return at once), then the dirty buckets' records unmarked and their
     // ordered sub-batch built in the launch that ends the batch
@@ -927,17 +948,17 @@ int fast_back(phip_handle* h, In in, u32 n, FastFront& ff, bool queued) {
       Launch l(h, "k_dirty_pass");
       const unsigned g = (unsigned)std::max<u64>(
           1, std::min<u64>(((u64)n + 1023) / 1024, (u64)h->ncu * 2));
-      k_dirty_pass<In><<<g, 1024, 0, h->stream>>>(in, n, ff.c, ff.mark, dset.key, table(h), msh);
+      k_dirty_pass<In><<<g, 1024, 0, h->stream>>>(in, n, p.c, p.mark, dset.key, table(h), msh);
       HIPCHK(h, hipGetLastError());
     }
     k_batch_end<In><<<1, kShards, 0, h->stream>>>(
-        in, ff.c, dset.key, table(h),
+        in, p.c, dset.key, table(h),
         SubOut{sb.off, sb.len, sb.a, sb.t, sb.e, sb.map, kSubBatchCap}, msh.cnt, h->ctr_map,
-        kCtrWords, queued ? fast_counts(h, ff.par ^ 1u) : nullptr, fctr(h, ff.par ^ 1u));
+        kCtrWords, queued ? fast_counts(h, p.par ^ 1u) : nullptr, fctr(h, p.par ^ 1u));
   } else {
-    k_shard_scan<<<1, kShards, 0, h->stream>>>(msh.cnt, ff.c, kCtrMiss, h->ctr_map, kCtrWords,
-                                               queued ? fast_counts(h, ff.par ^ 1u) : nullptr,
-                                               fctr(h, ff.par ^ 1u));
+    k_shard_scan<<<1, kShards, 0, h->stream>>>(msh.cnt, p.c, kCtrMiss, h->ctr_map, kCtrWords,
+                                               queued ? fast_counts(h, p.par ^ 1u) : nullptr,
+                                               fctr(h, p.par ^ 1u));
   }
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev_ctr, h->stream));
@@ -945,10 +966,7 @@ int fast_back(phip_handle* h, In in, u32 n, FastFront& ff, bool queued) {
   return PHIP_OK;
 }
 
-// *first_dirty: n when the batch's dirty buckets were set apart (iso ran and
-// at most kDirtyCap dirty messages, short names), else its first dirty
-// message (the prefix rule).  Updates the isolation policy: kIsoKeep passes
-// after one that met a dirty message.
+// The isolation policy: kIsoKeep passes after one that met a dirty message.
 constexpr u32 kIsoKeep = 256;
 // An optimistic pass whose undo log overflowed (a batch that grows a field
 // with most of its cold messages: uniform keys) left the overflowing
@@ -959,37 +977,46 @@ constexpr u32 kIsoKeep = 256;
 // message, and the handle's next kOptBackoff fast passes classify first.
 constexpr u32 kOptBackoff = 256;
 
-// The counters of an optimistic pass (mirrored to the host): its log's
-// statistics and the back-off.  True when the speculation failed: the pass
-// met a dirty message or a malformed name entry, or its log overflowed, and
-// it has to be undone.
-bool opt_failed(phip_handle* h, u32 n) {
-  h->stats.log_count = h->ctr_host[kCtrLogCount];
-  h->stats.log_over = h->ctr_host[kCtrLogOver];
-  if (h->stats.log_over) h->opt_left = kOptBackoff;
-  return h->ctr_host[kCtrDirty] < n || h->ctr_host[kCtrStop] < n || h->stats.log_over != 0;
+// The one place that moves the policy: a pass's counters (mirrored to the
+// host) applied to opt_left and iso_left, with an optimistic pass's log
+// statistics.  True: a failed speculation, to be undone -- the pass met a dirty
+// message or a malformed name entry, or its log overflowed (the pass that runs
+// the batch again then classifies first).  iso_left moves only with a pass
+// that stands: that second pass reports the dirty message.
+bool apply_policy(phip_handle* h, const FastPass& p) {
+  const u32* c = h->ctr_host;
+  if (p.kind == PassKind::kOptimistic) {
+    h->stats.log_count = c[kCtrLogCount];
+    h->stats.log_over = c[kCtrLogOver];
+    if (c[kCtrLogOver]) h->opt_left = kOptBackoff;
+    if (c[kCtrDirty] < p.n || c[kCtrStop] < p.n || c[kCtrLogOver]) return true;
+  } else if (h->opt_left) {
+    --h->opt_left;
+  }
+  if (c[kCtrDirty] < p.n) h->iso_left = kIsoKeep;
+  else if (h->iso_left) --h->iso_left;
+  return false;
 }
 
-// A failed optimistic pass undone: every record it touched back to its state
-// before the batch (k_undo).  Its miss list is dropped with its counters;
-// nothing was created, and the classified pass that follows fills the status
-// column again.
-int undo_pass(phip_handle* h, u32 n, const UndoLog& log) {
-  Launch l(h, "k_undo");
-  k_undo<<<fast_grid(h, n) * (kFastBlock / 64), 256, 0, h->stream>>>(log, table(h));
-  HIPCHK(h, hipGetLastError());
-  return PHIP_OK;
-}
+// What a settled pass left to do (finish_receive).  first_dirty: n when the
+// dirty buckets were set apart (an isolating pass, at most kDirtyCap dirty
+// messages, short names), else the first dirty message (the prefix rule).
+struct FastOutcome {
+  u32 first_dirty = 0;
+  u32 nmiss = 0;         // misses of the clean prefix, listed in B_MISS
+  u32 stop = 0;          // the first malformed datagram or name entry (n: none)
+  u32 ndef = 0;          // entries of the ordered sub-batch (the dirty buckets, run_deferred)
+  bool iso_ran = false;  // the pass was isolating (its nested pass must be too)
+  bool again = false;    // a failed speculation: a second fast pass ran the batch again
+};
 
-int fast_collect(phip_handle* h, u32 n, u32 par, u32* first_dirty, u32* nmiss, bool iso_ran,
-                 bool opt_ran = false) {
+int fast_collect(phip_handle* h, const FastPass& p, FastOutcome* o) {
   int rc;
   if ((rc = check_flags(h))) return rc;
-  if (!opt_ran && h->opt_left) --h->opt_left;
-  *nmiss = h->ctr_host[kCtrMiss];
-  if (*nmiss) {
+  o->nmiss = h->ctr_host[kCtrMiss];
+  if (o->nmiss) {
     Sharded msh;
-    if ((rc = fast_shards(h, n, par, &msh))) return rc;
+    if ((rc = fast_shards(h, p.n, p.par, &msh))) return rc;
     Launch l(h, "k_shard_compact");
     dim3 grid(grid_for(h->ctr_host[kCtrShardMax]), kShards);
     k_shard_compact<<<grid, 256, 0, h->stream>>>(msh.base, msh.cap, msh.cnt,
@@ -997,41 +1024,52 @@ int fast_collect(phip_handle* h, u32 n, u32 par, u32* first_dirty, u32* nmiss, b
     HIPCHK(h, hipGetLastError());
   }
   const u32 nd = h->ctr_host[kCtrNDirty];
-  const bool iso = iso_ran && nd != 0 && nd <= kDirtyCap;
-  *first_dirty = iso ? n : std::min<u32>(h->ctr_host[kCtrDirty], n);
-  if (h->ctr_host[kCtrDirty] < n) h->iso_left = kIsoKeep;
-  else if (h->iso_left) --h->iso_left;
-  h->coll_iso = iso_ran;
-  h->ndef = iso ? h->ctr_host[kCtrNDefer] : 0;   // (the ordered sub-batch, run_deferred)
+  o->iso_ran = p.kind == PassKind::kIsolating;
+  const bool apart = o->iso_ran && nd != 0 && nd <= kDirtyCap;
+  o->first_dirty = apart ? p.n : std::min<u32>(h->ctr_host[kCtrDirty], p.n);
+  o->stop = std::min<u32>(h->ctr_host[kCtrStop], p.n);
+  o->ndef = apart ? h->ctr_host[kCtrNDefer] : 0;
   h->stats.ordered = 0;   // (finish_receive: the messages it sends through the ordered path)
   h->stats.hot_entries = h->ctr_host[kCtrHotEntries];
   h->stats.hot_hits = h->ctr_host[kCtrHotHits];
-  h->stats.misses = *nmiss;
+  h->stats.misses = o->nmiss;
   return PHIP_OK;
 }
 
-// The whole fast path of a batch (SoaIn or WireIn; hsrc: its names for the
-// hot-directory sample), synchronously: resets the batch's counters,
-// classifies, builds the hot directory on stream2 and applies the batch's
-// clean prefix: the messages before the first dirty one (*first_dirty; n if
-// none) and before the first malformed datagram (kCtrStop).  The prefix's
-// misses (*nmiss of them) are listed in B_MISS.
-// opt: the pass may be optimistic (fast_front); one that fails is undone here
-// and the batch run again, classified, under the policy as it stood.
+// Settles a pass whose back is enqueued and whose counters have arrived.  A
+// failed speculation is undone (k_undo: every record it touched back to its
+// state before the batch; its miss list goes with its counters, nothing was
+// created) and the batch run again, synchronously, under the policy as it
+// stands (the status column is filled again).  Then the pass is collected.
 template <class In, class HotSrc>
-int fast_apply(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, u32* first_dirty,
-               u32* nmiss, int iso = -1, bool opt = false) {
+int fast_settle(phip_handle* h, In in, HotSrc hsrc, u8* status, FastPass* p, FastOutcome* o) {
   int rc;
-  FastFront ff;
-  if ((rc = fast_front(h, in, hsrc, n, status, &ff, true, iso, opt)) ||
-      (rc = fast_back(h, in, n, ff, false)))
-    return rc;
-  if (ff.opt && opt_failed(h, n)) {
-    if ((rc = undo_pass(h, n, ff.log)) || (rc = fast_front(h, in, hsrc, n, status, &ff, true, iso)) ||
-        (rc = fast_back(h, in, n, ff, false)))
+  o->again = apply_policy(h, *p);
+  if (o->again) {
+    {
+      Launch l(h, "k_undo");
+      k_undo<<<fast_grid(h, p->n) * (kFastBlock / 64), 256, 0, h->stream>>>(p->log, table(h));
+      HIPCHK(h, hipGetLastError());
+    }
+    if ((rc = fast_begin(h, in, hsrc, p->n, status, PassAsk::kPolicy, true, p)) ||
+        (rc = fast_back(h, in, *p, false)))
       return rc;
+    (void)apply_policy(h, *p);   // (not optimistic: it stands)
   }
-  return fast_collect(h, n, ff.par, first_dirty, nmiss, ff.iso, ff.opt);
+  return fast_collect(h, *p, o);
+}
+
+// The whole fast path of a batch (SoaIn or WireIn; hsrc: its names for the
+// hot-directory sample), synchronously: its clean prefix applied (*o).
+template <class In, class HotSrc>
+int fast_apply(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, PassAsk ask,
+               FastOutcome* o) {
+  int rc;
+  FastPass p;
+  if ((rc = fast_begin(h, in, hsrc, n, status, ask, true, &p)) ||
+      (rc = fast_back(h, in, p, false)))
+    return rc;
+  return fast_settle(h, in, hsrc, status, &p, o);
 }
 
 // One message per distinct name of list[0..n) (k_dedupe) into B_DEDUP.
@@ -1063,12 +1101,13 @@ int dedupe_names(phip_handle* h, Src src, const u32* list, u32 n, u32** out, u32
 // merged again to no effect, and the hot directory now covers the new hot
 // buckets: their messages fold in LDS instead of each sending a
 // device-scope atomic to one record (134 ms per 100M-message batch through
-// k_receive_list).  Returns the misses of the second pass
-// (names dropped by k_dedupe for a shared tag) in *nmiss2, listed in B_MISS.
+// k_receive_list).  *o: the first pass's outcome; the second's
+// misses (names k_dedupe dropped for a shared tag, in B_MISS) replace its own.
 template <class Src>
 int finish_many_misses(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t,
-                       const int64_t* e, u32 nmiss, u32 prefix, i64 now, u8* status, u32* nmiss2) {
+                       const int64_t* e, u32 prefix, i64 now, u8* status, FastOutcome* o) {
   u32* miss = (u32*)h->buf[B_MISS].p;
+  const u32 nmiss = o->nmiss;
   int rc;
   // 1. distinct names
   u32 *dedup, nd = 0;
@@ -1084,11 +1123,15 @@ int finish_many_misses(phip_handle* h, Src src, const uint64_t* a, const uint64_
     HIPCHK(h, hipGetLastError());
   }
   // 4. the fast pass again
-  u32 fd = prefix;
   // (as the pass being finished did: its dirty buckets stay apart)
-  if ((rc = fast_apply(h, SoaIn<Src>{src, a, t, e}, src, prefix, status, &fd, nmiss2,
-                       h->coll_iso ? 1 : 0)))
+  FastOutcome o2;
+  if ((rc = fast_apply(h, SoaIn<Src>{src, a, t, e}, src, prefix, status,
+                       o->iso_ran ? PassAsk::kIsolate : PassAsk::kNoIsolate, &o2)))
     return rc;
+  // The sub-batch run_deferred runs is the last pass's: this pass rebuilt it
+  // (whether it runs, the prefix and the stop stay the first's, finish_receive).
+  o->nmiss = o2.nmiss;
+  o->ndef = o2.ndef;
   // 5. PHIP_ST_CREATED after the second pass wrote its statuses
   if (status && n_claimed) {
     Launch l(h, "k_mark_created");
@@ -1099,16 +1142,17 @@ int finish_many_misses(phip_handle* h, Src src, const uint64_t* a, const uint64_
   return clear_new(h, n_claimed);
 }
 
-// The messages fast_apply missed: create their buckets, merge them with
+// The messages the fast pass missed: create their buckets, merge them with
 // creator tracking (PHIP_ST_CREATED on the first message of a new bucket).
 template <class Src>
 int finish_misses(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t, const int64_t* e,
-                  u32 nmiss, u32 prefix, i64 now, u8* status) {
-  if (nmiss == 0) return PHIP_OK;
+                  i64 now, u8* status, FastOutcome* o) {
+  if (o->nmiss == 0) return PHIP_OK;
   int rc;
-  if (nmiss >= kManyMisses &&
-      (rc = finish_many_misses(h, src, a, t, e, nmiss, prefix, now, status, &nmiss)))
+  if (o->nmiss >= kManyMisses &&
+      (rc = finish_many_misses(h, src, a, t, e, std::min(o->stop, o->first_dirty), now, status, o)))
     return rc;
+  const u32 nmiss = o->nmiss;
   if (nmiss == 0) return PHIP_OK;
   u32* miss = (u32*)h->buf[B_MISS].p;
   u32 n_claimed = 0;
@@ -1132,26 +1176,6 @@ int finish_misses(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t,
   if (const u32 left = h->ctr_host[kCtrMiss])
     return set_err(h, PHIP_ERR_INVALID, "internal: %u names missing after insert", left);
   return clear_new(h, n_claimed);
-}
-
-// Start the hot directory of a classified fast batch on stream2, beside
-// k_classify (joined by join_hot).
-template <class Src>
-int fork_hot(phip_handle* h, Src src, u32 n, FastFront* ff) {
-  if (n < kHotMinBatch) return PHIP_OK;
-  // ev_fork: recorded by fast_front before the classification (stream2 waits
-  // only for the batch's producers, not for k_classify)
-  HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-  int rc;
-  if ((rc = build_hot(h, src, n, h->stream2, nullptr, &ff->hot, &ff->dir, &ff->hot_zero))) return rc;
-  HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
-  ff->hot_join = true;
-  return PHIP_OK;
-}
-
-int join_hot(phip_handle* h, const FastFront& ff) {
-  if (ff.hot_join) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  return PHIP_OK;
 }
 
 // ------------------------------------------------------------ ordered ----
@@ -1592,16 +1616,15 @@ inline OutView shifted(OutView o, u32 k) {
   return o;
 }
 
-// The last fast pass's ordered sub-batch (its dirty buckets' dirty messages
-// and the merges of their cells, dirty_finish) through the ordered path,
+// The last fast pass's ordered sub-batch (nd entries: its dirty buckets' dirty
+// messages and the merges of their cells, dirty_finish) through the ordered path,
 // its statuses and replies scattered back.  The dirty buckets' other
 // messages were merged by the fast pass (before each bucket's first dirty
 // message) or folded into the cells (after it); no other bucket is touched,
 // and Receive is per bucket (repo.go:77-106), so applying the sub-batch
 // after the rest of the batch gives each dirty bucket the Go loop's states.
 template <class Src>
-int run_deferred(phip_handle* h, Src src, i64 now, const OutView& ow) {
-  const u32 nd = h->ndef;   // (the last fast pass's: a second pass rebuilt it)
+int run_deferred(phip_handle* h, Src src, i64 now, const OutView& ow, u32 nd) {
   // (kSubBatchOver included: dirty_finish counted more entries than the
   // sub-batch holds and wrote none)
   if (nd > kSubBatchCap) {
@@ -1632,22 +1655,21 @@ int run_deferred(phip_handle* h, Src src, i64 now, const OutView& ow) {
   return PHIP_OK;
 }
 
-// After the fast path: the clean prefix's new buckets (finish_misses), then
-// the ordered path over messages [first_dirty, stop), which starts from the
-// state the prefix left (the Go loop's state at that message) -- or, when the
-// fast pass deferred the dirty buckets (first_dirty == n), over their
-// messages (run_deferred).
+// After the fast path, what its outcome left: the clean prefix's new buckets
+// (finish_misses), then the ordered path over messages [first_dirty, stop),
+// which starts from the state the prefix left (the Go loop's state at that
+// message) -- or, when the fast pass deferred the dirty buckets
+// (first_dirty == n), over their messages (run_deferred).
 template <class Src>
 int finish_receive(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t,
-                   const int64_t* e, u32 stop, u32 first_dirty, u32 nmiss, i64 now,
-                   const OutView& ow, u32 n, bool deferred) {
+                   const int64_t* e, i64 now, const OutView& ow, FastOutcome o) {
   int rc;
-  if ((rc = finish_misses(h, src, a, t, e, nmiss, std::min(stop, first_dirty), now, ow.status)))
-    return rc;
-  if (deferred) return run_deferred(h, src, now, ow);
-  h->stats.ordered = first_dirty < stop ? stop - first_dirty : 0;
-  if (first_dirty >= stop) return PHIP_OK;
-  const u32 k = first_dirty;
+  const bool deferred = o.ndef != 0;   // (the first pass's; finish_misses may run a second)
+  if ((rc = finish_misses(h, src, a, t, e, now, ow.status, &o))) return rc;
+  if (deferred) return run_deferred(h, src, now, ow, o.ndef);
+  const u32 stop = o.stop, k = o.first_dirty;
+  h->stats.ordered = k < stop ? stop - k : 0;
+  if (k >= stop) return PHIP_OK;
   OpView ov{};
   ov.kind = nullptr; ov.kind0 = PHIP_OP_RECEIVE;
   ov.now = nullptr; ov.now0 = now;
@@ -1681,18 +1703,13 @@ int stopped_at_bad_name(phip_handle* h, const OutView& ow, u32 n, u32 stop) {
 // ordered path from its first incast or -0.0 on.
 template <class Src>
 int receive_decoded(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t,
-                    const int64_t* e, u32 n, i64 now, const OutView& ow, bool opt = true) {
+                    const int64_t* e, u32 n, i64 now, const OutView& ow, PassAsk ask) {
   int rc;
-  // The hot directory (read-only on the table and the batch) is built on
-  // stream2 while the batch is classified.
-  // (opt = false: the batch of a failed optimistic pass, run again)
-  u32 fd = n, nmiss = 0;
-  if ((rc = fast_apply(h, SoaIn<Src>{src, a, t, e}, src, n, ow.status, &fd, &nmiss, -1, opt)))
+  FastOutcome o;
+  if ((rc = fast_apply(h, SoaIn<Src>{src, a, t, e}, src, n, ow.status, ask, &o)) ||
+      (rc = finish_receive(h, src, a, t, e, now, ow, o)))
     return rc;
-  const u32 stop = std::min<u32>(h->ctr_host[kCtrStop], n);   // (a checked batch's malformed entry)
-  if ((rc = finish_receive(h, src, a, t, e, stop, fd, nmiss, now, ow, n, h->ndef != 0)))
-    return rc;
-  return stopped_at_bad_name(h, ow, n, stop);
+  return stopped_at_bad_name(h, ow, n, o.stop);   // (a checked batch's malformed entry)
 }
 
 // PHIP_RECV_ASYNC: the queued batch's counters, then what its fast pass left
@@ -1701,30 +1718,18 @@ int receive_decoded(phip_handle* h, Src src, const uint64_t* a, const uint64_t* 
 int finish_pending(phip_handle* h, bool* worked) {
   if (worked) *worked = false;
   if (!h->pend.active) return PHIP_OK;
-  const phip_handle::Pending p = h->pend;
+  phip_handle::Pending p = h->pend;
   h->pend.active = false;
   HIPCHK(h, hipEventSynchronize(h->ev_ctr));
-  u32 fd = p.n, nmiss = 0;
   int rc;
-  if (p.opt && opt_failed(h, p.n)) {
-    // A failed speculation: undone, and the batch run again through the
-    // classified path as a synchronous call would (a fast pass of its own,
-    // so the caller queues the next batch's front again).
-    if (worked) *worked = true;
-    if ((rc = undo_pass(h, p.n, p.log)) ||
-        (rc = receive_decoded(h, p.src, p.a, p.t, p.e, p.n, p.now, p.ow, false)))
-      return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return PHIP_OK;
-  }
-  if ((rc = fast_collect(h, p.n, p.par, &fd, &nmiss, p.iso, p.opt))) return rc;
-  const u32 stop = std::min<u32>(h->ctr_host[kCtrStop], p.n);   // (a checked batch's malformed entry)
-  const bool deferred = h->ndef != 0;
-  if (nmiss == 0 && fd >= stop && !deferred) return stopped_at_bad_name(h, p.ow, p.n, stop);
+  FastOutcome o;
+  // (a failed speculation runs a fast pass of its own: the caller queues its front again)
+  if ((rc = fast_settle(h, p.in, p.in.src, p.ow.status, &p.pass, &o))) return rc;
+  if (!o.again && o.nmiss == 0 && o.first_dirty >= o.stop && o.ndef == 0)
+    return stopped_at_bad_name(h, p.ow, p.pass.n, o.stop);   // (a checked batch's malformed entry)
   if (worked) *worked = true;
-  if ((rc = finish_receive(h, p.src, p.a, p.t, p.e, stop, fd, nmiss, p.now, p.ow, p.n,
-                           deferred)) ||
-      (rc = stopped_at_bad_name(h, p.ow, p.n, stop)))
+  if ((rc = finish_receive(h, p.in.src, p.in.ma, p.in.mt, p.in.me, p.now, p.ow, o)) ||
+      (rc = stopped_at_bad_name(h, p.ow, p.pass.n, o.stop)))
     return rc;
   // The leftover work (the miss merges, the ordered path's folds, which also
   // join stream2/stream4 into the handle's stream) writes this batch's
@@ -2551,6 +2556,7 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
   std::lock_guard<std::mutex> g(h->mu);
   bool dev = flags & PHIP_DEVICE_PTRS;
   u32 n = m->n;
+  const PassAsk ask = (flags & PHIP_RECV_CLASSIFY) ? PassAsk::kPolicy : PassAsk::kMayUndo;
   if ((flags & PHIP_RECV_ASYNC) && dev && n >= kHotMinBatch && m->names && m->name_offs &&
       m->added && m->taken && m->elapsed) {
     // Queue this batch's front (reset, directory with the status fill, or
@@ -2563,13 +2569,12 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
     NamesOffs src{m->names, m->name_offs, m->names_len};
     SoaIn<NamesOffs> in{src, m->added, m->taken, m->elapsed};
     OutView ow{};
-    FastFront ff;
+    FastPass pass;
     int rc;
     bool worked = false;
     if ((rc = outputs(h, res, n, true, &ow))) return rc;
     const bool prev = h->pend.active;
-    const bool opt = !(flags & PHIP_RECV_CLASSIFY);
-    if ((rc = fast_front(h, in, src, n, ow.status, &ff, !prev, -1, opt)))
+    if ((rc = fast_begin(h, in, src, n, ow.status, ask, !prev, &pass)))
       return after_error(h, rc);
     const u64 nfast = h->nfast, grows = h->grows;
     if (prev && (rc = finish_pending(h, &worked))) return after_error(h, rc);
@@ -2580,21 +2585,10 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
     // (a failed optimistic pass ran the batch again, a fast pass of its own:
     // the front queued again follows the policy as that batch left it)
     if (worked && (h->nfast != nfast || h->grows != grows) &&
-        (rc = fast_front(h, in, src, n, ow.status, &ff, true, -1, opt)))
+        (rc = fast_begin(h, in, src, n, ow.status, ask, true, &pass)))
       return after_error(h, rc);
-    if ((rc = fast_back(h, in, n, ff, true))) return after_error(h, rc);
-    h->pend.active = true;
-    h->pend.src = src;
-    h->pend.a = m->added;
-    h->pend.t = m->taken;
-    h->pend.e = m->elapsed;
-    h->pend.n = n;
-    h->pend.par = ff.par;
-    h->pend.iso = ff.iso;
-    h->pend.opt = ff.opt;
-    h->pend.log = ff.log;
-    h->pend.now = now;
-    h->pend.ow = ow;
+    if ((rc = fast_back(h, in, pass, true))) return after_error(h, rc);
+    h->pend = {true, in, now, ow, pass};
     return PHIP_OK;
   }
   if (int rc0 = begin_call(h)) return rc0;
@@ -2615,8 +2609,7 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
       (rc = stage(h, B_A, m->added, n, dev, &a)) || (rc = stage(h, B_T, m->taken, n, dev, &t)) ||
       (rc = stage(h, B_E, m->elapsed, n, dev, &e)) || (rc = outputs(h, res, n, dev, &ow)))
     return rc;
-  if ((rc = receive_decoded(h, src, a, t, e, n, now, ow, !(flags & PHIP_RECV_CLASSIFY))))
-    return after_error(h, rc);
+  if ((rc = receive_decoded(h, src, a, t, e, n, now, ow, ask))) return after_error(h, rc);
   return copy_outputs(h, res, n, dev, ow);
 }
 
@@ -2639,13 +2632,13 @@ int receive_datagrams_dev(phip_handle* h, const u8* d_bytes, const uint64_t* d_o
   // that need it; a batch's dirty buckets (at most kDirtyCap dirty messages)
   // go through the ordered path as a sub-batch dirty_finish
   // reads from the wire.
-  u32 fd = n, nmiss = 0;
-  if ((rc = fast_apply(h, WireIn{d_bytes, d_offs}, Datagrams{d_bytes, d_offs}, n, ow.status, &fd,
-                       &nmiss)))
+  FastOutcome o;
+  if ((rc = fast_apply(h, WireIn{d_bytes, d_offs}, Datagrams{d_bytes, d_offs}, n, ow.status,
+                       PassAsk::kPolicy, &o)))
     return after_error(h, rc);
-  const u32 stop = std::min<u32>(h->ctr_host[kCtrStop], n);   // (the first short datagram)
+  const u32 stop = o.stop;   // (the first short datagram)
   if ((rc = fill_stopped(h, ow.status, n, stop))) return rc;
-  if (fd < stop || nmiss || h->ndef) {
+  if (o.first_dirty < stop || o.nmiss || o.ndef) {
     uint64_t *a, *t, *no;
     int64_t* e;
     u8* nl;
@@ -2653,14 +2646,13 @@ int receive_datagrams_dev(phip_handle* h, const u8* d_bytes, const uint64_t* d_o
         (rc = ensure(h, B_DE, n, &e)) || (rc = ensure(h, B_NOFF, n, &no)) ||
         (rc = ensure(h, B_NLEN, n, &nl)))
       return rc;
-    if (fd < stop || nmiss) {   // (a batch whose dirty buckets alone are left reads no decode)
+    if (o.first_dirty < stop || o.nmiss) {   // (a batch whose dirty buckets alone are left reads no decode)
       Launch l(h, "k_decode");
       k_decode<<<grid_for(stop), kBlock, 0, h->stream>>>(d_bytes, d_offs, stop, a, t, e, no, nl,
                                                           h->ctr);
       HIPCHK(h, hipGetLastError());
     }
-    if ((rc = finish_receive(h, NamesPairs{d_bytes, no, nl}, a, t, e, stop, fd, nmiss, now, ow, n,
-                             h->ndef != 0)))
+    if ((rc = finish_receive(h, NamesPairs{d_bytes, no, nl}, a, t, e, now, ow, o)))
       return after_error(h, rc);
   }
   if ((rc = copy_outputs(h, res, n, dev, ow))) return rc;

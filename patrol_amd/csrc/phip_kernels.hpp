@@ -253,14 +253,14 @@ constexpr u32 kCtrRetry = 4;
 // Min-reduced: the first malformed datagram or name entry; the batch stops
 // there (F).  W: k_classify*, k_receive_fast<Opt>; k_decode on G, where nobody
 // reads it (it decodes below a stop already known).  R: k_dirty_build,
-// k_receive_fast, k_dirty_pass, opt_failed and the receive paths' `stop`.
+// k_receive_fast, k_dirty_pass, apply_policy and fast_collect (`stop`).
 constexpr u32 kCtrStop = 5;
 // The ordered path's long and huge segments (G).  W: k_seg_count (zeroes),
 // k_seg_finish (appends).  R: ordered().
 constexpr u32 kCtrLongSegs = 6;
 constexpr u32 kCtrHugeSegs = 9;
 // An optimistic pass's undo log: messages that found their wave's region
-// full, and the pass's entries (F).  W: k_receive_fast<Opt>.  R: opt_failed.
+// full, and the pass's entries (F).  W: k_receive_fast<Opt>.  R: apply_policy.
 // They share the segment words: those kernels run on G only, this one on F
 // only.
 constexpr u32 kCtrLogOver = kCtrLongSegs;
@@ -277,7 +277,7 @@ constexpr u32 kCtrHotHits = 10;
 constexpr u32 kCtrHotEntries = 11;
 // Min-reduced: the first dirty message (F, P).  W: k_classify*,
 // k_receive_fast<Opt>; k_route_count (P).  R: k_receive_fast, fast_collect,
-// opt_failed; k_route_count's recount, route_hot_n (P).
+// apply_policy; k_route_count's recount, route_hot_n (P).
 constexpr u32 kCtrDirty = 12;
 // A sharded list's largest shard (F, G).  W: shard_scan.  R: the host's
 // k_shard_compact grids.
@@ -862,7 +862,7 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
   __shared__ u32 best, nsel, last;
   if (blockIdx.x >= nblk) {
     // The workgroups behind the nblk sampling ones fill the batch's status
-    // column with PHIP_ST_MERGED (an optimistic batch: fast_front), in the
+    // column with PHIP_ST_MERGED (an optimistic batch: front_optimistic), in the
     // launch the sample's dependent loads leave idle: 16-byte stores over the
     // aligned middle, bytes at both ends.
     constexpr u32 b4 = PHIP_ST_MERGED * 0x01010101u;
@@ -1500,17 +1500,12 @@ constexpr u8 kMarkDirty = 0x40;
 // region are kept for the directory flush, which logs (slot, ca, ct, ce) as
 // it issues its atomics.  Every wave stores its count once, at the end (so
 // the counts need no reset).
-// (PHIP_UNDO_NT / PHIP_OPT_STATUS: tuning builds, tools/build_variants.sh --
-// plain instead of non-temporal log stores; the status column filled by the
-// kernel's lanes instead of the host's fill before the pass.  DESIGN.md §4
-// round 7 has the measurements behind the defaults.)
+// (PHIP_UNDO_NT: a tuning build, tools/build_variants.sh -- plain instead of
+// non-temporal log stores.  DESIGN.md §4 round 7 has the measurements behind
+// the default, and behind the host's status fill before the pass.)
 #ifndef PHIP_UNDO_NT
 #define PHIP_UNDO_NT 1
 #endif
-#ifndef PHIP_OPT_STATUS
-#define PHIP_OPT_STATUS 0
-#endif
-constexpr bool kOptStatus = PHIP_OPT_STATUS != 0;
 constexpr u32 kUndoFlushReserve = 64 * ((kHotMax + kFastBlock - 1) / kFastBlock);
 struct UndoLog {
   u64x2* base = nullptr;   // waves * cap entries of two 16-byte halves
@@ -1644,9 +1639,6 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     const u32 tid = chunk * 64 + lane;
     bool valid = tid < n;
     const u32 i = tid < n ? tid : n - 1;
-    if constexpr (Opt && kOptStatus) {
-      if (mark && tid < n) mark[tid] = PHIP_ST_MERGED;
-    }
     if constexpr (Opt && In::kSoa) {
       // checked names: a malformed entry reads as the empty name at offset 0
       // (NamesOffs::get) and ends the speculation
