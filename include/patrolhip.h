@@ -443,6 +443,102 @@ int phip_export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64
                       uint8_t* out, uint64_t out_cap, uint64_t* offs /* max_msgs+1 */,
                       uint32_t max_msgs, phip_sweep_stats* st, uint32_t flags);
 
+/* Partition digests: what a table holds, in 16 bytes per partition of the
+ * name space, so that two replicas find where they differ without sweeping
+ * (the Dynamo / Riak anti-entropy scheme; the reference has no counterpart).
+ * One reconcile round between two nodes:
+ *     both:  phip_table_digest(h, k, mine)              exchange 16 * 2^k bytes
+ *     both:  phip_digest_diff(mine, theirs, k, mask, &ndiff)
+ *     both:  loop phip_export_sweep_parts(h, &cur, ..., k, mask, ...) until
+ *            st.done, into the peer's phip_receive_datagrams
+ * after which, NaN fields aside (below), the digests are equal.
+ *
+ * Definitions (tests/_digest_cases.py restates them).  fmix(x) is murmur3's
+ * 64-bit finaliser: x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33;
+ * x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33.  canon(bits) is 0 for
+ * 0x8000000000000000 and bits otherwise: +0 and -0 never converge under Merge
+ * (Go's `<` keeps the zero seen first), so replicas that differ only in the
+ * sign of a zero count as equal.
+ *  - Covered records: exactly those phip_export_sweep writes with idle_ns = 0:
+ *    published, state not zero (a zero state's datagram would be an incast
+ *    request, and a bucket one side holds as a zero state and the other not at
+ *    all must not make them differ), name of at most PHIP_MAX_NAME_LEN bytes.
+ *    There is no idle filter: `created` is local to a node.
+ *  - Partition: k = log2_parts, 0 <= k <= PHIP_DIGEST_MAX_LOG2_PARTS;
+ *    part(tag, k) = k ? fmix(tag) >> (64 - k) : 0, where tag is the record's
+ *    stored tag: FNV-1a 64 of the name (phip_hash_names), masked by
+ *    phip_config.debug_tag_bits, 0 stored as 1.  It is the same on every node,
+ *    under every placement seed, table size and rebuild.  (The mix: the shard
+ *    map spends the tag's own top bits, and truncated test tags have none.)
+ *    Two tables are comparable only if opened with the same debug_tag_bits.
+ *  - Record hash, on IEEE bit patterns, never on created, flags or offsets:
+ *        h = fmix(tag + 0x9E3779B97F4A7C15)
+ *        h = fmix(h ^ canon(added));  h = fmix(h ^ canon(taken))
+ *        h = fmix(h ^ (uint64_t)elapsed)
+ *  - Entry p: sum = the covered records' h of partition p added mod 2^64,
+ *    count = how many.  Entries are additive: entry p at level k - 1 is entry
+ *    2p + entry 2p + 1 at level k (phip_digest_fold), so one pass at a fine
+ *    level gives every coarser one.
+ * Limits.  Names whose 64-bit tags collide are told apart by the table but not
+ * by the digest: a swap of states between two such names goes unseen (it takes
+ * an FNV-1a 64 collision).  A NaN field never converges (a local NaN sticks, a
+ * replica's NaN is never adopted): a partition holding a bucket whose replicas
+ * disagree on a NaN differs in every round and its few buckets are re-sent
+ * every round -- harmless, bounded by the partition.  Likewise fields below
+ * zero against a bucket the peer lacks or holds as a zero state: the receiver
+ * creates the bucket at zero and Merge never lowers, so one negative field
+ * takes a second round (the receiver's zero comes back), and a bucket all of
+ * whose fields are <= 0 never converges (the receiver's state stays zero, and
+ * a zero state is never sent).  The sums are no defence against a peer that
+ * crafts states.
+ *
+ * phip_table_digest reads the whole table once and leaves it untouched.  out:
+ * 2^log2_parts entries, host memory, or device memory (8-byte aligned) with
+ * PHIP_DEVICE_PTRS; any other flag bit, log2_parts > 20 or out == NULL is
+ * PHIP_ERR_INVALID, and a refused call touches neither out nor st.  st (host
+ * memory, may be NULL): records and bytes are what count mode reports with
+ * idle_ns = 0.  Serialised with the handle's other calls; a batch queued with
+ * PHIP_RECV_ASYNC is finished first, and its error is this call's.
+ *
+ * phip_digest_diff / phip_digest_fold are host only (no handle, no GPU).
+ * diff: bit p of mask (word p >> 6, bit p & 63; max(1, 2^k / 64) words) is set
+ * iff sum or count of entry p differ; bits beyond 2^k are zero; *ndiff (may be
+ * NULL) is the number of set bits.  fold: level log2_in to level log2_out <=
+ * log2_in (greater: PHIP_ERR_INVALID); in and out may be the same buffer.
+ *
+ * phip_export_sweep_parts is phip_export_sweep -- the same output, caps, cut
+ * at a record, cursor and layout count, restarted, pointer rules and count
+ * mode, idle_ns composing as there -- with one more condition on which
+ * buckets: bit part(tag, log2_parts) of part_mask must be set.  part_mask is
+ * host memory either way (max(1, 2^k / 64) words); NULL or log2_parts > 20 is
+ * PHIP_ERR_INVALID.  Window: with m set bits among the first 2^k, m == 0 reads
+ * no slot and returns n = 0, done = 1, slots_scanned = 0, offs[0] = 0 and the
+ * cursor at the end of the table (count mode: n = bytes = 0); otherwise
+ * W = max(4 * max_msgs * ceil(2^k / m), PHIP_SWEEP_TILE) rounded up to a
+ * multiple of PHIP_SWEEP_TILE (saturating, clipped to the table), so that a
+ * window holds about as many qualifying records as the unfiltered sweep's; a
+ * call still never reads past its window. */
+#define PHIP_DIGEST_MAX_LOG2_PARTS 20
+typedef struct phip_digest_part {
+  uint64_t sum;   /* covered records' hashes, added mod 2^64 */
+  uint64_t count; /* covered records                         */
+} phip_digest_part;
+typedef struct phip_digest_stats {
+  uint64_t records;       /* sum of count = count mode's n with idle_ns = 0        */
+  uint64_t bytes;         /* sum of 25 + name length of them = count mode's bytes  */
+  uint64_t slots_scanned; /* the table's slots                                     */
+} phip_digest_stats;
+int phip_table_digest(phip_handle* h, uint32_t log2_parts, phip_digest_part* out /* 2^k */,
+                      phip_digest_stats* st /* may be NULL */, uint32_t flags);
+int phip_digest_diff(const phip_digest_part* a, const phip_digest_part* b, uint32_t log2_parts,
+                     uint64_t* mask, uint64_t* ndiff /* may be NULL */);
+int phip_digest_fold(const phip_digest_part* in, uint32_t log2_in, uint32_t log2_out,
+                     phip_digest_part* out /* 2^log2_out */);
+int phip_export_sweep_parts(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64_t idle_ns,
+                            uint32_t log2_parts, const uint64_t* part_mask, uint8_t* out,
+                            uint64_t out_cap, uint64_t* offs /* max_msgs+1 */, uint32_t max_msgs,
+                            phip_sweep_stats* st, uint32_t flags);
+
 /* ---- hot path ---- */
 /* ReplicatedRepo.Receive over n raw datagrams (byte-identical wire format,
  * bucket.go:59-64): bytes[offs[i] .. offs[i+1]).  `now` is the clock reading

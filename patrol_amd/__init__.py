@@ -7,9 +7,9 @@ and bench.py.
 """
 from ._lib import EXPORTS, LIB_PATH, build_id, load  # noqa: F401
 from .engine import (BucketState, GPUGroup, GPURepo, PatrolHipError, Ring, TakeBatcher,  # noqa: F401
-                     incast_replies, marshal, names_blob, parse_rate, udp_recv_batch,
-                     udp_send_batch)
+                     digest_diff, digest_fold, incast_replies, marshal, names_blob, parse_rate,
+                     udp_recv_batch, udp_send_batch)
 
 __all__ = ["GPURepo", "GPUGroup", "BucketState", "PatrolHipError", "Ring", "TakeBatcher", "parse_rate", "marshal",
-           "names_blob", "udp_recv_batch", "udp_send_batch", "incast_replies", "load", "LIB_PATH",
-           "EXPORTS"]
+           "names_blob", "udp_recv_batch", "udp_send_batch", "incast_replies", "digest_diff",
+           "digest_fold", "load", "LIB_PATH", "EXPORTS"]

@@ -33,6 +33,7 @@ EXPORTS = [
     "phip_route_pack_ops", "phip_group_apply_mixed",
     "phip_undo_log_layout",
     "phip_export_sweep",
+    "phip_table_digest", "phip_digest_diff", "phip_digest_fold", "phip_export_sweep_parts",
 ]
 
 PHIP_OK = 0
@@ -60,6 +61,7 @@ SWEEP_COUNT = 0x200
 SWEEP_TILE = 4096        # PHIP_SWEEP_TILE: the sweep window's granule, slots
 PACKET_SIZE = 256
 BUCKET_FIXED_SIZE = 25   # PHIP_BUCKET_FIXED_SIZE: added, taken, elapsed, name length
+DIGEST_MAX_LOG2_PARTS = 20
 
 
 class phip_config(C.Structure):
@@ -109,6 +111,14 @@ class phip_sweep_cursor(C.Structure):
 class phip_sweep_stats(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bytes", C.c_uint64), ("slots_scanned", C.c_uint64),
                 ("done", C.c_uint32), ("restarted", C.c_uint32)]
+
+
+class phip_digest_part(C.Structure):
+    _fields_ = [("sum", C.c_uint64), ("count", C.c_uint64)]
+
+
+class phip_digest_stats(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("bytes", C.c_uint64), ("slots_scanned", C.c_uint64)]
 
 
 class phip_results(C.Structure):
@@ -244,5 +254,11 @@ def load(path: str = LIB_PATH):
     if hasattr(L, "phip_export_sweep"):
         L.phip_export_sweep.argtypes = [vp, C.POINTER(phip_sweep_cursor), i64, i64, vp, u64, vp,
                                         u32, C.POINTER(phip_sweep_stats), u32]
+    if hasattr(L, "phip_table_digest"):
+        L.phip_table_digest.argtypes = [vp, u32, vp, C.POINTER(phip_digest_stats), u32]
+        L.phip_digest_diff.argtypes = [vp, vp, u32, vp, C.POINTER(u64)]
+        L.phip_digest_fold.argtypes = [vp, u32, u32, vp]
+        L.phip_export_sweep_parts.argtypes = [vp, C.POINTER(phip_sweep_cursor), i64, i64, u32, vp,
+                                              vp, u64, vp, u32, C.POINTER(phip_sweep_stats), u32]
     _lib = L
     return L

@@ -62,7 +62,7 @@ enum BufId {
   B_WING, B_SEGXF, B_FOLDDBG, B_SMALL, B_HUGE2, B_LONG2,
   B_STATES, B_NAME1, B_HOT, B_ROUTE, B_EXPORT, B_MSHARD, B_MSCNT, B_FSCNT, B_DEDUP, B_DSET, B_TSTATS, B_SEGT, B_RHOT,
   B_DLIST, B_DTAB, B_DMARK, B_SMAP, B_SOFF, B_SLEN, B_SA, B_ST, B_SE, B_SSTAT, B_SREP, B_NCHK,
-  B_EVICT, B_ULOG, B_ULCNT, B_SWEEP,
+  B_EVICT, B_ULOG, B_ULCNT, B_SWEEP, B_DIGEST, B_DIGOUT,
   B_COUNT_
 };
 
@@ -3265,29 +3265,57 @@ int phip_evict_idle(phip_handle* h, int64_t now, int64_t idle_ns, uint64_t min_e
 // A device-pointer call reads the four counters back once, at its end; a
 // host-pointer call also reads the window's totals after the scan, to size
 // its staging buffers by what the window holds instead of by the caller's caps.
-int phip_export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64_t idle_ns,
-                      uint8_t* out, uint64_t out_cap, uint64_t* offs, uint32_t max_msgs,
-                      phip_sweep_stats* st, uint32_t flags) {
+// phip_export_sweep is the no-mask case (parts == false: the kernels'
+// unfiltered instantiations, the unfiltered window); phip_export_sweep_parts
+// copies its mask once per call behind the counters of the sweep's buffer and
+// widens the window by the share of the partitions it asks for.
+static int export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64_t idle_ns,
+                        bool parts, uint32_t log2_parts, const uint64_t* part_mask, uint8_t* out,
+                        uint64_t out_cap, uint64_t* offs, uint32_t max_msgs, phip_sweep_stats* st,
+                        uint32_t flags) {
   if (!h || !cur || !st) return PHIP_ERR_INVALID;
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = begin_call(h)) return rc0;   // (finishes a queued PHIP_RECV_ASYNC batch)
   if (flags & ~(PHIP_DEVICE_PTRS | PHIP_SWEEP_COUNT))
     return set_err(h, PHIP_ERR_INVALID, "sweep: unknown flag bits 0x%x", flags);
   if (idle_ns < 0) return set_err(h, PHIP_ERR_INVALID, "sweep: idle_ns must not be negative");
+  if (parts && (!part_mask || log2_parts > PHIP_DIGEST_MAX_LOG2_PARTS))
+    return set_err(h, PHIP_ERR_INVALID, "sweep: a partition mask and log2_parts <= %d are required",
+                   PHIP_DIGEST_MAX_LOG2_PARTS);
   const bool dev = flags & PHIP_DEVICE_PTRS;
+  // the mask's words, and m: its set bits among the first 2^k
+  const u64 nparts = parts ? 1ull << log2_parts : 1;
+  const size_t mw = parts ? (size_t)std::max<u64>(nparts / 64, 1) : 0;
+  u64 m = 0;
+  for (size_t w = 0; w < mw; ++w)
+    m += (u64)__builtin_popcountll(nparts < 64 ? part_mask[w] & ((1ull << nparts) - 1)
+                                               : part_mask[w]);
+  const bool none = parts && !m;
   int rc;
   u64 c[kSwWords] = {};
   phip_sweep_stats s{};
   if (flags & PHIP_SWEEP_COUNT) {
     if (out) return set_err(h, PHIP_ERR_INVALID, "sweep: count mode takes no output buffer");
+    if (none) {
+      *st = s;
+      return PHIP_OK;
+    }
     u64* ctr;
-    if ((rc = ensure(h, B_SWEEP, kSwWords, &ctr))) return rc;
+    if ((rc = ensure(h, B_SWEEP, kSwWords + mw, &ctr))) return rc;
     HIPCHK(h, hipMemsetAsync(ctr, 0, kSwWords * sizeof(u64), h->stream));
+    if (parts)
+      HIPCHK(h, hipMemcpyAsync(ctr + kSwWords, part_mask, mw * sizeof(u64), hipMemcpyHostToDevice,
+                               h->stream));
     {
       Launch l(h, "k_sweep_count");
-      k_sweep_count<false><<<std::min<unsigned>(grid_for(h->cap), 8u * (unsigned)h->ncu), kBlock,
-                             0, h->stream>>>(h->recs, 0, h->cap, now, idle_ns, nullptr, nullptr,
-                                             ctr);
+      const unsigned grid = std::min<unsigned>(grid_for(h->cap), 8u * (unsigned)h->ncu);
+      if (parts)
+        k_sweep_count<false, true><<<grid, kBlock, 0, h->stream>>>(
+            h->recs, 0, h->cap, now, idle_ns, nullptr, nullptr, ctr,
+            SweepParts<true>{ctr + kSwWords, log2_parts});
+      else
+        k_sweep_count<false, false><<<grid, kBlock, 0, h->stream>>>(
+            h->recs, 0, h->cap, now, idle_ns, nullptr, nullptr, ctr, SweepParts<false>{});
     }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
@@ -3318,23 +3346,35 @@ int phip_export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64
     }
   }
   s0 = std::min<u64>(s0, h->cap);
-  u64 W = std::max<u64>(4ull * max_msgs, PHIP_SWEEP_TILE);
+  if (none) s0 = h->cap;   // (an empty mask reads no slot and is done)
+  // (4 * 2^32 * 2^20 < 2^64: the product cannot wrap)
+  u64 W = std::max<u64>(4ull * max_msgs * ((nparts + std::max<u64>(m, 1) - 1) / std::max<u64>(m, 1)),
+                        PHIP_SWEEP_TILE);
   W = (W + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE * PHIP_SWEEP_TILE;
   const u64 s_end = std::min<u64>(s0 + W, h->cap);
   s.slots_scanned = s_end - s0;
   const u32 ntiles = (u32)((s_end - s0 + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE);
   u64 next = s_end;
   if (ntiles) {
-    // one buffer: the counters, the tiles' byte sums, the tiles' counts
+    // one buffer: the counters, the mask, the tiles' byte sums, the tiles' counts
     u64* ctr;
-    if ((rc = ensure(h, B_SWEEP, kSwWords + (size_t)ntiles + ((size_t)ntiles + 1) / 2, &ctr)))
+    if ((rc = ensure(h, B_SWEEP, kSwWords + mw + (size_t)ntiles + ((size_t)ntiles + 1) / 2, &ctr)))
       return rc;
-    u64* tile_bytes = ctr + kSwWords;
+    u64* d_mask = ctr + kSwWords;
+    u64* tile_bytes = d_mask + mw;
     u32* tile_cnt = (u32*)(tile_bytes + ntiles);
+    const SweepParts<true> sp{d_mask, log2_parts};
+    if (parts)
+      HIPCHK(h, hipMemcpyAsync(d_mask, part_mask, mw * sizeof(u64), hipMemcpyHostToDevice,
+                               h->stream));
     {
       Launch l(h, "k_sweep_count");
-      k_sweep_count<true><<<ntiles, kBlock, 0, h->stream>>>(h->recs, s0, s_end, now, idle_ns,
-                                                            tile_cnt, tile_bytes, ctr);
+      if (parts)
+        k_sweep_count<true, true><<<ntiles, kBlock, 0, h->stream>>>(h->recs, s0, s_end, now, idle_ns,
+                                                                    tile_cnt, tile_bytes, ctr, sp);
+      else
+        k_sweep_count<true, false><<<ntiles, kBlock, 0, h->stream>>>(
+            h->recs, s0, s_end, now, idle_ns, tile_cnt, tile_bytes, ctr, SweepParts<false>{});
     }
     {
       Launch l(h, "k_sweep_scan");
@@ -3354,9 +3394,14 @@ int phip_export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64
       // (long names are bounded by the arena's size, not its cursor: reading
       // the cursor would cost a device-pointer call a second round trip)
       Launch l(h, "k_sweep_write");
-      k_sweep_write<<<ntiles, kSweepBlock, 0, h->stream>>>(h->recs, h->arena, h->arena_cap, s0, s_end, now,
-                                                           idle_ns, tile_cnt, tile_bytes, max_msgs,
-                                                           budget, d_out, d_offs, ctr);
+      if (parts)
+        k_sweep_write<true><<<ntiles, kSweepBlock, 0, h->stream>>>(
+            h->recs, h->arena, h->arena_cap, s0, s_end, now, idle_ns, tile_cnt, tile_bytes,
+            max_msgs, budget, d_out, d_offs, ctr, sp);
+      else
+        k_sweep_write<false><<<ntiles, kSweepBlock, 0, h->stream>>>(
+            h->recs, h->arena, h->arena_cap, s0, s_end, now, idle_ns, tile_cnt, tile_bytes,
+            max_msgs, budget, d_out, d_offs, ctr, SweepParts<false>{});
     }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
@@ -3385,6 +3430,86 @@ int phip_export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64
   cur->layout = h->layout_gen;
   s.done = next >= h->cap;
   *st = s;
+  return PHIP_OK;
+}
+
+int phip_export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64_t idle_ns,
+                      uint8_t* out, uint64_t out_cap, uint64_t* offs, uint32_t max_msgs,
+                      phip_sweep_stats* st, uint32_t flags) {
+  return export_sweep(h, cur, now, idle_ns, false, 0, nullptr, out, out_cap, offs, max_msgs, st,
+                      flags);
+}
+
+int phip_export_sweep_parts(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int64_t idle_ns,
+                            uint32_t log2_parts, const uint64_t* part_mask, uint8_t* out,
+                            uint64_t out_cap, uint64_t* offs, uint32_t max_msgs,
+                            phip_sweep_stats* st, uint32_t flags) {
+  return export_sweep(h, cur, now, idle_ns, true, log2_parts, part_mask, out, out_cap, offs,
+                      max_msgs, st, flags);
+}
+
+// Table digest (patrolhip.h "Partition digests"; kernels in phip_kernels.hpp
+// "table digest").  Up to 2^12 partitions: k_digest sums in LDS and stores one
+// table per workgroup, k_digest_reduce adds them up -- nothing to clear.  From
+// 2^13 on: k_digest adds into the cleared result with global atomics, and
+// k_digest_reduce only sums the workgroups' record and byte counts.  The
+// result is built in the caller's device buffer, or in the handle's and copied.
+int phip_table_digest(phip_handle* h, uint32_t log2_parts, phip_digest_part* out,
+                      phip_digest_stats* st, uint32_t flags) {
+  if (!h) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;   // (finishes a queued PHIP_RECV_ASYNC batch)
+  if (flags & ~PHIP_DEVICE_PTRS)
+    return set_err(h, PHIP_ERR_INVALID, "digest: unknown flag bits 0x%x", flags);
+  if (!out || log2_parts > PHIP_DIGEST_MAX_LOG2_PARTS)
+    return set_err(h, PHIP_ERR_INVALID, "digest: out and log2_parts <= %d are required",
+                   PHIP_DIGEST_MAX_LOG2_PARTS);
+  const bool dev = flags & PHIP_DEVICE_PTRS;
+  if (dev && (reinterpret_cast<uintptr_t>(out) & 7))
+    return set_err(h, PHIP_ERR_INVALID, "digest: a device buffer is 8-byte aligned");
+  const u32 k = log2_parts;
+  const size_t nparts = (size_t)1 << k;
+  const bool lds = k <= kDigestLdsLog2;
+  // two workgroups of 16 waves a compute unit (48 KiB of LDS each)
+  const unsigned grid =
+      std::min<unsigned>(grid_for(h->cap, 2 * kDigestBlock), 2u * (unsigned)h->ncu);
+  int rc;
+  // one buffer: the stats, the workgroups' counts, then their tables
+  u64* stats;
+  if ((rc = ensure(h, B_DIGEST, kDgWords + (size_t)grid * kDgWords + (lds ? 2 * grid * nparts : 0),
+                   &stats)))
+    return rc;
+  u64* pstat = stats + kDgWords;
+  u64* partial = pstat + (size_t)grid * kDgWords;
+  phip_digest_part* res = out;
+  if (!dev && (rc = ensure(h, B_DIGOUT, nparts, &res))) return rc;
+  if (!lds) HIPCHK(h, hipMemsetAsync(res, 0, nparts * sizeof(phip_digest_part), h->stream));
+  {
+    Launch l(h, "k_digest");
+    if (lds)
+      k_digest<true><<<grid, kDigestBlock, 0, h->stream>>>(h->recs, h->cap, k, partial, nullptr,
+                                                           pstat);
+    else
+      k_digest<false><<<grid, kDigestBlock, 0, h->stream>>>(h->recs, h->cap, k, nullptr, res,
+                                                            pstat);
+  }
+  {
+    Launch l(h, "k_digest_reduce");
+    const unsigned rgrid = lds ? (unsigned)((nparts + 63) / 64) + 1 : 1;
+    k_digest_reduce<<<rgrid, kDigestBlock, 0, h->stream>>>(partial, grid, k, res, pstat, stats);
+  }
+  HIPCHK(h, hipGetLastError());
+  u64 sw[kDgWords] = {};
+  HIPCHK(h, hipMemcpyAsync(sw, stats, sizeof sw, hipMemcpyDeviceToHost, h->stream));
+  if (!dev)
+    HIPCHK(h, hipMemcpyAsync(out, res, nparts * sizeof(phip_digest_part), hipMemcpyDeviceToHost,
+                             h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (st) {
+    st->records = sw[kDgRecords];
+    st->bytes = sw[kDgBytes];
+    st->slots_scanned = h->cap;
+  }
   return PHIP_OK;
 }
 

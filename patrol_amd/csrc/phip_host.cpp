@@ -209,4 +209,44 @@ int phip_api_take(phip_handle* h, const uint8_t* name, uint32_t len, const char*
   return ok ? 200 : 429;
 }
 
+// Partition digests (patrolhip.h "Partition digests"): the two host helpers.
+int phip_digest_diff(const phip_digest_part* a, const phip_digest_part* b, uint32_t log2_parts,
+                     uint64_t* mask, uint64_t* ndiff) {
+  if (!a || !b || !mask || log2_parts > PHIP_DIGEST_MAX_LOG2_PARTS) return PHIP_ERR_INVALID;
+  const u64 parts = 1ull << log2_parts;
+  const u64 words = parts < 64 ? 1 : parts / 64;
+  u64 nd = 0;
+  for (u64 w = 0; w < words; ++w) {
+    u64 bits = 0;
+    for (u64 p = w * 64; p < parts && p < (w + 1) * 64; ++p)
+      if (a[p].sum != b[p].sum || a[p].count != b[p].count) {
+        bits |= 1ull << (p & 63);
+        ++nd;
+      }
+    mask[w] = bits;
+  }
+  if (ndiff) *ndiff = nd;
+  return PHIP_OK;
+}
+
+int phip_digest_fold(const phip_digest_part* in, uint32_t log2_in, uint32_t log2_out,
+                     phip_digest_part* out) {
+  if (!in || !out || log2_in > PHIP_DIGEST_MAX_LOG2_PARTS || log2_out > log2_in)
+    return PHIP_ERR_INVALID;
+  // entry p of the coarse level: the 2^(in - out) consecutive fine entries
+  // from p << (in - out); ascending p reads at or ahead of every write, so
+  // in == out works in place
+  const u64 n_out = 1ull << log2_out, span = 1ull << (log2_in - log2_out);
+  for (u64 p = 0; p < n_out; ++p) {
+    u64 s = 0, c = 0;
+    for (u64 q = p * span; q < (p + 1) * span; ++q) {
+      s += in[q].sum;
+      c += in[q].count;
+    }
+    out[p].sum = s;
+    out[p].count = c;
+  }
+  return PHIP_OK;
+}
+
 }  // extern "C"

@@ -5476,13 +5476,40 @@ constexpr u32 kSweepBlock = PHIP_SWEEP_BLOCK;
 static_assert(kSweepTile % kSweepBlock == 0 && kSweepTile % kBlock == 0 && kSweepBlock <= 1024,
               "sweep tile");
 
-// Datagram bytes of a record the sweep exports, 0 for one it skips.
-__device__ inline u32 sweep_size(const Rec& r, i64 now, i64 idle_ns) {
+// The digest partition of a stored tag at 2^k partitions (patrolhip.h "Partition
+// digests"): the top k bits of murmur3's finaliser, seeded_mix with seed 0 --
+// not the tag's own top bits, which the shard map spends (a shard would fill
+// 1/world of the partitions) and which a truncated test tag does not have.
+__host__ __device__ inline u32 digest_part(u64 tag, u32 k) {
+  return k ? (u32)(seeded_mix(tag, 0) >> (64 - k)) : 0u;
+}
+
+// phip_export_sweep_parts' set of partitions: bit p of mask[p >> 6].  The
+// unfiltered sweep's instantiations carry the empty form (the last kernel
+// argument, so the others keep their places).
+template <bool kParts>
+struct SweepParts {};
+template <>
+struct SweepParts<true> {
+  const u64* mask;   // device copy, 2^k bits
+  u32 k;
+};
+
+// Datagram bytes of a record the sweep exports, 0 for one it skips.  The
+// partition test comes last: one mix and one bit load, for the records that
+// passed the cheaper tests.
+template <bool kParts = false>
+__device__ inline u32 sweep_size(const Rec& r, i64 now, i64 idle_ns,
+                                 SweepParts<kParts> parts = SweepParts<kParts>{}) {
   if (!r.tag || !(rec_flags(r) & kRecPublished)) return 0;
   const u32 len = (u32)(r.name0 & 0xFFu);
   if (len > PHIP_MAX_NAME_LEN) return 0;
   if (state_is_zero(dec_f64(r.added), dec_f64(r.taken), r.elapsed)) return 0;
   if (idle_ns > 0 && bucket_idle(r.created, r.elapsed, now, idle_ns)) return 0;
+  if constexpr (kParts) {
+    const u32 p = digest_part(r.tag, parts.k);
+    if (!((parts.mask[p >> 6] >> (p & 63)) & 1)) return 0;
+  }
   return PHIP_BUCKET_FIXED_SIZE + len;
 }
 
@@ -5490,11 +5517,12 @@ __device__ inline u32 sweep_size(const Rec& r, i64 now, i64 idle_ns) {
 // tile_cnt[t] / tile_bytes[t] (plain stores, no atomics).  Otherwise (count
 // mode over the whole table) k_evict_count's grid: a few workgroups per
 // compute unit striding, sums in registers, one add per wave and counter.
-template <bool kTiles>
+template <bool kTiles, bool kParts>
 __global__ __launch_bounds__(kBlock) void k_sweep_count(const Rec* __restrict__ recs, u64 s0,
                                                         u64 s_end, i64 now, i64 idle_ns,
                                                         u32* __restrict__ tile_cnt,
-                                                        u64* __restrict__ tile_bytes, u64* ctr) {
+                                                        u64* __restrict__ tile_bytes, u64* ctr,
+                                                        SweepParts<kParts> parts) {
   u32 n = 0;
   u64 b = 0;
   if (kTiles) {
@@ -5503,14 +5531,14 @@ __global__ __launch_bounds__(kBlock) void k_sweep_count(const Rec* __restrict__ 
     for (u32 k = 0; k < kSweepTile / kBlock; ++k) {
       const u64 s = t0 + (u64)k * kBlock + threadIdx.x;
       if (s >= s_end) break;
-      const u32 sz = sweep_size(load_rec(&recs[s]), now, idle_ns);
+      const u32 sz = sweep_size<kParts>(load_rec(&recs[s]), now, idle_ns, parts);
       n += sz != 0;
       b += sz;
     }
   } else {
     const u64 stride = (u64)gridDim.x * kBlock;
     for (u64 s = s0 + (u64)blockIdx.x * kBlock + threadIdx.x; s < s_end; s += stride) {
-      const u32 sz = sweep_size(load_rec(&recs[s]), now, idle_ns);
+      const u32 sz = sweep_size<kParts>(load_rec(&recs[s]), now, idle_ns, parts);
       n += sz != 0;
       b += sz;
     }
@@ -5618,15 +5646,22 @@ __device__ inline void sweep_put8(u8* d, u64 w) {
 // slot over the totals k_sweep_scan left -- no atomics.  A tile whose base
 // rank is above max_msgs holds neither a written record nor that one, and
 // returns at once.
+template <bool kParts>
 __global__ __launch_bounds__(kSweepBlock) void k_sweep_write(
     const Rec* __restrict__ recs, const u8* __restrict__ arena, u64 arena_used, u64 s0, u64 s_end,
     i64 now, i64 idle_ns, const u32* __restrict__ tile_cnt, const u64* __restrict__ tile_bytes,
-    u32 max_msgs, u64 budget, u8* __restrict__ out, u64* __restrict__ offs, u64* ctr) {
+    u32 max_msgs, u64 budget, u8* __restrict__ out, u64* __restrict__ offs, u64* ctr,
+    SweepParts<kParts> parts) {
   __shared__ u32 wtot[2][kSweepBlock / 64];
   u64 rank0 = tile_cnt[blockIdx.x];
   u64 byte0 = tile_bytes[blockIdx.x];
   if (blockIdx.x == 0 && threadIdx.x == 0) offs[0] = 0;
   if (rank0 > max_msgs) return;
+  // (filtered: a tile the count pass found empty holds nothing to write and
+  // not the first unwritten record either; with few partitions asked for most
+  // tiles end here without reading a slot.  The last tile has no successor
+  // to tell by and always runs.)
+  if (kParts && blockIdx.x + 1 < gridDim.x && tile_cnt[blockIdx.x + 1] == rank0) return;
   const u32 wv = threadIdx.x >> 6;
   const u64 t0 = s0 + (u64)blockIdx.x * kSweepTile;
   for (u32 k = 0; k < kSweepTile / kSweepBlock; ++k) {
@@ -5635,7 +5670,7 @@ __global__ __launch_bounds__(kSweepBlock) void k_sweep_write(
     u32 sz = 0;
     if (s < s_end) {
       r = load_rec(&recs[s]);
-      sz = sweep_size(r, now, idle_ns);
+      sz = sweep_size<kParts>(r, now, idle_ns, parts);
     }
     const u32 v = sz ? (1u << 19) | sz : 0u;
     const u32 sc = wave_incl_scan(v);
@@ -5697,6 +5732,165 @@ __global__ __launch_bounds__(kSweepBlock) void k_sweep_write(
       for (; j < len; ++j) d[j] = arena[oa + j];
     }
   }
+}
+
+// ------------------------------------------------------ table digest -----
+// phip_table_digest: per partition of the tag space (digest_part), the sum
+// mod 2^64 of a hash of every record the unfiltered sweep would export, and
+// their number.  Sums are order-free, as the merge is, and additive: level
+// k - 1 is the pairwise sum of level k.  One streaming pass (k_digest), a
+// persistent grid striding over the slots with two whole-record loads in
+// flight per thread, then k_digest_reduce.
+//
+// k <= kDigestLdsLog2: a workgroup accumulates in LDS with LDS atomics and
+// stores its table to partial[workgroup][2][2^k] (plain stores), which
+// k_digest_reduce sums per partition: no global atomics, nothing pre-zeroed.
+// The LDS table holds R = min(64, 4096 >> k) copies of the 2^k entries and a
+// lane adds to copy lane & (R - 1): at k = 0 the 64 lanes of a wave add to 64
+// different words instead of one, at k <= 6 no two lanes of a wave-instruction
+// share a word, and from there on the partitions themselves spread the lanes.
+// The copies are folded when the table is stored.
+//
+// k > kDigestLdsLog2: the entries no longer fit LDS; every covered record
+// issues two no-return 64-bit global adds into the zeroed result (>= 8192
+// entries of 16 bytes, spread by the mix: no same-address pile-up).
+//
+// Either way a workgroup also stores its covered records' count and datagram
+// bytes to pstat[workgroup], summed by k_digest_reduce's last workgroup.
+constexpr u32 kDigestLdsLog2 = 12;
+constexpr u32 kDigestBlock = 1024;
+constexpr u32 kDigestLdsEntries = 1u << kDigestLdsLog2;   // 48 KiB: u64 sums, u32 counts
+constexpr u32 kDgRecords = 0;   // words of the stats k_digest_reduce leaves
+constexpr u32 kDgBytes = 1;
+constexpr u32 kDgWords = 2;
+
+__host__ __device__ inline u64 digest_canon(u64 bits) { return bits == kSign ? 0ull : bits; }
+
+// The record hash (patrolhip.h "Partition digests"): on IEEE bit patterns,
+// the two zeros as one (they never converge under Merge), never on created,
+// flags or arena offsets.
+__host__ __device__ inline u64 digest_hash(u64 tag, u64 added_bits, u64 taken_bits, i64 elapsed) {
+  u64 h = seeded_mix(tag + 0x9E3779B97F4A7C15ull, 0);
+  h = seeded_mix(h ^ digest_canon(added_bits), 0);
+  h = seeded_mix(h ^ digest_canon(taken_bits), 0);
+  return seeded_mix(h ^ (u64)elapsed, 0);
+}
+
+__host__ __device__ inline u32 digest_copies(u32 k) {
+  const u32 r = kDigestLdsEntries >> k;
+  return r < 64u ? r : 64u;
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(kDigestBlock) void k_digest(const Rec* __restrict__ recs, u64 cap,
+                                                         u32 k, u64* __restrict__ partial,
+                                                         phip_digest_part* __restrict__ out,
+                                                         u64* __restrict__ pstat) {
+  __shared__ u64 l_sum[kLds ? kDigestLdsEntries : 1];
+  __shared__ u32 l_cnt[kLds ? kDigestLdsEntries : 1];
+  __shared__ u64 w_n[kDigestBlock / 64], w_b[kDigestBlock / 64];
+  const u32 copies = kLds ? digest_copies(k) : 1u;
+  const u32 entries = copies << k;
+  if (kLds) {
+    for (u32 i = threadIdx.x; i < entries; i += kDigestBlock) { l_sum[i] = 0; l_cnt[i] = 0; }
+    __syncthreads();
+  }
+  const u32 copy = (threadIdx.x & (copies - 1)) << k;
+  u32 n = 0;
+  u64 b = 0;
+  auto add = [&](const Rec& r) {
+    const u32 sz = sweep_size(r, 0, 0);
+    if (!sz) return;
+    n += 1;
+    b += sz;
+    const u32 p = digest_part(r.tag, k);
+    const u64 h = digest_hash(r.tag, dec_f64(r.added), dec_f64(r.taken), r.elapsed);
+    if (kLds) {
+      __hip_atomic_fetch_add(&l_sum[copy + p], h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&l_cnt[copy + p], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    } else {
+      __hip_atomic_fetch_add(&out[p].sum, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&out[p].count, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  };
+  const u64 stride = (u64)gridDim.x * kDigestBlock;
+  for (u64 s = (u64)blockIdx.x * kDigestBlock + threadIdx.x; s < cap; s += 2 * stride) {
+    const Rec r0 = load_rec(&recs[s]);
+    Rec r1{};   // (an empty slot: not covered)
+    if (s + stride < cap) r1 = load_rec(&recs[s + stride]);
+    add(r0);
+    add(r1);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    n += __shfl_xor(n, d);
+    b += __shfl_xor(b, d);
+  }
+  if (__lane_id() == 0) { w_n[threadIdx.x >> 6] = n; w_b[threadIdx.x >> 6] = b; }
+  __syncthreads();   // (also: every LDS add of the workgroup has landed)
+  if (threadIdx.x == 0) {
+    u64 tn = 0, tb = 0;
+    for (u32 i = 0; i < kDigestBlock / 64; ++i) { tn += w_n[i]; tb += w_b[i]; }
+    pstat[(u64)blockIdx.x * kDgWords + kDgRecords] = tn;
+    pstat[(u64)blockIdx.x * kDgWords + kDgBytes] = tb;
+  }
+  if (kLds) {
+    const u32 parts = 1u << k;
+    u64* mine = partial + ((u64)blockIdx.x * 2) * parts;
+    for (u32 p = threadIdx.x; p < parts; p += kDigestBlock) {
+      u64 sm = 0, c = 0;
+      for (u32 q = 0; q < copies; ++q) { sm += l_sum[(q << k) + p]; c += l_cnt[(q << k) + p]; }
+      mine[p] = sm;
+      mine[parts + p] = c;
+    }
+  }
+}
+
+// Sums the workgroups' tables.  Workgroup w < ceil(2^k / 64) (partial != null)
+// takes the partitions [64 w, 64 w + pw), pw = min(2^k, 64): thread t reads
+// partition t % pw of the workgroups t / pw, t / pw + 1024 / pw, ... (a wave
+// reads 512 contiguous bytes of one workgroup's table), a tree over LDS sums
+// the kDigestBlock / pw threads of a partition.  The last workgroup sums
+// pstat into stats.
+__global__ __launch_bounds__(kDigestBlock) void k_digest_reduce(
+    const u64* __restrict__ partial, u32 nwg, u32 k, phip_digest_part* __restrict__ out,
+    const u64* __restrict__ pstat, u64* __restrict__ stats) {
+  __shared__ u64 t_sum[kDigestBlock], t_cnt[kDigestBlock];
+  const u32 t = threadIdx.x;
+  if (blockIdx.x + 1 == gridDim.x) {
+    u64 a = 0, c = 0;
+    for (u32 g = t; g < nwg; g += kDigestBlock) {
+      a += pstat[(u64)g * kDgWords + kDgRecords];
+      c += pstat[(u64)g * kDgWords + kDgBytes];
+    }
+    t_sum[t] = a;
+    t_cnt[t] = c;
+    __syncthreads();
+    for (u32 d = kDigestBlock / 2; d >= 1; d >>= 1) {
+      if (t < d) { t_sum[t] += t_sum[t + d]; t_cnt[t] += t_cnt[t + d]; }
+      __syncthreads();
+    }
+    if (t == 0) { stats[kDgRecords] = t_sum[0]; stats[kDgBytes] = t_cnt[0]; }
+    return;
+  }
+  const u32 parts = 1u << k;
+  const u32 pw = parts < 64u ? parts : 64u;
+  const u32 pl = t % pw, gl = t / pw, ng = kDigestBlock / pw;
+  const u32 p = blockIdx.x * 64 + pl;
+  u64 sm = 0, c = 0;
+  for (u32 g = gl; g < nwg; g += ng) {
+    const u64* tab = partial + ((u64)g * 2) * parts;
+    sm += tab[p];
+    c += tab[parts + p];
+  }
+  t_sum[t] = sm;
+  t_cnt[t] = c;
+  __syncthreads();
+  for (u32 d = ng / 2; d >= 1; d >>= 1) {
+    if (gl < d) { t_sum[t] += t_sum[t + d * pw]; t_cnt[t] += t_cnt[t + d * pw]; }
+    __syncthreads();
+  }
+  if (gl == 0) { out[p].sum = t_sum[t]; out[p].count = t_cnt[t]; }
 }
 
 }  // namespace phip

@@ -80,6 +80,52 @@ def _evict_dict(st) -> dict:
     return {k: int(getattr(st, k)) for k, _ in _lib.phip_evict_stats._fields_}
 
 
+def _part_mask(log2_parts: int, mask):
+    """A partition mask as the uint64 words phip_export_sweep_parts reads
+    (max(1, 2^k / 64) of them; shorter input is an error, not an over-read)."""
+    m = np.ascontiguousarray(mask, np.uint64)
+    k = int(log2_parts)
+    if 0 <= k <= _lib.DIGEST_MAX_LOG2_PARTS and m.size < max(1, (1 << k) // 64):
+        raise ValueError("partition mask shorter than 2^log2_parts bits")
+    return m if m.size else np.zeros(1, np.uint64)
+
+
+def _digest_entries(d):
+    """(sum, count[, stats]) -> (interleaved uint64[2^k, 2], k)."""
+    s, c = np.asarray(d[0], np.uint64), np.asarray(d[1], np.uint64)
+    k = int(s.size).bit_length() - 1
+    if s.size != c.size or s.size != 1 << k or k > _lib.DIGEST_MAX_LOG2_PARTS:
+        raise ValueError("a digest is 2^k sums and 2^k counts, k <= 20")
+    return np.ascontiguousarray(np.stack([s, c], axis=1)), k
+
+
+def digest_diff(a, b):
+    """phip_digest_diff of two digests (sum, count) of one level: -> (mask
+    uint64 words, bit p set iff partition p differs; how many differ).  The
+    mask goes into export_sweep(parts=(log2_parts, mask))."""
+    (ea, k), (eb, kb) = _digest_entries(a), _digest_entries(b)
+    if k != kb:
+        raise ValueError("digest_diff: the digests are of different levels")
+    mask = np.zeros(max(1, (1 << k) // 64), np.uint64)
+    nd = C.c_uint64()
+    rc = _lib.load().phip_digest_diff(ea.ctypes.data, eb.ctypes.data, k, mask.ctypes.data,
+                                      C.byref(nd))
+    if rc:
+        raise PatrolHipError(rc, "phip_digest_diff")
+    return mask, int(nd.value)
+
+
+def digest_fold(d, log2_out: int):
+    """phip_digest_fold: the digest (sum, count) at the coarser level
+    log2_out (entry p = entries 2p + 2p+1 of the level below)."""
+    e, k = _digest_entries(d)
+    rc = _lib.load().phip_digest_fold(e.ctypes.data, k, int(log2_out), e.ctypes.data)   # in place
+    if rc:
+        raise PatrolHipError(rc, "phip_digest_fold: log2_out above the digest's level")
+    n = 1 << int(log2_out)
+    return np.ascontiguousarray(e[:n, 0]), np.ascontiguousarray(e[:n, 1])
+
+
 @dataclass
 class BucketState:
     """A Bucket's replicated fields plus its local `created` (bucket.go:20-32)."""
@@ -320,23 +366,36 @@ class GPURepo:
     def _sweep_dict(st) -> dict:
         return {k: int(getattr(st, k)) for k, _ in _lib.phip_sweep_stats._fields_}
 
+    def _sweep_call(self, parts, cur, now, idle_ns, out, out_cap, offs, max_msgs, st, flags):
+        """phip_export_sweep, or with parts = (log2_parts, mask uint64 words)
+        phip_export_sweep_parts: only the buckets of the partitions whose bit
+        is set (digest_diff's mask)."""
+        if parts is None:
+            return self.L.phip_export_sweep(self.h, C.byref(cur), int(now), int(idle_ns), out,
+                                            out_cap, offs, max_msgs, C.byref(st), flags)
+        k, mask = int(parts[0]), _part_mask(*parts)
+        return self.L.phip_export_sweep_parts(self.h, C.byref(cur), int(now), int(idle_ns), k,
+                                              mask.ctypes.data, out, out_cap, offs, max_msgs,
+                                              C.byref(st), flags)
+
     def export_sweep(self, cursor=None, max_msgs: int = 1 << 16, out_cap: int | None = None,
-                     now: int = 0, idle_ns: int = 0):
+                     now: int = 0, idle_ns: int = 0, parts=None):
         """One call of the anti-entropy sweep (phip_export_sweep): the next
         window of the table as MarshalBinary datagrams (bucket.go:51-68), at
         most max_msgs of them in at most out_cap bytes (default 256 each).
         Zero states are skipped; idle_ns > 0 also skips the buckets
-        evict_idle(now, idle_ns) would evict.  cursor: None to start, then
-        the one the last call returned.  -> (datagrams, cursor, stats dict(n,
-        bytes, slots_scanned, done, restarted)); loop until stats["done"]."""
+        evict_idle(now, idle_ns) would evict; parts = (log2_parts, mask) keeps
+        only the partitions digest_diff marked (phip_export_sweep_parts).
+        cursor: None to start, then the one the last call returned.
+        -> (datagrams, cursor, stats dict(n, bytes, slots_scanned, done,
+        restarted)); loop until stats["done"]."""
         if out_cap is None:
             out_cap = _lib.PACKET_SIZE * max_msgs
         cur, st = self._sweep_cursor(cursor), _lib.phip_sweep_stats()
         out = np.zeros(max(int(out_cap), 1), np.uint8)
         offs = np.zeros(int(max_msgs) + 1, np.uint64)
-        rc = self.L.phip_export_sweep(self.h, C.byref(cur), int(now), int(idle_ns),
-                                      out.ctypes.data, int(out_cap), offs.ctypes.data,
-                                      int(max_msgs), C.byref(st), 0)
+        rc = self._sweep_call(parts, cur, now, idle_ns, out.ctypes.data, int(out_cap),
+                              offs.ctypes.data, int(max_msgs), st, 0)
         self._queued = None   # a queued batch is finished (or failed)
         self._check(rc)
         raw = out[:int(st.bytes)].tobytes()
@@ -346,40 +405,68 @@ class GPURepo:
         return dgs, (int(cur.slot), int(cur.layout)), d
 
     def export_sweep_device(self, out, offs, cursor, max_msgs: int, now: int = 0,
-                            idle_ns: int = 0):
+                            idle_ns: int = 0, parts=None):
         """phip_export_sweep with device pointers: out (uint8 CUDA tensor, 8-byte
         aligned, a multiple of 8 bytes; the byte budget is its size - 8), offs
         (int64[max_msgs + 1]).  Both can go unchanged into another repo's
-        receive_datagrams_device.  -> (n, cursor, stats dict)."""
+        receive_datagrams_device.  parts as in export_sweep (the mask stays
+        host memory).  -> (n, cursor, stats dict)."""
         cur, st = self._sweep_cursor(cursor), _lib.phip_sweep_stats()
         cap = int(out.numel() * out.element_size())
-        rc = self.L.phip_export_sweep(self.h, C.byref(cur), int(now), int(idle_ns), _ptr(out), cap,
-                                      _ptr(offs), int(max_msgs), C.byref(st), DEVICE_PTRS)
+        rc = self._sweep_call(parts, cur, now, idle_ns, _ptr(out), cap, _ptr(offs), int(max_msgs),
+                              st, DEVICE_PTRS)
         self._queued = None
         self._check(rc)
         return int(st.n), (int(cur.slot), int(cur.layout)), self._sweep_dict(st)
 
-    def sweep_count(self, now: int = 0, idle_ns: int = 0) -> dict:
+    def sweep_count(self, now: int = 0, idle_ns: int = 0, parts=None) -> dict:
         """What a whole sweep under this filter would write (PHIP_SWEEP_COUNT):
         dict(n, bytes, ...), to size buffers by."""
         cur, st = _lib.phip_sweep_cursor(), _lib.phip_sweep_stats()
-        rc = self.L.phip_export_sweep(self.h, C.byref(cur), int(now), int(idle_ns), None, 0, None,
-                                      0, C.byref(st), _lib.SWEEP_COUNT)
+        rc = self._sweep_call(parts, cur, now, idle_ns, None, 0, None, 0, st, _lib.SWEEP_COUNT)
         self._queued = None
         self._check(rc)
         return self._sweep_dict(st)
 
     def sweep(self, max_msgs: int = 1 << 16, out_cap: int | None = None, now: int = 0,
-              idle_ns: int = 0):
+              idle_ns: int = 0, parts=None):
         """Generator over a whole sweep: yields (datagrams, stats) per call
         until the cursor reaches the end of the table (a rebuild in between
         starts it over, stats["restarted"])."""
         cursor = None
         while True:
-            dgs, cursor, st = self.export_sweep(cursor, max_msgs, out_cap, now, idle_ns)
+            dgs, cursor, st = self.export_sweep(cursor, max_msgs, out_cap, now, idle_ns, parts)
             yield dgs, st
             if st["done"]:
                 return
+
+    # ------------------------------------------------------------ digest --
+    def digest(self, log2_parts: int):
+        """Partition digests of the table (phip_table_digest): per partition of
+        the name space the sum of a hash of every bucket a sweep would export
+        and their number.  -> (sum uint64[2^k], count uint64[2^k], stats
+        dict(records, bytes, slots_scanned)).  Two replicas compare them with
+        digest_diff and sweep only what differs (export_sweep(parts=...))."""
+        k = int(log2_parts)
+        out = np.zeros((1 << min(max(k, 0), _lib.DIGEST_MAX_LOG2_PARTS), 2), np.uint64)
+        st = _lib.phip_digest_stats()
+        rc = self.L.phip_table_digest(self.h, k, out.ctypes.data, C.byref(st), 0)
+        self._queued = None   # a queued batch is finished (or failed)
+        self._check(rc)
+        return (np.ascontiguousarray(out[:, 0]), np.ascontiguousarray(out[:, 1]),
+                {f: int(getattr(st, f)) for f, _ in _lib.phip_digest_stats._fields_})
+
+    def digest_device(self, out, log2_parts: int) -> dict:
+        """phip_table_digest with device pointers: out, an int64 CUDA tensor of
+        2^log2_parts (sum, count) pairs.  -> stats dict."""
+        k = int(log2_parts)
+        if out.numel() * out.element_size() < 16 << k:
+            raise ValueError("digest_device: out holds fewer than 2^log2_parts entries")
+        st = _lib.phip_digest_stats()
+        rc = self.L.phip_table_digest(self.h, k, _ptr(out), C.byref(st), DEVICE_PTRS)
+        self._queued = None
+        self._check(rc)
+        return {f: int(getattr(st, f)) for f, _ in _lib.phip_digest_stats._fields_}
 
     def dump_arrays(self):
         """Every bucket as arrays (unordered): (names uint8, offs uint64[n+1],
