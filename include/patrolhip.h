@@ -943,7 +943,14 @@ void phip_set_timing(phip_handle* h, int on);
  * optimistic pass and out[6] the messages of that pass that found their
  * wave's log full (such a pass is undone and the batch run again classified,
  * as one that met a dirty message; the handle then classifies its next 256
- * fast passes first).  Returns the number written (<= 7).
+ * fast passes first); out[7] the passes the batch's hot directory had served
+ * before this one (0: it was built for this batch; a handle keeps a
+ * directory for later optimistic passes while consecutive builds select the
+ * same buckets and the fraction folded holds, at most 32 passes, and drops it
+ * whenever records move); out[8] 1 if the batch's first optimistic kernel,
+ * queued behind a PHIP_RECV_ASYNC batch not yet finished, found its gate shut
+ * (that batch left work; this one was then queued again behind it).
+ * Returns the number written (<= 9).
  * Not a plain counter read: a batch queued with PHIP_RECV_ASYNC is finished
  * first (the call waits for it), so that the counters are that batch's.  The
  * call has no status to return an error in: if finishing the batch fails, its

@@ -87,6 +87,14 @@ struct FastPass {
   const HotEntry* dir = nullptr;
   void* hot_zero = nullptr;   // the directory kernel's count tables, for the fast kernel to clear
   bool hot_join = false;      // the directory was built on stream2 (fast_back joins it)
+  bool built = false;         // its front launched k_hot_dir
+  u32 hot_age = 0;            // passes its directory served before this one (0: built for it)
+  // optimistic, queued behind a pass not settled yet: that pass's counter
+  // set, the kernel's gate (nullptr: none); and whether the host, reading the
+  // same words in that pass's mirror, found it shut (receive_queued)
+  const u32* gate = nullptr;
+  bool gate_shut = false;
+  u8* fill = nullptr;   // optimistic, no k_hot_dir launch: the status column its back fills
   u8* mark = nullptr;   // isolating: the status column, or a cleared one (k_dirty_pass)
   UndoLog log{};        // optimistic: the undo log (cnt: set by the front; base, cap: by the back)
 };
@@ -113,7 +121,24 @@ struct phip_handle {
     uint64_t ordered = 0;    // messages it sent through the ordered path
     uint64_t log_count = 0, log_over = 0;   // last optimistic pass: log entries, messages
                                             // that found the log full
+    uint64_t hot_age = 0;     // passes the batch's directory served before it (FastPass::hot_age)
+    uint64_t gate_shut = 0;   // the batch's first optimistic kernel found its gate shut
   } stats;
+  // The kept hot directory (keep_take / keep_collect, beside apply_policy).
+  // B_HOT holds two directory slots, built into alternately; `slot` is the one
+  // built last.  An optimistic pass takes it without a build while the builds
+  // agree, the hit fraction holds, it is young and no record has moved.
+  struct HotKeep {
+    void* base = nullptr;   // the B_HOT allocation the slots lie in
+    u32 slot = 0;           // the slot built last
+    bool have = false;      // `slot` holds a directory, built under `gen`
+    u64 gen = 0;            // layout_gen at that build
+    u32 served = 0;         // passes that took it, the one it was built for included
+    // from the passes collected so far
+    bool agree = false;     // the latest build collected: kept * 8 >= own * 7, own > 0
+    u64 ref_hits = 0, ref_n = 0;   // that build's batch: messages folded, messages
+    bool sagged = false;    // a pass collected since folded < 7/8 of ref_hits / ref_n
+  } keep;
   hipStream_t stream = nullptr;      // the stream every call runs on (own_stream or the caller's)
   hipStream_t own_stream = nullptr;  // created by phip_open
   hipStream_t stream2 = nullptr;   // second stream: the hot-bucket fold overlaps the others
@@ -141,10 +166,18 @@ struct phip_handle {
   bool grow = true;          // !PHIP_CFG_NO_GROW
   bool small = true;         // !PHIP_CFG_NO_SMALL
   u64 grows = 0;             // table rehashes so far
-  // layout generation: bumped wherever the slot array is replaced or reloaded
-  // (grow_table, the move of phip_evict_idle, phip_restore); a sweep cursor
-  // (phip_export_sweep) made under another value starts over.  Never 0, the
-  // value of a zeroed cursor.
+  // layout generation: bumped by everything that moves, removes or re-seeds a
+  // record or an arena name -- wherever the slot array is replaced or reloaded:
+  //   grow_table (k_rehash into a new array),
+  //   phip_evict_idle's move (k_evict_move: idle records dropped, the rest and
+  //     their arena names placed anew),
+  //   phip_restore (array and arena overwritten by the image).
+  // Nothing else writes Rec::tag or the name words of a published record:
+  // k_claim / k_publish and k_small_mixed's inserts claim empty slots and
+  // append to the arena (phip_seed goes through them), k_clear_new* and the
+  // dirty marks touch the flags byte only.  A sweep cursor (phip_export_sweep)
+  // made under another value starts over, and a kept hot directory
+  // (HotKeep::gen) is dropped.  Never 0, the value of a zeroed cursor.
   u64 layout_gen = 1;
   u64 long_need = 0;         // arena bytes the last reserve() counted
   Rec* recs = nullptr;
@@ -154,7 +187,10 @@ struct phip_handle {
   u64 arena_open = 0;        // arena bytes at phip_open: a compacted arena is no smaller
   u64* arena_cursor = nullptr;
   u32* ctr = nullptr;        // device counters: kCtrWords general, then two fast-pass sets (fctr)
-  u32* ctr_host = nullptr;   // pinned mirror
+  // pinned mirror: kCtrWords of the general set, then kCtrWords per fast-pass
+  // set (fmirror) -- a queued pass's successor is enqueued before the host
+  // reads the pass's counters, and stores its own beside them
+  u32* ctr_host = nullptr;
   u32* ctr_map = nullptr;    // ctr_host as the device sees it (k_shard_scan stores there)
   u32 fpar = 0;              // parity of the last fast batch (its shard counters in B_FSCNT)
   u64 nfast = 0;             // fast passes begun (a queued front is redone after a nested one)
@@ -179,7 +215,7 @@ struct phip_handle {
     OutView ow{};
     FastPass pass{};   // its queued pass (front and back enqueued)
   } pend;
-  hipEvent_t ev_ctr = nullptr;   // a queued batch's counters reached ctr_host
+  hipEvent_t ev_ctr[2] = {nullptr, nullptr};   // a batch's counters reached its mirror (by parity)
   int deferred_rc = 0;   // a queued batch's error met by a call that returns no status
 };
 
@@ -280,13 +316,15 @@ int reset_ctr(phip_handle* h) {
   return PHIP_OK;
 }
 
-int check_flags(phip_handle* h) {
-  if (h->ctr_host[kCtrBadName])
+// (c: the mirror read -- the general set's, or a fast pass's own)
+int check_flags(phip_handle* h, const u32* c) {
+  if (c[kCtrBadName])
     return set_err(h, PHIP_ERR_INVALID, "malformed name offsets (names_len check): nothing applied");
-  if (h->ctr_host[kCtrTableFull]) return set_err(h, PHIP_ERR_FULL, "hash table full (probe wrapped)");
-  if (h->ctr_host[kCtrArenaFull]) return set_err(h, PHIP_ERR_ARENA, "long-name arena exhausted");
+  if (c[kCtrTableFull]) return set_err(h, PHIP_ERR_FULL, "hash table full (probe wrapped)");
+  if (c[kCtrArenaFull]) return set_err(h, PHIP_ERR_ARENA, "long-name arena exhausted");
   return PHIP_OK;
 }
+int check_flags(phip_handle* h) { return check_flags(h, h->ctr_host); }
 
 // A stats call's words into the caller's array of `max`; returns how many.
 template <int N>
@@ -298,7 +336,7 @@ int copy_words(const uint64_t (&v)[N], uint64_t* out, int max) {
 
 // Every entry point binds the handle's device first: Go goroutines migrate
 // across OS threads, and the HIP current device is per thread.
-int finish_pending(phip_handle* h, bool* worked = nullptr);
+int finish_pending(phip_handle* h, bool* worked = nullptr, bool* shut = nullptr);
 int after_error(phip_handle* h, int rc);
 
 // (finish_queued: a batch PHIP_RECV_ASYNC queued is finished first, and its
@@ -582,32 +620,44 @@ int after_error(phip_handle* h, int rc) {
 
 // ------------------------------------------------------- fast receive ----
 // Hot directory of a fast batch (phip_kernels.hpp k_hot_dir): one launch on
-// `st`, no host round trip.  Returns the header/directory to hand to
-// k_receive_fast (nullptr: none) and, in *zero_out, the kernel's count tables
-// and sync words, which have to be zero at its next launch: the fast kernel
-// that takes the directory clears them (fast_back).  Only a buffer just
+// `st`, no host round trip.  Sets the pass's header/directory to hand to
+// k_receive_fast (left nullptr: none) and its hot_zero, the kernel's count
+// tables and sync words, which have to be zero at its next launch: the fast
+// kernel that takes the directory clears them (fast_back).  Only a buffer just
 // created, or one whose directory no fast kernel took, is cleared in front.
+// B_HOT: those tables, the candidate list, then two {HotHdr, HotEntry[kHotMax]}
+// slots built into alternately (HotKeep), so that the kernel's last workgroup
+// reads the directory before while it writes the new one.
 // status: nothing runs beside the kernel (an optimistic batch): one sample
 // per lane, and further workgroups fill the batch's status column; nullptr:
 // it shares the chip with k_classify, which writes the statuses.
 template <class Src>
-int build_hot(phip_handle* h, Src src, u32 n, hipStream_t st, u8* status, const HotHdr** hdr_out,
-              const HotEntry** dir_out, void** zero_out) {
-  *hdr_out = nullptr;
-  *dir_out = nullptr;
-  *zero_out = nullptr;
+int build_hot(phip_handle* h, Src src, u32 n, hipStream_t st, u8* status, FastPass* p) {
   if (n < kHotMinBatch) return PHIP_OK;
   constexpr size_t kCnt = size_t(1) << kHotCntBits;
+  constexpr size_t kSlot = sizeof(HotHdr) + kHotMax * sizeof(HotEntry);
   u8* base;
   int rc;
-  if ((rc = ensure(h, B_HOT, kHotZeroBytes + kHotCandMax * sizeof(u32) + sizeof(HotHdr) +
-                                 kHotMax * sizeof(HotEntry), &base)))
+  if ((rc = ensure(h, B_HOT, kHotZeroBytes + kHotCandMax * sizeof(u32) + 2 * kSlot, &base)))
     return rc;
   u32* ckeys = (u32*)base;
   u32* ccnt = ckeys + kCnt;
   u32* sync = ccnt + kCnt;
   u32* cand = sync + kHotSyncWords;
-  HotHdr* hdr = (HotHdr*)(cand + kHotCandMax);
+  u8* slots = (u8*)(cand + kHotCandMax);
+  // The slot not built last; the one built last, while it still describes the
+  // table, is the directory the kernel's agreement sums compare with.
+  phip_handle::HotKeep& kp = h->keep;
+  // (only an optimistic pass's build is asked whether it agrees)
+  const bool prev = p->kind == PassKind::kOptimistic && kp.have && kp.base == base &&
+                    kp.gen == h->layout_gen;
+  const HotHdr* phdr = prev ? (const HotHdr*)(slots + kp.slot * kSlot) : nullptr;
+  kp.slot = kp.base == base ? kp.slot ^ 1u : 0u;
+  kp.base = base;
+  kp.have = true;
+  kp.gen = h->layout_gen;
+  kp.served = 1;
+  HotHdr* hdr = (HotHdr*)(slots + kp.slot * kSlot);
   HotEntry* dir = (HotEntry*)(hdr + 1);
   if (h->hot_clean != base) HIPCHK(h, hipMemsetAsync(base, 0, kHotZeroBytes, st));
   h->hot_clean = nullptr;
@@ -623,17 +673,20 @@ int build_hot(phip_handle* h, Src src, u32 n, hipStream_t st, u8* status, const 
       const unsigned fill =
           std::min<unsigned>(grid_for(n, kT * 64), 1024 / kT * (unsigned)h->ncu);
       k_hot_dir<Src, kT, 1><<<nblk + fill, kT, 0, st>>>(
-          src, n, stride, nsample, table(h), ckeys, ccnt, sync, cand, hdr, dir, nblk, status);
+          src, n, stride, nsample, table(h), ckeys, ccnt, sync, cand, hdr, dir, nblk, status, phdr,
+          phdr ? (const HotEntry*)(phdr + 1) : nullptr, p->c);
     } else {
       const unsigned nblk = grid_for(nsample, kHotSamplePerBlock);
       k_hot_dir<Src, 256, 4><<<nblk, 256, 0, st>>>(
-          src, n, stride, nsample, table(h), ckeys, ccnt, sync, cand, hdr, dir, nblk, nullptr);
+          src, n, stride, nsample, table(h), ckeys, ccnt, sync, cand, hdr, dir, nblk, nullptr, phdr,
+          phdr ? (const HotEntry*)(phdr + 1) : nullptr, p->c);
     }
   }
   HIPCHK(h, hipGetLastError());
-  *hdr_out = hdr;
-  *dir_out = dir;
-  *zero_out = base;
+  p->hot = hdr;
+  p->dir = dir;
+  p->hot_zero = base;
+  p->built = true;
   return PHIP_OK;
 }
 
@@ -661,7 +714,7 @@ int sharded(phip_handle* h, BufId base_id, u32 units, u32 per_unit, Sharded* out
 // returned in *total (one counter read-back).
 int pack_sharded(phip_handle* h, const Sharded& sh, u32 total_slot, u32* out, u32* total) {
   k_shard_scan<<<1, kShards, 0, h->stream>>>(sh.cnt, h->ctr, total_slot, nullptr, 0, nullptr,
-                                             nullptr);
+                                             nullptr, nullptr);
   HIPCHK(h, hipGetLastError());
   int rc;
   if ((rc = read_ctr(h))) return rc;
@@ -685,6 +738,7 @@ int pack_sharded(phip_handle* h, const Sharded& sh, u32 total_slot, u32* out, u3
 // a failed speculation run again, the policy moved, the pass collected).
 //   kind        front, main stream but marked    back, main stream
 //   optimistic  k_hot_dir with the status fill   k_receive_fast<Opt>, k_shard_scan
+//               (a kept directory: nothing)      (then the kernel fills the column)
 //   classified  k_classify (fills the column),   k_receive_fast, k_shard_scan
 //               k_hot_dir on stream2
 //   isolating   as classified                    k_dirty_build, k_receive_fast,
@@ -790,7 +844,7 @@ int fork_hot(phip_handle* h, Src src, FastPass* p) {
   // only for the batch's producers, not for k_classify)
   HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
   int rc;
-  if ((rc = build_hot(h, src, p->n, h->stream2, nullptr, &p->hot, &p->dir, &p->hot_zero))) return rc;
+  if ((rc = build_hot(h, src, p->n, h->stream2, nullptr, p))) return rc;
   HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
   p->hot_join = true;
   return PHIP_OK;
@@ -801,12 +855,20 @@ int fork_hot(phip_handle* h, Src src, FastPass* p) {
 // filling the status column (k_hot_dir's fill workgroups; why a fill:
 // front_classified).  A batch too small for a directory gets a plain fill,
 // one without a status column the directory a classified batch builds.
+// While the handle keeps a directory (keep_take), the front launches nothing
+// for it: the pass takes the slot built last, the kernel validates its entries
+// as it loads them, and the status column is the back's to fill (fast_back).
+bool keep_take(phip_handle* h, FastPass* p);
 template <class HotSrc>
 int front_optimistic(phip_handle* h, HotSrc hsrc, u8* status, FastPass* p) {
   int rc;
   if ((rc = ensure(h, B_ULCNT, undo_counts(h), &p->log.cnt))) return rc;
+  if (keep_take(h, p)) {
+    p->fill = status;
+    return PHIP_OK;
+  }
   if (p->n >= kHotMinBatch && status)
-    return build_hot(h, hsrc, p->n, h->stream, status, &p->hot, &p->dir, &p->hot_zero);
+    return build_hot(h, hsrc, p->n, h->stream, status, p);
   if (status) HIPCHK(h, hipMemsetAsync(status, PHIP_ST_MERGED, p->n, h->stream));
   if (p->n >= kHotMinBatch) HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
   return fork_hot(h, hsrc, p);
@@ -891,7 +953,22 @@ int fast_begin(phip_handle* h, In in, HotSrc hsrc, u32 n, u8* status, PassAsk as
     HIPCHK(h, hipGetLastError());
   }
   if (p->kind == PassKind::kOptimistic) return front_optimistic(h, hsrc, status, p);
+  h->keep.agree = false;   // (any other pass builds as ever, and the kept state goes)
   return front_classified(h, in, hsrc, status, p);
+}
+
+// Whether an optimistic pass's back over n messages finds its buffers -- the
+// miss list, its shards, the undo log -- large enough as they stand (ensure()
+// would replace none): a gated back is enqueued while the batch before still
+// needs their contents.
+inline bool holds(const phip_handle* h, BufId id, size_t bytes) {
+  return h->buf[id].cap >= std::max<size_t>(bytes, 64) + 64;
+}
+inline bool back_fits(const phip_handle* h, u32 n) {
+  return holds(h, B_MISS, (size_t)n * sizeof(u32)) &&
+         holds(h, B_MSHARD, (size_t)kShards * shard_cap((n + 63) / 64, 64) * sizeof(u32)) &&
+         holds(h, B_FSCNT, 4 * kShards * sizeof(u32)) &&
+         holds(h, B_ULOG, (size_t)undo_layout(n, (u32)h->ncu).halves * sizeof(u64x2));
 }
 
 // The fast kernel is enqueued behind the classification without a host
@@ -924,10 +1001,15 @@ int fast_back(phip_handle* h, In in, FastPass& p, bool queued) {
         const UndoLayout ul = undo_layout(n, (u32)h->ncu);
         p.log.cap = ul.cap;
         if ((rc = ensure(h, B_ULOG, (size_t)ul.halves, &p.log.base))) return rc;
+        // The status column of a pass whose front launched no k_hot_dir:
+        // stored by the kernel's own chunks, or (PHIP_STATUS_IN_KERNEL=0) by a
+        // fill in front of it.  DESIGN.md §4 round 9 has both measured.
+        u8* kstatus = PHIP_STATUS_IN_KERNEL ? p.fill : nullptr;
+        if (p.fill && !kstatus) HIPCHK(h, hipMemsetAsync(p.fill, PHIP_ST_MERGED, n, h->stream));
         Launch l(h, "k_receive_fast");
         k_receive_fast<In, true><<<ul.grid, kFastBlock, 0, h->stream>>>(
             in, 0, n, table(h), msh, p.c, p.hot, p.dir, nullptr, nullptr, p.log,
-            (uint4*)p.hot_zero);
+            (uint4*)p.hot_zero, p.hot_age != 0, p.gate, kstatus);
       }
       break;
     case PassKind::kClassified:
@@ -935,7 +1017,7 @@ int fast_back(phip_handle* h, In in, FastPass& p, bool queued) {
       Launch l(h, "k_receive_fast");
       k_receive_fast<In><<<fast_grid(h, n), kFastBlock, 0, h->stream>>>(
           in, 0, n, table(h), msh, p.c, p.hot, p.dir, iso ? dset.key : nullptr, p.mark,
-          UndoLog{}, (uint4*)p.hot_zero);
+          UndoLog{}, (uint4*)p.hot_zero, 0u, nullptr, nullptr);
     }
   }
   HIPCHK(h, hipGetLastError());
@@ -953,16 +1035,18 @@ int fast_back(phip_handle* h, In in, FastPass& p, bool queued) {
     }
     k_batch_end<In><<<1, kShards, 0, h->stream>>>(
         in, p.c, dset.key, table(h),
-        SubOut{sb.off, sb.len, sb.a, sb.t, sb.e, sb.map, kSubBatchCap}, msh.cnt, h->ctr_map,
-        kCtrWords, queued ? fast_counts(h, p.par ^ 1u) : nullptr, fctr(h, p.par ^ 1u));
+        SubOut{sb.off, sb.len, sb.a, sb.t, sb.e, sb.map, kSubBatchCap}, msh.cnt,
+        h->ctr_map + kCtrWords * (1 + p.par), kCtrWords,
+        queued ? fast_counts(h, p.par ^ 1u) : nullptr, fctr(h, p.par ^ 1u));
   } else {
-    k_shard_scan<<<1, kShards, 0, h->stream>>>(msh.cnt, p.c, kCtrMiss, h->ctr_map, kCtrWords,
+    k_shard_scan<<<1, kShards, 0, h->stream>>>(msh.cnt, p.c, kCtrMiss,
+                                               h->ctr_map + kCtrWords * (1 + p.par), kCtrWords,
                                                queued ? fast_counts(h, p.par ^ 1u) : nullptr,
-                                               fctr(h, p.par ^ 1u));
+                                               fctr(h, p.par ^ 1u), p.gate);
   }
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev_ctr, h->stream));
-  if (!queued) HIPCHK(h, hipEventSynchronize(h->ev_ctr));
+  HIPCHK(h, hipEventRecord(h->ev_ctr[p.par], h->stream));
+  if (!queued) HIPCHK(h, hipEventSynchronize(h->ev_ctr[p.par]));
   return PHIP_OK;
 }
 
@@ -983,18 +1067,76 @@ constexpr u32 kOptBackoff = 256;
 // message or a malformed name entry, or its log overflowed (the pass that runs
 // the batch again then classifies first).  iso_left moves only with a pass
 // that stands: that second pass reports the dirty message.
+//
+// The kept directory's policy lives here too.  keep_take (a pass's front): an
+// optimistic pass of kHotMinBatch messages or more, with a status column or
+// none, takes the directory built last, without a build, when
+//   - among the passes collected, the latest build agreed with the directory
+//     before it: kept * 8 >= own * 7 with own > 0 (k_hot_dir's sums),
+//   - no pass collected since folded less than 7/8 of the fraction hot_hits / n
+//     that build's batch folded,
+//   - the directory has served fewer than kHotKeepPasses passes (a bucket that
+//     turns hot later does not lower the hit fraction, it only contends on its
+//     record: the age bound finds it),
+//   - no record has moved (layout_gen).
+// These are conditions, not tuned figures.  Every other pass builds as ever;
+// one that is not optimistic drops the kept state (fast_begin).  keep_collect
+// (a pass that stands, from its counters): the agreement of a build, the sag.
+constexpr u32 kHotKeepPasses = 32;
+bool keep_take(phip_handle* h, FastPass* p) {
+  phip_handle::HotKeep& k = h->keep;
+  if (p->n < kHotMinBatch || !k.have || !k.agree || k.sagged || k.served >= kHotKeepPasses ||
+      k.gen != h->layout_gen || k.base != h->buf[B_HOT].p)
+    return false;
+  constexpr size_t kSlot = sizeof(HotHdr) + kHotMax * sizeof(HotEntry);
+  p->hot = (const HotHdr*)((u8*)k.base + kHotZeroBytes + kHotCandMax * sizeof(u32) + k.slot * kSlot);
+  p->dir = (const HotEntry*)(p->hot + 1);
+  p->hot_age = k.served++;
+  return true;
+}
+// (a pass served by the kept directory folded less than 7/8 of the fraction
+// the latest build's batch folded)
+bool keep_sagged(const phip_handle* h, const FastPass& p, const u32* c) {
+  const phip_handle::HotKeep& k = h->keep;
+  return p.hot_age != 0 && (unsigned __int128)c[kCtrHotHits] * k.ref_n * 8 <
+                               (unsigned __int128)k.ref_hits * p.n * 7;
+}
+void keep_collect(phip_handle* h, const FastPass& p, const u32* c) {
+  phip_handle::HotKeep& k = h->keep;
+  if (p.kind != PassKind::kOptimistic) {
+    k.agree = false;
+    return;
+  }
+  if (p.built) {
+    k.agree = c[kCtrHotOwn] > 0 && (u64)c[kCtrHotKept] * 8 >= (u64)c[kCtrHotOwn] * 7;
+    k.ref_hits = c[kCtrHotHits];
+    k.ref_n = p.n;
+    k.sagged = false;
+  } else if (keep_sagged(h, p, c)) {
+    k.sagged = true;
+  }
+}
+
+inline const u32* fmirror(const phip_handle* h, u32 par) { return h->ctr_host + kCtrWords * (1 + par); }
+
 bool apply_policy(phip_handle* h, const FastPass& p) {
-  const u32* c = h->ctr_host;
+  const u32* c = fmirror(h, p.par);
   if (p.kind == PassKind::kOptimistic) {
     h->stats.log_count = c[kCtrLogCount];
     h->stats.log_over = c[kCtrLogOver];
-    if (c[kCtrLogOver]) h->opt_left = kOptBackoff;
+    // (An overflow under a kept directory that no longer folds its share is
+    // the directory's: the hot set moved, and the buckets now hot went
+    // through the table path, every lane of a wave logging the same records.
+    // The pass fails and the batch runs again classified, which drops the kept
+    // state; the handle does not back off.)
+    if (c[kCtrLogOver] && !keep_sagged(h, p, c)) h->opt_left = kOptBackoff;
     if (c[kCtrDirty] < p.n || c[kCtrStop] < p.n || c[kCtrLogOver]) return true;
   } else if (h->opt_left) {
     --h->opt_left;
   }
   if (c[kCtrDirty] < p.n) h->iso_left = kIsoKeep;
   else if (h->iso_left) --h->iso_left;
+  keep_collect(h, p, c);
   return false;
 }
 
@@ -1012,27 +1154,30 @@ struct FastOutcome {
 
 int fast_collect(phip_handle* h, const FastPass& p, FastOutcome* o) {
   int rc;
-  if ((rc = check_flags(h))) return rc;
-  o->nmiss = h->ctr_host[kCtrMiss];
+  const u32* c = fmirror(h, p.par);
+  if ((rc = check_flags(h, c))) return rc;
+  o->nmiss = c[kCtrMiss];
   if (o->nmiss) {
     Sharded msh;
     if ((rc = fast_shards(h, p.n, p.par, &msh))) return rc;
     Launch l(h, "k_shard_compact");
-    dim3 grid(grid_for(h->ctr_host[kCtrShardMax]), kShards);
+    dim3 grid(grid_for(c[kCtrShardMax]), kShards);
     k_shard_compact<<<grid, 256, 0, h->stream>>>(msh.base, msh.cap, msh.cnt,
                                                  (u32*)h->buf[B_MISS].p);
     HIPCHK(h, hipGetLastError());
   }
-  const u32 nd = h->ctr_host[kCtrNDirty];
+  const u32 nd = c[kCtrNDirty];
   o->iso_ran = p.kind == PassKind::kIsolating;
   const bool apart = o->iso_ran && nd != 0 && nd <= kDirtyCap;
-  o->first_dirty = apart ? p.n : std::min<u32>(h->ctr_host[kCtrDirty], p.n);
-  o->stop = std::min<u32>(h->ctr_host[kCtrStop], p.n);
-  o->ndef = apart ? h->ctr_host[kCtrNDefer] : 0;
+  o->first_dirty = apart ? p.n : std::min<u32>(c[kCtrDirty], p.n);
+  o->stop = std::min<u32>(c[kCtrStop], p.n);
+  o->ndef = apart ? c[kCtrNDefer] : 0;
   h->stats.ordered = 0;   // (finish_receive: the messages it sends through the ordered path)
-  h->stats.hot_entries = h->ctr_host[kCtrHotEntries];
-  h->stats.hot_hits = h->ctr_host[kCtrHotHits];
+  h->stats.hot_entries = c[kCtrHotEntries];
+  h->stats.hot_hits = c[kCtrHotHits];
   h->stats.misses = o->nmiss;
+  h->stats.hot_age = p.hot_age;
+  h->stats.gate_shut = p.gate_shut;
   return PHIP_OK;
 }
 
@@ -1715,12 +1860,19 @@ int receive_decoded(phip_handle* h, Src src, const uint64_t* a, const uint64_t* 
 // PHIP_RECV_ASYNC: the queued batch's counters, then what its fast pass left
 // (misses, dirty buckets).  *worked: whether anything was left (its work
 // has used the counters and maybe moved the table).
-int finish_pending(phip_handle* h, bool* worked) {
+int finish_pending(phip_handle* h, bool* worked, bool* shut) {
   if (worked) *worked = false;
+  if (shut) *shut = false;
   if (!h->pend.active) return PHIP_OK;
   phip_handle::Pending p = h->pend;
   h->pend.active = false;
-  HIPCHK(h, hipEventSynchronize(h->ev_ctr));
+  HIPCHK(h, hipEventSynchronize(h->ev_ctr[p.pass.par]));
+  // (the words a successor's gate read, before a second pass of this batch
+  // stores its own over them)
+  if (shut && (*shut = gate_shut(fmirror(h, p.pass.par))))
+    h->hot_clean = nullptr;   // (the gated kernel cleared no count table: a front's k_hot_dir may have run)
+  if (p.pass.gate && fmirror(h, p.pass.par)[kCtrGateShut])
+    return set_err(h, PHIP_ERR_INVALID, "internal: a pass ran on as gated, its kernel found the gate shut");
   int rc;
   FastOutcome o;
   // (a failed speculation runs a fast pass of its own: the caller queues its front again)
@@ -2209,13 +2361,14 @@ int phip_open(const phip_config* cfg, phip_handle** out) {
   if ((e = hipEventCreateWithFlags(&h->ev_gather3, hipEventDisableTiming)) != hipSuccess)
     return fail(e);
   if ((e = hipEventCreateWithFlags(&h->ev_pack, hipEventDisableTiming)) != hipSuccess) return fail(e);
-  if ((e = hipEventCreateWithFlags(&h->ev_ctr, hipEventDisableTiming)) != hipSuccess) return fail(e);
+  for (hipEvent_t& ev : h->ev_ctr)
+    if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return fail(e);
   if ((e = hipMalloc(&h->recs, h->cap * sizeof(Rec))) != hipSuccess) return fail(e);
   if ((e = hipMalloc(&h->aux, h->cap * sizeof(u32))) != hipSuccess) return fail(e);
   if ((e = hipMalloc(&h->arena, h->arena_cap + 64)) != hipSuccess) return fail(e);
   if ((e = hipMalloc(&h->arena_cursor, 64)) != hipSuccess) return fail(e);
   if ((e = hipMalloc(&h->ctr, 3 * kCtrWords * sizeof(u32))) != hipSuccess) return fail(e);
-  if ((e = hipHostMalloc(&h->ctr_host, kCtrWords * sizeof(u32),
+  if ((e = hipHostMalloc(&h->ctr_host, 3 * kCtrWords * sizeof(u32),
                          hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
       (e = hipHostGetDevicePointer((void**)&h->ctr_map, h->ctr_host, 0)) != hipSuccess)
     return fail(e);
@@ -2259,7 +2412,8 @@ void phip_close(phip_handle* h) {
   if (h->ev_gather) (void)hipEventDestroy(h->ev_gather);
   if (h->ev_gather3) (void)hipEventDestroy(h->ev_gather3);
   if (h->ev_pack) (void)hipEventDestroy(h->ev_pack);
-  if (h->ev_ctr) (void)hipEventDestroy(h->ev_ctr);
+  for (hipEvent_t ev : h->ev_ctr)
+    if (ev) (void)hipEventDestroy(ev);
   if (h->stream2) (void)hipStreamDestroy(h->stream2);
   if (h->stream3) (void)hipStreamDestroy(h->stream3);
   if (h->stream4) (void)hipStreamDestroy(h->stream4);
@@ -2574,8 +2728,46 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
     bool worked = false;
     if ((rc = outputs(h, res, n, true, &ow))) return rc;
     const bool prev = h->pend.active;
+    const phip_handle::HotKeep keep0 = h->keep;
     if ((rc = fast_begin(h, in, src, n, ow.status, ask, !prev, &pass)))
       return after_error(h, rc);
+    // An optimistic pass behind a batch not settled yet goes on the stream
+    // whole, front and back, before the host waits for that batch: its kernel
+    // is gated on that batch's counters (k_receive_fast's `gate`), so the GPU
+    // goes from one fast kernel to the next while the host settles.  Shut --
+    // the host reads the same words in that batch's mirror -- the kernel
+    // wrote nothing; the batch is finished as ever and this pass queued again
+    // from its front (the directory state as before the gated front, the count
+    // tables as that front's k_hot_dir left them).
+    // (only where the back allocates nothing: that batch's log and miss shards
+    // are still to be read)
+    if (prev && pass.kind == PassKind::kOptimistic && back_fits(h, n)) {
+      pass.gate = fctr(h, h->pend.pass.par);
+      if ((rc = fast_back(h, in, pass, true))) return after_error(h, rc);
+      bool shut = false;
+      const u64 nfast = h->nfast;
+      if ((rc = finish_pending(h, &worked, &shut))) return after_error(h, rc);
+      if (shut) {
+        if (h->nfast == nfast) {
+          // (no pass of that batch's built since: the slot, its age and
+          // generation go back; what collecting that batch learned stays)
+          phip_handle::HotKeep k = keep0;
+          k.agree = h->keep.agree;
+          k.ref_hits = h->keep.ref_hits;
+          k.ref_n = h->keep.ref_n;
+          k.sagged = h->keep.sagged;
+          h->keep = k;
+        }
+        if ((rc = fast_begin(h, in, src, n, ow.status, ask, true, &pass)))
+          return after_error(h, rc);
+        pass.gate_shut = true;
+        if ((rc = fast_back(h, in, pass, true))) return after_error(h, rc);
+      } else if (worked) {
+        return after_error(h, set_err(h, PHIP_ERR_INVALID, "internal: work left behind an open gate"));
+      }
+      h->pend = {true, in, now, ow, pass};
+      return PHIP_OK;
+    }
     const u64 nfast = h->nfast, grows = h->grows;
     if (prev && (rc = finish_pending(h, &worked))) return after_error(h, rc);
     // The leftover work of the batch before (its misses, its dirty buckets)
@@ -3540,8 +3732,8 @@ int phip_last_stats(phip_handle* h, uint64_t* out, int max) {
   // own (its error, if any, is kept for the next call that returns one)
   if (h->pend.active && !h->deferred_rc) h->deferred_rc = begin_call(h);
   const phip_handle::LastStats& s = h->stats;
-  const uint64_t v[7] = {s.hot_entries, s.hot_hits,  s.misses,  h->grows,
-                         s.ordered,     s.log_count, s.log_over};   // (patrolhip.h's order)
+  const uint64_t v[9] = {s.hot_entries, s.hot_hits,  s.misses,   h->grows,  s.ordered,
+                         s.log_count,   s.log_over,  s.hot_age,  s.gate_shut};   // (patrolhip.h's order)
   return copy_words(v, out, max);
 }
 

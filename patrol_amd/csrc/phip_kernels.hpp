@@ -223,10 +223,12 @@ struct Sharded {
 //   G  the general set (phip_handle::ctr): ordered batches, inserts, the miss
 //      path, rehash, evict, dump; the host copies it back (read_ctr);
 //   F  the two fast-pass sets behind it (fctr, one per batch parity): a
-//      pass's last launch (shard_scan) stores its set into the host's mirror;
+//      pass's last launch (shard_scan) stores its set into the host's mirror
+//      of that parity;
 //   P  the block of a route pack (B_ROUTE), which the host never reads.
-// ctr_host mirrors G or F, whichever was stored last; every host reader reads
-// right after its own set's store.  Per word: what it holds; W its writers;
+// ctr_host mirrors G, and behind it each F set on its own (a queued pass's
+// successor may store its set before the host has read the pass's); every host
+// reader reads right after its own set's store.  Per word: what it holds; W its writers;
 // R its readers; the sets it is used in.
 
 // Dirty messages listed (F); above kDirtyCap, the last of them unlisted, the
@@ -302,6 +304,18 @@ constexpr u32 kCtrNDefer = 18;
 // whenever it leaves kCtrNDirty in 1..kDirtyCap.  R: k_dirty_pass,
 // dirty_finish, only then.
 constexpr u32 kCtrNSorted = 19;
+// A directory build's agreement with the directory built before it (F): the
+// sample counts of the entries it selected, summed over all of them (own) and
+// over those whose slot the previous directory also holds (kept; 0 without a
+// previous directory).  W: k_hot_dir's last workgroup, in every launch.
+// R: apply_policy (keep_collect), only after a pass whose front built.
+constexpr u32 kCtrHotOwn = 20;
+constexpr u32 kCtrHotKept = 21;
+// 1: the optimistic kernel found its gate shut -- the pass before it, whose
+// counter set it was given, left work -- and returned with nothing written; 0:
+// it ran (F).  W: k_receive_fast<Opt>, one lane, in every launch.
+// R: receive_queued, after a gated pass.
+constexpr u32 kCtrGateShut = 22;
 constexpr u32 kCtrWords = 32;
 // The two min-reduced words start at "none", the rest at zero.
 __host__ __device__ constexpr u32 ctr_reset_value(u32 w) {
@@ -317,7 +331,19 @@ static_assert(kCtrTableFull == kCtrArenaFull + 1, "evict_idle clears both flags 
 static_assert(kCtrLongBytes % 2 == 0 && kCtrLongBytes >= kCtrResetWords &&
               kCtrLongBytes + 2 <= kCtrWords, "an aligned u64 outside the reset");
 static_assert(kCtrNDefer >= kCtrResetWords && kCtrNDefer < kCtrWords &&
-              kCtrNSorted >= kCtrResetWords && kCtrNSorted < kCtrWords, "outside the reset");
+              kCtrNSorted >= kCtrResetWords && kCtrNSorted < kCtrWords &&
+              kCtrHotOwn >= kCtrResetWords && kCtrHotKept < kCtrWords &&
+              kCtrGateShut >= kCtrResetWords && kCtrGateShut < kCtrWords, "outside the reset");
+
+// The gate of a queued optimistic pass (k_receive_fast<Opt>'s `gate`, and the
+// host's reading of the same words in the mirror): c is the counter set of the
+// pass queued before it, final in stream order.  Shut when that pass left
+// anything to do -- a dirty message, a stop, a log overflow, a miss, a wrapped
+// probe: its undo, its second pass or its inserts must come first.
+__host__ __device__ inline bool gate_shut(const u32* c) {
+  return c[kCtrDirty] != ~0u || c[kCtrStop] != ~0u || c[kCtrNDirty] != 0 || c[kCtrLogOver] != 0 ||
+         c[kCtrMiss] != 0 || c[kCtrTableFull] != 0;
+}
 static_assert(kCtrResetWords <= kShards && kCtrWords <= kShards,
               "k_batch_reset and shard_scan's host mirror: one lane per word");
 
@@ -336,17 +362,23 @@ __global__ __launch_bounds__(kShards) void k_batch_reset(u32* ctr, u32* shard_cn
 // counter words are then stored there, which ends a fast batch without a copy; with
 // `next`, the next batch's counters (next_ctr: the other fast set) and its
 // shard counters are reset as k_batch_reset does, so a queued batch's
-// successor needs no reset launch.
+// successor needs no reset launch.  `gate`: the scan ends a gated pass (its
+// k_receive_fast's gate: the counter set of the pass before, which is
+// next_ctr); shut, nothing is reset -- that pass's miss list is still to be
+// packed from those shard counters, and the host queues this pass again with a
+// reset of its own.
 __device__ inline void shard_scan(u32* cnt, u32* ctr, u32 tot, u32* host, u32 words, u32* next,
-                                  u32* next_ctr);
+                                  u32* next_ctr, const u32* gate = nullptr);
 __global__ __launch_bounds__(kShards) void k_shard_scan(u32* cnt, u32* ctr, u32 tot, u32* host,
-                                                        u32 words, u32* next, u32* next_ctr) {
-  shard_scan(cnt, ctr, tot, host, words, next, next_ctr);
+                                                        u32 words, u32* next, u32* next_ctr,
+                                                        const u32* gate) {
+  shard_scan(cnt, ctr, tot, host, words, next, next_ctr, gate);
 }
 __device__ inline void shard_scan(u32* cnt, u32* ctr, u32 tot, u32* host, u32 words, u32* next,
-                                  u32* next_ctr) {
+                                  u32* next_ctr, const u32* gate) {
   __shared__ u32 v[kShards];
   __shared__ u32 wmax[kShards / 64];
+  if (gate && gate_shut(gate)) next = nullptr;   // (read here, ahead of the barriers and the reset)
   const u32 t = threadIdx.x, c = cnt[t];
   v[t] = c;
   u32 m = c;
@@ -851,15 +883,19 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
                                                       Table T, u32* ckeys, u32* ccnt, u32* sync,
                                                       u32* cand, HotHdr* hdr,
                                                       HotEntry* __restrict__ dir, u32 nblk,
-                                                      u8* __restrict__ status) {
+                                                      u8* __restrict__ status,
+                                                      const HotHdr* prev_hdr,
+                                                      const HotEntry* prev_dir, u32* ctr) {
   constexpr u32 kPerBlock = kThreads * kRounds;
   constexpr u32 kL = 2 * kPerBlock;
   static_assert(kHotHist % kThreads == 0 && 4096 % kThreads == 0, "the last workgroup's shares");
   constexpr u32 kWords = 2 * kL > kHotHist ? 2 * kL : kHotHist;
   __shared__ u32 lds[kWords];
   __shared__ u32 part[kThreads];
-  __shared__ u32 sel[kHotMax];
-  __shared__ u32 best, nsel, last;
+  __shared__ u32 sel[kHotMax], selcnt[kHotMax];
+  __shared__ u32 best, nsel, last, own, kept;
+  constexpr u32 kPrevSet = 4096;   // the previous directory's slots, looked up in `lds`
+  static_assert(kWords >= kPrevSet && kPrevSet * 2 >= kHotMax * 3, "the previous directory's set");
   if (blockIdx.x >= nblk) {
     // The workgroups behind the nblk sampling ones fill the batch's status
     // column with PHIP_ST_MERGED (an optimistic batch: front_optimistic), in the
@@ -974,7 +1010,7 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
   for (u32 k = 0; k < kU; ++k) hh0[k] = k * kThreads + threadIdx.x < ncand ? hh0[k] & mask : ~0u;
   u32* hist = lds;
   for (u32 e = threadIdx.x; e < kHotHist; e += kThreads) hist[e] = 0;
-  if (threadIdx.x == 0) { best = kHotHist; nsel = 0; }
+  if (threadIdx.x == 0) { best = kHotHist; nsel = 0; own = 0; kept = 0; }
   __syncthreads();
   auto counts = [&](const u32 (&hh)[kU], u32 (&cc)[kU], u32 (&kk)[kU]) {
 #pragma unroll
@@ -1031,7 +1067,10 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
     for (u32 k = 0; k < kU; ++k) {
       if (cc[k] < thresh) continue;
       const u32 idx = atomicAdd(&nsel, 1u);
-      if (idx < kHotMax) sel[idx] = kk[k] - 1;   // (always: the threshold bounds the count)
+      if (idx < kHotMax) {   // (always: the threshold bounds the count)
+        sel[idx] = kk[k] - 1;
+        selcnt[idx] = cc[k];
+      }
     }
   };
   pick(cc0, kk0);
@@ -1042,12 +1081,41 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
   }
   __syncthreads();
   const u32 ns = min(nsel, kHotMax);
+  // Agreement with the directory built before this one (prev_hdr, prev_dir:
+  // the other slot of the pair; nullptr: none): its slots into a set in `lds`
+  // (the histogram is done with), then own = the selected entries' sample
+  // counts and kept = the counts of those the set holds.  The host keeps a
+  // directory for later batches while consecutive builds agree (keep_collect).
+  const u32 np = prev_hdr ? min(prev_hdr->n, kHotMax) : 0u;
+  for (u32 e = threadIdx.x; e < kPrevSet; e += kThreads) lds[e] = 0;
+  __syncthreads();
+  for (u32 j = threadIdx.x; j < np; j += kThreads) {
+    const u32 s = prev_dir[j].slot;
+    u32 ph = (s * 2654435761u) & (kPrevSet - 1);
+    for (;;) {   // at most kHotMax keys in kPrevSet entries
+      const u32 old = atomicCAS(&lds[ph], 0u, s + 1);
+      if (old == 0 || old == s + 1) break;
+      ph = (ph + 1) & (kPrevSet - 1);
+    }
+  }
+  __syncthreads();
+  u32 o = 0, kp = 0;
 #pragma unroll
   for (u32 k = 0; k < (kHotMax + kThreads - 1) / kThreads; ++k) {
     const u32 j = k * kThreads + threadIdx.x;
-    if (j < ns) dir[j] = hot_entry(T, sel[j]);
+    if (j >= ns) continue;
+    const u32 s = sel[j];
+    dir[j] = hot_entry(T, s);
+    o += selcnt[j];
+    for (u32 ph = (s * 2654435761u) & (kPrevSet - 1); lds[ph]; ph = (ph + 1) & (kPrevSet - 1))
+      if (lds[ph] == s + 1) { kp += selcnt[j]; break; }
   }
+  if (o) atomicAdd(&own, o);
+  if (kp) atomicAdd(&kept, kp);
+  __syncthreads();
   if (threadIdx.x == 0) {
+    ctr[kCtrHotOwn] = own;
+    ctr[kCtrHotKept] = kept;
     hdr->n = nsel;
     hdr->thresh = thresh;
     st_co32(&sync[0], 0u);
@@ -1092,8 +1160,9 @@ __global__ __launch_bounds__(256) void k_hot_select(const u32* __restrict__ hist
 
 // ----------------------------------------------------- fast receive --------
 // Statuses: the caller's status column is filled with PHIP_ST_MERGED
-// before the kernel (by k_classify_soa2, a fill beside k_classify, or an
-// optimistic batch's k_hot_dir); every
+// before the kernel's loop (by k_classify_soa2, a fill beside k_classify, an
+// optimistic batch's k_hot_dir, or, where that pass takes a kept directory
+// and launches none, the kernel's own prologue); every
 // message the kernel does not merge is written again later (misses by the
 // miss path, dirty buckets by the ordered path).
 // Persistent workgroups; every wave walks its own 64-message chunks
@@ -1489,8 +1558,9 @@ constexpr u8 kMarkDirty = 0x40;
 // a -0.0 field) or one with a malformed name entry (checked names), and
 // min-reduces their indices into ctr[kCtrDirty] / ctr[kCtrStop].  A pass that found
 // one is a failed speculation: the host undoes it and runs the batch again
-// through the classified path.  The status column is filled by the host
-// before the pass.
+// through the classified path.  The status column is filled by the pass's
+// front (k_hot_dir's fill workgroups) or, without one, in this kernel's
+// prologue.
 // The log: a region of `cap` 32-byte entries {slot, 0 | added | taken |
 // elapsed} per wave, the cursor a wave-uniform register, no atomic counter;
 // the lanes that log in an iteration store their entries side by side (mbcnt).
@@ -1505,6 +1575,14 @@ constexpr u8 kMarkDirty = 0x40;
 // the default, and behind the host's status fill before the pass.)
 #ifndef PHIP_UNDO_NT
 #define PHIP_UNDO_NT 1
+#endif
+// (PHIP_STATUS_IN_KERNEL: the status column of an optimistic pass that takes a
+// kept directory, whose front has no k_hot_dir launch to fill it -- 1: the
+// kernel fills it ahead of its loop; 2: its chunks store their 64 bytes in the
+// loop; 0: a fill in front of the kernel.  tools/build_variants.sh builds the
+// others; DESIGN.md §4 round 9 has them measured.)
+#ifndef PHIP_STATUS_IN_KERNEL
+#define PHIP_STATUS_IN_KERNEL 1
 #endif
 constexpr u32 kUndoFlushReserve = 64 * ((kHotMax + kFastBlock - 1) / kFastBlock);
 struct UndoLog {
@@ -1554,7 +1632,40 @@ template <class In, bool Opt = false>
 __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_receive_fast(
     In in, u32 lo, u32 n, Table T, Sharded miss, u32* ctr,
     const HotHdr* __restrict__ hot, const HotEntry* __restrict__ hot_dir, const u64* dtab,
-    u8* __restrict__ mark, UndoLog ulog, uint4* __restrict__ hot_zero) {
+    u8* __restrict__ mark, UndoLog ulog, uint4* __restrict__ hot_zero, u32 hot_kept,
+    const u32* gate, u8* __restrict__ status) {
+  // Opt, gate: the counter set of the pass queued before this one, whose
+  // settling the host has not done yet (receive_queued).  Shut (gate_shut):
+  // that pass's undo, second pass or inserts come first, so every workgroup
+  // returns here, before its first write -- the log and its counts (that
+  // pass's k_undo reads them), the statuses, the miss shards and hot_zero all
+  // stay as they are -- and the host queues this pass again.  Nobody waits:
+  // the words are final in stream order.
+  if constexpr (Opt) {
+    const bool shut = gate && gate_shut(gate);
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctr[kCtrGateShut] = shut;
+    if (shut) return;
+    // The status column of a pass whose front launched no k_hot_dir (status:
+    // else nullptr), filled with PHIP_ST_MERGED as that kernel's fill
+    // workgroups would: 16-byte stores over the aligned middle, grid-strided
+    // over every lane of the launch, bytes at both ends.  Here, ahead of the
+    // loop and behind the gate: the stores are issued and left to drain under
+    // the first chunks' loads, and cost the loop no register (stored per chunk
+    // inside it -- PHIP_STATUS_IN_KERNEL=2 -- they spill four).
+    if (PHIP_STATUS_IN_KERNEL == 1 && status) {
+      constexpr u32 b4 = PHIP_ST_MERGED * 0x01010101u;
+      const u64 head = min((u64)n, (u64)(-(uintptr_t)status & 15));
+      const u64 n16 = (n - head) / 16;
+      uint4* body = reinterpret_cast<uint4*>(status + head);
+      for (u64 k = (u64)blockIdx.x * kFastBlock + threadIdx.x; k < n16; k += (u64)gridDim.x * kFastBlock)
+        body[k] = uint4{b4, b4, b4, b4};
+      if (blockIdx.x == 0) {
+        if (threadIdx.x < head) status[threadIdx.x] = PHIP_ST_MERGED;
+        const u64 done = head + n16 * 16;
+        if (done + threadIdx.x < n) status[done + threadIdx.x] = PHIP_ST_MERGED;
+      }
+    }
+  }
   __shared__ u32 hslot[kHotLds];        // directory index + 1 (0 = empty)
   __shared__ u64 htag[kHotMax], hw0[kHotMax], hw1[kHotMax], hw2[kHotMax];
   __shared__ u32 hrec[kHotMax], haoff[kHotMax];
@@ -1563,14 +1674,14 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   __shared__ u32 hhits;
   __shared__ u32 hlog[2];               // Opt: the workgroup's log entries, overflowed messages
 
-  // Gate (k_classify ran before, over every message up to n): only the clean
+  // The classified prefix (k_classify ran before, over every message up to n): only the clean
   // prefix is applied, the messages before the first dirty one
   // (ctr[kCtrDirty]) and before the first malformed datagram (ctr[kCtrStop]); none:
   // ~0.
   // (dirty buckets, decoded batches: with a dirty set, the whole batch up to
   // the first malformed message; the messages that may name a dirty bucket
   // are marked for k_dirty_pass)
-  // (Opt: no classification ran and there is no gate; the kernel finds the
+  // (Opt: no classification ran and no prefix is cut; the kernel finds the
   // dirty and malformed messages itself and leaves them alone)
   // The directory kernel's count tables and sync words (kHotZeroBytes at
   // hot_zero), cleared for the next batch's k_hot_dir: a store or two per
@@ -1598,6 +1709,22 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     hrec[j] = d.slot | (iso && (rec_flags(T.recs[d.slot]) & kRecDirty) ? 0x80000000u : 0u);
     haoff[j] = d.aoff;
     for (u32 k = 0; k < kHotTailWords; ++k) htail[k][j] = d.tail[k];
+    // A directory kept from an earlier batch (hot_kept) is validated on load:
+    // an entry whose record no longer carries its tag and canonical name
+    // words, or is not published, stays out of the lookup, and its names
+    // take the table path.  (The host drops a kept directory whenever records
+    // move -- phip_handle::layout_gen; this is the net under that.)
+    if (hot_kept) {
+      bool same = d.slot <= T.mask();
+      if (same) {
+        const Rec r = load_rec(&T.recs[d.slot]);
+        const bool arena = (r.name0 & 0xFFu) > kInlineName;
+        same = r.tag == d.tag && (rec_flags(r) & kRecPublished) &&
+               (arena ? (r.name0 & 0xFFu) : (r.name0 & ~0xFF00ull)) == d.w0 && r.name1 == d.w1 &&
+               r.name2 == d.w2 && (arena ? (u32)(r.name0 >> 32) : 0u) == d.aoff;
+      }
+      if (!same) continue;
+    }
     u32 hs = hot_home(d.tag);
     while (atomicCAS(&hslot[hs], 0u, j + 1) != 0) hs = (hs + 1) & (kHotLds - 1);
   }
@@ -1639,6 +1766,19 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     const u32 tid = chunk * 64 + lane;
     bool valid = tid < n;
     const u32 i = tid < n ? tid : n - 1;
+    if constexpr (Opt && PHIP_STATUS_IN_KERNEL == 2) {
+      // (the tuning build that stores a chunk's statuses with the chunk: four
+      // lanes 16 bytes each where the chunk is whole and the column aligned,
+      // else every lane its byte; wave-uniform branches)
+      if (status) {
+        constexpr u32 b4 = PHIP_ST_MERGED * 0x01010101u;
+        if ((u64)chunk * 64 + 64 <= n && ((uintptr_t)status & 15) == 0) {
+          if (lane < 4) reinterpret_cast<uint4*>(status + (size_t)chunk * 64)[lane] = uint4{b4, b4, b4, b4};
+        } else if (tid < n) {
+          status[tid] = PHIP_ST_MERGED;
+        }
+      }
+    }
     if constexpr (Opt && In::kSoa) {
       // checked names: a malformed entry reads as the empty name at offset 0
       // (NamesOffs::get) and ends the speculation

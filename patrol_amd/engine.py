@@ -240,9 +240,11 @@ class GPURepo:
         last fast-path Receive batch, the table's growths since open, and the
         batch's messages that went through the ordered path; then the undo-log
         entries of the last optimistic pass and its messages that found the
-        log full."""
-        out = (C.c_uint64 * 7)()
-        k = self.L.phip_last_stats(self.h, out, 7)
+        log full; then the passes the batch's hot directory served before it
+        (0: built for this batch) and whether its first optimistic kernel
+        found its gate shut."""
+        out = (C.c_uint64 * 9)()
+        k = self.L.phip_last_stats(self.h, out, 9)
         return tuple(int(out[i]) for i in range(k))
 
     def table_stats(self):

@@ -2,6 +2,9 @@
 # Tuning builds of libpatrolhip with overridden kernel constants, for A/B
 # timing on the GPU box (PATROLHIP_LIB=tools/var/<name>.so python tools/exp_c2.py).
 # Usage: tools/build_variants.sh "name:-DPHIP_HOT_MAX=640 -DPHIP_HOT_LDS=1024" ...
+# (the status column of a pass on a kept directory, DESIGN.md §4 round 9:
+#  "st0:-DPHIP_STATUS_IN_KERNEL=0" a fill in front of the fast kernel,
+#  "st2:-DPHIP_STATUS_IN_KERNEL=2" stored chunk by chunk in its loop)
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/var
