@@ -568,6 +568,79 @@ int phip_upsert_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip_
                     uint32_t flags);
 /* Ordered mixed stream of TAKE / RECEIVE / UPSERT ops. */
 int phip_apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, uint32_t flags);
+
+/* Coalesced egress: a batch's replication traffic, written by the batch's own
+ * call.  In the reference every take ends in UpsertBucket, whose broadcast
+ * sends the bucket's state to every peer, granted or denied (api.go:67-74,
+ * repo.go:123-158), and a take whose GetBucket created the bucket sends a
+ * zero-state incast request first (repo.go:96-106): one datagram per peer per
+ * take.  phip_apply_mixed_egress is phip_apply_mixed -- the same statuses,
+ * results, errors, flags and checked-offset rule -- plus one datagram per
+ * bucket the batch touched, in the layout phip_udp_send_batch and a peer's
+ * phip_receive_datagrams take: datagram i is out[offs[i] .. offs[i+1]),
+ * offs[0] = 0, bytes = offs[n].
+ *
+ * State section, datagrams [n_incast, n).  For every bucket named by at least
+ * one PHIP_OP_TAKE or PHIP_OP_UPSERT op of the batch: the byte-identical
+ * MarshalBinary (bucket.go:51-68) of the state the table holds after the
+ * batch's last op.  A bucket named only by PHIP_OP_RECEIVE ops gets nothing:
+ * received merges are never rebroadcast (repo.go:78-79), and its incast
+ * replies stay in phip_results.reply, unicast to one peer.  Left out, by the
+ * sweep's rule (phip_export_sweep with idle_ns = 0): a bucket whose final
+ * state is zero (its datagram would be an incast request) and a name over
+ * PHIP_MAX_NAME_LEN.
+ *
+ * Incast section, datagrams [0, n_incast).  For every bucket the batch created
+ * whose first op in batch order is a TAKE -- the op that reports
+ * PHIP_ST_CREATED -- the request ReplicatedRepo.GetBucket broadcasts: 24 zero
+ * bytes, the length byte, the name.  A bucket created by a RECEIVE or UPSERT
+ * op sends none (repo.go:78, repo.go:215-235).
+ *
+ * Each section is in table slot order, as the sweep writes.
+ *
+ * What coalescing means, and its limit.  A peer that merges the state section
+ * ends where it would after merging the reference's per-op broadcasts in
+ * order, whenever each bucket's post-op states are field-wise non-decreasing:
+ * Merge keeps the field-wise maximum, and the final state is then that
+ * maximum.  Takes at one rate per bucket with a non-decreasing clock are such
+ * a sequence.  It does not hold in general: a take at a smaller capacity than
+ * the tokens held lowers `added` (bucket.go:210-213, missing < 0), and a peer
+ * that saw the intermediate state would keep the higher value.  The datagram
+ * is the final state, which is what the reference's last broadcast of that
+ * bucket carries; the join of the intermediate states is not computed.
+ *
+ * Caps.  Checked before anything is applied, against the batch's worst case
+ * (every op a new bucket's TAKE): max_msgs >= 2 * n and out_cap >=
+ * 2 * (25 * n + name_bytes), name_bytes being name_offs[n] - name_offs[0] for
+ * a host batch, names_len for a checked device batch and 231 * n for an
+ * unchecked one.  With PHIP_DEVICE_PTRS `out` must be 8-byte aligned and
+ * out_cap a multiple of 8 with 8 bytes more than that, as phip_export_sweep
+ * requires, and out / offs then go unchanged into a peer handle's
+ * phip_receive_datagrams(..., PHIP_DEVICE_PTRS).  phip_egress_caps (host
+ * arithmetic only; flags: 0 or PHIP_DEVICE_PTRS) returns exactly these
+ * figures.  Caps below them are PHIP_ERR_INVALID with the table and every
+ * output untouched, so a valid call never truncates.
+ *
+ * eg is host memory; out and offs follow PHIP_DEVICE_PTRS like every other
+ * pointer of the call, and a host-pointer call copies back only the bytes and
+ * offsets written.  res may be NULL, and so may any column of it.  n == 0
+ * gives n = n_incast = bytes = 0 and offs[0] = 0.  On any error return the
+ * three out fields are zero.  The call is serialised with the handle's other
+ * calls; a batch queued with PHIP_RECV_ASYNC is finished first. */
+typedef struct phip_egress {
+  uint8_t*  out;       /* in: datagram bytes */
+  uint64_t  out_cap;   /* in */
+  uint64_t* offs;      /* in: max_msgs + 1 entries */
+  uint32_t  max_msgs;  /* in */
+  uint32_t  n_incast;  /* out */
+  uint32_t  n;         /* out: all datagrams */
+  uint32_t  reserved;
+  uint64_t  bytes;     /* out: = offs[n] */
+} phip_egress;
+int phip_egress_caps(uint32_t n_ops, uint64_t name_bytes, uint32_t flags, uint32_t* max_msgs,
+                     uint64_t* out_cap);
+int phip_apply_mixed_egress(phip_handle* h, const phip_ops* ops, const phip_results* res,
+                            phip_egress* eg, uint32_t flags);
 /* All-TAKE convenience form of phip_apply_mixed. */
 int phip_take(phip_handle* h, const uint8_t* names, const uint32_t* name_offs, uint32_t n,
               const int64_t* now, const int64_t* freq, const int64_t* per, const uint64_t* count,
@@ -618,8 +691,12 @@ int phip_batcher_api_take(phip_batcher* b, const uint8_t* name, uint32_t len, co
                           uint32_t rate_len, const char* count, uint32_t count_len, int64_t now,
                           char* body, uint32_t* body_len);
 /* out[0] batches run, out[1] requests served, out[2] largest batch,
- * out[3] ns spent in phip_apply_mixed, out[4] batches that failed.
- * Returns the number written (<= 5). */
+ * out[3] ns spent in phip_apply_mixed, out[4] batches that failed; past
+ * those, for a batcher opened with phip_batcher_open_egress (zeros otherwise):
+ * out[5] egress batches queued, out[6] datagrams queued, out[7] ns the
+ * dispatcher waited for a free egress slot.
+ * Returns the number written (<= 8; a caller passing max = 5 sees the first
+ * five as before). */
 int phip_batcher_stats(phip_batcher* b, uint64_t* out, int max);
 /* Everything the reference handler does after GetBucket -> Take ->
  * UpsertBucket (api.go:67-74), from the same batched launch: whether the
@@ -645,6 +722,43 @@ int phip_batcher_api_take_reply(phip_batcher* b, const uint8_t* name, uint32_t l
                                 const char* rate, uint32_t rate_len, const char* count,
                                 uint32_t count_len, int64_t now, char* body, uint32_t* body_len,
                                 phip_take_reply* out);
+
+/* The batcher with coalesced egress ("Coalesced egress" above): every batch
+ * runs through phip_apply_mixed_egress into the next of `egress_slots` pinned
+ * host buffers (0: 4), each sized by phip_egress_caps(max_batch,
+ * 231 * max_batch, 0), and a batch that produced datagrams (n > 0) is queued
+ * for phip_batcher_egress_next.  Batches come out in order, numbered from 0
+ * without gaps.  A caller of a take entry point is woken only after its
+ * batch's egress is queued, so when a take returns its replication is already
+ * with the sender.  The per-request entry points work as with
+ * phip_batcher_open, phip_take_reply.datagram included; phip_batcher_open
+ * itself is unchanged and produces no egress.
+ *
+ * Somebody has to drain.  When every slot is queued or handed out the
+ * dispatcher waits for phip_batcher_egress_done before it runs the next batch
+ * -- the reference's handler waits for its WriteTo calls too -- and the takes
+ * of that batch wait with it (phip_batcher_stats out[7] counts the time).
+ *
+ * phip_batcher_egress_next: 1 with *out filled (bytes / offs as
+ * phip_udp_send_batch takes them: datagrams [0, n_incast) are incast
+ * requests, [n_incast, n) states; valid until phip_batcher_egress_done(batch)
+ * gives the slot back), 0 after timeout_ms without a batch (< 0: no timeout)
+ * or on a batcher being closed, < 0 on error (not an egress batcher).
+ * phip_batcher_close wakes a blocked phip_batcher_egress_next, which returns 0,
+ * and a blocked dispatcher, whose remaining batches then run without egress;
+ * batches still queued at close are dropped with the ring, so drain first. */
+int phip_batcher_open_egress(phip_handle* h, const phip_batcher_config* cfg,
+                             uint32_t egress_slots, phip_batcher** out);
+typedef struct phip_egress_batch {
+  const uint8_t* bytes;
+  const uint64_t* offs;
+  uint32_t n, n_incast;
+  uint64_t batch;        /* batch number, from 0 */
+  uint64_t first_seq;    /* arrival number of its first request */
+  uint32_t requests, reserved;
+} phip_egress_batch;
+int phip_batcher_egress_next(phip_batcher* b, int timeout_ms, phip_egress_batch* out);
+int phip_batcher_egress_done(phip_batcher* b, uint64_t batch);
 
 /* ---- batched UDP ingest (command.go's replicator) ----
  * The reference's Receive goroutine reads ONE datagram per iteration into a

@@ -34,6 +34,8 @@ EXPORTS = [
     "phip_undo_log_layout",
     "phip_export_sweep",
     "phip_table_digest", "phip_digest_diff", "phip_digest_fold", "phip_export_sweep_parts",
+    "phip_egress_caps", "phip_apply_mixed_egress", "phip_batcher_open_egress",
+    "phip_batcher_egress_next", "phip_batcher_egress_done",
 ]
 
 PHIP_OK = 0
@@ -119,6 +121,18 @@ class phip_digest_part(C.Structure):
 
 class phip_digest_stats(C.Structure):
     _fields_ = [("records", C.c_uint64), ("bytes", C.c_uint64), ("slots_scanned", C.c_uint64)]
+
+
+class phip_egress(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("out_cap", C.c_uint64), ("offs", C.c_void_p),
+                ("max_msgs", C.c_uint32), ("n_incast", C.c_uint32), ("n", C.c_uint32),
+                ("reserved", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+class phip_egress_batch(C.Structure):
+    _fields_ = [("bytes", C.c_void_p), ("offs", C.c_void_p), ("n", C.c_uint32),
+                ("n_incast", C.c_uint32), ("batch", C.c_uint64), ("first_seq", C.c_uint64),
+                ("requests", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class phip_results(C.Structure):
@@ -260,5 +274,13 @@ def load(path: str = LIB_PATH):
         L.phip_digest_fold.argtypes = [vp, u32, u32, vp]
         L.phip_export_sweep_parts.argtypes = [vp, C.POINTER(phip_sweep_cursor), i64, i64, u32, vp,
                                               vp, u64, vp, u32, C.POINTER(phip_sweep_stats), u32]
+    if hasattr(L, "phip_apply_mixed_egress"):
+        L.phip_egress_caps.argtypes = [u32, u64, u32, C.POINTER(u32), C.POINTER(u64)]
+        L.phip_apply_mixed_egress.argtypes = [vp, C.POINTER(phip_ops), C.POINTER(phip_results),
+                                              C.POINTER(phip_egress), u32]
+        L.phip_batcher_open_egress.argtypes = [vp, C.POINTER(phip_batcher_config), u32,
+                                               C.POINTER(vp)]
+        L.phip_batcher_egress_next.argtypes = [vp, C.c_int, C.POINTER(phip_egress_batch)]
+        L.phip_batcher_egress_done.argtypes = [vp, u64]
     _lib = L
     return L

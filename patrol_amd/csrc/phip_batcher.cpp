@@ -14,7 +14,14 @@
 // arrive while a batch is on the GPU form the next batch, so under load the
 // batches grow by themselves.
 //
-// Host code only: every device call goes through the public C ABI.
+// A batcher opened with phip_batcher_open_egress also hands out each batch's
+// replication traffic (phip_apply_mixed_egress: one datagram per bucket the
+// batch touched) through a ring of pinned buffers, in batch order, to whoever
+// calls phip_batcher_egress_next; its callers are woken only once their
+// batch's egress is queued there.
+//
+// Host code only: every device call goes through the public C ABI (the ring's
+// buffers are pinned host memory, the one HIP call here).
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -24,6 +31,8 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "patrolhip.h"
 #include "phip_host.hpp"
@@ -44,6 +53,16 @@ struct Req {
   int rc = 0;
   bool done = false;
   std::condition_variable cv;   // its caller waits here (woken alone, not with every waiter)
+};
+
+// One buffer of the egress ring: free, filled and queued for
+// phip_batcher_egress_next, or handed out until phip_batcher_egress_done.
+struct EgressSlot {
+  enum State { kFree, kQueued, kHanded } state = kFree;
+  uint8_t* bytes = nullptr;   // pinned: out_cap bytes, then the max_msgs + 1 offsets
+  uint64_t* offs = nullptr;
+  uint32_t n = 0, n_incast = 0, requests = 0;
+  uint64_t batch = 0, first_seq = 0;
 };
 
 }  // namespace
@@ -71,12 +90,22 @@ struct phip_batcher {
   std::vector<int64_t> now, freq, per;
   std::vector<uint64_t> count, remaining;
   std::vector<phip_state> post;
+  // egress ring (empty: none, the batcher of phip_batcher_open).  Batch k of
+  // the queued ones lives in slot k % size; all under mu.
+  std::vector<EgressSlot> slots;
+  uint32_t eg_msgs = 0;
+  uint64_t eg_cap = 0;
+  uint64_t eg_tail = 0, eg_head = 0;   // batches queued, batches handed out
+  std::condition_variable cv_slot;     // the dispatcher waits for a free slot
+  std::condition_variable cv_egress;   // phip_batcher_egress_next waits for a queued batch
+  uint64_t eg_batches = 0, eg_datagrams = 0, eg_wait_ns = 0;
 
   void run();
-  void dispatch(std::vector<Req*>& batch);
+  int dispatch(std::vector<Req*>& batch, EgressSlot* slot);
 };
 
-void phip_batcher::dispatch(std::vector<Req*>& batch) {
+// slot: where the batch's egress goes (nullptr: no egress).
+int phip_batcher::dispatch(std::vector<Req*>& batch, EgressSlot* slot) {
   const uint32_t n = (uint32_t)batch.size();
   kind.assign(n, PHIP_OP_TAKE);
   offs.resize(n + 1);
@@ -108,7 +137,19 @@ void phip_batcher::dispatch(std::vector<Req*>& batch) {
   res.remaining = remaining.data();
   res.reply = post.data();   // each Take's post state: its broadcast, in the same launch
   const auto t0 = Clock::now();
-  const int rc = phip_apply_mixed(h, &ops, &res, 0);
+  int rc;
+  if (slot) {
+    phip_egress eg{};
+    eg.out = slot->bytes;
+    eg.out_cap = eg_cap;
+    eg.offs = slot->offs;
+    eg.max_msgs = eg_msgs;
+    rc = phip_apply_mixed_egress(h, &ops, &res, &eg, 0);
+    slot->n = eg.n;
+    slot->n_incast = eg.n_incast;
+  } else {
+    rc = phip_apply_mixed(h, &ops, &res, 0);
+  }
   gpu_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t0).count();
   for (uint32_t i = 0; i < n; ++i) {
     batch[i]->rc = rc;
@@ -117,6 +158,7 @@ void phip_batcher::dispatch(std::vector<Req*>& batch) {
     batch[i]->post = post[i];
   }
   if (rc) ++errors;
+  return rc;
 }
 
 void phip_batcher::run() {
@@ -142,9 +184,32 @@ void phip_batcher::run() {
     batch.assign(pending.begin(), pending.begin() + take);
     pending.erase(pending.begin(), pending.begin() + take);
     if (!pending.empty()) first_arrival = Clock::now();
+    // An egress batcher fills the ring's next slot; while every slot is full
+    // or handed out the dispatcher waits for phip_batcher_egress_done, as the
+    // reference's handler waits for its WriteTo calls.  A closing batcher
+    // waits no longer: what is still pending then runs without egress.
+    EgressSlot* slot = nullptr;
+    if (!slots.empty()) {
+      EgressSlot* s = &slots[eg_tail % slots.size()];
+      if (s->state != EgressSlot::kFree && !stop) {
+        const auto w0 = Clock::now();
+        cv_slot.wait(l, [&] { return stop || s->state == EgressSlot::kFree; });
+        eg_wait_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - w0).count();
+      }
+      if (s->state == EgressSlot::kFree) slot = s;
+    }
     l.unlock();
-    dispatch(batch);
+    const int rc = dispatch(batch, slot);
     l.lock();
+    if (slot && !rc && slot->n) {
+      slot->batch = eg_tail++;
+      slot->first_seq = batch[0]->seq;
+      slot->requests = (uint32_t)batch.size();
+      slot->state = EgressSlot::kQueued;
+      ++eg_batches;
+      eg_datagrams += slot->n;
+      cv_egress.notify_all();
+    }
     ++batches;
     requests += batch.size();
     max_seen = std::max<uint64_t>(max_seen, batch.size());
@@ -202,11 +267,15 @@ void fill_reply(const Req& r, phip_take_reply* out) {
   out->datagram_len = sz > 0 ? (uint16_t)sz : 0;
 }
 
-}  // namespace
+void free_slots(phip_batcher* b) {
+  for (EgressSlot& s : b->slots)
+    if (s.bytes) (void)hipHostFree(s.bytes);
+  b->slots.clear();
+}
 
-extern "C" {
-
-int phip_batcher_open(phip_handle* h, const phip_batcher_config* cfg, phip_batcher** out) {
+// egress_slots: 0 for the plain batcher, else the ring's size.
+int batcher_open(phip_handle* h, const phip_batcher_config* cfg, uint32_t egress_slots,
+                 phip_batcher** out) {
   if (!h || !out) return PHIP_ERR_INVALID;
   *out = nullptr;
   phip_batcher* b = new phip_batcher;
@@ -215,13 +284,94 @@ int phip_batcher_open(phip_handle* h, const phip_batcher_config* cfg, phip_batch
     b->window_us = cfg->window_us;
     if (cfg->max_batch) b->max_batch = cfg->max_batch;
   }
+  if (egress_slots) {
+    // every slot holds a batch's worst case: a full batch of 231-byte names
+    if (phip_egress_caps(b->max_batch, (uint64_t)PHIP_MAX_NAME_LEN * b->max_batch, 0, &b->eg_msgs,
+                         &b->eg_cap)) {
+      delete b;
+      return PHIP_ERR_INVALID;
+    }
+    b->slots.resize(egress_slots);
+    const size_t off = (size_t)((b->eg_cap + 7) & ~7ull);
+    for (EgressSlot& s : b->slots) {
+      void* p = nullptr;
+      if (hipHostMalloc(&p, off + ((size_t)b->eg_msgs + 1) * sizeof(uint64_t), hipHostMallocPortable) !=
+          hipSuccess) {
+        (void)hipGetLastError();
+        free_slots(b);
+        delete b;
+        return PHIP_ERR_HIP;
+      }
+      s.bytes = (uint8_t*)p;
+      s.offs = (uint64_t*)(s.bytes + off);
+    }
+  }
   try {
     b->th = std::thread([b] { b->run(); });
   } catch (...) {
+    free_slots(b);
     delete b;
     return PHIP_ERR_INVALID;
   }
   *out = b;
+  return PHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int phip_batcher_open(phip_handle* h, const phip_batcher_config* cfg, phip_batcher** out) {
+  return batcher_open(h, cfg, 0, out);
+}
+
+int phip_batcher_open_egress(phip_handle* h, const phip_batcher_config* cfg, uint32_t egress_slots,
+                             phip_batcher** out) {
+  return batcher_open(h, cfg, egress_slots ? egress_slots : 4, out);
+}
+
+int phip_batcher_egress_next(phip_batcher* b, int timeout_ms, phip_egress_batch* out) {
+  if (!b || !out) return PHIP_ERR_INVALID;
+  std::unique_lock<std::mutex> l(b->mu);
+  if (b->slots.empty()) return PHIP_ERR_INVALID;
+  if (b->stop) return 0;
+  ++b->waiters;   // (close() waits for it to leave, as for a taker)
+  // (the slot of the next batch to hand out: looked up at every wake-up, another
+  // drainer may have taken a batch meanwhile)
+  auto head = [&] { return &b->slots[b->eg_head % b->slots.size()]; };
+  auto queued = [&] { return head()->state == EgressSlot::kQueued && head()->batch == b->eg_head; };
+  auto ready = [&] { return b->stop || queued(); };
+  if (timeout_ms < 0)
+    b->cv_egress.wait(l, ready);
+  else
+    b->cv_egress.wait_for(l, std::chrono::milliseconds(timeout_ms), ready);
+  int got = 0;
+  if (!b->stop && queued()) {
+    EgressSlot* s = head();
+    s->state = EgressSlot::kHanded;
+    ++b->eg_head;
+    out->bytes = s->bytes;
+    out->offs = s->offs;
+    out->n = s->n;
+    out->n_incast = s->n_incast;
+    out->batch = s->batch;
+    out->first_seq = s->first_seq;
+    out->requests = s->requests;
+    out->reserved = 0;
+    got = 1;
+  }
+  if (--b->waiters == 0 && b->stop) b->cv_idle.notify_all();
+  return got;
+}
+
+int phip_batcher_egress_done(phip_batcher* b, uint64_t batch) {
+  if (!b) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> l(b->mu);
+  if (b->slots.empty()) return PHIP_ERR_INVALID;
+  EgressSlot* s = &b->slots[batch % b->slots.size()];
+  if (s->state != EgressSlot::kHanded || s->batch != batch) return PHIP_ERR_INVALID;
+  s->state = EgressSlot::kFree;
+  b->cv_slot.notify_all();
   return PHIP_OK;
 }
 
@@ -232,11 +382,14 @@ void phip_batcher_close(phip_batcher* b) {
     b->stop = true;
   }
   b->cv_submit.notify_all();
+  b->cv_slot.notify_all();     // a dispatcher waiting for a free egress slot
+  b->cv_egress.notify_all();   // a blocked phip_batcher_egress_next: it returns 0
   if (b->th.joinable()) b->th.join();
   {
     std::unique_lock<std::mutex> l(b->mu);
     b->cv_idle.wait(l, [&] { return b->waiters == 0; });
   }
+  free_slots(b);
   delete b;
 }
 
@@ -306,9 +459,10 @@ int phip_batcher_api_take_reply(phip_batcher* b, const uint8_t* name, uint32_t l
 int phip_batcher_stats(phip_batcher* b, uint64_t* out, int max) {
   if (!b || !out) return 0;
   std::lock_guard<std::mutex> l(b->mu);
-  const uint64_t v[5] = {b->batches, b->requests, b->max_seen, b->gpu_ns, b->errors};
+  const uint64_t v[8] = {b->batches,    b->requests,     b->max_seen,  b->gpu_ns, b->errors,
+                         b->eg_batches, b->eg_datagrams, b->eg_wait_ns};
   int k = 0;
-  for (; k < max && k < 5; ++k) out[k] = v[k];
+  for (; k < max && k < 8; ++k) out[k] = v[k];
   return k;
 }
 

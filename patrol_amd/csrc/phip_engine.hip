@@ -63,6 +63,7 @@ enum BufId {
   B_STATES, B_NAME1, B_HOT, B_ROUTE, B_EXPORT, B_MSHARD, B_MSCNT, B_FSCNT, B_DEDUP, B_DSET, B_TSTATS, B_SEGT, B_RHOT,
   B_DLIST, B_DTAB, B_DMARK, B_SMAP, B_SOFF, B_SLEN, B_SA, B_ST, B_SE, B_SSTAT, B_SREP, B_NCHK,
   B_EVICT, B_ULOG, B_ULCNT, B_SWEEP, B_DIGEST, B_DIGOUT,
+  B_EGSZ, B_EGTILE, B_EGOUT, B_EGOFFS,
   B_COUNT_
 };
 
@@ -1413,10 +1414,70 @@ int resolve_all(phip_handle* h, Src src, u32 n, const int64_t* now_arr, i64 now0
   return PHIP_OK;
 }
 
+// phip_apply_mixed_egress' part of ordered(): where the batch's datagrams go
+// (device memory) and the caps its caller checked against the batch's worst
+// case.  uniform: every op has one kind, known to the host (wants: whether it
+// is TAKE or UPSERT), and the kernels read no kinds.
+struct EgressOut {
+  u8* out;
+  u64* offs;
+  u32 max_msgs;
+  u64 budget;
+  bool uniform, wants;
+};
+
+// The batch egress behind the folds (phip_kernels.hpp "batch egress"), on the
+// main stream; the totals stay in the egress counter words for the caller.
+int egress_launches(phip_handle* h, const EgressOut& eg, u32 nseg, const u32* uslot,
+                    const u32* sstart, const u32* scnt, const u32* sidx, const u32* lng, u32 nlong,
+                    const u32* huge, u32 nhuge, const u8* status) {
+  const u32 ntiles = (nseg + kSweepTile - 1) / kSweepTile;
+  u32* esz;
+  u64* tile_bytes;
+  int rc;
+  // one buffer: the tiles' byte sums, then their counts (both sections each)
+  if ((rc = ensure(h, B_EGSZ, nseg, &esz)) ||
+      (rc = ensure(h, B_EGTILE, 3 * (size_t)ntiles, &tile_bytes)))
+    return rc;
+  u32* tile_cnt = (u32*)(tile_bytes + 2 * (size_t)ntiles);
+  if (!eg.uniform && (nlong || nhuge)) {
+    Launch l(h, "k_egress_wants");
+    k_egress_wants<<<(nlong + kBlock / 64 - 1) / (kBlock / 64) + nhuge, kBlock, 0, h->stream>>>(
+        lng, nlong, huge, nhuge, sstart, scnt, sidx, esz);
+  }
+  {
+    Launch l(h, "k_egress_count");
+    if (eg.uniform)
+      k_egress_count<true><<<ntiles, kBlock, 0, h->stream>>>(h->recs, uslot, sstart, scnt, sidx, nseg,
+                                                            status, eg.wants, esz, ntiles, tile_cnt,
+                                                            tile_bytes);
+    else
+      k_egress_count<false><<<ntiles, kBlock, 0, h->stream>>>(h->recs, uslot, sstart, scnt, sidx,
+                                                             nseg, status, false, esz, ntiles,
+                                                             tile_cnt, tile_bytes);
+  }
+  {
+    Launch l(h, "k_egress_scan");
+    k_egress_scan<<<1, kSweepBlock, 0, h->stream>>>(tile_cnt, tile_bytes, ntiles, h->ctr);
+  }
+  {
+    // (long names are bounded by the arena's size, as in the sweep)
+    Launch l(h, "k_egress_write");
+    k_egress_write<<<ntiles, kSweepBlock, 0, h->stream>>>(h->recs, h->arena, h->arena_cap, uslot, esz,
+                                                          nseg, ntiles, tile_cnt, tile_bytes,
+                                                          eg.max_msgs, eg.budget, eg.out, eg.offs,
+                                                          h->ctr);
+  }
+  HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
+}
+
 // Apply a mixed op stream in seq order.  The NEW flag of created buckets is
-// consumed (cleared) by the fold itself.
+// consumed (cleared) by the fold itself.  eg: the batch's egress is written
+// behind the folds (ow.status is then required).
 template <class Src>
-int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow) {
+int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow,
+            const EgressOut* eg = nullptr) {
   if (n == 0) return PHIP_OK;
   if (n > kMaxOrderedOps)
     return set_err(h, PHIP_ERR_INVALID, "ordered batch of %u ops exceeds 2^30", n);
@@ -1672,6 +1733,10 @@ int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow)
     HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
   }
   (void)n_claimed;  // NEW flags cleared by store_state in the folds
+  // (every fold has joined the main stream: the records and statuses are final)
+  if (eg)
+    return egress_launches(h, *eg, nseg, uslot, sstart, scnt, sidx, lng, nlong, huge, nhuge,
+                           ow.status);
   return PHIP_OK;
 }
 
@@ -1906,7 +1971,12 @@ inline bool has_reply_state(u8 status, u8 kind) {
 // *done = false leaves the batch to the large path with nothing changed: too
 // many ops or name bytes, a bucket bound past the load limit (the large path
 // grows the table), or a long-name arena the kernel found too small.
-int small_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, bool* done) {
+// eg (phip_apply_mixed_egress, its caps checked by the caller): the same
+// launch, k_small_mixed<true>, also writes the batch's egress into the staging
+// buffer; it travels back with the results when its worst case is small, and
+// in a second copy of just the bytes written otherwise.
+int small_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, bool* done,
+                phip_egress* eg = nullptr) {
   *done = false;
   const u32 n = ops->n;
   if (n > kSmallMax || h->n_buckets + n > h->max_load) return PHIP_OK;
@@ -1922,7 +1992,13 @@ int small_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, bo
   // outputs: header | status | remaining | have | reply
   const size_t o_st = sizeof(SmallHdr), o_rem = al(o_st + n), o_have = o_rem + 8 * n;
   const size_t o_reply = o_have + 8 * n, out_bytes = o_reply + sizeof(phip_state) * n;
-  const size_t total = in_bytes + out_bytes;
+  // egress: header | offsets | datagrams (the batch's worst case, 8 bytes of slack)
+  const u32 eg_msgs = 2 * n;
+  const u64 eg_budget = 2 * ((u64)PHIP_BUCKET_FIXED_SIZE * n + (nbytes - ops->name_offs[0]));
+  const size_t o_eg = al(out_bytes), o_egoffs = o_eg + sizeof(SmallEgHdr);
+  const size_t o_egdata = al(o_egoffs + 8 * ((size_t)eg_msgs + 1));
+  const size_t eg_end = al(o_egdata + (size_t)eg_budget + 8);
+  const size_t total = in_bytes + (eg ? eg_end : out_bytes);
   if (h->small_pin_cap < total) {
     if (h->small_pin) HIPCHK(h, hipHostFree(h->small_pin));
     h->small_pin = nullptr;
@@ -1969,18 +2045,29 @@ int small_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, bo
   phip_results r{};
   if (res) r = *res;
   OutView ow{};
-  ow.status = r.status ? dout + o_st : nullptr;
+  ow.status = (r.status || eg) ? dout + o_st : nullptr;   // (the egress reads who created what)
   ow.remaining = r.remaining ? (uint64_t*)(dout + o_rem) : nullptr;
   ow.have = r.have ? (uint64_t*)(dout + o_have) : nullptr;
   ow.reply = r.reply ? (phip_state*)(dout + o_reply) : nullptr;
   {
     Launch l(h, "k_small_mixed");
-    k_small_mixed<<<1, kSmallMax, 0, h->stream>>>(src, ov, n, table(h), h->arena, h->arena_cap,
-                                                  h->arena_cursor, ow, (SmallHdr*)dout);
+    if (eg)
+      k_small_mixed<true><<<1, kSmallMax, 0, h->stream>>>(
+          src, ov, n, table(h), h->arena, h->arena_cap, h->arena_cursor, ow, (SmallHdr*)dout,
+          SmallEgress<true>{dout + o_egdata, (u64*)(dout + o_egoffs), (SmallEgHdr*)(dout + o_eg),
+                            eg_msgs, eg_budget});
+    else
+      k_small_mixed<false><<<1, kSmallMax, 0, h->stream>>>(src, ov, n, table(h), h->arena,
+                                                           h->arena_cap, h->arena_cursor, ow,
+                                                           (SmallHdr*)dout, SmallEgress<false>{});
   }
   HIPCHK(h, hipGetLastError());
-  // the header and the columns the caller asked for, in one copy
-  const size_t back = r.reply ? out_bytes : r.have ? o_reply : r.remaining ? o_have : o_rem;
+  // the header and the columns the caller asked for, in one copy (with the
+  // egress: its header too, and all of it when its worst case is small)
+  constexpr size_t kEgOneCopy = 64 << 10;
+  const bool eg_one = eg && eg_end - o_eg <= kEgOneCopy;
+  const size_t back = eg ? (eg_one ? eg_end : o_egoffs)
+                         : r.reply ? out_bytes : r.have ? o_reply : r.remaining ? o_have : o_rem;
   u8* pout = pin + in_bytes;
   HIPCHK(h, hipMemcpyAsync(pout, dout, back, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1989,6 +2076,27 @@ int small_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, bo
   h->n_buckets += hd.created;
   if (hd.fallback) return PHIP_OK;
   if (hd.full) return set_err(h, PHIP_ERR_FULL, "internal: small batch probe wrapped the table");
+  if (eg) {
+    SmallEgHdr eh;
+    std::memcpy(&eh, pout + o_eg, sizeof eh);
+    if (eh.err || eh.n > eg_msgs || eh.n_incast > eh.n || eh.bytes > eg_budget)
+      return set_err(h, PHIP_ERR_INVALID, "internal: egress of %u datagrams, %llu bytes (flag %u)",
+                     eh.n, (unsigned long long)eh.bytes, eh.err);
+    if (!eg_one) {
+      // only what was written travels back
+      HIPCHK(h, hipMemcpyAsync(pout + o_egoffs, dout + o_egoffs, 8 * ((size_t)eh.n + 1),
+                               hipMemcpyDeviceToHost, h->stream));
+      if (eh.bytes)
+        HIPCHK(h, hipMemcpyAsync(pout + o_egdata, dout + o_egdata, eh.bytes, hipMemcpyDeviceToHost,
+                                 h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    std::memcpy(eg->offs, pout + o_egoffs, 8 * ((size_t)eh.n + 1));
+    std::memcpy(eg->out, pout + o_egdata, eh.bytes);
+    eg->n_incast = eh.n_incast;
+    eg->n = eh.n;
+    eg->bytes = eh.bytes;
+  }
   if (r.status) std::memcpy(r.status, pout + o_st, n);
   if (r.remaining) std::memcpy(r.remaining, pout + o_rem, 8 * n);
   if (r.have) std::memcpy(r.have, pout + o_have, 8 * n);
@@ -3075,28 +3183,95 @@ int phip_upsert_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip_
   return copy_outputs(h, res, n, dev, ow);
 }
 
-int phip_apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, uint32_t flags) {
+// The caps of a batch's egress (patrolhip.h "Coalesced egress"): every op a
+// new bucket's TAKE, a request and a state datagram each.
+static bool egress_need(u64 n, u64 name_bytes, bool dev, u64* msgs, u64* cap) {
+  // (an ordered batch has at most 2^30 ops; the bound on the bytes keeps the sums in 64 bits)
+  if (n > kMaxOrderedOps || name_bytes > (u64)kMaxOrderedOps * PHIP_BUCKET_PACKET_SIZE) return false;
+  *msgs = 2 * n;
+  u64 c = 2 * (PHIP_BUCKET_FIXED_SIZE * n + name_bytes);
+  if (dev) c = ((c + 7) & ~7ull) + 8;   // (the sweep's device form: a multiple of 8, 8 bytes past the budget)
+  *cap = c;
+  return true;
+}
+
+int phip_egress_caps(uint32_t n_ops, uint64_t name_bytes, uint32_t flags, uint32_t* max_msgs,
+                     uint64_t* out_cap) {
+  u64 m, c;
+  if (!max_msgs || !out_cap || (flags & ~PHIP_DEVICE_PTRS) ||
+      !egress_need(n_ops, name_bytes, flags & PHIP_DEVICE_PTRS, &m, &c))
+    return PHIP_ERR_INVALID;
+  *max_msgs = (u32)m;
+  *out_cap = c;
+  return PHIP_OK;
+}
+
+// phip_apply_mixed (eg == nullptr: exactly that call) and
+// phip_apply_mixed_egress, on the same paths: small_mixed, or ordered() with
+// the egress launches behind its folds.
+static int apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res,
+                       phip_egress* eg, uint32_t flags) {
+  if (eg) eg->n_incast = eg->n = 0, eg->bytes = 0;
   if (!h || !ops) return PHIP_ERR_INVALID;
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = begin_call(h)) return rc0;
   u32 n = ops->n;
-  if (n == 0) return PHIP_OK;
-  if (!ops->kind || !ops->names || !ops->name_offs || !ops->now) return PHIP_ERR_INVALID;
   bool dev = flags & PHIP_DEVICE_PTRS;
+  if (eg && (!eg->out || !eg->offs))
+    return set_err(h, PHIP_ERR_INVALID, "egress: out and offs are required");
+  if (n == 0) {
+    if (!eg) return PHIP_OK;
+    if (dev) {
+      HIPCHK(h, hipMemsetAsync(eg->offs, 0, sizeof(u64), h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else {
+      eg->offs[0] = 0;
+    }
+    return PHIP_OK;
+  }
+  if (!ops->kind || !ops->names || !ops->name_offs || !ops->now) return PHIP_ERR_INVALID;
   if (!dev && !names_ok(ops->name_offs, n)) return set_err(h, PHIP_ERR_NAME_TOO_LARGE, "name > 231 bytes");
+  bool uniform = false;
   if (!dev) {
     bool need_take = false, need_state = false;
+    uniform = true;
     for (u32 i = 0; i < n; ++i) {
       if (ops->kind[i] > PHIP_OP_UPSERT) return set_err(h, PHIP_ERR_INVALID, "bad op kind at %u", i);
       if (ops->kind[i] == PHIP_OP_TAKE) need_take = true; else need_state = true;
+      uniform &= ops->kind[i] == ops->kind[0];
     }
     if (need_take && (!ops->freq || !ops->per || !ops->count)) return PHIP_ERR_INVALID;
     if (need_state && (!ops->added || !ops->taken || !ops->elapsed)) return PHIP_ERR_INVALID;
   }
   int rc;
+  EgressOut eo{};
+  u64 need_cap = 0;
+  if (eg) {
+    // the caps, before anything is applied: a valid call never truncates
+    const u64 name_bytes = !dev ? (u64)ops->name_offs[n] - ops->name_offs[0]
+                                : ops->names_len ? (u64)ops->names_len : (u64)PHIP_MAX_NAME_LEN * n;
+    u64 need_msgs;
+    if (!egress_need(n, name_bytes, dev, &need_msgs, &need_cap))
+      return set_err(h, PHIP_ERR_INVALID, "egress: a batch of %u ops exceeds 2^30", n);
+    if (dev && ((reinterpret_cast<uintptr_t>(eg->out) & 7) || (eg->out_cap & 7)))
+      return set_err(h, PHIP_ERR_INVALID, "egress: a device buffer is 8-byte aligned and a multiple of 8");
+    if (eg->max_msgs < need_msgs || eg->out_cap < need_cap)
+      return set_err(h, PHIP_ERR_INVALID,
+                     "egress: max_msgs %u, out_cap %llu below the batch's worst case %llu, %llu "
+                     "(phip_egress_caps): nothing applied",
+                     eg->max_msgs, (unsigned long long)eg->out_cap, (unsigned long long)need_msgs,
+                     (unsigned long long)need_cap);
+    eo.max_msgs = (u32)need_msgs;
+    eo.budget = dev ? need_cap - 8 : need_cap;
+    eo.uniform = uniform;
+    eo.wants = uniform && ops->kind[0] != PHIP_OP_RECEIVE;
+  }
   if (!dev && h->small) {
     bool done = false;
-    if ((rc = small_mixed(h, ops, res, &done))) return after_error(h, rc);
+    if ((rc = small_mixed(h, ops, res, &done, eg))) {
+      if (eg) eg->n_incast = eg->n = 0, eg->bytes = 0;
+      return after_error(h, rc);
+    }
     if (done) return PHIP_OK;
   }
   NamesOffs src;
@@ -3114,8 +3289,47 @@ int phip_apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* re
       (rc = stage(h, B_E, ops->elapsed, n, dev, &ov.e)) || (rc = outputs(h, res, n, dev, &ow)))
     return rc;
   ov.kind = kind;
-  if ((rc = ordered(h, src, n, ov, ow))) return after_error(h, rc);
-  return copy_outputs(h, res, n, dev, ow);
+  if (!eg) {
+    if ((rc = ordered(h, src, n, ov, ow))) return after_error(h, rc);
+    return copy_outputs(h, res, n, dev, ow);
+  }
+  // the statuses say which buckets the batch created: a column of the
+  // library's own when the caller asked for none
+  if (!ow.status && (rc = ensure(h, B_STATUS, n, &ow.status))) return rc;
+  eo.out = eg->out;
+  eo.offs = reinterpret_cast<u64*>(eg->offs);
+  if (!dev && ((rc = ensure(h, B_EGOUT, (size_t)need_cap + 8, &eo.out)) ||
+               (rc = ensure(h, B_EGOFFS, 2 * (size_t)n + 1, &eo.offs))))
+    return rc;
+  if ((rc = ordered(h, src, n, ov, ow, &eo))) return after_error(h, rc);
+  if ((rc = read_ctr(h))) return rc;
+  const u32* c = h->ctr_host;
+  u64 bytes;
+  std::memcpy(&bytes, c + kCtrEgBytes, sizeof bytes);
+  if (c[kCtrEgErr] || c[kCtrEgN] > eo.max_msgs || bytes > eo.budget || c[kCtrEgIncast] > c[kCtrEgN])
+    return set_err(h, PHIP_ERR_INVALID, "internal: egress of %u datagrams, %llu bytes (flag %u)",
+                   c[kCtrEgN], (unsigned long long)bytes, c[kCtrEgErr]);
+  if (!dev) {
+    // only what was written travels back
+    if (bytes) HIPCHK(h, hipMemcpyAsync(eg->out, eo.out, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(eg->offs, eo.offs, ((size_t)c[kCtrEgN] + 1) * sizeof(u64),
+                             hipMemcpyDeviceToHost, h->stream));
+  }
+  if ((rc = copy_outputs(h, res, n, dev, ow))) return rc;
+  eg->n_incast = c[kCtrEgIncast];
+  eg->n = c[kCtrEgN];
+  eg->bytes = bytes;
+  return PHIP_OK;
+}
+
+int phip_apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, uint32_t flags) {
+  return apply_mixed(h, ops, res, nullptr, flags);
+}
+
+int phip_apply_mixed_egress(phip_handle* h, const phip_ops* ops, const phip_results* res,
+                            phip_egress* eg, uint32_t flags) {
+  if (!eg) return PHIP_ERR_INVALID;
+  return apply_mixed(h, ops, res, eg, flags);
 }
 
 int phip_take(phip_handle* h, const uint8_t* names, const uint32_t* name_offs, uint32_t n,

@@ -316,6 +316,19 @@ constexpr u32 kCtrHotKept = 21;
 // it ran (F).  W: k_receive_fast<Opt>, one lane, in every launch.
 // R: receive_queued, after a gated pass.
 constexpr u32 kCtrGateShut = 22;
+// A batch's egress (G; "batch egress" below): its incast requests, all its
+// datagrams, and a record k_egress_write skipped because it would have ended
+// past a cap (internal: the caps are checked before the batch is applied) or
+// whose long name lies outside the arena.  W: k_egress_scan (the totals, the
+// flag's zero), k_egress_write (the flag).  R: apply_mixed (phip_engine.hip),
+// once, after the write.
+constexpr u32 kCtrEgIncast = 23;
+constexpr u32 kCtrEgN = 24;
+constexpr u32 kCtrEgErr = 25;
+// Two u64: the requests' bytes and all the datagrams' (= offs[n]) (G).
+// W: k_egress_scan.  R: apply_mixed.
+constexpr u32 kCtrEgIncastBytes = 26;
+constexpr u32 kCtrEgBytes = 28;
 constexpr u32 kCtrWords = 32;
 // The two min-reduced words start at "none", the rest at zero.
 __host__ __device__ constexpr u32 ctr_reset_value(u32 w) {
@@ -334,6 +347,9 @@ static_assert(kCtrNDefer >= kCtrResetWords && kCtrNDefer < kCtrWords &&
               kCtrNSorted >= kCtrResetWords && kCtrNSorted < kCtrWords &&
               kCtrHotOwn >= kCtrResetWords && kCtrHotKept < kCtrWords &&
               kCtrGateShut >= kCtrResetWords && kCtrGateShut < kCtrWords, "outside the reset");
+static_assert(kCtrEgIncast > kCtrGateShut && kCtrEgErr < kCtrEgIncastBytes &&
+              kCtrEgIncastBytes % 2 == 0 && kCtrEgBytes == kCtrEgIncastBytes + 2 &&
+              kCtrEgBytes + 2 <= kCtrWords, "the egress words: two aligned u64 behind three u32");
 
 // The gate of a queued optimistic pass (k_receive_fast<Opt>'s `gate`, and the
 // host's reading of the same words in the mirror): c is the counter set of the
@@ -2714,6 +2730,12 @@ constexpr u32 kOpIdxBits = 30;
 static_assert(kOpIdxBits == kSortValKindShift, "k_resolve's sort values");
 constexpr u32 kOpIdxMask = (1u << kOpIdxBits) - 1;
 constexpr u32 kMaxOrderedOps = 1u << kOpIdxBits;
+// A sort value whose op is broadcast by the reference (UpsertBucket after a
+// take, an upsert): its bucket gets a state datagram in the batch's egress.
+__device__ inline bool egress_kind(u32 v) {
+  const u32 kind = v >> kOpIdxBits;
+  return kind == PHIP_OP_TAKE || kind == PHIP_OP_UPSERT;
+}
 
 struct SOp {
   i64 now;
@@ -3089,6 +3111,10 @@ __global__ __launch_bounds__(64) void k_fold_wave(
 //     one (rounds of 64 ops against the current state, as k_fold_wave).
 // The NEW flag of a created bucket is consumed by its fold (store_state), and
 // the creating op gets PHIP_ST_CREATED from step_sop, as on the large path.
+// k_small_mixed<true> (phip_apply_mixed_egress) also writes the batch's
+// egress behind the folds, in the same launch (small_egress, "batch egress"
+// below); k_small_mixed<false> is the kernel without it, its last argument
+// the empty form.
 constexpr u32 kSmallMax = 1024;
 struct SmallHdr {
   u32 created;    // buckets this launch created
@@ -3105,10 +3131,33 @@ __device__ inline Rec load_rec_co(const Rec* p) {
   return r;
 }
 
+// Where k_small_mixed<true> leaves the batch's egress (device staging): the
+// totals, the datagrams, their offsets.
+struct SmallEgHdr {
+  u32 n_incast, n;
+  u32 err;       // a datagram past a cap or a long name outside the arena (internal)
+  u32 pad;
+  u64 bytes;     // = offs[n]
+  u64 pad2;
+};
+template <bool kEgress>
+struct SmallEgress {};
+template <>
+struct SmallEgress<true> {
+  u8* out;
+  u64* offs;
+  SmallEgHdr* hdr;
+  u32 max_msgs;
+  u64 budget;
+};
+__device__ void small_egress(const SmallEgress<true>& eg, u32 n, const u32* sorted, const u64* skey,
+                             const u32* sval, const Table& T, u64 arena_used, const u8* status);
+
+template <bool kEgress>
 __global__ __launch_bounds__(kSmallMax) void k_small_mixed(NamesOffs src, OpView ov, u32 n, Table T,
                                                          u8* arena, u64 arena_cap,
                                                          u64* arena_cursor, OutView ow,
-                                                         SmallHdr* hdr) {
+                                                         SmallHdr* hdr, SmallEgress<kEgress> eg) {
   __shared__ OpRec sop[kSmallMax];
   __shared__ u32 sval[kSmallMax];
   __shared__ u64 skey[kSmallMax];
@@ -3267,6 +3316,7 @@ __global__ __launch_bounds__(kSmallMax) void k_small_mixed(NamesOffs src, OpView
     if (lane == 0) store_state(rec, S);
   }
   if (i == 0) hdr->created = created;
+  if constexpr (kEgress) small_egress(eg, n, sorted, skey, sval, T, arena_cap, ow.status);
 }
 
 // ---- window summaries: skip provably quiet windows of a hot bucket -------
@@ -5773,6 +5823,48 @@ __device__ inline void sweep_put8(u8* d, u64 w) {
 #endif
 }
 
+// One MarshalBinary datagram at d (bucket.go:51-68): the three state words
+// big-endian, the length byte, the `len` name bytes of record r -- an inline
+// name shifted out of the canonical words, an arena name copied from the arena
+// (one that would end past arena_used is left unwritten and *err set).  The
+// sweep passes the record's state, the batch egress also zeros (an incast
+// request).
+template <class Err>
+__device__ __forceinline__ void put_datagram(u8* d, u64 added, u64 taken, u64 elapsed, const Rec& r,
+                                             u32 len, const u8* __restrict__ arena, u64 arena_used,
+                                             Err* err) {
+  sweep_put8(d, __builtin_bswap64(added));
+  sweep_put8(d + 8, __builtin_bswap64(taken));
+  sweep_put8(d + 16, __builtin_bswap64(elapsed));
+  d[24] = (u8)len;
+  d += PHIP_BUCKET_FIXED_SIZE;
+  if (len <= kInlineName) {
+    // name byte j is byte j + 2 of the canonical words
+    const u64 w[4] = {r.name0, r.name1, r.name2, 0};
+    u32 j = 0;
+#pragma unroll
+    for (u32 q = 0; q < 3; ++q)
+      if (j + 8 <= len) {
+        sweep_put8(d + j, (w[q] >> 16) | (w[q + 1] << 48));
+        j += 8;
+      }
+    for (; j < len; ++j) d[j] = (u8)(w[(j + 2) >> 3] >> (((j + 2) & 7) * 8));
+  } else {
+    const u64 oa = r.name0 >> 32;
+    if (oa + len > arena_used) {
+      *err = 1;
+      return;
+    }
+    u32 j = 0;
+    for (; j + 8 <= len; j += 8) {
+      u64 x;
+      __builtin_memcpy(&x, arena + oa + j, 8);
+      sweep_put8(d + j, x);
+    }
+    for (; j < len; ++j) d[j] = arena[oa + j];
+  }
+}
+
 // Write pass, one workgroup per tile, its 4096 slots in eight steps of 512
 // consecutive slots.  A step packs (qualifies << 19 | bytes) per lane (a step
 // holds at most 1024 * 256 = 2^18 bytes), scans it per wave and adds the
@@ -5839,39 +5931,302 @@ __global__ __launch_bounds__(kSweepBlock) void k_sweep_write(
       continue;
     }
     offs[rank + 1] = end;
-    u8* d = out + start;
-    sweep_put8(d, __builtin_bswap64(dec_f64(r.added)));
-    sweep_put8(d + 8, __builtin_bswap64(dec_f64(r.taken)));
-    sweep_put8(d + 16, __builtin_bswap64((u64)r.elapsed));
-    const u32 len = sz - PHIP_BUCKET_FIXED_SIZE;
-    d[24] = (u8)len;
-    d += PHIP_BUCKET_FIXED_SIZE;
-    if (len <= kInlineName) {
-      // name byte j is byte j + 2 of the canonical words
-      const u64 w[4] = {r.name0, r.name1, r.name2, 0};
-      u32 j = 0;
+    put_datagram(out + start, dec_f64(r.added), dec_f64(r.taken), (u64)r.elapsed, r,
+                 sz - PHIP_BUCKET_FIXED_SIZE, arena, arena_used, &ctr[kSwErr]);
+  }
+}
+
+// ------------------------------------------------------ batch egress -----
+// phip_apply_mixed_egress: an ordered batch's replication traffic (patrolhip.h
+// "Coalesced egress"), written behind its folds from what the ordered path
+// already holds: uslot[0..nseg) names the distinct slots the batch touched, in
+// slot order, sstart / scnt their runs of sorted values (op index | kind <<
+// kOpIdxBits), and the records hold the states after the batch's last op.  A
+// segment gets a state datagram when one of its ops is a TAKE or an UPSERT
+// and sweep_size takes the record, and an incast request in front of all the
+// states when its first op is a TAKE whose status says PHIP_ST_CREATED.
+//   k_egress_wants  mixed kinds only: the OR of "TAKE or UPSERT" over every
+//                   segment above kLongSeg ops, one wave per long segment and
+//                   one workgroup per huge one (the fold's lists), into esz[s];
+//   k_egress_count  one workgroup per tile of kSweepTile segments: each
+//                   segment's two datagram sizes into esz[s] (a thread walks
+//                   the kinds of a segment of at most kLongSeg ops itself and
+//                   reads the longer ones' flag), the tile's counts and bytes
+//                   into the tile arrays, plain stores;
+//   k_egress_scan   one exclusive scan over the 2 * ntiles entries, the
+//                   requests' tiles in front of the states': a state tile's
+//                   base is behind every request;
+//   k_egress_write  k_sweep_write's ranking over esz, both sections at once,
+//                   the records indirect through uslot.
+// The two tile kernels have no data-dependent barrier: the wide reductions,
+// whose trip counts differ per segment, are k_egress_wants' alone.
+constexpr u32 kEgIncastShift = 16;   // esz[s]: state bytes | request bytes << 16 (<= 256 each)
+static_assert(PHIP_BUCKET_PACKET_SIZE < (1u << kEgIncastShift), "esz");
+
+__global__ __launch_bounds__(kBlock) void k_egress_wants(
+    const u32* __restrict__ lng, u32 nlong, const u32* __restrict__ huge, u32 nhuge,
+    const u32* __restrict__ sstart, const u32* __restrict__ scnt, const u32* __restrict__ sidx,
+    u32* __restrict__ esz) {
+  constexpr u32 kWaves = kBlock / 64;
+  const u32 lblocks = (nlong + kWaves - 1) / kWaves;
+  if (blockIdx.x < lblocks) {
+    // (no barrier on this branch: a wave may leave)
+    const u32 l = blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (l >= nlong) return;
+    const u32 g = lng[l], st = sstart[g], cnt = scnt[g];
+    bool found = false;
+    for (u32 j0 = 0; j0 < cnt && !found; j0 += 64) {
+      const u32 j = j0 + __lane_id();
+      found = __ballot(j < cnt && egress_kind(sidx[st + j])) != 0;
+    }
+    if (__lane_id() == 0) esz[g] = found;
+    return;
+  }
+  const u32 hi = blockIdx.x - lblocks;
+  if (hi >= nhuge) return;   // (the whole workgroup)
+  const u32 g = huge[hi], st = sstart[g], cnt = scnt[g];
+  constexpr u32 kStep = 16;   // ops per thread between two votes
+  int found = 0;
+  for (u32 j0 = 0; j0 < cnt && !found; j0 += kBlock * kStep) {
+    bool w = false;
+#pragma unroll 4
+    for (u32 k = 0; k < kStep; ++k) {
+      const u32 j = j0 + k * kBlock + threadIdx.x;
+      if (j < cnt) w |= egress_kind(sidx[st + j]);
+    }
+    found = __syncthreads_or(w);   // (cnt and found are the workgroup's: every thread votes)
+  }
+  if (threadIdx.x == 0) esz[g] = found != 0;
+}
+
+// wants0: a batch of one kind (the host knows it) reads no kinds.
+template <bool kUniform>
+__global__ __launch_bounds__(kBlock) void k_egress_count(
+    const Rec* __restrict__ recs, const u32* __restrict__ uslot, const u32* __restrict__ sstart,
+    const u32* __restrict__ scnt, const u32* __restrict__ sidx, u32 nseg,
+    const u8* __restrict__ status, bool wants0, u32* __restrict__ esz, u32 ntiles,
+    u32* __restrict__ tile_cnt, u64* __restrict__ tile_bytes) {
+  u32 n = 0;   // states | requests << 16 (a tile holds 4096 segments)
+  u64 b = 0;   // their bytes, states | requests << 32
+#pragma unroll 2
+  for (u32 k = 0; k < kSweepTile / kBlock; ++k) {
+    const u64 s64 = (u64)blockIdx.x * kSweepTile + (u64)k * kBlock + threadIdx.x;
+    if (s64 >= nseg) break;
+    const u32 s = (u32)s64;
+    const u32 st = sstart[s];
+    const u32 v0 = sidx[st];
+    bool wants = wants0;
+    if (!kUniform) {
+      const u32 cnt = scnt[s];
+      if (cnt > kLongSeg) {
+        wants = esz[s] != 0;   // (k_egress_wants)
+      } else {
+        wants = egress_kind(v0);
+        for (u32 j = 1; j < cnt && !wants; ++j) wants = egress_kind(sidx[st + j]);
+      }
+    }
+    const bool ic = (v0 >> kOpIdxBits) == PHIP_OP_TAKE &&
+                    (status[v0 & kOpIdxMask] & PHIP_ST_CREATED) != 0;
+    u32 e = 0;
+    if (wants || ic) {
+      const Rec r = load_rec(&recs[uslot[s]]);
+      if (wants) e = sweep_size(r, 0, 0);
+      const u32 len = (u32)(r.name0 & 0xFFu);
+      if (ic && len <= PHIP_MAX_NAME_LEN) e |= (PHIP_BUCKET_FIXED_SIZE + len) << kEgIncastShift;
+    }
+    esz[s] = e;
+    const u32 sz = e & 0xFFFFu, iz = e >> kEgIncastShift;
+    n += (u32)(sz != 0) | ((u32)(iz != 0) << 16);
+    b += (u64)sz | ((u64)iz << 32);
+  }
 #pragma unroll
-      for (u32 q = 0; q < 3; ++q)
-        if (j + 8 <= len) {
-          sweep_put8(d + j, (w[q] >> 16) | (w[q + 1] << 48));
-          j += 8;
-        }
-      for (; j < len; ++j) d[j] = (u8)(w[(j + 2) >> 3] >> (((j + 2) & 7) * 8));
-    } else {
-      const u64 oa = r.name0 >> 32;
-      if (oa + len > arena_used) {
-        ctr[kSwErr] = 1;
-        continue;
+  for (int d = 32; d >= 1; d >>= 1) {
+    n += __shfl_xor(n, d);
+    b += __shfl_xor(b, d);
+  }
+  __shared__ u32 wn[kBlock / 64];
+  __shared__ u64 wb[kBlock / 64];
+  if (__lane_id() == 0) { wn[threadIdx.x >> 6] = n; wb[threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u32 tn = 0;
+    u64 tb = 0;
+    for (u32 i = 0; i < kBlock / 64; ++i) { tn += wn[i]; tb += wb[i]; }
+    tile_cnt[blockIdx.x] = tn >> 16;
+    tile_bytes[blockIdx.x] = tb >> 32;
+    tile_cnt[ntiles + blockIdx.x] = tn & 0xFFFFu;
+    tile_bytes[ntiles + blockIdx.x] = tb & 0xFFFFFFFFull;
+  }
+}
+
+__global__ __launch_bounds__(kSweepBlock) void k_egress_scan(u32* __restrict__ tile_cnt,
+                                                             u64* __restrict__ tile_bytes,
+                                                             u32 ntiles, u32* ctr) {
+  // (k_sweep_scan's loop over the 2 * ntiles entries; that kernel keeps its own copy)
+  __shared__ u32 wn[kSweepBlock / 64];
+  __shared__ u64 wb[kSweepBlock / 64];
+  const u32 wv = threadIdx.x >> 6, nt = 2 * ntiles;
+  u64 carry_n = 0, carry_b = 0;
+  for (u32 base = 0; base < nt; base += kSweepBlock) {
+    const u32 i = base + threadIdx.x;
+    const u32 c = i < nt ? tile_cnt[i] : 0u;
+    const u64 b = i < nt ? tile_bytes[i] : 0ull;
+    const u32 sc = wave_incl_scan(c);
+    const u64 sb = wave_incl_scan64(b);
+    if (__lane_id() == 63) { wn[wv] = sc; wb[wv] = sb; }
+    __syncthreads();
+    u64 pn = 0, pb = 0, tn = 0, tb = 0;
+    for (u32 w = 0; w < kSweepBlock / 64; ++w) {
+      if (w < wv) { pn += wn[w]; pb += wb[w]; }
+      tn += wn[w];
+      tb += wb[w];
+    }
+    if (i < nt) {
+      tile_cnt[i] = (u32)(carry_n + pn + sc - c);   // (at most 2^31 datagrams)
+      tile_bytes[i] = carry_b + pb + sb - b;
+    }
+    carry_n += tn;
+    carry_b += tb;
+    __syncthreads();   // (the totals are read before the next chunk overwrites them)
+  }
+  if (threadIdx.x == 0) {
+    // (the first state tile's base is the requests' total; the loop ended on a barrier)
+    ctr[kCtrEgIncast] = tile_cnt[ntiles];
+    ctr[kCtrEgN] = (u32)carry_n;
+    ctr[kCtrEgErr] = 0;
+    *reinterpret_cast<u64*>(ctr + kCtrEgIncastBytes) = tile_bytes[ntiles];
+    *reinterpret_cast<u64*>(ctr + kCtrEgBytes) = carry_b;
+  }
+}
+
+// One workgroup per tile, eight steps of 512 segments, two packed scans a step
+// (k_sweep_write's, one per section).  The caps were checked against the
+// batch's worst case before it was applied, so nothing is ever cut; a
+// datagram that would still end past them is skipped and flagged.
+__global__ __launch_bounds__(kSweepBlock) void k_egress_write(
+    const Rec* __restrict__ recs, const u8* __restrict__ arena, u64 arena_used,
+    const u32* __restrict__ uslot, const u32* __restrict__ esz, u32 nseg, u32 ntiles,
+    const u32* __restrict__ tile_cnt, const u64* __restrict__ tile_bytes, u32 max_msgs, u64 budget,
+    u8* __restrict__ out, u64* __restrict__ offs, u32* ctr) {
+  __shared__ u32 wtot[2][2][kSweepBlock / 64];
+  u64 rank_i = tile_cnt[blockIdx.x], byte_i = tile_bytes[blockIdx.x];
+  u64 rank_s = tile_cnt[ntiles + blockIdx.x], byte_s = tile_bytes[ntiles + blockIdx.x];
+  if (blockIdx.x == 0 && threadIdx.x == 0) offs[0] = 0;
+  const u32 wv = threadIdx.x >> 6;
+  auto put = [&](u64 rank, u64 start, u32 sz, const Rec& r, bool state) {
+    const u64 end = start + sz;
+    if (rank >= max_msgs || end > budget) {
+      ctr[kCtrEgErr] = 1;
+      return;
+    }
+    offs[rank + 1] = end;
+    const u64 a = state ? dec_f64(r.added) : 0ull, t = state ? dec_f64(r.taken) : 0ull;
+    const u64 e = state ? (u64)r.elapsed : 0ull;
+    put_datagram(out + start, a, t, e, r, sz - PHIP_BUCKET_FIXED_SIZE, arena, arena_used,
+                 &ctr[kCtrEgErr]);
+  };
+  for (u32 k = 0; k < kSweepTile / kSweepBlock; ++k) {
+    const u64 s = (u64)blockIdx.x * kSweepTile + (u64)k * kSweepBlock + threadIdx.x;
+    const u32 e = s < nseg ? esz[s] : 0u;
+    const u32 sz = e & 0xFFFFu, iz = e >> kEgIncastShift;
+    const u32 vs = sz ? (1u << 19) | sz : 0u, vi = iz ? (1u << 19) | iz : 0u;
+    const u32 ss = wave_incl_scan(vs), si = wave_incl_scan(vi);
+    if (__lane_id() == 63) { wtot[k & 1][0][wv] = ss; wtot[k & 1][1][wv] = si; }
+    __syncthreads();   // (no thread leaves the loop early: every step has its barrier)
+    u32 pre_s = 0, tot_s = 0, pre_i = 0, tot_i = 0;
+#pragma unroll
+    for (u32 w = 0; w < kSweepBlock / 64; ++w) {
+      const u32 x = wtot[k & 1][0][w], y = wtot[k & 1][1][w];
+      if (w < wv) { pre_s += x; pre_i += y; }
+      tot_s += x;
+      tot_i += y;
+    }
+    const u32 ex_s = pre_s + ss - vs, ex_i = pre_i + si - vi;
+    const u64 rs = rank_s + (ex_s >> 19), bs = byte_s + (ex_s & 0x7FFFFu);
+    const u64 ri = rank_i + (ex_i >> 19), bi = byte_i + (ex_i & 0x7FFFFu);
+    rank_s += tot_s >> 19;
+    byte_s += tot_s & 0x7FFFFu;
+    rank_i += tot_i >> 19;
+    byte_i += tot_i & 0x7FFFFu;
+    if (!e) continue;
+    const Rec r = load_rec(&recs[uslot[s]]);
+    if (iz) put(ri, bi, iz, r, false);
+    if (sz) put(rs, bs, sz, r, true);
+  }
+}
+
+// The small path's egress, the tail of k_small_mixed<true>: one workgroup of
+// kSmallMax threads, thread i standing at position i of the batch's (slot, seq)
+// order in sorted[] (skey[o] >> 32: op o's slot; sval[o]: its sort value).
+// The head of each bucket's run computes the two sizes as k_egress_count does
+// (it walks the run's kinds until one asks for a datagram), a workgroup scan
+// of the packed (qualifies << 19 | bytes) values places both sections -- a
+// position order is a slot order -- and the heads write the datagrams.
+__device__ void small_egress(const SmallEgress<true>& eg, u32 n, const u32* sorted, const u64* skey,
+                             const u32* sval, const Table& T, u64 arena_used, const u8* status) {
+  __shared__ u32 wtot[2][kSmallMax / 64];
+  const u32 i = threadIdx.x, wv = i >> 6;
+  if (i == 0) eg.hdr->err = 0;
+  __threadfence();
+  __syncthreads();   // every fold has stored its record and its statuses
+  u32 sz = 0, iz = 0;
+  Rec r{};
+  if (i < n) {
+    const u32 o0 = sorted[i];
+    const u32 sl = (u32)(skey[o0] >> 32);
+    if (i == 0 || (u32)(skey[sorted[i - 1]] >> 32) != sl) {
+      bool wants = egress_kind(sval[o0]);
+      for (u32 j = i + 1; j < n && !wants; ++j) {
+        const u32 o = sorted[j];
+        if ((u32)(skey[o] >> 32) != sl) break;
+        wants = egress_kind(sval[o]);
       }
-      u32 j = 0;
-      for (; j + 8 <= len; j += 8) {
-        u64 x;
-        __builtin_memcpy(&x, arena + oa + j, 8);
-        sweep_put8(d + j, x);
+      const bool ic = (sval[o0] >> kOpIdxBits) == PHIP_OP_TAKE &&
+                      (__hip_atomic_load(status + o0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &
+                       PHIP_ST_CREATED) != 0;
+      if (wants || ic) {
+        r = load_rec_co(&T.recs[sl]);
+        if (wants) sz = sweep_size(r, 0, 0);
+        const u32 len = (u32)(r.name0 & 0xFFu);
+        if (ic && len <= PHIP_MAX_NAME_LEN) iz = PHIP_BUCKET_FIXED_SIZE + len;
       }
-      for (; j < len; ++j) d[j] = arena[oa + j];
     }
   }
+  const u32 vs = sz ? (1u << 19) | sz : 0u, vi = iz ? (1u << 19) | iz : 0u;
+  const u32 ss = wave_incl_scan(vs), si = wave_incl_scan(vi);
+  if (__lane_id() == 63) { wtot[0][wv] = ss; wtot[1][wv] = si; }
+  __syncthreads();
+  u32 pre_s = 0, tot_s = 0, pre_i = 0, tot_i = 0;
+#pragma unroll
+  for (u32 w = 0; w < kSmallMax / 64; ++w) {
+    const u32 x = wtot[0][w], y = wtot[1][w];
+    if (w < wv) { pre_s += x; pre_i += y; }
+    tot_s += x;
+    tot_i += y;
+  }
+  // the states stand behind every request
+  const u32 ex_s = pre_s + ss - vs, ex_i = pre_i + si - vi;
+  const u32 n_i = tot_i >> 19, b_i = tot_i & 0x7FFFFu;
+  if (i == 0) {
+    eg.offs[0] = 0;
+    eg.hdr->n_incast = n_i;
+    eg.hdr->n = n_i + (tot_s >> 19);
+    eg.hdr->bytes = (u64)b_i + (tot_s & 0x7FFFFu);
+  }
+  auto put = [&](u32 rank, u32 start, u32 bytes, bool state) {
+    const u32 end = start + bytes;
+    if (rank >= eg.max_msgs || end > eg.budget) {
+      eg.hdr->err = 1;
+      return;
+    }
+    eg.offs[rank + 1] = end;
+    const u64 a = state ? dec_f64(r.added) : 0ull, t = state ? dec_f64(r.taken) : 0ull;
+    const u64 e = state ? (u64)r.elapsed : 0ull;
+    put_datagram(eg.out + start, a, t, e, r, bytes - PHIP_BUCKET_FIXED_SIZE, T.arena, arena_used,
+                 &eg.hdr->err);
+  };
+  if (iz) put(ex_i >> 19, ex_i & 0x7FFFFu, iz, false);
+  if (sz) put(n_i + (ex_s >> 19), b_i + (ex_s & 0x7FFFFu), sz, true);
 }
 
 // ------------------------------------------------------ table digest -----

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
 from dataclasses import dataclass
 from typing import Iterable, Sequence
 
@@ -588,9 +589,22 @@ class GPURepo:
         self._check(self.L.phip_upsert_soa(self.h, C.byref(m), int(now), C.byref(res), 0))
         return dict(status=st[:n])
 
+    def egress_caps(self, n: int, name_bytes: int, device: bool = False):
+        """phip_egress_caps: (max_msgs, out_cap) a batch of n ops and name_bytes
+        of names needs for its coalesced egress."""
+        m, c = C.c_uint32(), C.c_uint64()
+        self._check(self.L.phip_egress_caps(n, int(name_bytes), DEVICE_PTRS if device else 0,
+                                            C.byref(m), C.byref(c)))
+        return m.value, c.value
+
     def apply_mixed(self, kind, names, now, freq=None, per=None, count=None, added=None,
-                    taken=None, elapsed=None):
-        """Ordered TAKE/RECEIVE/UPSERT stream (api.go:67-74, repo.go:78-90, :215-235)."""
+                    taken=None, elapsed=None, egress=False, want_status=True):
+        """Ordered TAKE/RECEIVE/UPSERT stream (api.go:67-74, repo.go:78-90, :215-235).
+        egress=True: phip_apply_mixed_egress; the dict gains egress = dict(data,
+        offs, n, n_incast): the batch's incast requests, then one state
+        datagram per bucket its TAKE / UPSERT ops named (data uint8, datagram
+        i = data[offs[i]:offs[i+1]]).  want_status=False (egress only) passes no
+        status column."""
         n = len(names)
         blob, offs = names_blob(names)
         arrs = dict(kind=_np(kind, np.uint8), now=_np(now, np.int64), freq=_np(freq, np.int64),
@@ -601,8 +615,19 @@ class GPURepo:
                        _ptr(arrs["now"]), _ptr(arrs["freq"]), _ptr(arrs["per"]), _ptr(arrs["count"]),
                        _ptr(arrs["added"]), _ptr(arrs["taken"]), _ptr(arrs["elapsed"]))
         res, st, rem, have, reply = self._results(n, want_remaining=True, want_reply=True)
-        self._check(self.L.phip_apply_mixed(self.h, C.byref(ops), C.byref(res), 0))
-        return dict(status=st[:n], remaining=rem[:n], have=have[:n], reply=reply[:n])
+        if not egress:
+            self._check(self.L.phip_apply_mixed(self.h, C.byref(ops), C.byref(res), 0))
+            return dict(status=st[:n], remaining=rem[:n], have=have[:n], reply=reply[:n])
+        if not want_status:
+            res.status = None
+        max_msgs, cap = self.egress_caps(n, int(offs[n]))
+        data = np.zeros(max(cap, 1), np.uint8)
+        eoffs = np.zeros(max_msgs + 1, np.uint64)
+        eg = _lib.phip_egress(data.ctypes.data, cap, eoffs.ctypes.data, max_msgs, 0, 0, 0, 0)
+        self._check(self.L.phip_apply_mixed_egress(self.h, C.byref(ops), C.byref(res), C.byref(eg), 0))
+        return dict(status=st[:n], remaining=rem[:n], have=have[:n], reply=reply[:n],
+                    egress=dict(data=data[:eg.bytes], offs=eoffs[:eg.n + 1], n=int(eg.n),
+                                n_incast=int(eg.n_incast)))
 
     def apply_mixed_device(self, n, kind, names, name_offs, now, freq=None, per=None, count=None,
                            added=None, taken=None, elapsed=None, status=None, remaining=None,
@@ -614,6 +639,25 @@ class GPURepo:
                        _ptr(per), _ptr(count), _ptr(added), _ptr(taken), _ptr(elapsed))
         res = phip_results(_ptr(status), _ptr(remaining), _ptr(have), None)
         self._check(self.L.phip_apply_mixed(self.h, C.byref(ops), C.byref(res), DEVICE_PTRS))
+
+    def apply_mixed_egress_device(self, n, kind, names, name_offs, now, out, offs, max_msgs,
+                                  freq=None, per=None, count=None, added=None, taken=None,
+                                  elapsed=None, status=None, remaining=None, have=None,
+                                  names_len=None, out_cap=None):
+        """phip_apply_mixed_egress with every array a torch CUDA tensor
+        (PHIP_DEVICE_PTRS): out (uint8, 8-byte aligned, egress_caps(...,
+        device=True) bytes) and offs (int64[max_msgs + 1]) receive the
+        datagrams and go unchanged into a peer's receive_datagrams_device.
+        Returns dict(n, n_incast, bytes)."""
+        ops = phip_ops(n, _names_len(names, names_len), _ptr(kind), _ptr(names), _ptr(name_offs),
+                       _ptr(now), _ptr(freq),
+                       _ptr(per), _ptr(count), _ptr(added), _ptr(taken), _ptr(elapsed))
+        res = phip_results(_ptr(status), _ptr(remaining), _ptr(have), None)
+        cap = int(out.numel()) if out_cap is None else int(out_cap)
+        eg = _lib.phip_egress(_ptr(out), cap, _ptr(offs), int(max_msgs), 0, 0, 0, 0)
+        self._check(self.L.phip_apply_mixed_egress(self.h, C.byref(ops), C.byref(res), C.byref(eg),
+                                                   DEVICE_PTRS))
+        return dict(n=int(eg.n), n_incast=int(eg.n_incast), bytes=int(eg.bytes))
 
     def route_pack_ops_device(self, n, world, kind, names, name_offs, now, freq=None, per=None,
                               count=None, added=None, taken=None, elapsed=None, names_len=None):
@@ -863,17 +907,74 @@ class TakeBatcher:
     include/patrolhip.h): the drop-in form of the POST /take handler
     (api.go:51-86) for one-request-per-thread callers.  take()/api_take()
     block until the request's batch ran; they release the GIL (ctypes), so
-    many Python threads can wait at once."""
+    many Python threads can wait at once.  egress_slots (None: no egress, 0:
+    the library's default ring): phip_batcher_open_egress, each batch's
+    coalesced replication traffic comes out of egress_next() and somebody has
+    to drain it."""
 
-    def __init__(self, repo: "GPURepo", window_us: int = 20, max_batch: int = 0):
+    def __init__(self, repo: "GPURepo", window_us: int = 20, max_batch: int = 0,
+                 egress_slots: int | None = None):
         self.repo, self.L = repo, repo.L
         b = C.c_void_p()
         cfg = _lib.phip_batcher_config(window_us, max_batch)
-        repo._check(self.L.phip_batcher_open(repo.h, C.byref(cfg), C.byref(b)))
+        if egress_slots is None:
+            repo._check(self.L.phip_batcher_open(repo.h, C.byref(cfg), C.byref(b)))
+        else:
+            repo._check(self.L.phip_batcher_open_egress(repo.h, C.byref(cfg), int(egress_slots),
+                                                        C.byref(b)))
         self.b = b
+        # egress_next calls in flight: close() lets them leave before the
+        # batcher is freed under them
+        self._idle = threading.Condition()
+        self._draining = 0
+        self._closing = False
+
+    def egress_next(self, timeout_ms: int = -1):
+        """phip_batcher_egress_next: the next batch's datagrams, copied out of
+        its slot, as dict(data, offs, n, n_incast, batch, first_seq, requests);
+        None after timeout_ms without one or on a batcher being closed.  The
+        slot stays handed out until egress_done(batch)."""
+        e = _lib.phip_egress_batch()
+        with self._idle:
+            if self._closing or not self.b:
+                return None
+            self._draining += 1
+        try:
+            # (waited in slices, so that a close() from another thread is seen)
+            left, rc = int(timeout_ms), 0
+            while rc == 0 and not self._closing:
+                step = 20 if left < 0 else min(left, 20)
+                rc = self.L.phip_batcher_egress_next(self.b, step, C.byref(e))
+                if left >= 0:
+                    left -= step
+                    if left <= 0:
+                        break
+        finally:
+            with self._idle:
+                self._draining -= 1
+                self._idle.notify_all()
+        if rc < 0:
+            raise PatrolHipError(rc, "phip_batcher_egress_next failed")
+        if rc == 0:
+            return None
+        offs = np.ctypeslib.as_array(C.cast(e.offs, C.POINTER(C.c_uint64)), (e.n + 1,)).copy()
+        nb = int(offs[e.n])
+        data = (np.ctypeslib.as_array(C.cast(e.bytes, C.POINTER(C.c_uint8)), (nb,)).copy()
+                if nb else np.zeros(0, np.uint8))
+        return dict(data=data, offs=offs, n=int(e.n), n_incast=int(e.n_incast), batch=int(e.batch),
+                    first_seq=int(e.first_seq), requests=int(e.requests))
+
+    def egress_done(self, batch: int):
+        rc = self.L.phip_batcher_egress_done(self.b, int(batch))
+        if rc != 0:
+            raise PatrolHipError(rc, "phip_batcher_egress_done failed")
 
     def close(self):
         if getattr(self, "b", None):
+            with self._idle:
+                self._closing = True
+                while self._draining:
+                    self._idle.wait()
             self.L.phip_batcher_close(self.b)
             self.b = None
 
@@ -933,10 +1034,12 @@ class TakeBatcher:
         return code, body.raw[:bl.value].decode(), self._reply(r)
 
     def stats(self):
-        """dict(batches, requests, max_batch, gpu_ns, errors)."""
-        out = (C.c_uint64 * 5)()
-        k = self.L.phip_batcher_stats(self.b, out, 5)
-        keys = ("batches", "requests", "max_batch", "gpu_ns", "errors")
+        """dict(batches, requests, max_batch, gpu_ns, errors, egress_batches,
+        egress_datagrams, egress_wait_ns)."""
+        out = (C.c_uint64 * 8)()
+        k = self.L.phip_batcher_stats(self.b, out, 8)
+        keys = ("batches", "requests", "max_batch", "gpu_ns", "errors", "egress_batches",
+                "egress_datagrams", "egress_wait_ns")
         return {keys[i]: int(out[i]) for i in range(k)}
 
 

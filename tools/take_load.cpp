@@ -5,7 +5,7 @@
 // line: takes/s over the whole run, p50/p99/p999 request latency, batch
 // statistics.  Links libpatrolhip through its C ABI only.
 //
-//   take_load [threads] [per_thread] [window_us] [buckets] [peers] [new_frac]
+//   take_load [threads] [per_thread] [window_us] [buckets] [peers] [new_frac] [coalesce]
 //
 // peers = 0: the bare batched Take (phip_batcher_take).
 // peers > 0: the whole drop-in handler (INTEGRATION.md takeBucket): the
@@ -17,6 +17,12 @@
 //   (UpsertBucket -> broadcast, repo.go:123-158), one sendto per peer per
 //   take (a UDP sink on 127.0.0.1 stands in for the peers).  new_frac of the
 //   requests name buckets that do not exist yet.
+// coalesce = 1 (with peers > 0): the batcher is opened with egress
+//   (phip_batcher_open_egress), the handler threads send nothing, and one
+//   replicator thread drains phip_batcher_egress_next and sends each batch --
+//   one datagram per bucket the batch touched, its incast requests in front
+//   -- to every peer with one phip_udp_send_batch per peer.
+// datagrams_sent counts what was sent in either mode.
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <sys/socket.h>
@@ -43,6 +49,7 @@ int main(int argc, char** argv) {
   const uint32_t K = argc > 4 ? (uint32_t)atoi(argv[4]) : 100000;
   const int peers = argc > 5 ? atoi(argv[5]) : 0;
   const double new_frac = argc > 6 ? atof(argv[6]) : 0.01;
+  const bool coalesce = argc > 7 && atoi(argv[7]) != 0 && peers > 0;
   phip_config cfg{};
   cfg.device = 0;
   cfg.log2_slots = 20;
@@ -63,15 +70,19 @@ int main(int argc, char** argv) {
     }
     if (phip_seed(h, (const uint8_t*)blob.data(), offs.data(), K, st.data(), 0)) return 1;
   }
-  phip_batcher_config bc{window, 0};
+  // (coalesce: a batch holds at most one request per client thread; the bound
+  // sizes the egress ring's pinned slots)
+  phip_batcher_config bc{window, coalesce ? (uint32_t)std::max(T, 1024) : 0u};
   phip_batcher* b = nullptr;
-  if (phip_batcher_open(h, &bc, &b)) return 1;
+  if (coalesce ? phip_batcher_open_egress(h, &bc, 0, &b) : phip_batcher_open(h, &bc, &b)) return 1;
   // the peers' stand-in: one UDP sink on the loopback, drained by a thread
   int sink = -1, tx = -1;
   sockaddr_in sink_addr{};
   std::atomic<bool> stop{false};
   std::atomic<uint64_t> got_dgrams{0};
-  std::thread drain;
+  std::thread drain, replicator;
+  std::atomic<bool> clients_done{false};
+  std::atomic<uint64_t> coalesced_sent{0}, egress_batches{0};
   if (peers > 0) {
     sink = socket(AF_INET, SOCK_DGRAM, 0);
     tx = socket(AF_INET, SOCK_DGRAM, 0);
@@ -92,6 +103,28 @@ int main(int argc, char** argv) {
       uint8_t buf[512];
       while (!stop.load()) {
         if (recv(sink, buf, sizeof buf, 0) > 0) got_dgrams.fetch_add(1);
+      }
+    });
+  }
+  if (coalesce) {
+    replicator = std::thread([&] {
+      for (;;) {
+        phip_egress_batch e;
+        const int got = phip_batcher_egress_next(b, 20, &e);
+        if (got < 0) { fprintf(stderr, "egress_next failed\n"); std::exit(1); }
+        if (got == 0) {
+          // (a take returns only once its batch's egress is queued: nothing
+          // arrives after the clients are done and the queue ran empty)
+          if (clients_done.load()) return;
+          continue;
+        }
+        for (int p = 0; p < peers; ++p) {
+          uint32_t sent_now = 0;
+          phip_udp_send_batch(tx, e.bytes, e.offs, e.n, (const uint8_t*)&sink_addr, 0, &sent_now);
+          coalesced_sent.fetch_add(sent_now);
+        }
+        egress_batches.fetch_add(1);
+        phip_batcher_egress_done(b, e.batch);
       }
     });
   }
@@ -139,6 +172,10 @@ int main(int argc, char** argv) {
           std::exit(1);
         }
         oks[tid] += code == 200;
+        created[tid] += rep.created && coalesce;
+        if (coalesce) {
+          // the replicator thread sends the batch's coalesced egress
+        } else {
         if (rep.created) {   // ReplicatedRepo.GetBucket's incast (repo.go:96-106)
           ++created[tid];
           std::memset(incast, 0, 24);
@@ -150,6 +187,7 @@ int main(int argc, char** argv) {
         for (int p = 0; p < peers; ++p)   // UpsertBucket's broadcast (repo.go:129-158)
           sent[tid] += sendto(tx, rep.datagram, rep.datagram_len, 0, (sockaddr*)&sink_addr,
                               sizeof sink_addr) > 0;
+        }
       }
       lat[tid].push_back(std::chrono::duration<double, std::micro>(
                              std::chrono::steady_clock::now() - a).count());
@@ -160,6 +198,10 @@ int main(int argc, char** argv) {
   for (int t = 0; t < T; ++t) th.emplace_back(client, t);
   for (auto& x : th) x.join();
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
+  if (coalesce) {
+    clients_done.store(true);
+    replicator.join();
+  }
   if (peers > 0) {
     std::this_thread::sleep_for(std::chrono::milliseconds(200));
     stop.store(true);
@@ -175,16 +217,19 @@ int main(int argc, char** argv) {
   phip_batcher_stats(b, s, 5);
   uint64_t okn = 0, cr = 0, sn = 0;
   for (int t = 0; t < T; ++t) { okn += oks[t]; cr += created[t]; sn += sent[t]; }
+  sn += coalesced_sent.load();
   printf("{\"mode\": \"%s\", \"threads\": %d, \"requests\": %zu, \"window_us\": %u, \"buckets\": %u, "
          "\"peers\": %d, \"takes_per_s\": %.1f, \"p50_us\": %.1f, \"p99_us\": %.1f, \"p999_us\": %.1f, "
          "\"batches\": %llu, \"mean_batch\": %.1f, \"max_batch\": %llu, "
          "\"gpu_call_us_per_batch\": %.1f, \"ok_fraction\": %.3f, \"created\": %llu, "
-         "\"datagrams_sent\": %llu, \"datagrams_received\": %llu}\n",
+         "\"datagrams_sent\": %llu, \"datagrams_received\": %llu, \"coalesce\": %d, "
+         "\"egress_batches\": %llu}\n",
          peers ? "handler" : "take", T, all.size(), window, K, peers, all.size() / wall, pct(0.5),
          pct(0.99), pct(0.999), (unsigned long long)s[0], (double)s[1] / std::max<uint64_t>(1, s[0]),
          (unsigned long long)s[2], s[3] / 1e3 / std::max<uint64_t>(1, s[0]),
          (double)okn / all.size(), (unsigned long long)cr, (unsigned long long)sn,
-         (unsigned long long)got_dgrams.load());
+         (unsigned long long)got_dgrams.load(), (int)coalesce,
+         (unsigned long long)egress_batches.load());
   phip_batcher_close(b);
   phip_close(h);
   return 0;
