@@ -142,6 +142,10 @@ enum {
                                    a batch that turns out to hold an incast, a -0.0 field or
                                    a malformed name entry is undone and run again classified,
                                    with the same results.  For A/B measurements and tests. */
+#define PHIP_CFG_TRACK_CHANGES 0x20u /* the handle keeps a change set: the buckets its TAKE /
+                                   UPSERT ops touched, for phip_export_changed ("Change set"
+                                   below).  Two bits per slot; without the flag a handle
+                                   launches exactly what it launched before the flag existed */
 
 typedef struct phip_config {
   int32_t device;        /* HIP device ordinal                                          */
@@ -641,6 +645,86 @@ int phip_egress_caps(uint32_t n_ops, uint64_t name_bytes, uint32_t flags, uint32
                      uint64_t* out_cap);
 int phip_apply_mixed_egress(phip_handle* h, const phip_ops* ops, const phip_results* res,
                             phip_egress* eg, uint32_t flags);
+
+/* Change set: the buckets this handle's own takes touched since they were
+ * last exported, for a replicator that runs on its own clock.  A handle opened
+ * with PHIP_CFG_TRACK_CHANGES remembers them; phip_export_changed writes their
+ * replication traffic in the layout of "Coalesced egress" above and forgets
+ * what it wrote:
+ *     every window:  loop phip_export_changed -> phip_udp_send_batch per peer
+ *                    (or a peer handle's phip_receive_datagrams) until st->done
+ * This is "Coalesced egress" with the window chosen by the caller instead of
+ * by the batch: a take pays a mark, not a datagram, and a bucket taken from in
+ * a hundred batches of one window leaves once.
+ *
+ * What marks.  Two marks per bucket, the two rules of "Coalesced egress" made
+ * persistent:
+ *  - state pending: a PHIP_OP_TAKE or PHIP_OP_UPSERT op named the bucket (every
+ *    take ends in UpsertBucket's broadcast, granted or denied, api.go:67-74,
+ *    repo.go:123-158);
+ *  - request pending: a batch created the bucket and its first op on it is a
+ *    TAKE, the op that reports PHIP_ST_CREATED (GetBucket's incast request,
+ *    repo.go:96-106).
+ * They are set by every call that runs ordered ops: phip_apply_mixed, phip_take,
+ * phip_api_take, the batcher, and the owner's apply inside
+ * phip_group_apply_mixed (every owner marks its own table:
+ * phip_group_handle(g, i) and this call are the owners' egress).  They are set
+ * behind the batch's last op, once the batch stands.  Nothing is set by
+ * PHIP_OP_RECEIVE ops and the phip_receive_* calls (received merges are never
+ * rebroadcast, repo.go:78-79), by phip_upsert_soa and phip_seed
+ * (LocalRepo.UpsertBucket broadcasts nothing, repo.go:215-235), by
+ * phip_apply_mixed_egress (its datagrams left with the call), or by a batch
+ * that is refused (PHIP_ERR_FULL / PHIP_ERR_ARENA before any claim, a
+ * malformed offset column).
+ *
+ * Output.  Datagram i is out[offs[i] .. offs[i+1]), offs[0] = 0, bytes =
+ * offs[n].  The requests come first, datagrams [0, n_incast): 24 zero bytes,
+ * the length byte, the name.  The states follow, [n_incast, n): the
+ * byte-identical MarshalBinary (bucket.go:51-68) of the state the table holds
+ * at the export.  Each section is in table slot order.  Left out, as in the
+ * egress and the sweep: a state that is zero and a name over PHIP_MAX_NAME_LEN;
+ * their marks are cleared all the same.  The coalescing limit is the one
+ * stated under "Coalesced egress": the datagram is the final state, the join
+ * of the intermediate states is not computed.
+ *
+ * Bounds and progress.  A call writes at most max_msgs datagrams and out_cap
+ * bytes, cut at a record.  max_msgs == 0 or out_cap < PHIP_BUCKET_PACKET_SIZE
+ * is PHIP_ERR_INVALID, so every valid call with something pending makes
+ * progress.  A mark is cleared exactly when its datagram was written or was
+ * left out by the rule above; what was cut stays pending for the next call.
+ * The state section starts only in a call whose request section left no
+ * request pending, so no bucket's state ever leaves before its request, across
+ * calls as within one.  st->pending counts the marks still set after the call
+ * (requests and states), st->done = (pending == 0).  An argument error reads
+ * and clears nothing.
+ *
+ * Count mode.  PHIP_SWEEP_COUNT with out == NULL (offs, out_cap and max_msgs
+ * are ignored): st->n, st->n_incast and st->bytes of a full drain, st->pending
+ * the marks set, and nothing is cleared.
+ *
+ * Layout changes.  The marks belong to buckets, not slots: table growth and
+ * phip_evict_idle's move carry a surviving bucket's marks along, an evicted
+ * bucket's marks go with it (as after a node restart), and phip_restore clears
+ * the set (a snapshot does not hold it).
+ *
+ * Pointers and flags.  Host pointers, or PHIP_DEVICE_PTRS under
+ * phip_export_sweep's rules: `out` 8-byte aligned, out_cap a multiple of 8 and
+ * at least PHIP_BUCKET_PACKET_SIZE + 8, the byte budget out_cap - 8; out / offs
+ * then go unchanged into phip_receive_datagrams(..., PHIP_DEVICE_PTRS).  st is
+ * host memory.  Unknown flag bits, and a handle opened without
+ * PHIP_CFG_TRACK_CHANGES, are PHIP_ERR_INVALID.  The call is serialised with
+ * the handle's other calls; a batch queued with PHIP_RECV_ASYNC is finished
+ * first, and its error is this call's. */
+typedef struct phip_changes_stats {
+  uint64_t n;         /* datagrams written (count mode: what a full drain would write) */
+  uint64_t bytes;     /* = offs[n]                                                      */
+  uint32_t n_incast;  /* the requests, datagrams [0, n_incast)                          */
+  uint32_t done;      /* 1: nothing is pending after this call                          */
+  uint64_t pending;   /* marks still set after this call (requests + states)            */
+} phip_changes_stats;
+int phip_export_changed(phip_handle* h, uint8_t* out, uint64_t out_cap,
+                        uint64_t* offs /* max_msgs+1 */, uint32_t max_msgs,
+                        phip_changes_stats* st, uint32_t flags);
 /* All-TAKE convenience form of phip_apply_mixed. */
 int phip_take(phip_handle* h, const uint8_t* names, const uint32_t* name_offs, uint32_t n,
               const int64_t* now, const int64_t* freq, const int64_t* per, const uint64_t* count,

@@ -36,6 +36,7 @@ EXPORTS = [
     "phip_table_digest", "phip_digest_diff", "phip_digest_fold", "phip_export_sweep_parts",
     "phip_egress_caps", "phip_apply_mixed_egress", "phip_batcher_open_egress",
     "phip_batcher_egress_next", "phip_batcher_egress_done",
+    "phip_export_changed",
 ]
 
 PHIP_OK = 0
@@ -52,6 +53,7 @@ CFG_NO_SMALL = 0x2
 CFG_FIXED_SEED = 0x4
 CFG_ISOLATE = 0x8
 CFG_CLASSIFY_FIRST = 0x10
+CFG_TRACK_CHANGES = 0x20
 ROUTE_COMBINE = 0x2
 GROUP_RCCL_SELF = 0x4
 GROUP_SMALL_CHUNKS = 0x8
@@ -127,6 +129,11 @@ class phip_egress(C.Structure):
     _fields_ = [("out", C.c_void_p), ("out_cap", C.c_uint64), ("offs", C.c_void_p),
                 ("max_msgs", C.c_uint32), ("n_incast", C.c_uint32), ("n", C.c_uint32),
                 ("reserved", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+class phip_changes_stats(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("bytes", C.c_uint64), ("n_incast", C.c_uint32),
+                ("done", C.c_uint32), ("pending", C.c_uint64)]
 
 
 class phip_egress_batch(C.Structure):
@@ -282,5 +289,7 @@ def load(path: str = LIB_PATH):
                                                C.POINTER(vp)]
         L.phip_batcher_egress_next.argtypes = [vp, C.c_int, C.POINTER(phip_egress_batch)]
         L.phip_batcher_egress_done.argtypes = [vp, u64]
+    if hasattr(L, "phip_export_changed"):
+        L.phip_export_changed.argtypes = [vp, vp, u64, vp, u32, C.POINTER(phip_changes_stats), u32]
     _lib = L
     return L

@@ -183,6 +183,11 @@ struct phip_handle {
   u64 long_need = 0;         // arena bytes the last reserve() counted
   Rec* recs = nullptr;
   u32* aux = nullptr;
+  // PHIP_CFG_TRACK_CHANGES: the change set (phip_kernels.hpp "change set"), two
+  // bit sets of mark_words(cap) words in one allocation, allocated, replaced
+  // and freed with the table; null pointers on a handle that keeps none
+  bool track = false;
+  Marks marks{};
   u8* arena = nullptr;
   u64 arena_cap = 0;
   u64 arena_open = 0;        // arena bytes at phip_open: a compacted arena is no smaller
@@ -391,12 +396,31 @@ int copy_back(phip_handle* h, T* user, const T* dev_buf, size_t count, bool dev)
 // ----------------------------------------------------------- inserts -----
 inline u64 load_limit(u64 cap, u32 pct) { return cap * pct / 100; }
 
+// The change set of a table of `cap` slots: words per set, and a cleared pair
+// of sets (one allocation, freed through Marks::state) enqueued on the stream.
+inline u64 mark_words(u64 cap) { return std::max<u64>(cap / 32, 1); }
+int alloc_marks(phip_handle* h, u64 cap, Marks* out) {
+  const u64 w = mark_words(cap);
+  u32* p = nullptr;
+  if (hipMalloc(&p, 2 * w * sizeof(u32)) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(h, PHIP_ERR_FULL, "change set of %llu slots: device memory", (unsigned long long)cap);
+  }
+  if (hipMemsetAsync(p, 0, 2 * w * sizeof(u32), h->stream) != hipSuccess) {
+    (void)hipFree(p);
+    return set_err(h, PHIP_ERR_HIP, "change set: clearing failed");
+  }
+  *out = Marks{p, p + w};
+  return PHIP_OK;
+}
+
 // Rehash the table into 2^newL slots (k_rehash).  Both tables are resident
 // while records move; the old one is freed after.
 int grow_table(phip_handle* h, u32 newL) {
   const u64 ncap = 1ull << newL;
   Rec* nrecs = nullptr;
   u32* naux = nullptr;
+  Marks nmarks{};
   if (hipMalloc(&nrecs, ncap * sizeof(Rec)) != hipSuccess) {
     (void)hipGetLastError();
     return set_err(h, PHIP_ERR_FULL, "table growth to 2^%u slots: device memory", newL);
@@ -411,8 +435,11 @@ int grow_table(phip_handle* h, u32 newL) {
     (void)hipStreamSynchronize(h->stream);
     (void)hipFree(nrecs);
     (void)hipFree(naux);
+    if (nmarks.state) (void)hipFree(nmarks.state);
     return rc;
   };
+  if (h->track)
+    if (int rc = alloc_marks(h, ncap, &nmarks)) return drop_new(rc);
   if (hipMemsetAsync(nrecs, 0, ncap * sizeof(Rec), h->stream) != hipSuccess ||
       hipMemsetAsync(naux, 0, ncap * sizeof(u32), h->stream) != hipSuccess ||
       hipMemsetAsync(h->ctr + kCtrTableFull, 0, sizeof(u32), h->stream) != hipSuccess)
@@ -423,7 +450,8 @@ int grow_table(phip_handle* h, u32 newL) {
   nt.L = newL;
   {
     Launch l(h, "k_rehash");
-    k_rehash<<<grid_for(h->cap), kBlock, 0, h->stream>>>(h->recs, h->aux, h->cap, nt, h->ctr);
+    k_rehash<<<grid_for(h->cap), kBlock, 0, h->stream>>>(h->recs, h->aux, h->cap, nt, h->ctr,
+                                                         h->marks, nmarks);
   }
   if (hipGetLastError() != hipSuccess)
     return drop_new(set_err(h, PHIP_ERR_HIP, "k_rehash launch failed"));
@@ -433,8 +461,10 @@ int grow_table(phip_handle* h, u32 newL) {
     return drop_new(set_err(h, PHIP_ERR_INVALID, "internal: rehash probe wrapped"));
   HIPCHK(h, hipFree(h->recs));
   HIPCHK(h, hipFree(h->aux));
+  if (h->marks.state) HIPCHK(h, hipFree(h->marks.state));
   h->recs = nrecs;
   h->aux = naux;
+  h->marks = nmarks;
   h->L = newL;
   h->cap = ncap;
   h->max_load = load_limit(ncap, h->load_pct);
@@ -1472,12 +1502,45 @@ int egress_launches(phip_handle* h, const EgressOut& eg, u32 nseg, const u32* us
   return PHIP_OK;
 }
 
+// phip_apply_mixed's part of ordered() on a handle that keeps a change set:
+// the batch's marks (phip_kernels.hpp "change set"), with the egress' uniform
+// form.
+struct MarkPlan {
+  bool uniform, wants;
+};
+
+// The marks behind the folds, on the main stream: k_changes_mark, behind
+// k_egress_wants when mixed kinds meet segments above kLongSeg ops.
+int mark_launches(phip_handle* h, const MarkPlan& mp, u32 nseg, const u32* uslot, const u32* sstart,
+                  const u32* scnt, const u32* sidx, const u32* lng, u32 nlong, const u32* huge,
+                  u32 nhuge, const u8* status) {
+  u32* esz = nullptr;
+  if (!mp.uniform && (nlong || nhuge)) {
+    if (int rc = ensure(h, B_EGSZ, nseg, &esz)) return rc;
+    Launch l(h, "k_egress_wants");
+    k_egress_wants<<<(nlong + kBlock / 64 - 1) / (kBlock / 64) + nhuge, kBlock, 0, h->stream>>>(
+        lng, nlong, huge, nhuge, sstart, scnt, sidx, esz);
+  }
+  {
+    Launch l(h, "k_changes_mark");
+    if (mp.uniform)
+      k_changes_mark<true><<<grid_for(nseg), kBlock, 0, h->stream>>>(
+          uslot, sstart, scnt, sidx, nseg, status, mp.wants, esz, h->marks);
+    else
+      k_changes_mark<false><<<grid_for(nseg), kBlock, 0, h->stream>>>(
+          uslot, sstart, scnt, sidx, nseg, status, false, esz, h->marks);
+  }
+  HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
+}
+
 // Apply a mixed op stream in seq order.  The NEW flag of created buckets is
 // consumed (cleared) by the fold itself.  eg: the batch's egress is written
-// behind the folds (ow.status is then required).
+// behind the folds; mp: its marks are set there (ow.status is required by
+// either).
 template <class Src>
 int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow,
-            const EgressOut* eg = nullptr) {
+            const EgressOut* eg = nullptr, const MarkPlan* mp = nullptr) {
   if (n == 0) return PHIP_OK;
   if (n > kMaxOrderedOps)
     return set_err(h, PHIP_ERR_INVALID, "ordered batch of %u ops exceeds 2^30", n);
@@ -1737,6 +1800,9 @@ int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow,
   if (eg)
     return egress_launches(h, *eg, nseg, uslot, sstart, scnt, sidx, lng, nlong, huge, nhuge,
                            ow.status);
+  if (mp)
+    return mark_launches(h, *mp, nseg, uslot, sstart, scnt, sidx, lng, nlong, huge, nhuge,
+                         ow.status);
   return PHIP_OK;
 }
 
@@ -1975,8 +2041,10 @@ inline bool has_reply_state(u8 status, u8 kind) {
 // launch, k_small_mixed<true>, also writes the batch's egress into the staging
 // buffer; it travels back with the results when its worst case is small, and
 // in a second copy of just the bytes written otherwise.
+// track (phip_apply_mixed on a handle that keeps a change set, never with eg):
+// the same launch, k_small_mixed<false, true>, also sets the batch's marks.
 int small_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, bool* done,
-                phip_egress* eg = nullptr) {
+                phip_egress* eg = nullptr, bool track = false) {
   *done = false;
   const u32 n = ops->n;
   if (n > kSmallMax || h->n_buckets + n > h->max_load) return PHIP_OK;
@@ -2045,7 +2113,8 @@ int small_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, bo
   phip_results r{};
   if (res) r = *res;
   OutView ow{};
-  ow.status = (r.status || eg) ? dout + o_st : nullptr;   // (the egress reads who created what)
+  // (the egress and the marks read who created what)
+  ow.status = (r.status || eg || track) ? dout + o_st : nullptr;
   ow.remaining = r.remaining ? (uint64_t*)(dout + o_rem) : nullptr;
   ow.have = r.have ? (uint64_t*)(dout + o_have) : nullptr;
   ow.reply = r.reply ? (phip_state*)(dout + o_reply) : nullptr;
@@ -2056,6 +2125,10 @@ int small_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, bo
           src, ov, n, table(h), h->arena, h->arena_cap, h->arena_cursor, ow, (SmallHdr*)dout,
           SmallEgress<true>{dout + o_egdata, (u64*)(dout + o_egoffs), (SmallEgHdr*)(dout + o_eg),
                             eg_msgs, eg_budget});
+    else if (track)
+      k_small_mixed<false, true><<<1, kSmallMax, 0, h->stream>>>(
+          src, ov, n, table(h), h->arena, h->arena_cap, h->arena_cursor, ow, (SmallHdr*)dout,
+          SmallEgress<false>{}, SmallMarks<true>{h->marks});
     else
       k_small_mixed<false><<<1, kSmallMax, 0, h->stream>>>(src, ov, n, table(h), h->arena,
                                                            h->arena_cap, h->arena_cursor, ow,
@@ -2437,6 +2510,7 @@ int phip_open(const phip_config* cfg, phip_handle** out) {
   h->iso_always = cfg->flags & PHIP_CFG_ISOLATE;
   h->classify_first = cfg->flags & PHIP_CFG_CLASSIFY_FIRST;
   h->small = !(cfg->flags & PHIP_CFG_NO_SMALL);
+  h->track = cfg->flags & PHIP_CFG_TRACK_CHANGES;
   h->arena_cap = h->arena_open = cfg->arena_bytes ? cfg->arena_bytes : (1ull << 20);
   if (cfg->debug_tag_bits && cfg->debug_tag_bits < 64) h->tag_mask = (1ull << cfg->debug_tag_bits) - 1;
   if (cfg->flags & PHIP_CFG_FIXED_SEED) {
@@ -2482,6 +2556,7 @@ int phip_open(const phip_config* cfg, phip_handle** out) {
     return fail(e);
   if ((e = hipMemsetAsync(h->recs, 0, h->cap * sizeof(Rec), h->stream)) != hipSuccess) return fail(e);
   if ((e = hipMemsetAsync(h->aux, 0, h->cap * sizeof(u32), h->stream)) != hipSuccess) return fail(e);
+  if (h->track && alloc_marks(h, h->cap, &h->marks)) return fail(hipErrorOutOfMemory);
   if ((e = hipMemsetAsync(h->arena_cursor, 0, 64, h->stream)) != hipSuccess) return fail(e);
   if ((e = hipMemsetAsync(h->ctr, 0, 3 * kCtrWords * sizeof(u32), h->stream)) != hipSuccess)
     return fail(e);
@@ -2508,6 +2583,7 @@ void phip_close(phip_handle* h) {
   }
   if (h->recs) (void)hipFree(h->recs);
   if (h->aux) (void)hipFree(h->aux);
+  if (h->marks.state) (void)hipFree(h->marks.state);
   if (h->arena) (void)hipFree(h->arena);
   if (h->arena_cursor) (void)hipFree(h->arena_cursor);
   if (h->ctr) (void)hipFree(h->ctr);
@@ -2692,17 +2768,22 @@ int phip_restore(phip_handle* h, const uint8_t* in, uint64_t len) {
     // opened): the handle's table is replaced by one of that size.
     Rec* nrecs = nullptr;
     u32* naux = nullptr;
+    Marks nmarks{};
     if (hipMalloc(&nrecs, scap * sizeof(Rec)) != hipSuccess ||
-        hipMalloc(&naux, scap * sizeof(u32)) != hipSuccess) {
+        hipMalloc(&naux, scap * sizeof(u32)) != hipSuccess ||
+        (h->track && alloc_marks(h, scap, &nmarks))) {
       (void)hipGetLastError();
       if (nrecs) (void)hipFree(nrecs);
+      if (naux) (void)hipFree(naux);
       return set_err(h, PHIP_ERR_FULL, "restore: no device memory for 2^%u slots", hd.log2_slots);
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipFree(h->recs));
     HIPCHK(h, hipFree(h->aux));
+    if (h->marks.state) HIPCHK(h, hipFree(h->marks.state));
     h->recs = nrecs;
     h->aux = naux;
+    h->marks = nmarks;
     h->L = hd.log2_slots;
     h->cap = scap;
     h->max_load = load_limit(scap, h->load_pct);
@@ -2713,6 +2794,9 @@ int phip_restore(phip_handle* h, const uint8_t* in, uint64_t len) {
   if (hd.arena_used)
     HIPCHK(h, hipMemcpyAsync(h->arena, p + h->cap * sizeof(Rec), hd.arena_used, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemsetAsync(h->aux, 0, h->cap * sizeof(u32), h->stream));
+  // (a snapshot holds no change set: the image's buckets start unmarked)
+  if (h->marks.state)
+    HIPCHK(h, hipMemsetAsync(h->marks.state, 0, 2 * mark_words(h->cap) * sizeof(u32), h->stream));
   HIPCHK(h, hipMemcpyAsync(h->arena_cursor, &hd.arena_used, sizeof(u64), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->n_buckets = hd.n_buckets;
@@ -3244,6 +3328,9 @@ static int apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* 
     if (need_state && (!ops->added || !ops->taken || !ops->elapsed)) return PHIP_ERR_INVALID;
   }
   int rc;
+  // the change set: this call's TAKE / UPSERT ops mark their buckets, unless
+  // its datagrams leave with it (eg)
+  const bool track = h->track && !eg;
   EgressOut eo{};
   u64 need_cap = 0;
   if (eg) {
@@ -3268,7 +3355,7 @@ static int apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* 
   }
   if (!dev && h->small) {
     bool done = false;
-    if ((rc = small_mixed(h, ops, res, &done, eg))) {
+    if ((rc = small_mixed(h, ops, res, &done, eg, track))) {
       if (eg) eg->n_incast = eg->n = 0, eg->bytes = 0;
       return after_error(h, rc);
     }
@@ -3289,6 +3376,13 @@ static int apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* 
       (rc = stage(h, B_E, ops->elapsed, n, dev, &ov.e)) || (rc = outputs(h, res, n, dev, &ow)))
     return rc;
   ov.kind = kind;
+  if (track) {
+    // (as for the egress below: a status column of the library's own)
+    if (!ow.status && (rc = ensure(h, B_STATUS, n, &ow.status))) return rc;
+    const MarkPlan mp{uniform, uniform && ops->kind[0] != PHIP_OP_RECEIVE};
+    if ((rc = ordered(h, src, n, ov, ow, nullptr, &mp))) return after_error(h, rc);
+    return copy_outputs(h, res, n, dev, ow);
+  }
   if (!eg) {
     if ((rc = ordered(h, src, n, ov, ow))) return after_error(h, rc);
     return copy_outputs(h, res, n, dev, ow);
@@ -3580,12 +3674,15 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
   Rec* nrecs = nullptr;
   u32* naux = nullptr;
   u8* narena = nullptr;
+  Marks nmarks{};
   if (hipMalloc(&nrecs, ncap * sizeof(Rec)) != hipSuccess ||
       hipMalloc(&naux, ncap * sizeof(u32)) != hipSuccess ||
-      (narena_cap && hipMalloc(&narena, narena_cap + 64) != hipSuccess)) {
+      (narena_cap && hipMalloc(&narena, narena_cap + 64) != hipSuccess) ||
+      (h->track && alloc_marks(h, ncap, &nmarks))) {
     (void)hipGetLastError();
     if (nrecs) (void)hipFree(nrecs);
     if (naux) (void)hipFree(naux);
+    if (narena) (void)hipFree(narena);
     return set_err(h, PHIP_ERR_FULL, "evict: device memory for 2^%u slots and %llu arena bytes",
                    newL, (unsigned long long)narena_cap);
   }
@@ -3595,6 +3692,7 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
     (void)hipFree(nrecs);
     (void)hipFree(naux);
     if (narena) (void)hipFree(narena);
+    if (nmarks.state) (void)hipFree(nmarks.state);
     return err;
   };
   if (hipMemsetAsync(nrecs, 0, ncap * sizeof(Rec), h->stream) != hipSuccess ||
@@ -3611,7 +3709,7 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
     Launch l(h, "k_evict_move");
     k_evict_move<<<grid_for(h->cap, kEvictBlock), kEvictBlock, 0, h->stream>>>(
         h->recs, h->aux, h->cap, h->arena, used, now, idle_ns, nt, ncap, narena, narena_cap, ev,
-        h->ctr);
+        h->ctr, h->marks, nmarks);
   }
   if (hipGetLastError() != hipSuccess)
     return drop_new(set_err(h, PHIP_ERR_HIP, "k_evict_move launch failed"));
@@ -3631,9 +3729,11 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
     return drop_new(set_err(h, PHIP_ERR_HIP, "evict: setting the arena cursor failed"));
   Rec* orecs = h->recs;
   u32* oaux = h->aux;
+  u32* omarks = h->marks.state;
   u8* oarena = narena ? h->arena : nullptr;
   h->recs = nrecs;
   h->aux = naux;
+  h->marks = nmarks;
   h->L = newL;
   h->cap = ncap;
   h->max_load = load_limit(ncap, h->load_pct);
@@ -3651,6 +3751,7 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
   if (out) *out = st;
   HIPCHK(h, hipFree(orecs));
   HIPCHK(h, hipFree(oaux));
+  if (omarks) HIPCHK(h, hipFree(omarks));
   if (oarena) HIPCHK(h, hipFree(oarena));
   return PHIP_OK;
 }
@@ -3852,6 +3953,110 @@ int phip_export_sweep_parts(phip_handle* h, phip_sweep_cursor* cur, int64_t now,
                             phip_sweep_stats* st, uint32_t flags) {
   return export_sweep(h, cur, now, idle_ns, true, log2_parts, part_mask, out, out_cap, offs,
                       max_msgs, st, flags);
+}
+
+// Change-set export (patrolhip.h "Change set"; kernels in phip_kernels.hpp
+// "change set"): count per tile of the bit sets, the egress' scan, write.  The
+// totals of a full drain stand in the egress counter words after the scan; the
+// write cuts them to what fitted.  As in the sweep, a device-pointer call reads
+// the counters back once, at its end, and a host-pointer call also after the
+// scan, to size its staging buffers by what is pending instead of by the caps.
+int phip_export_changed(phip_handle* h, uint8_t* out, uint64_t out_cap, uint64_t* offs,
+                        uint32_t max_msgs, phip_changes_stats* st, uint32_t flags) {
+  if (!h || !st) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;   // (finishes a queued PHIP_RECV_ASYNC batch)
+  if (!h->track)
+    return set_err(h, PHIP_ERR_INVALID, "changes: the handle was opened without PHIP_CFG_TRACK_CHANGES");
+  if (flags & ~(PHIP_DEVICE_PTRS | PHIP_SWEEP_COUNT))
+    return set_err(h, PHIP_ERR_INVALID, "changes: unknown flag bits 0x%x", flags);
+  const bool dev = flags & PHIP_DEVICE_PTRS, count = flags & PHIP_SWEEP_COUNT;
+  if (count) {
+    if (out) return set_err(h, PHIP_ERR_INVALID, "changes: count mode takes no output buffer");
+  } else {
+    if (!out || !offs) return set_err(h, PHIP_ERR_INVALID, "changes: out and offs are required");
+    if (!max_msgs) return set_err(h, PHIP_ERR_INVALID, "changes: max_msgs must be positive");
+    if (out_cap < PHIP_BUCKET_PACKET_SIZE)
+      return set_err(h, PHIP_ERR_INVALID, "changes: out_cap below one datagram (%d bytes)",
+                     PHIP_BUCKET_PACKET_SIZE);
+    if (dev && ((reinterpret_cast<uintptr_t>(out) & 7) || (out_cap & 7) ||
+                out_cap < PHIP_BUCKET_PACKET_SIZE + 8))
+      return set_err(h, PHIP_ERR_INVALID,
+                     "changes: a device buffer is 8-byte aligned, a multiple of 8 and >= %d bytes",
+                     PHIP_BUCKET_PACKET_SIZE + 8);
+  }
+  const u64 budget = dev ? out_cap - 8 : out_cap;
+  const u64 nwords = mark_words(h->cap);
+  const u32 ntiles = (u32)((h->cap + kSweepTile - 1) / kSweepTile);
+  int rc;
+  // one buffer: the tiles' byte sums, then their counts (both sections each)
+  u64* tile_bytes;
+  if ((rc = ensure(h, B_EGTILE, 3 * (size_t)ntiles, &tile_bytes))) return rc;
+  u32* tile_cnt = (u32*)(tile_bytes + 2 * (size_t)ntiles);
+  HIPCHK(h, hipMemsetAsync(h->ctr + kCtrChgMarks, 0, 2 * sizeof(u32), h->stream));
+  {
+    Launch l(h, "k_changed_count");
+    k_changed_count<<<ntiles, kBlock, 0, h->stream>>>(h->recs, h->cap, nwords, h->marks, ntiles,
+                                                      tile_cnt, tile_bytes, h->ctr);
+  }
+  {
+    Launch l(h, "k_egress_scan");
+    k_egress_scan<<<1, kSweepBlock, 0, h->stream>>>(tile_cnt, tile_bytes, ntiles, h->ctr);
+  }
+  HIPCHK(h, hipGetLastError());
+  const u32* c = h->ctr_host;
+  u64 bytes;
+  phip_changes_stats s{};
+  if (count) {
+    if ((rc = read_ctr(h))) return rc;
+    std::memcpy(&bytes, c + kCtrEgBytes, sizeof bytes);
+    s.n = c[kCtrEgN];
+    s.bytes = bytes;
+    s.n_incast = c[kCtrEgIncast];
+    s.pending = c[kCtrChgMarks];
+    s.done = s.pending == 0;
+    *st = s;
+    return PHIP_OK;
+  }
+  u8* d_out = out;
+  u64* d_offs = reinterpret_cast<u64*>(offs);
+  if (!dev) {
+    if ((rc = read_ctr(h))) return rc;
+    std::memcpy(&bytes, c + kCtrEgBytes, sizeof bytes);
+    if ((rc = ensure(h, B_EGOUT, (size_t)std::min<u64>(out_cap, bytes), &d_out)) ||
+        (rc = ensure(h, B_EGOFFS, (size_t)std::min<u64>(max_msgs, c[kCtrEgN]) + 1, &d_offs)))
+      return rc;
+  }
+  {
+    // (long names are bounded by the arena's size, as in the sweep)
+    Launch l(h, "k_changed_write");
+    k_changed_write<<<ntiles, kSweepBlock, 0, h->stream>>>(
+        h->recs, h->cap, nwords, h->arena, h->arena_cap, h->marks, ntiles, tile_cnt, tile_bytes,
+        max_msgs, budget, d_out, d_offs, h->ctr);
+  }
+  HIPCHK(h, hipGetLastError());
+  if ((rc = read_ctr(h))) return rc;
+  std::memcpy(&bytes, c + kCtrEgBytes, sizeof bytes);
+  if (c[kCtrEgErr] || c[kCtrEgN] > max_msgs || bytes > budget || c[kCtrChgCleared] > c[kCtrChgMarks])
+    return set_err(h, PHIP_ERR_INVALID,
+                   "internal: change set wrote %u datagrams, %llu bytes, cleared %u of %u (flag %u)",
+                   c[kCtrEgN], (unsigned long long)bytes, c[kCtrChgCleared], c[kCtrChgMarks],
+                   c[kCtrEgErr]);
+  s.n = c[kCtrEgN];
+  s.bytes = bytes;
+  // (kCtrEgIncast: every pending request; the written ones are a prefix of the output)
+  s.n_incast = std::min<u32>(c[kCtrEgIncast], c[kCtrEgN]);
+  s.pending = c[kCtrChgMarks] - c[kCtrChgCleared];
+  s.done = s.pending == 0;
+  if (!dev) {
+    // only what was written travels back
+    if (s.bytes) HIPCHK(h, hipMemcpyAsync(out, d_out, s.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(offs, d_offs, (s.n + 1) * sizeof(u64), hipMemcpyDeviceToHost,
+                             h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  *st = s;
+  return PHIP_OK;
 }
 
 // Table digest (patrolhip.h "Partition digests"; kernels in phip_kernels.hpp

@@ -329,6 +329,15 @@ constexpr u32 kCtrEgErr = 25;
 // W: k_egress_scan.  R: apply_mixed.
 constexpr u32 kCtrEgIncastBytes = 26;
 constexpr u32 kCtrEgBytes = 28;
+// phip_export_changed (G; "change set" below) leaves its totals in the egress
+// words above -- k_egress_scan stores a full drain's, and the first datagram
+// k_changed_write cuts stores the written prefix over kCtrEgN / kCtrEgBytes --
+// and counts the marks here: those set when the call began (both sets), and
+// those the call cleared.  W: the host (zeroes), k_changed_count (one add per
+// tile that holds a mark), k_changed_write (one add per tile that cleared one).
+// R: export_changed (phip_engine.hip), once, at the call's end.
+constexpr u32 kCtrChgMarks = 30;
+constexpr u32 kCtrChgCleared = 31;
 constexpr u32 kCtrWords = 32;
 // The two min-reduced words start at "none", the rest at zero.
 __host__ __device__ constexpr u32 ctr_reset_value(u32 w) {
@@ -350,6 +359,8 @@ static_assert(kCtrNDefer >= kCtrResetWords && kCtrNDefer < kCtrWords &&
 static_assert(kCtrEgIncast > kCtrGateShut && kCtrEgErr < kCtrEgIncastBytes &&
               kCtrEgIncastBytes % 2 == 0 && kCtrEgBytes == kCtrEgIncastBytes + 2 &&
               kCtrEgBytes + 2 <= kCtrWords, "the egress words: two aligned u64 behind three u32");
+static_assert(kCtrChgMarks == kCtrEgBytes + 2 && kCtrChgCleared == kCtrChgMarks + 1 &&
+              kCtrChgCleared < kCtrWords, "the change set's words: zeroed in one memset");
 
 // The gate of a queued optimistic pass (k_receive_fast<Opt>'s `gate`, and the
 // host's reading of the same words in the mirror): c is the counter set of the
@@ -2482,10 +2493,29 @@ __global__ __launch_bounds__(kBlock) void k_list_long_bytes(Src src, u32 n,
 // every record of the old table moves to its home in the new one (2x the
 // slots) by linear probing.  Names are distinct, so a slot is claimed by a
 // CAS on its tag and no name is compared; the record (state, name words,
-// created, flags) and its aux word move as they are, arena offsets included.
+// created, flags) and its aux word move as they are, arena offsets included,
+// and so do its marks (carry_marks) on a handle that keeps a change set.
+//
+// The change set of a tracking handle ("change set" below): one bit per slot
+// in each of two sets, bit s & 31 of word s >> 5.  Null on a handle opened
+// without PHIP_CFG_TRACK_CHANGES.
+struct Marks {
+  u32* state = nullptr;   // a TAKE / UPSERT op named the bucket since its last export
+  u32* req = nullptr;     // a TAKE created it: its incast request is still to leave
+};
+// A record moving from slot s of one table to slot d of another takes its
+// marks along (the new sets start cleared; neighbours share words).
+__device__ inline void carry_marks(const Marks& from, u64 s, const Marks& to, u32 d) {
+  if (!from.state) return;
+  const u32 bit = 1u << (s & 31), nbit = 1u << (d & 31);
+  if (from.state[s >> 5] & bit) atomicOr(&to.state[d >> 5], nbit);
+  if (from.req[s >> 5] & bit) atomicOr(&to.req[d >> 5], nbit);
+}
+
 __global__ __launch_bounds__(kBlock) void k_rehash(const Rec* __restrict__ old,
                                                    const u32* __restrict__ old_aux, u64 old_cap,
-                                                   Table T, u32* ctr) {
+                                                   Table T, u32* ctr, Marks old_marks,
+                                                   Marks new_marks) {
   const u64 s = (u64)blockIdx.x * kBlock + threadIdx.x;
   if (s >= old_cap) return;
   const Rec r = load_rec(&old[s]);
@@ -2500,6 +2530,7 @@ __global__ __launch_bounds__(kBlock) void k_rehash(const Rec* __restrict__ old,
   q->added = r.added; q->taken = r.taken; q->elapsed = r.elapsed;
   q->name0 = r.name0; q->name1 = r.name1; q->created = r.created; q->name2 = r.name2;
   T.aux[d] = old_aux[s];
+  carry_marks(old_marks, s, new_marks, d);
 }
 
 // Placement quality (phip_table_stats): every bucket's probe distance from
@@ -3152,12 +3183,25 @@ struct SmallEgress<true> {
 };
 __device__ void small_egress(const SmallEgress<true>& eg, u32 n, const u32* sorted, const u64* skey,
                              const u32* sval, const Table& T, u64 arena_used, const u8* status);
+// k_small_mixed<false, true> (a handle that keeps a change set): the batch's
+// marks, set behind the folds in the same launch (small_marks, "change set"
+// below).  The other instantiations carry the empty form and are the kernels
+// they were without it.
+template <bool kTrack>
+struct SmallMarks {};
+template <>
+struct SmallMarks<true> {
+  Marks m;
+};
+__device__ void small_marks(const SmallMarks<true>& mk, u32 n, const u32* sorted, const u64* skey,
+                            const u32* sval, const u8* status);
 
-template <bool kEgress>
+template <bool kEgress, bool kTrack = false>
 __global__ __launch_bounds__(kSmallMax) void k_small_mixed(NamesOffs src, OpView ov, u32 n, Table T,
                                                          u8* arena, u64 arena_cap,
                                                          u64* arena_cursor, OutView ow,
-                                                         SmallHdr* hdr, SmallEgress<kEgress> eg) {
+                                                         SmallHdr* hdr, SmallEgress<kEgress> eg,
+                                                         SmallMarks<kTrack> mk = SmallMarks<kTrack>{}) {
   __shared__ OpRec sop[kSmallMax];
   __shared__ u32 sval[kSmallMax];
   __shared__ u64 skey[kSmallMax];
@@ -3317,6 +3361,7 @@ __global__ __launch_bounds__(kSmallMax) void k_small_mixed(NamesOffs src, OpView
   }
   if (i == 0) hdr->created = created;
   if constexpr (kEgress) small_egress(eg, n, sorted, skey, sval, T, arena_cap, ow.status);
+  if constexpr (kTrack) small_marks(mk, n, sorted, skey, sval, ow.status);
 }
 
 // ---- window summaries: skip provably quiet windows of a hot bucket -------
@@ -5574,7 +5619,8 @@ constexpr u32 kEvictBlock = 1024;
 __global__ __launch_bounds__(kEvictBlock) void k_evict_move(
     const Rec* __restrict__ old, const u32* __restrict__ old_aux, u64 old_cap,
     const u8* __restrict__ old_arena, u64 old_used, i64 now, i64 idle_ns, Table T, u64 new_cap,
-    u8* __restrict__ new_arena, u64 new_arena_cap, u64* ev, u32* ctr) {
+    u8* __restrict__ new_arena, u64 new_arena_cap, u64* ev, u32* ctr, Marks old_marks,
+    Marks new_marks) {
   __shared__ u32 wave_off[kEvictBlock / 64];
   __shared__ u64 block_base;
   const u64 s = (u64)blockIdx.x * kEvictBlock + threadIdx.x;
@@ -5632,6 +5678,7 @@ __global__ __launch_bounds__(kEvictBlock) void k_evict_move(
   q->added = r.added; q->taken = r.taken; q->elapsed = r.elapsed;
   q->name0 = r.name0; q->name1 = r.name1; q->created = r.created; q->name2 = r.name2;
   T.aux[d] = old_aux[s];
+  carry_marks(old_marks, s, new_marks, d);   // (an evicted bucket's marks stay behind)
 }
 
 // ------------------------------------------------------ export sweep -----
@@ -5999,6 +6046,29 @@ __global__ __launch_bounds__(kBlock) void k_egress_wants(
   if (threadIdx.x == 0) esz[g] = found != 0;
 }
 
+// The two questions a segment is asked, by the batch egress and by the change
+// set's marks ("change set" below) alike.
+// wants: one of its ops is a TAKE or an UPSERT.  v0: the segment's first sort
+// value, at sidx[st].  kUniform: a batch of one kind (the host knows it) reads
+// no kinds and answers wants0; otherwise a segment above kLongSeg ops reads
+// the flag k_egress_wants left in esz[s], and a shorter one walks its kinds.
+template <bool kUniform>
+__device__ __forceinline__ bool seg_wants(u32 s, u32 st, u32 v0, const u32* __restrict__ scnt,
+                                          const u32* __restrict__ sidx,
+                                          const u32* __restrict__ esz, bool wants0) {
+  if (kUniform) return wants0;
+  const u32 cnt = scnt[s];
+  if (cnt > kLongSeg) return esz[s] != 0;   // (k_egress_wants)
+  bool wants = egress_kind(v0);
+  for (u32 j = 1; j < cnt && !wants; ++j) wants = egress_kind(sidx[st + j]);
+  return wants;
+}
+// created by take: the bucket's first op in batch order is a TAKE whose status
+// byte says PHIP_ST_CREATED (GetBucket's incast request, repo.go:96-106).
+__device__ __forceinline__ bool created_by_take(u32 v0, u32 status_byte) {
+  return (v0 >> kOpIdxBits) == PHIP_OP_TAKE && (status_byte & PHIP_ST_CREATED) != 0;
+}
+
 // wants0: a batch of one kind (the host knows it) reads no kinds.
 template <bool kUniform>
 __global__ __launch_bounds__(kBlock) void k_egress_count(
@@ -6015,18 +6085,8 @@ __global__ __launch_bounds__(kBlock) void k_egress_count(
     const u32 s = (u32)s64;
     const u32 st = sstart[s];
     const u32 v0 = sidx[st];
-    bool wants = wants0;
-    if (!kUniform) {
-      const u32 cnt = scnt[s];
-      if (cnt > kLongSeg) {
-        wants = esz[s] != 0;   // (k_egress_wants)
-      } else {
-        wants = egress_kind(v0);
-        for (u32 j = 1; j < cnt && !wants; ++j) wants = egress_kind(sidx[st + j]);
-      }
-    }
-    const bool ic = (v0 >> kOpIdxBits) == PHIP_OP_TAKE &&
-                    (status[v0 & kOpIdxMask] & PHIP_ST_CREATED) != 0;
+    const bool wants = seg_wants<kUniform>(s, st, v0, scnt, sidx, esz, wants0);
+    const bool ic = created_by_take(v0, status[v0 & kOpIdxMask]);
     u32 e = 0;
     if (wants || ic) {
       const Rec r = load_rec(&recs[uslot[s]]);
@@ -6155,6 +6215,25 @@ __global__ __launch_bounds__(kSweepBlock) void k_egress_write(
   }
 }
 
+// seg_wants and created_by_take for the head of a bucket's run in
+// k_small_mixed's (slot, seq) order: position i of sorted[], whose run it walks
+// until a kind asks for a datagram.  The statuses were stored by other waves
+// of the launch, behind a fence and a barrier.
+__device__ __forceinline__ void small_run_asks(u32 i, u32 n, const u32* sorted, const u64* skey,
+                                               const u32* sval, const u8* status, bool& wants,
+                                               bool& ic) {
+  const u32 o0 = sorted[i];
+  const u32 sl = (u32)(skey[o0] >> 32);
+  wants = egress_kind(sval[o0]);
+  for (u32 j = i + 1; j < n && !wants; ++j) {
+    const u32 o = sorted[j];
+    if ((u32)(skey[o] >> 32) != sl) break;
+    wants = egress_kind(sval[o]);
+  }
+  ic = created_by_take(sval[o0], __hip_atomic_load(status + o0, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT));
+}
+
 // The small path's egress, the tail of k_small_mixed<true>: one workgroup of
 // kSmallMax threads, thread i standing at position i of the batch's (slot, seq)
 // order in sorted[] (skey[o] >> 32: op o's slot; sval[o]: its sort value).
@@ -6175,15 +6254,8 @@ __device__ void small_egress(const SmallEgress<true>& eg, u32 n, const u32* sort
     const u32 o0 = sorted[i];
     const u32 sl = (u32)(skey[o0] >> 32);
     if (i == 0 || (u32)(skey[sorted[i - 1]] >> 32) != sl) {
-      bool wants = egress_kind(sval[o0]);
-      for (u32 j = i + 1; j < n && !wants; ++j) {
-        const u32 o = sorted[j];
-        if ((u32)(skey[o] >> 32) != sl) break;
-        wants = egress_kind(sval[o]);
-      }
-      const bool ic = (sval[o0] >> kOpIdxBits) == PHIP_OP_TAKE &&
-                      (__hip_atomic_load(status + o0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &
-                       PHIP_ST_CREATED) != 0;
+      bool wants, ic;
+      small_run_asks(i, n, sorted, skey, sval, status, wants, ic);
       if (wants || ic) {
         r = load_rec_co(&T.recs[sl]);
         if (wants) sz = sweep_size(r, 0, 0);
@@ -6227,6 +6299,260 @@ __device__ void small_egress(const SmallEgress<true>& eg, u32 n, const u32* sort
   };
   if (iz) put(ex_i >> 19, ex_i & 0x7FFFFu, iz, false);
   if (sz) put(n_i + (ex_s >> 19), b_i + (ex_s & 0x7FFFFu), sz, true);
+}
+
+// -------------------------------------------------------- change set -----
+// PHIP_CFG_TRACK_CHANGES (patrolhip.h "Change set"): the batch egress' two
+// rules made persistent.  A handle keeps two bit sets (Marks, one bit per
+// slot): `state`, a TAKE / UPSERT op named the bucket, and `req`, a TAKE
+// created it.  Ordered batches set bits behind their folds and read no record
+// for it; phip_export_changed turns the set bits into the egress' two sections
+// and clears what it wrote.
+//   k_changes_mark   large path, one thread per segment of uslot[0..nseg):
+//                    seg_wants and created_by_take, the answers as bits of the
+//                    slot's word.  uslot is in slot order, so a wave's lanes
+//                    hold non-decreasing words in contiguous runs: a segmented
+//                    OR (six shuffle steps) joins the bits of equal words, and
+//                    the last lane of a run issues one atomicOr per set that
+//                    has a bit (neighbouring waves and tiles can share a word,
+//                    hence the atomic).  Mixed kinds with segments above
+//                    kLongSeg ops run k_egress_wants first, as the egress does.
+//   small_marks      small path, the tail of k_small_mixed<false, true>: the
+//                    head thread of each bucket's run, behind the folds'
+//                    barrier.
+//   k_changed_count  one workgroup per tile of kSweepTile slots (kChgTileWords
+//                    words a set): a tile without a set bit stores its zeros
+//                    and returns after reading its words; otherwise only the
+//                    marked slots load their record, and the tile's counts and
+//                    bytes go into the tile arrays as k_egress_count's do;
+//   k_egress_scan    requests' tiles in front of states': one rank and byte
+//                    space over both sections;
+//   k_changed_write  k_egress_write's ranking, cut as k_sweep_write cuts: a
+//                    datagram is written iff its rank < max_msgs and its end
+//                    <= budget.  Ranks and ends grow through the requests and
+//                    on through the states, so the written datagrams are a
+//                    prefix of that order, and a state is written only when
+//                    every request was.  The first datagram cut stores the
+//                    prefix's count and bytes over the totals the scan left.
+//                    A mark is cleared when its datagram was written, or when
+//                    it has none (a zero state, a name over PHIP_MAX_NAME_LEN)
+//                    and everything before it was written.  Plain stores: a
+//                    word's 32 slots are 32 consecutive lanes, one ballot per
+//                    set, and the handle's mutex keeps the markers out.
+constexpr u32 kChgTileWords = kSweepTile / 32;
+static_assert(kBlock == 2 * kChgTileWords && kSweepBlock >= 2 * kChgTileWords,
+              "a tile's words of both sets: one per thread");
+
+template <bool kUniform>
+__global__ __launch_bounds__(kBlock) void k_changes_mark(
+    const u32* __restrict__ uslot, const u32* __restrict__ sstart, const u32* __restrict__ scnt,
+    const u32* __restrict__ sidx, u32 nseg, const u8* __restrict__ status, bool wants0,
+    const u32* __restrict__ esz, Marks mk) {
+  const u64 s64 = (u64)blockIdx.x * kBlock + threadIdx.x;
+  u32 word = ~0u, bs = 0, br = 0;   // (~0: no segment; behind every real word)
+  if (s64 < nseg) {
+    const u32 s = (u32)s64, st = sstart[s], v0 = sidx[st], slot = uslot[s];
+    word = slot >> 5;
+    const u32 bit = 1u << (slot & 31);
+    if (seg_wants<kUniform>(s, st, v0, scnt, sidx, esz, wants0)) bs = bit;
+    if (created_by_take(v0, status[v0 & kOpIdxMask])) br = bit;
+  }
+  // (no lane has left: every lane takes part in the shuffles)
+  const u32 lane = __lane_id();
+#pragma unroll
+  for (u32 d = 1; d < 64; d <<= 1) {
+    const u32 ow = __shfl_up(word, d), os = __shfl_up(bs, d), orq = __shfl_up(br, d);
+    if (lane >= d && ow == word) { bs |= os; br |= orq; }
+  }
+  const u32 nw = __shfl_down(word, 1);
+  if (word == ~0u || (lane != 63 && nw == word)) return;   // not the last lane of its run
+  if (bs) atomicOr(&mk.state[word], bs);
+  if (br) atomicOr(&mk.req[word], br);
+}
+
+__device__ void small_marks(const SmallMarks<true>& mk, u32 n, const u32* sorted, const u64* skey,
+                            const u32* sval, const u8* status) {
+  __threadfence();
+  __syncthreads();   // every fold has stored its record and its statuses
+  const u32 i = threadIdx.x;
+  if (i >= n) return;
+  const u32 sl = (u32)(skey[sorted[i]] >> 32);
+  if (i != 0 && (u32)(skey[sorted[i - 1]] >> 32) == sl) return;
+  bool wants, ic;
+  small_run_asks(i, n, sorted, skey, sval, status, wants, ic);
+  const u32 bit = 1u << (sl & 31);
+  if (wants) atomicOr(&mk.m.state[sl >> 5], bit);
+  if (ic) atomicOr(&mk.m.req[sl >> 5], bit);
+}
+
+// The datagram sizes of a marked record: its state's (bs; sweep_size, 0 for a
+// state that is left out) | its request's << kEgIncastShift (br; 0 for a name
+// MarshalBinary refuses).
+__device__ inline u32 changed_sizes(const Rec& r, bool bs, bool br) {
+  u32 e = 0;
+  if (bs) e = sweep_size(r, 0, 0);
+  const u32 len = (u32)(r.name0 & 0xFFu);
+  if (br && r.tag && (rec_flags(r) & kRecPublished) && len <= PHIP_MAX_NAME_LEN)
+    e |= (PHIP_BUCKET_FIXED_SIZE + len) << kEgIncastShift;
+  return e;
+}
+
+// A tile's words of both sets into LDS (threads [0, kChgTileWords) the states',
+// the next kChgTileWords the requests'); returns this thread's word.
+__device__ inline u32 changed_stage(const Marks& mk, u64 nwords, u32 (&ws)[kChgTileWords],
+                                    u32 (&wr)[kChgTileWords]) {
+  const u32 t = threadIdx.x, k = t & (kChgTileWords - 1);
+  const u64 w = (u64)blockIdx.x * kChgTileWords + k;
+  u32 v = 0;
+  if (t < 2 * kChgTileWords) {
+    if (w < nwords) v = t < kChgTileWords ? mk.state[w] : mk.req[w];
+    if (t < kChgTileWords) ws[k] = v; else wr[k] = v;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(kBlock) void k_changed_count(const Rec* __restrict__ recs, u64 cap,
+                                                          u64 nwords, Marks mk, u32 ntiles,
+                                                          u32* __restrict__ tile_cnt,
+                                                          u64* __restrict__ tile_bytes, u32* ctr) {
+  __shared__ u32 ws[kChgTileWords], wr[kChgTileWords];
+  __shared__ u32 wn[kBlock / 64], wm[kBlock / 64];
+  __shared__ u64 wb[kBlock / 64];
+  const u32 v = changed_stage(mk, nwords, ws, wr);
+  if (!__syncthreads_or(v != 0)) {   // (the workgroup's vote: all leave or none)
+    if (threadIdx.x == 0) {
+      tile_cnt[blockIdx.x] = 0;
+      tile_bytes[blockIdx.x] = 0;
+      tile_cnt[ntiles + blockIdx.x] = 0;
+      tile_bytes[ntiles + blockIdx.x] = 0;
+    }
+    return;
+  }
+  u32 n = 0;   // states | requests << 16 (a tile holds 4096 slots)
+  u64 b = 0;   // their bytes, states | requests << 32
+  u32 marks = (u32)__popc(v);
+  for (u32 k = 0; k < kSweepTile / kBlock; ++k) {
+    const u32 j = k * kBlock + threadIdx.x;
+    const bool bs = (ws[j >> 5] >> (j & 31)) & 1, br = (wr[j >> 5] >> (j & 31)) & 1;
+    const u64 s = (u64)blockIdx.x * kSweepTile + j;
+    if (!(bs | br) || s >= cap) continue;
+    const u32 e = changed_sizes(load_rec(&recs[s]), bs, br);
+    const u32 sz = e & 0xFFFFu, iz = e >> kEgIncastShift;
+    n += (u32)(sz != 0) | ((u32)(iz != 0) << 16);
+    b += (u64)sz | ((u64)iz << 32);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    n += __shfl_xor(n, d);
+    b += __shfl_xor(b, d);
+    marks += __shfl_xor(marks, d);
+  }
+  if (__lane_id() == 0) { wn[threadIdx.x >> 6] = n; wb[threadIdx.x >> 6] = b; wm[threadIdx.x >> 6] = marks; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u32 tn = 0, tm = 0;
+    u64 tb = 0;
+    for (u32 i = 0; i < kBlock / 64; ++i) { tn += wn[i]; tb += wb[i]; tm += wm[i]; }
+    tile_cnt[blockIdx.x] = tn >> 16;
+    tile_bytes[blockIdx.x] = tb >> 32;
+    tile_cnt[ntiles + blockIdx.x] = tn & 0xFFFFu;
+    tile_bytes[ntiles + blockIdx.x] = tb & 0xFFFFFFFFull;
+    atomicAdd(&ctr[kCtrChgMarks], tm);
+  }
+}
+
+__global__ __launch_bounds__(kSweepBlock) void k_changed_write(
+    const Rec* __restrict__ recs, u64 cap, u64 nwords, const u8* __restrict__ arena, u64 arena_used,
+    Marks mk, u32 ntiles, const u32* __restrict__ tile_cnt, const u64* __restrict__ tile_bytes,
+    u32 max_msgs, u64 budget, u8* __restrict__ out, u64* __restrict__ offs, u32* ctr) {
+  __shared__ u32 ws[kChgTileWords], wr[kChgTileWords];
+  __shared__ u32 wtot[2][2][kSweepBlock / 64];
+  __shared__ u32 wclr[kSweepBlock / 64];
+  if (blockIdx.x == 0 && threadIdx.x == 0) offs[0] = 0;
+  const u32 v = changed_stage(mk, nwords, ws, wr);
+  if (!__syncthreads_or(v != 0)) return;   // (the workgroup's vote)
+  u64 rank_i = tile_cnt[blockIdx.x], byte_i = tile_bytes[blockIdx.x];
+  u64 rank_s = tile_cnt[ntiles + blockIdx.x], byte_s = tile_bytes[ntiles + blockIdx.x];
+  // (every rank of the tile is at least rank_i: above max_msgs nothing of it
+  // is written, cleared, or the first datagram cut)
+  if (rank_i > max_msgs) return;
+  const u32 wv = threadIdx.x >> 6, lane = __lane_id();
+  // what stands before (rank, start) was written: it starts the output, or its
+  // predecessor fitted both caps
+  auto before_written = [&](u64 rank, u64 start) {
+    return rank == 0 || (rank - 1 < max_msgs && start <= budget);
+  };
+  // One marked slot's part in a section: true when its mark is to be cleared.
+  auto deal = [&](u64 rank, u64 start, u32 bytes, const Rec& r, bool state) -> bool {
+    if (!bytes) return before_written(rank, start);   // (left out: no datagram to wait for)
+    const u64 end = start + bytes;
+    if (rank >= max_msgs || end > budget) {
+      if (before_written(rank, start)) {   // the first datagram cut
+        ctr[kCtrEgN] = (u32)rank;
+        *reinterpret_cast<u64*>(ctr + kCtrEgBytes) = start;
+      }
+      return false;
+    }
+    offs[rank + 1] = end;
+    const u64 a = state ? dec_f64(r.added) : 0ull, t = state ? dec_f64(r.taken) : 0ull;
+    const u64 e = state ? (u64)r.elapsed : 0ull;
+    put_datagram(out + start, a, t, e, r, bytes - PHIP_BUCKET_FIXED_SIZE, arena, arena_used,
+                 &ctr[kCtrEgErr]);
+    return true;
+  };
+  u32 cleared = 0;
+  for (u32 k = 0; k < kSweepTile / kSweepBlock; ++k) {
+    const u32 j = k * kSweepBlock + threadIdx.x;
+    const u64 s = (u64)blockIdx.x * kSweepTile + j;
+    const bool bs = s < cap && ((ws[j >> 5] >> (j & 31)) & 1);
+    const bool br = s < cap && ((wr[j >> 5] >> (j & 31)) & 1);
+    Rec r{};
+    u32 e = 0;
+    if (bs | br) {
+      r = load_rec(&recs[s]);
+      e = changed_sizes(r, bs, br);
+    }
+    const u32 sz = e & 0xFFFFu, iz = e >> kEgIncastShift;
+    const u32 vs = sz ? (1u << 19) | sz : 0u, vi = iz ? (1u << 19) | iz : 0u;
+    const u32 ss = wave_incl_scan(vs), si = wave_incl_scan(vi);
+    if (lane == 63) { wtot[k & 1][0][wv] = ss; wtot[k & 1][1][wv] = si; }
+    __syncthreads();   // (no thread leaves the loop early: every step has its barrier)
+    u32 pre_s = 0, tot_s = 0, pre_i = 0, tot_i = 0;
+#pragma unroll
+    for (u32 w = 0; w < kSweepBlock / 64; ++w) {
+      const u32 x = wtot[k & 1][0][w], y = wtot[k & 1][1][w];
+      if (w < wv) { pre_s += x; pre_i += y; }
+      tot_s += x;
+      tot_i += y;
+    }
+    const u32 ex_s = pre_s + ss - vs, ex_i = pre_i + si - vi;
+    const u64 rs = rank_s + (ex_s >> 19), bys = byte_s + (ex_s & 0x7FFFFu);
+    const u64 ri = rank_i + (ex_i >> 19), byi = byte_i + (ex_i & 0x7FFFFu);
+    rank_s += tot_s >> 19;
+    byte_s += tot_s & 0x7FFFFu;
+    rank_i += tot_i >> 19;
+    byte_i += tot_i & 0x7FFFFu;
+    const bool clr_r = br && deal(ri, byi, iz, r, false);
+    const bool clr_s = bs && deal(rs, bys, sz, r, true);
+    // (every lane votes: the loop has no `continue`)
+    const u64 mr = __ballot(clr_r), ms = __ballot(clr_s);
+    if ((lane & 31) == 0) {
+      const u32 cr = (u32)(mr >> (lane & 32)), cs = (u32)(ms >> (lane & 32));
+      const u64 w = (u64)blockIdx.x * kChgTileWords + (j >> 5);
+      if (cr) mk.req[w] = wr[j >> 5] & ~cr;
+      if (cs) mk.state[w] = ws[j >> 5] & ~cs;
+      cleared += (u32)__popc(cr) + (u32)__popc(cs);
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) cleared += __shfl_xor(cleared, d);
+  if (lane == 0) wclr[wv] = cleared;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u32 tc = 0;
+    for (u32 i = 0; i < kSweepBlock / 64; ++i) tc += wclr[i];
+    if (tc) atomicAdd(&ctr[kCtrChgCleared], tc);
+  }
 }
 
 // ------------------------------------------------------ table digest -----

@@ -150,20 +150,23 @@ class GPURepo:
     def __init__(self, device: int = 0, log2_slots: int = 20, arena_bytes: int = 1 << 24,
                  max_load_pct: int = 90, debug_tag_bits: int = 0, grow: bool = True,
                  small: bool = True, hash_seed: int | None = None, isolate: bool = False,
-                 classify_first: bool = False):
+                 classify_first: bool = False, track_changes: bool = False):
         """hash_seed: None = a random placement seed per handle (the default,
         as Go's map seeds its hash per process); an int pins it
         (PHIP_CFG_FIXED_SEED; 0 = the unseeded placement).  isolate: set every
         Receive batch's dirty buckets apart (PHIP_CFG_ISOLATE; by default only
         after a dirty batch).  classify_first: classify every decoded Receive
         batch before merging it instead of merging optimistically
-        (PHIP_CFG_CLASSIFY_FIRST; same results)."""
+        (PHIP_CFG_CLASSIFY_FIRST; same results).  track_changes: keep the change
+        set export_changed drains (PHIP_CFG_TRACK_CHANGES)."""
         self.L = _lib.load()
         flags = (0 if grow else _lib.CFG_NO_GROW) | (0 if small else _lib.CFG_NO_SMALL)
         if isolate:
             flags |= _lib.CFG_ISOLATE
         if classify_first:
             flags |= _lib.CFG_CLASSIFY_FIRST
+        if track_changes:
+            flags |= _lib.CFG_TRACK_CHANGES
         if hash_seed is not None:
             flags |= _lib.CFG_FIXED_SEED
         cfg = phip_config(device, log2_slots, arena_bytes, max_load_pct, debug_tag_bits, flags, 0,
@@ -441,6 +444,64 @@ class GPURepo:
             dgs, cursor, st = self.export_sweep(cursor, max_msgs, out_cap, now, idle_ns, parts)
             yield dgs, st
             if st["done"]:
+                return
+
+    # -------------------------------------------------------- change set --
+    @staticmethod
+    def _changes_dict(st) -> dict:
+        return {k: int(getattr(st, k)) for k, _ in _lib.phip_changes_stats._fields_}
+
+    def export_changed(self, max_msgs: int = 1 << 16, out_cap: int | None = None) -> dict:
+        """One call of phip_export_changed on a repo opened with
+        track_changes=True: the replication traffic of the buckets this repo's
+        own TAKE / UPSERT ops touched since they were last exported, at most
+        max_msgs datagrams in at most out_cap bytes (default 256 each), and
+        their marks cleared.  -> dict(data uint8, offs uint64[n + 1], n,
+        n_incast, bytes, pending, done): datagram i = data[offs[i]:offs[i+1]],
+        the incast requests [0, n_incast) first, then one state datagram per
+        bucket; loop until done (drain_changes)."""
+        if out_cap is None:
+            out_cap = _lib.PACKET_SIZE * max_msgs
+        st = _lib.phip_changes_stats()
+        out = np.zeros(max(int(out_cap), 1), np.uint8)
+        offs = np.zeros(int(max_msgs) + 1, np.uint64)
+        rc = self.L.phip_export_changed(self.h, out.ctypes.data, int(out_cap), offs.ctypes.data,
+                                        int(max_msgs), C.byref(st), 0)
+        self._queued = None   # a queued batch is finished (or failed)
+        self._check(rc)
+        d = self._changes_dict(st)
+        d["data"], d["offs"] = out[:int(st.bytes)], offs[:int(st.n) + 1]
+        return d
+
+    def export_changed_device(self, out, offs, max_msgs: int) -> dict:
+        """phip_export_changed with device pointers: out (uint8 CUDA tensor,
+        8-byte aligned, a multiple of 8 bytes; the byte budget is its size - 8),
+        offs (int64[max_msgs + 1]).  Both can go unchanged into another repo's
+        receive_datagrams_device.  -> dict(n, n_incast, bytes, pending, done)."""
+        st = _lib.phip_changes_stats()
+        cap = int(out.numel() * out.element_size())
+        rc = self.L.phip_export_changed(self.h, _ptr(out), cap, _ptr(offs), int(max_msgs),
+                                        C.byref(st), DEVICE_PTRS)
+        self._queued = None
+        self._check(rc)
+        return self._changes_dict(st)
+
+    def changes_count(self) -> dict:
+        """What a full drain would write now (PHIP_SWEEP_COUNT): dict(n,
+        n_incast, bytes, pending, done); nothing is cleared."""
+        st = _lib.phip_changes_stats()
+        rc = self.L.phip_export_changed(self.h, None, 0, None, 0, C.byref(st), _lib.SWEEP_COUNT)
+        self._queued = None
+        self._check(rc)
+        return self._changes_dict(st)
+
+    def drain_changes(self, max_msgs: int = 1 << 16, out_cap: int | None = None):
+        """Generator over a whole drain: yields export_changed's dict per call
+        until nothing is pending."""
+        while True:
+            d = self.export_changed(max_msgs, out_cap)
+            yield d
+            if d["done"]:
                 return
 
     # ------------------------------------------------------------ digest --
@@ -735,9 +796,13 @@ class GPUGroup:
 
     @classmethod
     def open_all(cls, devices, log2_slots: int = 20, arena_bytes: int = 1 << 24,
-                 max_load_pct: int = 90):
+                 max_load_pct: int = 90, track_changes: bool = False):
+        """track_changes: every member keeps a change set (PHIP_CFG_TRACK_CHANGES):
+        an owner marks the buckets it applied ops to, and repos[i].export_changed
+        is that owner's egress."""
         L = _lib.load()
-        cfg = phip_config(0, log2_slots, arena_bytes, max_load_pct, 0, 0, 0, 0)
+        cfg = phip_config(0, log2_slots, arena_bytes, max_load_pct, 0,
+                          _lib.CFG_TRACK_CHANGES if track_changes else 0, 0, 0)
         devs = (C.c_int32 * len(devices))(*devices)
         g = C.c_void_p()
         rc = L.phip_group_open_all(C.byref(cfg), devs, len(devices), C.byref(g))

@@ -5,7 +5,7 @@
 // line: takes/s over the whole run, p50/p99/p999 request latency, batch
 // statistics.  Links libpatrolhip through its C ABI only.
 //
-//   take_load [threads] [per_thread] [window_us] [buckets] [peers] [new_frac] [coalesce]
+//   take_load [threads] [per_thread] [window_us] [buckets] [peers] [new_frac] [coalesce] [drain_us]
 //
 // peers = 0: the bare batched Take (phip_batcher_take).
 // peers > 0: the whole drop-in handler (INTEGRATION.md takeBucket): the
@@ -22,7 +22,14 @@
 //   replicator thread drains phip_batcher_egress_next and sends each batch --
 //   one datagram per bucket the batch touched, its incast requests in front
 //   -- to every peer with one phip_udp_send_batch per peer.
-// datagrams_sent counts what was sent in either mode.
+// coalesce = 2 (with peers > 0): a plain batcher on a handle opened with
+//   PHIP_CFG_TRACK_CHANGES; the handler threads send nothing, and one
+//   replicator thread wakes every drain_us microseconds (default 1000), drains
+//   the change set (phip_export_changed until done) and sends every call's
+//   datagrams to every peer with one phip_udp_send_batch per peer: one
+//   datagram per bucket the takes of that window touched.  egress_batches
+//   counts the export calls that wrote something.
+// datagrams_sent counts what was sent in any mode.
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <sys/socket.h>
@@ -49,11 +56,14 @@ int main(int argc, char** argv) {
   const uint32_t K = argc > 4 ? (uint32_t)atoi(argv[4]) : 100000;
   const int peers = argc > 5 ? atoi(argv[5]) : 0;
   const double new_frac = argc > 6 ? atof(argv[6]) : 0.01;
-  const bool coalesce = argc > 7 && atoi(argv[7]) != 0 && peers > 0;
+  const int mode = argc > 7 && peers > 0 ? atoi(argv[7]) : 0;
+  const bool coalesce = mode == 1, changes = mode == 2;
+  const uint32_t drain_us = argc > 8 ? (uint32_t)atoi(argv[8]) : 1000;
   phip_config cfg{};
   cfg.device = 0;
   cfg.log2_slots = 20;
   cfg.arena_bytes = 1 << 20;
+  if (changes) cfg.flags |= PHIP_CFG_TRACK_CHANGES;
   phip_handle* h = nullptr;
   if (phip_open(&cfg, &h)) { fprintf(stderr, "phip_open failed\n"); return 1; }
   // K buckets b0..b{K-1}, created now
@@ -128,6 +138,35 @@ int main(int argc, char** argv) {
       }
     });
   }
+  if (changes) {
+    replicator = std::thread([&] {
+      const uint32_t max_msgs = 4096;
+      std::vector<uint8_t> out((size_t)max_msgs * PHIP_BUCKET_PACKET_SIZE);
+      std::vector<uint64_t> offs(max_msgs + 1);
+      for (;;) {
+        // (read before the drain: a take that returned before the flag was set
+        // has marked its bucket before this drain reads the set)
+        const bool last = clients_done.load();
+        phip_changes_stats st{};
+        do {
+          if (phip_export_changed(h, out.data(), out.size(), offs.data(), max_msgs, &st, 0)) {
+            fprintf(stderr, "export_changed failed: %s\n", phip_last_error(h));
+            std::exit(1);
+          }
+          if (!st.n) break;
+          for (int p = 0; p < peers; ++p) {
+            uint32_t sent_now = 0;
+            phip_udp_send_batch(tx, out.data(), offs.data(), (uint32_t)st.n,
+                                (const uint8_t*)&sink_addr, 0, &sent_now);
+            coalesced_sent.fetch_add(sent_now);
+          }
+          egress_batches.fetch_add(1);
+        } while (!st.done);
+        if (last) return;
+        std::this_thread::sleep_for(std::chrono::microseconds(drain_us));
+      }
+    });
+  }
   // Zipf(1.1) ranks -> ids (a fixed scatter), per thread its own stream
   std::vector<double> cdf(K);
   double acc = 0;
@@ -172,9 +211,9 @@ int main(int argc, char** argv) {
           std::exit(1);
         }
         oks[tid] += code == 200;
-        created[tid] += rep.created && coalesce;
-        if (coalesce) {
-          // the replicator thread sends the batch's coalesced egress
+        created[tid] += rep.created && (coalesce || changes);
+        if (coalesce || changes) {
+          // the replicator thread sends the coalesced egress
         } else {
         if (rep.created) {   // ReplicatedRepo.GetBucket's incast (repo.go:96-106)
           ++created[tid];
@@ -198,7 +237,7 @@ int main(int argc, char** argv) {
   for (int t = 0; t < T; ++t) th.emplace_back(client, t);
   for (auto& x : th) x.join();
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
-  if (coalesce) {
+  if (coalesce || changes) {
     clients_done.store(true);
     replicator.join();
   }
@@ -223,13 +262,13 @@ int main(int argc, char** argv) {
          "\"batches\": %llu, \"mean_batch\": %.1f, \"max_batch\": %llu, "
          "\"gpu_call_us_per_batch\": %.1f, \"ok_fraction\": %.3f, \"created\": %llu, "
          "\"datagrams_sent\": %llu, \"datagrams_received\": %llu, \"coalesce\": %d, "
-         "\"egress_batches\": %llu}\n",
+         "\"egress_batches\": %llu, \"drain_us\": %u}\n",
          peers ? "handler" : "take", T, all.size(), window, K, peers, all.size() / wall, pct(0.5),
          pct(0.99), pct(0.999), (unsigned long long)s[0], (double)s[1] / std::max<uint64_t>(1, s[0]),
          (unsigned long long)s[2], s[3] / 1e3 / std::max<uint64_t>(1, s[0]),
          (double)okn / all.size(), (unsigned long long)cr, (unsigned long long)sn,
-         (unsigned long long)got_dgrams.load(), (int)coalesce,
-         (unsigned long long)egress_batches.load());
+         (unsigned long long)got_dgrams.load(), mode,
+         (unsigned long long)egress_batches.load(), changes ? drain_us : 0u);
   phip_batcher_close(b);
   phip_close(h);
   return 0;
