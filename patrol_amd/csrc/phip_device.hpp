@@ -68,12 +68,12 @@ __host__ __device__ inline u64 as_bits(double x) { return __builtin_bit_cast(u64
 
 // ------------------------------------------------------------- Take -----
 // x86-64 CVTTSD2SQ (what Go's amd64 backend uses for float->int).
-__device__ inline i64 cvttsd2sq(double x) {
+__host__ __device__ inline i64 cvttsd2sq(double x) {
   if (!(x >= -9223372036854775808.0 && x < 9223372036854775808.0)) return (i64)kSign;
   return (i64)x;
 }
 // Go uint64(float64) on amd64: cutoff at 2^63 (ssagen floatToUint).
-__device__ inline u64 go_u64(double x) {
+__host__ __device__ inline u64 go_u64(double x) {
   if (x < 9223372036854775808.0) return (u64)cvttsd2sq(x);
   return (u64)cvttsd2sq(x - 9223372036854775808.0) | kSign;
 }
@@ -96,20 +96,20 @@ __host__ __device__ inline i64 rate_interval(i64 freq, i64 per) {
 constexpr u64 kQuietBit = 0x0008000000000000ull;
 constexpr u64 kX86DefaultNaN = 0xFFF8000000000000ull;
 
-__device__ inline double x86_nan_fix(double r, double a, double b) {
+__host__ __device__ inline double x86_nan_fix(double r, double a, double b) {
   if (__builtin_expect(r == r, 1)) return r;
   const u64 ab = as_bits(a), bb = as_bits(b);
   if (is_nan_bits(ab)) return as_f64(ab | kQuietBit);
   if (is_nan_bits(bb)) return as_f64(bb | kQuietBit);
   return as_f64(kX86DefaultNaN);
 }
-__device__ inline double go_add(double a, double b) { return x86_nan_fix(a + b, a, b); }
-__device__ inline double go_sub(double a, double b) { return x86_nan_fix(a - b, a, b); }
+__host__ __device__ inline double go_add(double a, double b) { return x86_nan_fix(a + b, a, b); }
+__host__ __device__ inline double go_sub(double a, double b) { return x86_nan_fix(a - b, a, b); }
 
 // dt of Take (bucket.go:198-207): last = created.Add(elapsed) (exact),
 // clamped to now, then now.Sub(last) saturating to the int64 range.  The
 // int64 fast path is exact whenever created + elapsed does not overflow.
-__device__ inline i64 take_dt(i64 created, i64 elapsed, i64 now) {
+__host__ __device__ inline i64 take_dt(i64 created, i64 elapsed, i64 now) {
   i64 last;
   if (__builtin_expect(!__builtin_add_overflow(created, elapsed, &last), 1)) {
     if (now < last) return 0;
@@ -142,8 +142,9 @@ struct TakeResult {
 // overflow here), now.Sub(last) saturates like time.Time.Sub, and
 // elapsed += dt wraps like Go int64.
 // capacity = float64(Freq) and t = float64(n) come precomputed (k_pack_ops).
-__device__ inline TakeResult take_step(double& added, double& taken, i64& elapsed, i64 created,
-                                       i64 now, i64 interval, double capacity, double t) {
+__host__ __device__ inline TakeResult take_step(double& added, double& taken, i64& elapsed,
+                                                i64 created, i64 now, i64 interval,
+                                                double capacity, double t) {
   //                                                              :192 capacity
   if (added == 0) added = capacity;                            // :194-196
   const i64 dt = take_dt(created, elapsed, now);                // :198-207
@@ -163,7 +164,8 @@ __device__ inline TakeResult take_step(double& added, double& taken, i64& elapse
 }
 
 // Bucket.Merge for one `other` (bucket.go:250-260) on raw values.
-__device__ inline void go_merge(double& a, double& t, i64& e, double oa, double ot, i64 oe) {
+__host__ __device__ inline void go_merge(double& a, double& t, i64& e, double oa, double ot,
+                                         i64 oe) {
   if (a < oa) a = oa;
   if (t < ot) t = ot;
   if (e < oe) e = oe;

@@ -2780,7 +2780,7 @@ __device__ inline OpRec load_oprec(const OpRec* p) {
   ulonglong2 a = q[0], b = q[1];
   return OpRec{(i64)a.x, a.y, b.x, b.y};
 }
-__device__ inline SOp make_sop(const OpRec& r, u32 v) {
+__host__ __device__ inline SOp make_sop(const OpRec& r, u32 v) {
   return SOp{r.now, r.x, r.y, r.z, v & kOpIdxMask, v >> kOpIdxBits};
 }
 __device__ inline SOp load_sop(const OpRec* ops, u32 v) {
@@ -2854,7 +2854,7 @@ struct OpOut {
 // Returns whether S2 differs from S (bitwise, or existence).  kOut: also
 // fill the op's results (the state test alone lets the compiler drop them).
 template <bool kOut>
-__device__ inline bool step_sop(const SOp& op, const FState& S, FState& S2, OpOut& out) {
+__host__ __device__ inline bool step_sop(const SOp& op, const FState& S, FState& S2, OpOut& out) {
   S2 = S;
   u8 cflag = 0;
   if (!S.existed) { S2.c = op.now; S2.existed = true; cflag = 0x80; }   // repo.go:208
@@ -2894,10 +2894,10 @@ __device__ inline bool step_sop(const SOp& op, const FState& S, FState& S2, OpOu
   return !S.existed || as_bits(S2.a) != as_bits(S.a) || as_bits(S2.t) != as_bits(S.t) ||
          S2.e != S.e;
 }
-__device__ inline bool eval_sop(const SOp& op, const FState& S, FState& S2, OpOut& out) {
+__host__ __device__ inline bool eval_sop(const SOp& op, const FState& S, FState& S2, OpOut& out) {
   return step_sop<true>(op, S, S2, out);
 }
-__device__ inline bool apply_sop(const SOp& op, const FState& S, FState& S2) {
+__host__ __device__ inline bool apply_sop(const SOp& op, const FState& S, FState& S2) {
   OpOut unused;
   return step_sop<false>(op, S, S2, unused);
 }
@@ -3388,7 +3388,7 @@ struct alignas(16) WinSum {
 constexpr u32 kSumTake = 1, kSumMixed = 2, kSumMerge = 4;
 constexpr u32 kSumDirty = 8;   // a merge with a -0.0 replica field (E max != Go's merge)
 
-__device__ inline bool window_quiet(const WinSum& q, const FState& S) {
+__host__ __device__ inline bool window_quiet(const WinSum& q, const FState& S) {
   if (!S.existed) return false;
   if (q.flags & kSumMerge) {
     if (q.ea > enc_f64(as_bits(S.a)) || q.et > enc_f64(as_bits(S.t)) ||
@@ -3643,14 +3643,14 @@ __device__ inline void put_run(u32* run_pos, RunState* run_st, u32 k, u32 pos, c
 struct GMax {
   u64 a, t, e;
 };
-__device__ inline GMax gmax(const GMax& x, const GMax& y) {
+__host__ __device__ inline GMax gmax(const GMax& x, const GMax& y) {
   return GMax{x.a > y.a ? x.a : y.a, x.t > y.t ? x.t : y.t, x.e > y.e ? x.e : y.e};
 }
-__device__ inline GMax gmax_of(const WinSum& q) { return GMax{q.ea, q.et, q.ee}; }
-__device__ inline bool gmax_empty(const GMax& g) { return !(g.a | g.t | g.e); }
+__host__ __device__ inline GMax gmax_of(const WinSum& q) { return GMax{q.ea, q.et, q.ee}; }
+__host__ __device__ inline bool gmax_empty(const GMax& g) { return !(g.a | g.t | g.e); }
 
 // X = max(R, G) in E order, field by field.
-__device__ inline FState join_state(const FState& R, const GMax& g) {
+__host__ __device__ inline FState join_state(const FState& R, const GMax& g) {
   FState X = R;
   if (g.a > enc_f64(as_bits(R.a))) X.a = as_f64(dec_f64(g.a));
   if (g.t > enc_f64(as_bits(R.t))) X.t = as_f64(dec_f64(g.t));
@@ -3660,7 +3660,7 @@ __device__ inline FState join_state(const FState& R, const GMax& g) {
 
 // A change from S to S2 that keeps X_k = max(R, G_k) exact afterwards: no
 // field is lowered in E order.
-__device__ inline bool state_grew(const FState& S, const FState& S2) {
+__host__ __device__ inline bool state_grew(const FState& S, const FState& S2) {
   return enc_f64(as_bits(S2.a)) >= enc_f64(as_bits(S.a)) &&
          enc_f64(as_bits(S2.t)) >= enc_f64(as_bits(S.t)) && S2.e >= S.e;
 }
@@ -3675,7 +3675,8 @@ __device__ inline bool state_grew(const FState& S, const FState& S2) {
 // `missing` is below the uncapped one, and + is monotone).  t > bound then
 // means every Take of the window is denied; added > 0 at the start (it only
 // grows) rules out the added = capacity write of bucket.go:194-196.
-__device__ inline bool window_absorbable(const WinSum& q, const FState& Xs, const FState& Xe) {
+__host__ __device__ inline bool window_absorbable(const WinSum& q, const FState& Xs,
+                                                  const FState& Xe) {
   if (!Xs.existed || (q.flags & kSumDirty)) return false;
   if (!(q.flags & kSumTake)) return true;
   if (q.flags & kSumMixed) return false;
@@ -3880,7 +3881,7 @@ __device__ inline void block_prefix_gmax(GMax x, FoldShared& sh, u32 tid) {
 
 // A merge op's contribution to the running replica maximum G (E' codes,
 // elapsed biased; 0 for Takes and incast requests, which merge nothing).
-__device__ inline GMax merge_contrib(const OpRec& r, u32 v) {
+__host__ __device__ inline GMax merge_contrib(const OpRec& r, u32 v) {
   const u32 kind = v >> kOpIdxBits;
   if (kind == PHIP_OP_TAKE || (kind == PHIP_OP_RECEIVE && state_is_zero(r.x, r.y, (i64)r.z)))
     return GMax{0, 0, 0};

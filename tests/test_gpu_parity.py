@@ -310,7 +310,9 @@ def assert_replies(out, ref, kind, tag=None):
     return int(rep.sum())
 
 
-def _check_mixed(pa, args, log2_slots, reply=False):
+def _check_mixed(pa, args, log2_slots, reply=False, replies=False):
+    """reply: the stream must hold incast replies, and every reply state is
+    compared; replies: compare every reply state, whatever kinds occur."""
     g = pa.GPURepo(log2_slots=log2_slots)
     o = O.Repo()
     out = g.apply_mixed(*args)
@@ -321,6 +323,8 @@ def _check_mixed(pa, args, log2_slots, reply=False):
     assert np.array_equal(out["have"][take], ref["have"][take])
     if reply:
         assert ((ref["status"] & 0x7F) == 2).any()
+        assert assert_replies(out, ref, args[0]) > 0
+    elif replies:
         assert assert_replies(out, ref, args[0]) > 0
     assert_same_dump(gpu_dump(g), o.dump())
 
@@ -496,8 +500,10 @@ def test_take_clock_extremes(pa):
 def test_hot_bucket_quiet_window_skips(pa, freq, per):
     """k_fold_block skips windows its summary proves quiet: one uniform rate
     per run (positive, negative and zero intervals), jittered clocks (now not
-    monotone), merges carrying -0.0, NaN and negatives, an incast now and
-    then; 3 buckets of ~40k ops each (about 20 windows of 2048)."""
+    monotone), merges carrying NaN and zeros (np.abs below removes every
+    -0.0 and every negative field; tests/test_fold_directed.py has the -0.0
+    cases), an incast now and then; 3 buckets of ~40k ops each (about 80
+    windows of 512)."""
     rng = np.random.default_rng(abs(freq) * 7 + 3)
     n = 120000
     ids = rng.integers(0, 3, n)
@@ -550,7 +556,7 @@ def test_hot_bucket_absorbing_merges(pa, variant):
         cnt[rng.random(n) < 0.002] = 2
     args = [kind, names, now, fr, pe, cnt, a, t, e]
     if variant != "seeded":
-        _check_mixed(pa, args, 12, reply=False)
+        _check_mixed(pa, args, 12, reply=False, replies=True)
         return
     g = pa.GPURepo(log2_slots=12)
     o = O.Repo()
@@ -565,6 +571,7 @@ def test_hot_bucket_absorbing_merges(pa, variant):
     assert np.array_equal(out["remaining"], ref["remaining"])
     take = kind == 0
     assert np.array_equal(out["have"][take], ref["have"][take])
+    assert assert_replies(out, ref, kind, variant) > 0
     assert_same_dump(gpu_dump(g), o.dump())
 
 
