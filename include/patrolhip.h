@@ -90,6 +90,7 @@ enum {
   PHIP_ST_TAKE_OK = 6,         /* Take returned ok=true                                 */
   PHIP_ST_TAKE_DENIED = 7,     /* Take returned ok=false (HTTP 429)                     */
   PHIP_ST_UPSERT_INSERTED = 8, /* UpsertBucket inserted the state as-is (repo.go:225-230) */
+  PHIP_ST_ABSENT = 0x40,       /* flag (phip_peek only): the bucket does not exist      */
   PHIP_ST_CREATED = 0x80       /* flag: this op's GetBucket created the bucket          */
 };
 
@@ -729,6 +730,85 @@ int phip_export_changed(phip_handle* h, uint8_t* out, uint64_t out_cap,
 int phip_take(phip_handle* h, const uint8_t* names, const uint32_t* name_offs, uint32_t n,
               const int64_t* now, const int64_t* freq, const int64_t* per, const uint64_t* count,
               uint64_t* remaining_out, uint8_t* ok_out, uint32_t flags);
+
+/* Peek: batched read-only quota queries with an exact retry time.  Every other
+ * entry point that answers "may this request pass?" also spends the tokens
+ * (GetBucket + Bucket.Take, bucket.go:186-225, api.go:67-74).  Peek answers
+ * the two questions a deployed rate limiter is asked without spending any: how
+ * much is left for this key (an X-RateLimit-Remaining header, a dashboard, a
+ * per-user and a per-org limit checked before taking from either), and when
+ * may a denied key come back (the Retry-After of a 429, the expiry of a deny
+ * entry cached at a load balancer).
+ *
+ * A query is (name, now, freq, per, count): the TAKE operands of phip_ops.
+ *  1. State read.  A present bucket gives its record (added, taken, elapsed,
+ *     created).  An absent bucket gives what GetBucket would have created
+ *     (repo.go:189-211): the zero state with created = now.  Nothing is created.
+ *  2. Evaluation.  Bucket.Take runs on that copy with Rate{freq, per} and
+ *     count tokens, bit-exact as everywhere here.  status is PHIP_ST_TAKE_OK or
+ *     PHIP_ST_TAKE_DENIED, with PHIP_ST_ABSENT or-ed in for an absent bucket;
+ *     remaining and have are exactly what phip_apply_mixed reports for a TAKE
+ *     op with these operands applied to that state (phip_results.remaining /
+ *     .have).  count is used as given, 0 included: api.go:63's 0 -> 1 belongs
+ *     to the HTTP helper (phip_api_peek).
+ *  3. retry_at (int64 ns on the clock of `now`).  Let ok(t) be step 2 with
+ *     `now` replaced by t and everything else unchanged (an absent bucket's
+ *     created stays the query's `now`).  Granted: retry_at = now.  Denied: the
+ *     least t in (now, INT64_MAX] with ok(t); if ok(INT64_MAX) is false,
+ *     PHIP_PEEK_NEVER (INT64_MIN, which no valid answer can be: those are >
+ *     now).  The value is defined by this predicate, not by a formula: from a
+ *     denial ok(t) goes from false to true at most once (Take's dt does not
+ *     decrease in t, nor do dt / interval, its clamp and tokens + it when
+ *     interval > 0; with interval <= 0 the refill never grows and the answer
+ *     is never), and the library bisects it: at most 66
+ *     evaluations of Take's verdict a query, none for a granted one.
+ *  4. Nothing is written: table, arena, change set, layout count, the hot
+ *     directory and phip_len stay as they are.  The call is serialised with
+ *     the handle's other calls, as phip_export_datagrams is; a batch queued
+ *     with PHIP_RECV_ASYNC is finished first, its error is this call's, and
+ *     the peek sees its merges.
+ *
+ * phip_peek.  Of q it reads n, names, name_offs, names_len, now, freq, per and
+ * count; a NULL operand column reads as zeros; kind, added, taken and elapsed
+ * are ignored.  Any column of res may be NULL, and so may res.  Host pointers
+ * are staged as phip_export_datagrams stages them (one stream synchronise), and
+ * a name over PHIP_MAX_NAME_LEN is PHIP_ERR_NAME_TOO_LARGE; PHIP_DEVICE_PTRS
+ * makes every pointer device memory; any other flag bit is PHIP_ERR_INVALID.
+ * A device batch with names_len != 0 has its offset column checked first (the
+ * rule of phip_msgs): a malformed entry is PHIP_ERR_INVALID, no name is read
+ * and the result columns are untouched.  n == 0 is PHIP_OK.
+ *
+ * phip_peek_eval is steps 2 and 3 on the host (no handle, no GPU), the same
+ * function the kernel calls: a handler that holds a phip_take_reply.state
+ * computes the Retry-After of the 429 it just issued without a device call.
+ * s == NULL stands for an absent bucket.  Returns the status byte (without
+ * PHIP_ST_ABSENT), or PHIP_ERR_INVALID when one of the three outputs is NULL.
+ *
+ * phip_api_peek is phip_api_take's request parsing (api.go:55-65: ParseRate's
+ * values beside its errors, count 0 -> 1, 400 with ErrNameTooLarge's text
+ * before any device call) over one phip_peek: the body is `remaining` in
+ * decimal, the return 200 or 429 (or 400, or < 0).  *retry_after_ns (may be
+ * NULL): 0 with 200; with 429 retry_at - now, saturating at INT64_MAX, or -1
+ * for never; untouched otherwise.
+ *
+ * Not here: a PEEK kind inside ordered streams, peeks through the Take
+ * batcher, an owner-routed phip_group_peek (a single-process group can peek
+ * each member's phip_group_handle by the shard map meanwhile), and a
+ * "currently throttled" sweep of the table. */
+#define PHIP_PEEK_NEVER INT64_MIN
+typedef struct phip_peek_results { /* any pointer may be NULL */
+  uint8_t* status;     /* PHIP_ST_TAKE_OK / _DENIED (| PHIP_ST_ABSENT)          */
+  uint64_t* remaining; /* uint64(remaining) as Go returns it                    */
+  uint64_t* have;      /* float64 bits, as phip_results.have                    */
+  int64_t* retry_at;   /* now, the least later reading that grants, or NEVER    */
+  phip_state* state;   /* the state evaluated (absent: zeros, created = now)    */
+} phip_peek_results;
+int phip_peek(phip_handle* h, const phip_ops* q, const phip_peek_results* res, uint32_t flags);
+int phip_peek_eval(const phip_state* s /* NULL: absent */, int64_t now, int64_t freq, int64_t per,
+                   uint64_t count, uint64_t* remaining, uint64_t* have, int64_t* retry_at);
+int phip_api_peek(phip_handle* h, const uint8_t* name, uint32_t len, const char* rate,
+                  uint32_t rate_len, const char* count, uint32_t count_len, int64_t now,
+                  char* body, uint32_t* body_len, int64_t* retry_after_ns);
 
 /* ---- host helpers (no device work) ---- */
 /* ParseRate: returns 0 or <0 on error; freq and per receive the values Go

@@ -37,6 +37,7 @@ EXPORTS = [
     "phip_egress_caps", "phip_apply_mixed_egress", "phip_batcher_open_egress",
     "phip_batcher_egress_next", "phip_batcher_egress_done",
     "phip_export_changed",
+    "phip_peek", "phip_peek_eval", "phip_api_peek",
 ]
 
 PHIP_OK = 0
@@ -46,6 +47,8 @@ GROUP_ID_BYTES = 128
 PEER_BYTES = 128   # PHIP_PEER_BYTES = sizeof(struct sockaddr_storage)
 ST_MERGED, ST_INCAST_REPLY, ST_INCAST_NOREPLY, ST_SHORT, ST_NOT_PROCESSED = 1, 2, 3, 4, 5
 ST_TAKE_OK, ST_TAKE_DENIED, ST_UPSERT_INSERTED, ST_CREATED = 6, 7, 8, 0x80
+ST_ABSENT = 0x40             # PHIP_ST_ABSENT (phip_peek): the bucket does not exist
+PEEK_NEVER = -(1 << 63)      # PHIP_PEEK_NEVER: no clock reading grants the take
 OP_TAKE, OP_RECEIVE, OP_UPSERT = 0, 1, 2
 DEVICE_PTRS = 0x1
 CFG_NO_GROW = 0x1
@@ -145,6 +148,11 @@ class phip_egress_batch(C.Structure):
 class phip_results(C.Structure):
     _fields_ = [("status", C.c_void_p), ("remaining", C.c_void_p), ("have", C.c_void_p),
                 ("reply", C.c_void_p)]
+
+
+class phip_peek_results(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("remaining", C.c_void_p), ("have", C.c_void_p),
+                ("retry_at", C.c_void_p), ("state", C.c_void_p)]
 
 
 _lib = None
@@ -291,5 +299,11 @@ def load(path: str = LIB_PATH):
         L.phip_batcher_egress_done.argtypes = [vp, u64]
     if hasattr(L, "phip_export_changed"):
         L.phip_export_changed.argtypes = [vp, vp, u64, vp, u32, C.POINTER(phip_changes_stats), u32]
+    if hasattr(L, "phip_peek"):
+        L.phip_peek.argtypes = [vp, C.POINTER(phip_ops), C.POINTER(phip_peek_results), u32]
+        L.phip_peek_eval.argtypes = [C.POINTER(phip_state), i64, i64, i64, u64, C.POINTER(u64),
+                                     C.POINTER(u64), C.POINTER(i64)]
+        L.phip_api_peek.argtypes = [vp, C.c_char_p, u32, C.c_char_p, u32, C.c_char_p, u32, i64,
+                                    C.c_char_p, C.POINTER(u32), C.POINTER(i64)]
     _lib = L
     return L

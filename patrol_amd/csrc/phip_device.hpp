@@ -163,6 +163,77 @@ __host__ __device__ inline TakeResult take_step(double& added, double& taken, i6
   return TakeResult{go_u64(rem), as_bits(rem), true};          // :224
 }
 
+// ------------------------------------------------------------- Peek -----
+// phip_peek / phip_peek_eval (patrolhip.h "Peek"): Take evaluated on a copy of
+// a bucket's state, plus the least clock reading at which the same Take would
+// be granted.
+struct PeekResult {
+  u64 remaining;
+  u64 have_bits;
+  i64 retry_at;   // now (granted), the least later reading that grants, or PHIP_PEEK_NEVER
+  bool ok;
+};
+
+// take_step's verdict alone, at the reading `at`, from the parts of it that do
+// not depend on the clock (tokens = added - taken after :194-196, missing =
+// capacity - tokens, fi = float64(interval)).  A NaN's payload and a zero's
+// sign cannot change `t > have`, so the plain + stands in for go_add.
+__host__ __device__ inline bool take_ok_at(i64 created, i64 elapsed, i64 at, i64 interval,
+                                           double fi, double tokens, double missing, double t) {
+  const i64 dt = take_dt(created, elapsed, at);
+  double add = !interval ? 0.0 : (double)dt / fi;
+  if (add > missing) add = missing;
+  return !(t > tokens + add);
+}
+
+// One lane's own verdict on "does anybody still search" (the host form).
+struct PeekVoteSelf {
+  __host__ __device__ inline bool operator()(bool pending) const { return pending; }
+};
+
+// The evaluation.  Step 1 is take_step itself on the copy, so status,
+// remaining and have are what a TAKE op reports.  A denied query then looks
+// for the least reading in (now, INT64_MAX] that grants: from a denial the
+// verdict is monotone in the clock, so after one probe of
+// INT64_MAX (false: never) a bisection keeps lo denied / hi granted and halves
+// hi - lo <= 2^64 - 1 in 64 steps: at most 66 verdicts a query, none when it
+// was granted.  `any` turns "this lane still searches" into "some lane of the
+// wave does" (k_peek: a ballot), so the loop is uniform across a wave and a
+// wave without a denial skips it; every lane of the wave must make the call.
+template <class Vote = PeekVoteSelf>
+__host__ __device__ inline PeekResult peek_eval(double added, double taken, i64 elapsed,
+                                                i64 created, i64 now, i64 interval,
+                                                double capacity, double t, Vote any = Vote()) {
+  double a = added, k = taken;
+  i64 e = elapsed;
+  const TakeResult r = take_step(a, k, e, created, now, interval, capacity, t);
+  PeekResult out{r.remaining, r.have_bits, now, r.ok};
+  const double fi = (double)interval;
+  const double tokens = (added == 0 ? capacity : added) - taken;
+  const double missing = capacity - tokens;
+  const i64 kMax = 0x7FFFFFFFFFFFFFFFll;
+  bool search = !r.ok;
+  if (any(search)) {
+    if (search && !take_ok_at(created, elapsed, kMax, interval, fi, tokens, missing, t)) {
+      out.retry_at = (i64)kSign;   // PHIP_PEEK_NEVER
+      search = false;
+    }
+  }
+  i64 lo = now, hi = kMax;   // (searching lanes: lo denied, hi granted, lo < hi)
+  for (int step = 0; step < 64; ++step) {
+    const u64 gap = (u64)hi - (u64)lo;
+    const bool pending = search && gap > 1;
+    if (!any(pending)) break;
+    if (pending) {
+      const i64 mid = (i64)((u64)lo + (gap >> 1));
+      if (take_ok_at(created, elapsed, mid, interval, fi, tokens, missing, t)) hi = mid;
+      else lo = mid;
+    }
+  }
+  if (search) out.retry_at = hi;
+  return out;
+}
+
 // Bucket.Merge for one `other` (bucket.go:250-260) on raw values.
 __host__ __device__ inline void go_merge(double& a, double& t, i64& e, double oa, double ot,
                                          i64 oe) {

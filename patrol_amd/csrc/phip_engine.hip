@@ -64,6 +64,7 @@ enum BufId {
   B_DLIST, B_DTAB, B_DMARK, B_SMAP, B_SOFF, B_SLEN, B_SA, B_ST, B_SE, B_SSTAT, B_SREP, B_NCHK,
   B_EVICT, B_ULOG, B_ULCNT, B_SWEEP, B_DIGEST, B_DIGOUT,
   B_EGSZ, B_EGTILE, B_EGOUT, B_EGOFFS,
+  B_PEEKAT, B_PEEKST,
   B_COUNT_
 };
 
@@ -2826,6 +2827,60 @@ int phip_export_datagrams(phip_handle* h, const uint8_t* names, const uint32_t* 
   }
   HIPCHK(h, hipGetLastError());
   if ((rc = copy_back(h, out, d_out, nbytes, dev)) || (rc = copy_back(h, found, d_found, n, dev)))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PHIP_OK;
+}
+
+// Peek (patrolhip.h "Peek"): one launch of k_peek over the queries, staged as
+// phip_export_datagrams stages its names.  Nothing of the handle changes: no
+// reserve, no insert, no counter word, no mark.
+int phip_peek(phip_handle* h, const phip_ops* q, const phip_peek_results* res, uint32_t flags) {
+  if (!h || !q) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;   // (finishes a queued PHIP_RECV_ASYNC batch)
+  if (flags & ~PHIP_DEVICE_PTRS)
+    return set_err(h, PHIP_ERR_INVALID, "peek: unknown flag bits 0x%x", flags);
+  const u32 n = q->n;
+  if (n == 0) return PHIP_OK;
+  if (!q->names || !q->name_offs)
+    return set_err(h, PHIP_ERR_INVALID, "peek: names and name_offs are required");
+  const bool dev = flags & PHIP_DEVICE_PTRS;
+  if (!dev && !names_ok(q->name_offs, n)) return set_err(h, PHIP_ERR_NAME_TOO_LARGE, "name > 231 bytes");
+  int rc;
+  NamesOffs src;
+  if ((rc = stage_names(h, q->names, q->name_offs, n, dev, &src, q->names_len))) return rc;
+  // a checked device batch: the offset column first, so that no name is read
+  // and no result written for a batch with a malformed entry
+  u32 first_bad;
+  if ((rc = check_offsets_on(h, h->stream, src.blob, src.offs, src.lim, n, &first_bad))) return rc;
+  if (first_bad != ~0u)
+    return set_err(h, PHIP_ERR_INVALID, "peek: malformed name offsets at query %u (names_len check)",
+                   first_bad);
+  OpView ov{};
+  phip_peek_results r{};
+  if (res) r = *res;
+  PeekOut po{};
+  if ((rc = stage(h, B_NOW, q->now, n, dev, &ov.now)) ||
+      (rc = stage(h, B_FREQ, q->freq, n, dev, &ov.freq)) ||
+      (rc = stage(h, B_PER, q->per, n, dev, &ov.per)) ||
+      (rc = stage(h, B_COUNT, q->count, n, dev, &ov.count)) ||
+      (rc = out_buf(h, B_STATUS, r.status, n, dev, &po.status)) ||
+      (rc = out_buf(h, B_REM, r.remaining, n, dev, &po.remaining)) ||
+      (rc = out_buf(h, B_HAVE, r.have, n, dev, &po.have)) ||
+      (rc = out_buf(h, B_PEEKAT, r.retry_at, n, dev, &po.retry_at)) ||
+      (rc = out_buf(h, B_PEEKST, r.state, n, dev, &po.state)))
+    return rc;
+  {
+    Launch l(h, "k_peek");
+    k_peek<<<grid_for(n), kBlock, 0, h->stream>>>(src, ov, n, table(h), po);
+  }
+  HIPCHK(h, hipGetLastError());
+  if ((rc = copy_back(h, r.status, po.status, n, dev)) ||
+      (rc = copy_back(h, r.remaining, po.remaining, n, dev)) ||
+      (rc = copy_back(h, r.have, po.have, n, dev)) ||
+      (rc = copy_back(h, r.retry_at, po.retry_at, n, dev)) ||
+      (rc = copy_back(h, r.state, po.state, n, dev)))
     return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return PHIP_OK;

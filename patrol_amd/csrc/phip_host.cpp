@@ -12,6 +12,7 @@
 #include <string>
 
 #include "patrolhip.h"
+#include "phip_device.hpp"
 #include "phip_host.hpp"
 
 namespace {
@@ -206,6 +207,65 @@ int phip_api_take(phip_handle* h, const uint8_t* name, uint32_t len, const char*
   std::string s = std::to_string(rem);                            // api.go:84-85
   memcpy(body, s.data(), s.size());
   *body_len = (uint32_t)s.size();
+  return ok ? 200 : 429;
+}
+
+// Peek on the host (patrolhip.h "Peek"): phip::peek_eval is the function
+// k_peek calls, compiled here for the host from the same header.
+int phip_peek_eval(const phip_state* s, int64_t now, int64_t freq, int64_t per, uint64_t count,
+                   uint64_t* remaining, uint64_t* have, int64_t* retry_at) {
+  if (!remaining || !have || !retry_at) return PHIP_ERR_INVALID;
+  const phip_state st = s ? *s : phip_state{0, 0, 0, now};   // absent: GetBucket's (repo.go:189-211)
+  const phip::PeekResult r =
+      phip::peek_eval(phip::as_f64(st.added), phip::as_f64(st.taken), st.elapsed, st.created, now,
+                      phip::rate_interval(freq, per), (double)freq, (double)count);
+  *remaining = r.remaining;
+  *have = r.have_bits;
+  *retry_at = r.retry_at;
+  return r.ok ? PHIP_ST_TAKE_OK : PHIP_ST_TAKE_DENIED;
+}
+
+// API.takeBucket's parsing (api.go:55-65) over one phip_peek: nothing is taken.
+int phip_api_peek(phip_handle* h, const uint8_t* name, uint32_t len, const char* rate,
+                  uint32_t rate_len, const char* count, uint32_t count_len, int64_t now,
+                  char* body, uint32_t* body_len, int64_t* retry_after_ns) {
+  if (!body || !body_len) return PHIP_ERR_INVALID;
+  int64_t freq, per;
+  uint64_t n;
+  const int pre = phip_host::api_prepare(name, len, rate, rate_len, count, count_len, &freq, &per,
+                                         &n, body, body_len);
+  if (pre) return pre;
+  uint32_t offs[2] = {0, len};
+  uint8_t empty = 0;
+  uint8_t st = 0;
+  uint64_t rem = 0;
+  int64_t at = 0;
+  phip_ops q{};
+  q.n = 1;
+  q.names = len ? name : &empty;
+  q.name_offs = offs;
+  q.now = &now;
+  q.freq = &freq;
+  q.per = &per;
+  q.count = &n;
+  phip_peek_results res{};
+  res.status = &st;
+  res.remaining = &rem;
+  res.retry_at = &at;
+  const int rc = phip_peek(h, &q, &res, 0);
+  if (rc < 0) return rc;
+  const std::string s = std::to_string(rem);                      // api.go:84-85
+  memcpy(body, s.data(), s.size());
+  *body_len = (uint32_t)s.size();
+  const bool ok = (st & 0x3F) == PHIP_ST_TAKE_OK;
+  if (retry_after_ns) {
+    if (ok) *retry_after_ns = 0;
+    else if (at == PHIP_PEEK_NEVER) *retry_after_ns = -1;
+    else {   // at > now: the difference fits 64 unsigned bits
+      const u64 d = (u64)at - (u64)now;
+      *retry_after_ns = d > (u64)INT64_MAX ? INT64_MAX : (i64)d;
+    }
+  }
   return ok ? 200 : 429;
 }
 

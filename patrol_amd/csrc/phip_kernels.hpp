@@ -6715,4 +6715,63 @@ __global__ __launch_bounds__(kDigestBlock) void k_digest_reduce(
   if (gl == 0) { out[p].sum = t_sum[t]; out[p].count = t_cnt[t]; }
 }
 
+// ---------------------------------------------------------------- peek ----
+// phip_peek (patrolhip.h "Peek"): Take evaluated on a copy of each named
+// bucket's state -- status, remaining, have as a TAKE op reports them -- and
+// the least clock reading at which the same Take would be granted.  One lane
+// per query.  Reads the table and writes nothing but its result columns: no
+// LDS, no atomics, no aux / arena / mark access.
+//
+// Every lane of a wave stays to the end (a lane past n works on query n - 1
+// and stores nothing): peek_eval's retry search votes across the wave.
+struct PeekOut {
+  u8* status;
+  uint64_t* remaining;
+  uint64_t* have;
+  int64_t* retry_at;
+  phip_state* state;
+};
+
+struct PeekVoteWave {
+  __device__ inline bool operator()(bool pending) const { return __ballot(pending) != 0; }
+};
+
+__global__ __launch_bounds__(kBlock) void k_peek(NamesOffs src, OpView ov, u32 n, Table T,
+                                                 PeekOut po) {
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  const bool live = i < n;
+  const u32 j = live ? i : n - 1;
+  // the batch's columns are read once: non-temporal, all issued before the probe
+  u64 off; u32 len;
+  src.get<true>(j, off, len);
+  const i64 now = ov.now ? ld<true>(ov.now + j) : ov.now0;
+  const i64 freq = ov.freq ? ld<true>(ov.freq + j) : 0;
+  const i64 per = ov.per ? ld<true>(ov.per + j) : 0;
+  const u64 count = ov.count ? ld<true>(ov.count + j) : 0;
+  Name nm;
+  load_name_wide<false>(src.blob, off, len, nm);
+  u32 s;
+  Rec r;
+  const bool hit = probe(T, nm, src.blob, &s, &r) == kFound;
+  // an absent bucket: what GetBucket would have created (repo.go:189-211)
+  phip_state st{0, 0, 0, now};
+  if (hit) {
+    r = load_rec(&T.recs[s]);   // probe's copy may be the 48-byte view
+    st.added = dec_f64(r.added);
+    st.taken = dec_f64(r.taken);
+    st.elapsed = r.elapsed;
+    st.created = r.created;
+  }
+  const PeekResult pr =
+      peek_eval(as_f64(st.added), as_f64(st.taken), st.elapsed, st.created, now,
+                rate_interval(freq, per), (double)freq, (double)count, PeekVoteWave());
+  if (!live) return;
+  if (po.status)
+    po.status[i] = (u8)((pr.ok ? PHIP_ST_TAKE_OK : PHIP_ST_TAKE_DENIED) | (hit ? 0 : PHIP_ST_ABSENT));
+  if (po.remaining) po.remaining[i] = pr.remaining;
+  if (po.have) po.have[i] = pr.have_bits;
+  if (po.retry_at) po.retry_at[i] = pr.retry_at;
+  if (po.state) po.state[i] = st;
+}
+
 }  // namespace phip

@@ -772,6 +772,71 @@ class GPURepo:
                                                 len(count), int(now), body, C.byref(bl)))
         return code, body.raw[:bl.value].decode()
 
+    # -------------------------------------------------------------- peek --
+    def peek(self, names, now, freq, per, count) -> dict:
+        """phip_peek over host arrays: Bucket.Take evaluated on a copy of each
+        named bucket's state; nothing is created or written.  -> dict(status
+        (ST_TAKE_OK / ST_TAKE_DENIED, | ST_ABSENT), remaining, have (float64
+        bits), retry_at (now when granted, the least later clock reading that
+        grants, or PEEK_NEVER), state (a/t/e/c records: the state evaluated))."""
+        n = len(names)
+        blob, offs = names_blob(names)
+        now, freq, per = _np(now, np.int64), _np(freq, np.int64), _np(per, np.int64)
+        count = _np(count, np.uint64)
+        z = max(n, 1)
+        status, rem, have = np.zeros(z, np.uint8), np.zeros(z, np.uint64), np.zeros(z, np.uint64)
+        at = np.zeros(z, np.int64)
+        state = np.zeros(z, dtype=[("a", "<u8"), ("t", "<u8"), ("e", "<i8"), ("c", "<i8")])
+        q = phip_ops(n, 0, None, blob.ctypes.data, offs.ctypes.data, _ptr(now), _ptr(freq),
+                     _ptr(per), _ptr(count), None, None, None)
+        res = _lib.phip_peek_results(_ptr(status), _ptr(rem), _ptr(have), _ptr(at), _ptr(state))
+        self._check(self.L.phip_peek(self.h, C.byref(q), C.byref(res), 0))
+        return dict(status=status[:n], remaining=rem[:n], have=have[:n], retry_at=at[:n],
+                    state=state[:n])
+
+    def peek_device(self, n, names, name_offs, now, freq=None, per=None, count=None, status=None,
+                    remaining=None, have=None, retry_at=None, state=None, names_len=None):
+        """phip_peek with every array a torch CUDA tensor (PHIP_DEVICE_PTRS):
+        names (uint8 blob, 8 bytes of read slack), name_offs (int32[n+1]), the
+        operand columns (int64), and the result columns wanted (status uint8,
+        remaining / have / retry_at int64, state int64 [n, 4]); names_len as
+        receive_soa's."""
+        q = phip_ops(n, _names_len(names, names_len), None, _ptr(names), _ptr(name_offs),
+                     _ptr(now), _ptr(freq), _ptr(per), _ptr(count), None, None, None)
+        res = _lib.phip_peek_results(_ptr(status), _ptr(remaining), _ptr(have), _ptr(retry_at),
+                                     _ptr(state))
+        self._check(self.L.phip_peek(self.h, C.byref(q), C.byref(res), DEVICE_PTRS))
+
+    def api_peek(self, name: bytes, rate: bytes, count: bytes, now: int):
+        """API.takeBucket's request (api.go:51-86) answered without taking:
+        (HTTP status, body, retry_after_ns: 0 with 200; with 429 the wait until
+        the same request would pass, -1 for never; None with 400)."""
+        body = C.create_string_buffer(64)
+        bl = C.c_uint32()
+        after = C.c_int64()
+        code = self._check(self.L.phip_api_peek(self.h, name, len(name), rate, len(rate), count,
+                                                len(count), int(now), body, C.byref(bl),
+                                                C.byref(after)))
+        return code, body.raw[:bl.value].decode(), (None if code == 400 else int(after.value))
+
+
+def peek_eval(state, now: int, freq: int, per: int, count: int):
+    """phip_peek_eval (host only, no handle, no GPU): phip_peek's evaluation of
+    one query on a state the caller holds (a BucketState, an (added bits, taken
+    bits, elapsed, created) tuple, or None for an absent bucket) ->
+    (status, remaining, have bits, retry_at)."""
+    s = None
+    if state is not None:
+        a, t, e, c = ((state.added, state.taken, state.elapsed, state.created)
+                      if isinstance(state, BucketState) else state)
+        s = C.byref(phip_state(int(a), int(t), int(e), int(c)))
+    rem, have, at = C.c_uint64(), C.c_uint64(), C.c_int64()
+    st = _lib.load().phip_peek_eval(s, int(now), int(freq), int(per), int(count), C.byref(rem),
+                                    C.byref(have), C.byref(at))
+    if st < 0:
+        raise PatrolHipError(st, "phip_peek_eval")
+    return st, int(rem.value), int(have.value), int(at.value)
+
 
 class GPUGroup:
     """A shard group over RCCL (phip_group_*, include/patrolhip.h): the
