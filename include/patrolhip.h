@@ -792,9 +792,10 @@ int phip_take(phip_handle* h, const uint8_t* names, const uint32_t* name_offs, u
  * for never; untouched otherwise.
  *
  * Not here: a PEEK kind inside ordered streams, peeks through the Take
- * batcher, an owner-routed phip_group_peek (a single-process group can peek
- * each member's phip_group_handle by the shard map meanwhile), and a
- * "currently throttled" sweep of the table. */
+ * batcher, and an owner-routed phip_group_peek (a single-process group can
+ * peek each member's phip_group_handle by the shard map meanwhile).  The
+ * reverse question -- which buckets are denied now -- is "Throttled sweep"
+ * below. */
 #define PHIP_PEEK_NEVER INT64_MIN
 typedef struct phip_peek_results { /* any pointer may be NULL */
   uint8_t* status;     /* PHIP_ST_TAKE_OK / _DENIED (| PHIP_ST_ABSENT)          */
@@ -809,6 +810,113 @@ int phip_peek_eval(const phip_state* s /* NULL: absent */, int64_t now, int64_t 
 int phip_api_peek(phip_handle* h, const uint8_t* name, uint32_t len, const char* rate,
                   uint32_t rate_len, const char* count, uint32_t count_len, int64_t now,
                   char* body, uint32_t* body_len, int64_t* retry_after_ns);
+
+/* Throttled sweep: the buckets a rate denies now, with their retry times.
+ * Peek answers for names the caller already has; this answers the reverse
+ * question -- which keys are throttled right now, and until when -- for a deny
+ * list pushed to a load balancer or edge cache, a dashboard of throttled
+ * tenants, a "throttled buckets per class" metric.  It is the export sweep's
+ * resumable window walk ("Anti-entropy sweep") with Peek's evaluation as the
+ * filter; a caller loops phip_export_throttled until st->done.
+ *
+ * Rules.  The table stores no rate: a rate arrives with each request
+ * (api.go:55-65).  The caller says which rate belongs to which bucket with
+ * 1..PHIP_THROTTLE_MAX_RULES rules, name prefix -> (freq, per, count).
+ *  - Match.  Rule r matches a name iff len >= prefix_len and the first
+ *    prefix_len bytes are equal; prefix_len == 0 matches every name, the empty
+ *    one too.  The first matching rule in array order gives the bucket's
+ *    query; bytes of `prefix` past prefix_len are ignored.  A bucket that no
+ *    rule matches is not reported.  phip_throttle_match is the same function
+ *    on the host (no handle, no GPU), the one the kernels call.
+ *  - A prefix is at most PHIP_THROTTLE_MAX_PREFIX = 16 bytes: a table record
+ *    carries an inline name (up to 22 bytes) whole and the first 16 bytes of a
+ *    longer one, so matching never reads the name arena.
+ *  - count is used as given, 0 included, as phip_peek uses it.
+ *
+ * Which buckets.  A record is reported iff it is published, its name is at
+ * most PHIP_MAX_NAME_LEN bytes (a 232..255-byte name that came in by datagram
+ * is skipped, as the export sweep skips it), a rule matches, and with that
+ * rule's (freq, per, count) Take evaluated on a copy of the record's state
+ * (step 2 of "Peek") is denied at `now` and also denied at now + min_wait_ns,
+ * the sum saturating at INT64_MAX.  With min_wait_ns == 0 the two conditions
+ * are one; min_wait_ns > 0 leaves out denials that end within the wait, which
+ * are not worth caching.  By Peek's monotonicity the second condition is
+ * retry_at > now + min_wait_ns, or never; the contract is the predicate, not
+ * that formula.  min_wait_ns < 0 is PHIP_ERR_INVALID.  Unlike the export
+ * sweep, a zero-state record is not special: it is evaluated like any other
+ * (added == 0 becomes capacity, bucket.go:194-196).
+ *
+ * Per entry.  Entry i's name is names[offs[i] .. offs[i+1]), offs[0] = 0, the
+ * names back to back (an empty name is an entry of no bytes).  retry_at[i] is
+ * exactly what phip_peek gives a denied query: the least t > now that grants,
+ * or PHIP_PEEK_NEVER; remaining[i] is what the denied TAKE reports; rule[i] is
+ * the index of the rule that matched.  All are bit-exact against phip_peek /
+ * phip_peek_eval for the same (state, now, rate, count).  Within a call the
+ * entries are in slot order.  retry_at, remaining and rule may each be NULL.
+ *
+ * Bounds, window, cursor, rebuilds: the export sweep's.  A call writes at most
+ * max_entries entries and at most names_cap name bytes, cut at a record, and
+ * sets *cur to the slot of the first record it did not write, or to the end
+ * of the slots it covered.  It reads the slots [cur->slot, cur->slot + W)
+ * clipped to the table, W = max(4 * max_entries, PHIP_SWEEP_TILE) rounded up
+ * to a multiple of PHIP_SWEEP_TILE, and never the rest.  A cursor of another
+ * table layout starts again at slot 0 and the call reports restarted = 1; a
+ * zeroed cursor never does.  st->n, st->bytes (= offs[n]: name bytes only),
+ * st->slots_scanned and st->done are filled as there.  max_entries == 0 or
+ * names_cap < PHIP_MAX_NAME_LEN is PHIP_ERR_INVALID, so every valid call makes
+ * progress.
+ *
+ * Count mode.  PHIP_SWEEP_COUNT with out == NULL: one pass over the whole
+ * table; st->n and st->bytes receive what a whole sweep would report, and
+ * *cur is left untouched.
+ *
+ * Pointers.  rules, cur, st and the phip_throttled_out struct are host memory.
+ * The five buffers inside it are host memory, or device memory with
+ * PHIP_DEVICE_PTRS (no alignment asked beyond each column's own type; every
+ * byte of names_cap is budget).  A host-pointer call copies back only what
+ * was written.
+ *
+ * Errors and locking.  n_rules outside 1..PHIP_THROTTLE_MAX_RULES, a
+ * prefix_len above PHIP_THROTTLE_MAX_PREFIX, NULL rules / cur / st, a missing
+ * out / names / offs outside count mode, or any flag bit other than
+ * PHIP_DEVICE_PTRS and PHIP_SWEEP_COUNT is PHIP_ERR_INVALID, with nothing read
+ * from the table and nothing written.  The call is serialised with the
+ * handle's other calls; a batch queued with PHIP_RECV_ASYNC is finished first,
+ * its error is this call's, and the sweep sees its merges.
+ *
+ * Nothing is written to the handle: table, arena, change set, layout count,
+ * the hot directory and phip_len stay as they are.
+ *
+ * Stated limit.  `created` is local to a node (it is not on the wire), so the
+ * list is this node's view.  Not here: rates stored per bucket, prefixes over
+ * 16 bytes, a group-wide sweep (each owner's phip_group_handle can be swept
+ * meanwhile). */
+#define PHIP_THROTTLE_MAX_RULES 8
+#define PHIP_THROTTLE_MAX_PREFIX 16
+typedef struct phip_throttle_rule { /* 48 bytes */
+  uint8_t prefix[PHIP_THROTTLE_MAX_PREFIX];
+  uint32_t prefix_len; /* 0..16; 0 matches every name, the empty one too */
+  uint32_t reserved;
+  int64_t freq, per;   /* Rate{freq, per} */
+  uint64_t count;      /* tokens asked for, used as given (as phip_peek) */
+} phip_throttle_rule;
+typedef struct phip_throttled_out { /* names and offs required outside count mode */
+  uint8_t* names;      /* entry i's name is names[offs[i] .. offs[i+1]) */
+  uint64_t names_cap;
+  uint64_t* offs;      /* max_entries + 1 entries, offs[0] = 0 */
+  uint32_t max_entries, reserved;
+  int64_t* retry_at;   /* may be NULL */
+  uint64_t* remaining; /* may be NULL */
+  uint8_t* rule;       /* may be NULL: index of the rule that matched */
+} phip_throttled_out;
+int phip_export_throttled(phip_handle* h, phip_sweep_cursor* cur, const phip_throttle_rule* rules,
+                          uint32_t n_rules, int64_t now, int64_t min_wait_ns,
+                          const phip_throttled_out* out, phip_sweep_stats* st, uint32_t flags);
+/* host only, no handle: *rule_out = index of the first matching rule, or -1;
+ * PHIP_ERR_INVALID for n_rules outside 1..8, a prefix_len over 16, NULL rules
+ * or rule_out, or a NULL name with len > 0 */
+int phip_throttle_match(const phip_throttle_rule* rules, uint32_t n_rules, const uint8_t* name,
+                        uint32_t len, int32_t* rule_out);
 
 /* ---- host helpers (no device work) ---- */
 /* ParseRate: returns 0 or <0 on error; freq and per receive the values Go

@@ -9,7 +9,7 @@ from ._lib import EXPORTS, LIB_PATH, build_id, load  # noqa: F401
 from .engine import (BucketState, GPUGroup, GPURepo, PatrolHipError, Ring, TakeBatcher,  # noqa: F401
                      digest_diff, digest_fold, incast_replies, marshal, names_blob, parse_rate,
                      udp_recv_batch, udp_send_batch)
-from .engine import peek_eval  # noqa: F401
+from .engine import peek_eval, throttle_match  # noqa: F401
 
 __all__ = ["GPURepo", "GPUGroup", "BucketState", "PatrolHipError", "Ring", "TakeBatcher", "parse_rate", "marshal",
            "names_blob", "udp_recv_batch", "udp_send_batch", "incast_replies", "digest_diff",

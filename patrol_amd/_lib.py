@@ -38,6 +38,7 @@ EXPORTS = [
     "phip_batcher_egress_next", "phip_batcher_egress_done",
     "phip_export_changed",
     "phip_peek", "phip_peek_eval", "phip_api_peek",
+    "phip_export_throttled", "phip_throttle_match",
 ]
 
 PHIP_OK = 0
@@ -69,6 +70,9 @@ SWEEP_TILE = 4096        # PHIP_SWEEP_TILE: the sweep window's granule, slots
 PACKET_SIZE = 256
 BUCKET_FIXED_SIZE = 25   # PHIP_BUCKET_FIXED_SIZE: added, taken, elapsed, name length
 DIGEST_MAX_LOG2_PARTS = 20
+MAX_NAME_LEN = 231         # PHIP_MAX_NAME_LEN
+THROTTLE_MAX_RULES = 8     # PHIP_THROTTLE_MAX_RULES
+THROTTLE_MAX_PREFIX = 16   # PHIP_THROTTLE_MAX_PREFIX
 
 
 class phip_config(C.Structure):
@@ -153,6 +157,17 @@ class phip_results(C.Structure):
 class phip_peek_results(C.Structure):
     _fields_ = [("status", C.c_void_p), ("remaining", C.c_void_p), ("have", C.c_void_p),
                 ("retry_at", C.c_void_p), ("state", C.c_void_p)]
+
+
+class phip_throttle_rule(C.Structure):
+    _fields_ = [("prefix", C.c_uint8 * 16), ("prefix_len", C.c_uint32), ("reserved", C.c_uint32),
+                ("freq", C.c_int64), ("per", C.c_int64), ("count", C.c_uint64)]
+
+
+class phip_throttled_out(C.Structure):
+    _fields_ = [("names", C.c_void_p), ("names_cap", C.c_uint64), ("offs", C.c_void_p),
+                ("max_entries", C.c_uint32), ("reserved", C.c_uint32), ("retry_at", C.c_void_p),
+                ("remaining", C.c_void_p), ("rule", C.c_void_p)]
 
 
 _lib = None
@@ -305,5 +320,12 @@ def load(path: str = LIB_PATH):
                                      C.POINTER(u64), C.POINTER(i64)]
         L.phip_api_peek.argtypes = [vp, C.c_char_p, u32, C.c_char_p, u32, C.c_char_p, u32, i64,
                                     C.c_char_p, C.POINTER(u32), C.POINTER(i64)]
+    if hasattr(L, "phip_export_throttled"):
+        L.phip_export_throttled.argtypes = [vp, C.POINTER(phip_sweep_cursor),
+                                            C.POINTER(phip_throttle_rule), u32, i64, i64,
+                                            C.POINTER(phip_throttled_out),
+                                            C.POINTER(phip_sweep_stats), u32]
+        L.phip_throttle_match.argtypes = [C.POINTER(phip_throttle_rule), u32, C.c_char_p, u32,
+                                          C.POINTER(C.c_int32)]
     _lib = L
     return L

@@ -191,31 +191,24 @@ struct PeekVoteSelf {
   __host__ __device__ inline bool operator()(bool pending) const { return pending; }
 };
 
-// The evaluation.  Step 1 is take_step itself on the copy, so status,
-// remaining and have are what a TAKE op reports.  A denied query then looks
-// for the least reading in (now, INT64_MAX] that grants: from a denial the
-// verdict is monotone in the clock, so after one probe of
-// INT64_MAX (false: never) a bisection keeps lo denied / hi granted and halves
-// hi - lo <= 2^64 - 1 in 64 steps: at most 66 verdicts a query, none when it
-// was granted.  `any` turns "this lane still searches" into "some lane of the
-// wave does" (k_peek: a ballot), so the loop is uniform across a wave and a
-// wave without a denial skips it; every lane of the wave must make the call.
+// The retry search of a query denied at `now` (search == true; a lane with
+// search == false gets `now` back): the least reading in (now, INT64_MAX] that
+// grants, or PHIP_PEEK_NEVER.  From a denial the verdict is monotone in the
+// clock, so after one probe of INT64_MAX (false: never) a
+// bisection keeps lo denied / hi granted and halves hi - lo <= 2^64 - 1 in 64
+// steps: at most 65 verdicts.  `any` turns "this lane still searches" into
+// "some lane of the wave does" (k_peek, k_throttle_write: a ballot), so the
+// loop is uniform across a wave and a wave without a searching lane skips it;
+// every lane of the wave must make the call.
 template <class Vote = PeekVoteSelf>
-__host__ __device__ inline PeekResult peek_eval(double added, double taken, i64 elapsed,
-                                                i64 created, i64 now, i64 interval,
-                                                double capacity, double t, Vote any = Vote()) {
-  double a = added, k = taken;
-  i64 e = elapsed;
-  const TakeResult r = take_step(a, k, e, created, now, interval, capacity, t);
-  PeekResult out{r.remaining, r.have_bits, now, r.ok};
-  const double fi = (double)interval;
-  const double tokens = (added == 0 ? capacity : added) - taken;
-  const double missing = capacity - tokens;
+__host__ __device__ inline i64 retry_search(bool search, i64 created, i64 elapsed, i64 now,
+                                            i64 interval, double fi, double tokens, double missing,
+                                            double t, Vote any = Vote()) {
+  i64 retry_at = now;
   const i64 kMax = 0x7FFFFFFFFFFFFFFFll;
-  bool search = !r.ok;
   if (any(search)) {
     if (search && !take_ok_at(created, elapsed, kMax, interval, fi, tokens, missing, t)) {
-      out.retry_at = (i64)kSign;   // PHIP_PEEK_NEVER
+      retry_at = (i64)kSign;   // PHIP_PEEK_NEVER
       search = false;
     }
   }
@@ -230,8 +223,95 @@ __host__ __device__ inline PeekResult peek_eval(double added, double taken, i64 
       else lo = mid;
     }
   }
-  if (search) out.retry_at = hi;
+  if (search) retry_at = hi;
+  return retry_at;
+}
+
+// The evaluation.  Step 1 is take_step itself on the copy, so status,
+// remaining and have are what a TAKE op reports.  A denied query then runs
+// retry_search: at most 66 verdicts a query, none when it was granted.  Every
+// lane of a wave must make the call (retry_search's vote).
+template <class Vote = PeekVoteSelf>
+__host__ __device__ inline PeekResult peek_eval(double added, double taken, i64 elapsed,
+                                                i64 created, i64 now, i64 interval,
+                                                double capacity, double t, Vote any = Vote()) {
+  double a = added, k = taken;
+  i64 e = elapsed;
+  const TakeResult r = take_step(a, k, e, created, now, interval, capacity, t);
+  PeekResult out{r.remaining, r.have_bits, now, r.ok};
+  const double fi = (double)interval;
+  const double tokens = (added == 0 ? capacity : added) - taken;
+  const double missing = capacity - tokens;
+  out.retry_at = retry_search(!r.ok, created, elapsed, now, interval, fi, tokens, missing, t, any);
   return out;
+}
+
+// ---------------------------------------------------------- throttled -----
+// phip_export_throttled / phip_throttle_match (patrolhip.h "Throttled sweep"):
+// the caller's rule table as the kernels take it, by value.  A rule's prefix
+// is two little-endian words (its byte masks follow from its length), so that
+// a match is two and-compares on the first 16 name bytes a record carries
+// (Rec: an inline name has all its bytes in the record, a long one its first
+// 16); the rate is held as take_step wants it, derived once on the host as
+// k_pack_ops does.
+struct ThrottleRule {
+  u64 p0, p1;        // prefix bytes 0..7, 8..15; bytes past len are zero
+  i64 interval;      // rate_interval(freq, per)
+  double capacity;   // float64(freq)
+  double t;          // float64(count)
+  u32 len;
+  u32 pad;
+};
+struct ThrottleRules {
+  ThrottleRule r[PHIP_THROTTLE_MAX_RULES];
+  u32 n;
+};
+
+__host__ __device__ inline u64 low_bytes_mask(u32 k) {   // k in 0..8
+  return k >= 8 ? ~0ull : (1ull << (8 * k)) - 1;
+}
+
+inline ThrottleRule throttle_rule(const phip_throttle_rule& in) {
+  ThrottleRule o{};
+  u64 w[2] = {0, 0};
+  for (u32 k = 0; k < in.prefix_len; ++k) w[k >> 3] |= (u64)in.prefix[k] << ((k & 7) * 8);
+  o.p0 = w[0];
+  o.p1 = w[1];
+  o.interval = rate_interval(in.freq, in.per);
+  o.capacity = (double)in.freq;
+  o.t = (double)in.count;
+  o.len = in.prefix_len;
+  return o;
+}
+
+// The first rule, in array order, that matches a name of `len` bytes whose
+// first 16 bytes are n0, n1 (little-endian words; what lies past the name does
+// not matter: a rule longer than the name never matches, and a shorter one
+// masks it off): its index, or -1, and its rate.  A rule matches iff len >=
+// its prefix length and the first prefix-length bytes are equal.  The loop is
+// uniform (the rules are kernel arguments, read with scalar loads); a lane
+// keeps its first hit by selects, so no lane indexes the arguments.
+struct ThrottleHit {
+  int rule;
+  i64 interval;
+  double capacity, t;
+};
+__host__ __device__ inline ThrottleHit throttle_match(const ThrottleRules& R, u64 n0, u64 n1,
+                                                      u32 len) {
+  ThrottleHit h{-1, 0, 0.0, 0.0};
+  u32 i = 0;
+  do {   // (R.n >= 1: every caller checks n_rules first)
+    const ThrottleRule& q = R.r[i];
+    // (& not &&: three compares and selects, no branch per clause)
+    const u64 m0 = low_bytes_mask(q.len < 8 ? q.len : 8);   // 0xFF for each prefix byte
+    const u64 m1 = low_bytes_mask(q.len < 8 ? 0 : q.len - 8);
+    const bool m = (h.rule < 0) & (len >= q.len) & ((n0 & m0) == q.p0) & ((n1 & m1) == q.p1);
+    h.rule = m ? (int)i : h.rule;
+    h.interval = m ? q.interval : h.interval;
+    h.capacity = m ? q.capacity : h.capacity;
+    h.t = m ? q.t : h.t;
+  } while (++i < R.n);
+  return h;
 }
 
 // Bucket.Merge for one `other` (bucket.go:250-260) on raw values.

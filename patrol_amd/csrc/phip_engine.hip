@@ -4010,6 +4010,161 @@ int phip_export_sweep_parts(phip_handle* h, phip_sweep_cursor* cur, int64_t now,
                       max_msgs, st, flags);
 }
 
+// Throttled sweep (patrolhip.h "Throttled sweep"; kernels in phip_kernels.hpp
+// "throttled sweep"): export_sweep's window, cursor, tile arrays, scan and
+// read-backs, with the rule table -- rates derived here, once -- as a kernel
+// argument.  Nothing of the handle changes but its scratch buffers.
+int phip_export_throttled(phip_handle* h, phip_sweep_cursor* cur, const phip_throttle_rule* rules,
+                          uint32_t n_rules, int64_t now, int64_t min_wait_ns,
+                          const phip_throttled_out* out, phip_sweep_stats* st, uint32_t flags) {
+  if (!h || !cur || !st || !rules) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;   // (finishes a queued PHIP_RECV_ASYNC batch)
+  if (flags & ~(PHIP_DEVICE_PTRS | PHIP_SWEEP_COUNT))
+    return set_err(h, PHIP_ERR_INVALID, "throttled: unknown flag bits 0x%x", flags);
+  if (n_rules < 1 || n_rules > PHIP_THROTTLE_MAX_RULES)
+    return set_err(h, PHIP_ERR_INVALID, "throttled: n_rules must be 1..%d", PHIP_THROTTLE_MAX_RULES);
+  ThrottleRules R{};
+  R.n = n_rules;
+  for (u32 i = 0; i < n_rules; ++i) {
+    if (rules[i].prefix_len > PHIP_THROTTLE_MAX_PREFIX)
+      return set_err(h, PHIP_ERR_INVALID, "throttled: rule %u has a prefix over %d bytes", i,
+                     PHIP_THROTTLE_MAX_PREFIX);
+    R.r[i] = throttle_rule(rules[i]);
+  }
+  if (min_wait_ns < 0)
+    return set_err(h, PHIP_ERR_INVALID, "throttled: min_wait_ns must not be negative");
+  i64 later;
+  if (__builtin_add_overflow((i64)now, (i64)min_wait_ns, &later)) later = INT64_MAX;
+  const bool dev = flags & PHIP_DEVICE_PTRS;
+  int rc;
+  u64 c[kSwWords] = {};
+  phip_sweep_stats s{};
+  if (flags & PHIP_SWEEP_COUNT) {
+    if (out) return set_err(h, PHIP_ERR_INVALID, "throttled: count mode takes no output");
+    u64* ctr;
+    if ((rc = ensure(h, B_SWEEP, kSwWords, &ctr))) return rc;
+    HIPCHK(h, hipMemsetAsync(ctr, 0, kSwWords * sizeof(u64), h->stream));
+    {
+      Launch l(h, "k_throttle_count");
+      const unsigned grid = std::min<unsigned>(grid_for(h->cap), 8u * (unsigned)h->ncu);
+      k_throttle_count<false><<<grid, kBlock, 0, h->stream>>>(h->recs, 0, h->cap, now, later, nullptr,
+                                                              nullptr, ctr, R);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    s.n = c[kSwN];
+    s.bytes = c[kSwBytes];
+    s.slots_scanned = h->cap;
+    *st = s;
+    return PHIP_OK;
+  }
+  if (!out || !out->names || !out->offs)
+    return set_err(h, PHIP_ERR_INVALID, "throttled: out, its names and its offs are required");
+  const phip_throttled_out o = *out;
+  if (!o.max_entries) return set_err(h, PHIP_ERR_INVALID, "throttled: max_entries must be positive");
+  if (o.names_cap < PHIP_MAX_NAME_LEN)
+    return set_err(h, PHIP_ERR_INVALID, "throttled: names_cap below one name (%d bytes)",
+                   PHIP_MAX_NAME_LEN);
+  const u64 budget = o.names_cap;
+
+  u64 s0 = cur->slot;
+  if ((cur->slot || cur->layout) && cur->layout != h->layout_gen) {
+    s0 = 0;
+    s.restarted = 1;
+  }
+  s0 = std::min<u64>(s0, h->cap);
+  u64 W = std::max<u64>(4ull * o.max_entries, PHIP_SWEEP_TILE);
+  W = (W + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE * PHIP_SWEEP_TILE;
+  const u64 s_end = std::min<u64>(s0 + W, h->cap);
+  s.slots_scanned = s_end - s0;
+  const u32 ntiles = (u32)((s_end - s0 + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE);
+  u64 next = s_end;
+  if (ntiles) {
+    // one buffer: the counters, the tiles' byte sums, the tiles' counts
+    u64* ctr;
+    if ((rc = ensure(h, B_SWEEP, kSwWords + (size_t)ntiles + ((size_t)ntiles + 1) / 2, &ctr)))
+      return rc;
+    u64* tile_bytes = ctr + kSwWords;
+    u32* tile_cnt = (u32*)(tile_bytes + ntiles);
+    {
+      Launch l(h, "k_throttle_count");
+      k_throttle_count<true><<<ntiles, kBlock, 0, h->stream>>>(h->recs, s0, s_end, now, later,
+                                                               tile_cnt, tile_bytes, ctr, R);
+    }
+    {
+      Launch l(h, "k_sweep_scan");
+      k_sweep_scan<<<1, kSweepBlock, 0, h->stream>>>(tile_cnt, tile_bytes, ntiles, ctr);
+    }
+    HIPCHK(h, hipGetLastError());
+    ThrottledOut d{o.names, reinterpret_cast<u64*>(o.offs), reinterpret_cast<i64*>(o.retry_at),
+                   reinterpret_cast<u64*>(o.remaining), o.rule};
+    if (!dev) {
+      // staging sized by what the window holds, not by the caller's caps
+      HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      const size_t ne = (size_t)std::min<u64>(o.max_entries, c[kSwN]);
+      if ((rc = ensure(h, B_EXPORT, (size_t)std::min<u64>(o.names_cap, c[kSwBytes]), &d.names)) ||
+          (rc = ensure(h, B_OFFS, ne + 1, &d.offs)) ||
+          (rc = out_buf(h, B_PEEKAT, reinterpret_cast<i64*>(o.retry_at), ne, false, &d.retry_at)) ||
+          (rc = out_buf(h, B_REM, reinterpret_cast<u64*>(o.remaining), ne, false, &d.remaining)) ||
+          (rc = out_buf(h, B_STATUS, o.rule, ne, false, &d.rule)))
+        return rc;
+    }
+    {
+      // (long names are bounded by the arena's size, as in export_sweep)
+      Launch l(h, "k_throttle_write");
+      k_throttle_write<<<ntiles, kSweepBlock, 0, h->stream>>>(
+          h->recs + s0, (u32)(s_end - s0), h->arena, h->arena_cap, now, later, o.max_entries, budget,
+          d, ctr, R);   // (the tile arrays: behind ctr, by the layout above)
+    }
+    // the retry search, one lane per written entry; their number is on the
+    // device (the counter word), the grid goes by what the host knows of it:
+    // the window's total after the scan, or (device pointers) the window
+    const u64 most = std::min<u64>(o.max_entries, dev ? s_end - s0 : c[kSwN]);
+    if (d.retry_at && most) {
+      Launch l(h, "k_throttle_retry");
+      const unsigned grid = std::min<unsigned>(grid_for(most), 16u * (unsigned)h->ncu);
+      k_throttle_retry<<<grid, kBlock, 0, h->stream>>>(h->recs + s0, (u32)(s_end - s0), now,
+                                                       d.retry_at, ctr, R);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (c[kSwErr])
+      return set_err(h, PHIP_ERR_INVALID, "internal: throttled sweep met a long name outside the arena");
+    if (c[kSwN] > o.max_entries || c[kSwBytes] > budget)
+      return set_err(h, PHIP_ERR_INVALID, "internal: throttled sweep wrote %llu entries, %llu bytes",
+                     (unsigned long long)c[kSwN], (unsigned long long)c[kSwBytes]);
+    s.n = c[kSwN];
+    s.bytes = c[kSwBytes];
+    if (c[kSwNext] != ~0ull) next = s0 + c[kSwNext];   // (the kernel counts from the window's first)
+    if (!dev) {
+      // only what was written travels back
+      if (s.bytes)
+        HIPCHK(h, hipMemcpyAsync(o.names, d.names, s.bytes, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(o.offs, d.offs, (s.n + 1) * sizeof(u64), hipMemcpyDeviceToHost,
+                               h->stream));
+      if ((rc = copy_back(h, reinterpret_cast<i64*>(o.retry_at), d.retry_at, s.n, false)) ||
+          (rc = copy_back(h, reinterpret_cast<u64*>(o.remaining), d.remaining, s.n, false)) ||
+          (rc = copy_back(h, o.rule, d.rule, s.n, false)))
+        return rc;
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+  } else if (dev) {
+    HIPCHK(h, hipMemsetAsync(o.offs, 0, sizeof(u64), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  } else {
+    o.offs[0] = 0;
+  }
+  cur->slot = next;
+  cur->layout = h->layout_gen;
+  s.done = next >= h->cap;
+  *st = s;
+  return PHIP_OK;
+}
+
 // Change-set export (patrolhip.h "Change set"; kernels in phip_kernels.hpp
 // "change set"): count per tile of the bit sets, the egress' scan, write.  The
 // totals of a full drain stand in the egress counter words after the scan; the

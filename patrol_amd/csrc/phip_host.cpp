@@ -269,6 +269,24 @@ int phip_api_peek(phip_handle* h, const uint8_t* name, uint32_t len, const char*
   return ok ? 200 : 429;
 }
 
+// Throttled sweep on the host (patrolhip.h "Throttled sweep"): phip::throttle_match
+// is the function the sweep's kernels call, over the same derived rule table.
+int phip_throttle_match(const phip_throttle_rule* rules, uint32_t n_rules, const uint8_t* name,
+                        uint32_t len, int32_t* rule_out) {
+  if (!rules || !rule_out || (!name && len) || n_rules < 1 || n_rules > PHIP_THROTTLE_MAX_RULES)
+    return PHIP_ERR_INVALID;
+  phip::ThrottleRules R{};
+  R.n = n_rules;
+  for (uint32_t i = 0; i < n_rules; ++i) {
+    if (rules[i].prefix_len > PHIP_THROTTLE_MAX_PREFIX) return PHIP_ERR_INVALID;
+    R.r[i] = phip::throttle_rule(rules[i]);
+  }
+  u64 w[2] = {0, 0};   // the first 16 name bytes, as a record carries them
+  for (uint32_t k = 0; k < len && k < 16; ++k) w[k >> 3] |= (u64)name[k] << ((k & 7) * 8);
+  *rule_out = phip::throttle_match(R, w[0], w[1], len).rule;
+  return PHIP_OK;
+}
+
 // Partition digests (patrolhip.h "Partition digests"): the two host helpers.
 int phip_digest_diff(const phip_digest_part* a, const phip_digest_part* b, uint32_t log2_parts,
                      uint64_t* mask, uint64_t* ndiff) {

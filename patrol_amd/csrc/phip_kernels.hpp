@@ -6774,4 +6774,259 @@ __global__ __launch_bounds__(kBlock) void k_peek(NamesOffs src, OpView ov, u32 n
   if (po.state) po.state[i] = st;
 }
 
+// ----------------------------------------------------- throttled sweep ----
+// phip_export_throttled (patrolhip.h "Throttled sweep"): the export sweep's
+// count -> scan -> write over a window of tiles, with Peek's evaluation as the
+// filter and names, retry times and remainders as the output.  k_sweep_scan,
+// the tile arrays and the counter words are the export sweep's own.
+//   k_throttle_count  per tile (or, in count mode, over the whole table) the
+//                     reported records and their name bytes: the verdicts
+//                     only, no retry search;
+//   k_throttle_write  k_sweep_write's ranking; the written entries store
+//                     their name, offs, remaining, rule and, for the next
+//                     kernel, their slot;
+//   k_throttle_retry  one lane per written entry: the retry search.
+// The rules travel by value (ThrottleRules, rates derived on the host).
+//
+// An entry's size is its name length, 0 for the empty name, so "qualifies" is
+// a bit of its own everywhere and never `size != 0`.
+struct Throttled {
+  bool q;          // reported: published, a name that fits, a rule, denied at both readings
+  u32 len;         // name bytes
+  int rule;
+  u64 remaining;   // what the denied TAKE reports
+};
+
+// The clock-free parts of a record's verdict under its rule (take_ok_at's
+// operands, as peek_eval derives them).
+struct ThrottleParts {
+  ThrottleHit hit;
+  double fi, tokens, missing;
+};
+
+// Every lane walks the rules, an empty slot's too: a wave has live lanes
+// anyway, and one flat region keeps the scalar registers of nested ones free.
+__device__ __forceinline__ ThrottleParts throttle_parts(const Rec& r, const ThrottleRules& R) {
+  const u32 len = (u32)(r.name0 & 0xFFu);
+  // the first 16 name bytes: an inline name starts at canonical byte 2 (zero
+  // padded), a long one keeps them at canonical bytes 8..23
+  const bool inl = len <= kInlineName;
+  const u64 n0 = inl ? (r.name0 >> 16) | (r.name1 << 48) : r.name1;
+  const u64 n1 = inl ? (r.name1 >> 16) | (r.name2 << 48) : r.name2;
+  ThrottleParts p;
+  p.hit = throttle_match(R, n0, n1, len);
+  const double added = as_f64(dec_f64(r.added)), taken = as_f64(dec_f64(r.taken));
+  p.fi = (double)p.hit.interval;
+  p.tokens = (added == 0 ? p.hit.capacity : added) - taken;
+  p.missing = p.hit.capacity - p.tokens;
+  return p;
+}
+
+// `later` = now + min_wait_ns, saturated; later == now: one reading.
+__device__ __forceinline__ Throttled throttle_eval(const Rec& r, const ThrottleRules& R, i64 now,
+                                                   i64 later) {
+  const u32 len = (u32)(r.name0 & 0xFFu);
+  const ThrottleParts p = throttle_parts(r, R);
+  Throttled o{};
+  if (r.tag && (rec_flags(r) & kRecPublished) && len <= PHIP_MAX_NAME_LEN && p.hit.rule >= 0) {
+    double a = as_f64(dec_f64(r.added)), k = as_f64(dec_f64(r.taken));
+    i64 e = r.elapsed;
+    const TakeResult tr =
+        take_step(a, k, e, r.created, now, p.hit.interval, p.hit.capacity, p.hit.t);
+    // (with later == now the second verdict is the first again: no uniform
+    // test of that, whose mask the write pass would carry through its loop)
+    bool denied = !tr.ok;
+    if (denied)
+      denied = !take_ok_at(r.created, r.elapsed, later, p.hit.interval, p.fi, p.tokens, p.missing,
+                           p.hit.t);
+    o = Throttled{denied, len, p.hit.rule, tr.remaining};
+  }
+  return o;
+}
+
+// Count pass: k_sweep_count's two grids (kTiles: workgroup t sums tile t of
+// the window; otherwise count mode's striding grid with one add per wave).
+template <bool kTiles>
+__global__ __launch_bounds__(kBlock) void k_throttle_count(const Rec* __restrict__ recs, u64 s0,
+                                                           u64 s_end, i64 now, i64 later,
+                                                           u32* __restrict__ tile_cnt,
+                                                           u64* __restrict__ tile_bytes, u64* ctr,
+                                                           ThrottleRules R) {
+  u32 n = 0;
+  u64 b = 0;
+  if (kTiles) {
+    const u64 t0 = s0 + (u64)blockIdx.x * kSweepTile;
+#pragma unroll 2
+    for (u32 k = 0; k < kSweepTile / kBlock; ++k) {
+      const u64 s = t0 + (u64)k * kBlock + threadIdx.x;
+      if (s >= s_end) break;
+      const Throttled v = throttle_eval(load_rec(&recs[s]), R, now, later);
+      n += v.q;
+      b += v.q ? v.len : 0u;
+    }
+  } else {
+    const u64 stride = (u64)gridDim.x * kBlock;
+    for (u64 s = s0 + (u64)blockIdx.x * kBlock + threadIdx.x; s < s_end; s += stride) {
+      const Throttled v = throttle_eval(load_rec(&recs[s]), R, now, later);
+      n += v.q;
+      b += v.q ? v.len : 0u;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    n += __shfl_xor(n, d);
+    b += __shfl_xor(b, d);
+  }
+  if (kTiles) {
+    __shared__ u32 wn[kBlock / 64];
+    __shared__ u64 wb[kBlock / 64];
+    if (__lane_id() == 0) { wn[threadIdx.x >> 6] = n; wb[threadIdx.x >> 6] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      u32 tn = 0;
+      u64 tb = 0;
+      for (u32 i = 0; i < kBlock / 64; ++i) { tn += wn[i]; tb += wb[i]; }
+      tile_cnt[blockIdx.x] = tn;
+      tile_bytes[blockIdx.x] = tb;
+    }
+  } else if (__lane_id() == 0) {
+    if (n) atomicAdd(&ctr[kSwN], (u64)n);
+    if (b) atomicAdd(&ctr[kSwBytes], b);
+  }
+}
+
+// The `len` name bytes of record r at d, put_datagram's name part: whole
+// 8-byte words wherever eight bytes of the name are left, single bytes for
+// the rest, so no lane writes outside its own entry.
+template <class Err>
+__device__ __forceinline__ void put_name(u8* d, const Rec& r, u32 len, const u8* __restrict__ arena,
+                                         u64 arena_used, Err* err) {
+  if (len <= kInlineName) {
+    const u64 w[4] = {r.name0, r.name1, r.name2, 0};
+    u32 j = 0;
+#pragma unroll
+    for (u32 q = 0; q < 3; ++q)
+      if (j + 8 <= len) {
+        sweep_put8(d + j, (w[q] >> 16) | (w[q + 1] << 48));
+        j += 8;
+      }
+    for (; j < len; ++j) d[j] = (u8)(w[(j + 2) >> 3] >> (((j + 2) & 7) * 8));
+  } else {
+    const u64 oa = r.name0 >> 32;
+    if (oa + len > arena_used) {
+      *err = 1;
+      return;
+    }
+    u32 j = 0;
+    for (; j + 8 <= len; j += 8) {
+      u64 x;
+      __builtin_memcpy(&x, arena + oa + j, 8);
+      sweep_put8(d + j, x);
+    }
+    for (; j < len; ++j) d[j] = arena[oa + j];
+  }
+}
+
+struct ThrottledOut {
+  u8* names;
+  u64* offs;
+  i64* retry_at;    // the three columns may be null
+  u64* remaining;
+  u8* rule;
+};
+
+// Write pass: k_sweep_write's workgroup, steps, packing (qualifies << 19 |
+// name bytes; a step holds at most 512 * 231 bytes), scan and cut.  Entry
+// `rank` is written iff rank < max_entries and its end <= budget: its name at
+// its start byte, offs[rank + 1] = its end, remaining and rule where asked
+// for, and in retry_at[rank] its slot, for k_throttle_retry to replace.  The
+// first record not written is told by the qualify bit, not by a size.  Slots
+// are counted from the window's first (win = recs + s0, nwin of them, 32 bits:
+// the host adds s0 to the next-slot word); a lane past the window reads the
+// window's last record and drops it.  The tile arrays stand behind the counter
+// words, one entry per workgroup.
+__global__ __launch_bounds__(kSweepBlock) void k_throttle_write(
+    const Rec* __restrict__ win, u32 nwin, const u8* __restrict__ arena, u64 arena_used, i64 now,
+    i64 later, u32 max_entries, u64 budget, ThrottledOut out, u64* ctr, ThrottleRules R) {
+  __shared__ u32 wtot[2][kSweepBlock / 64];
+  // the sweep buffer's layout: the counters, the tiles' byte sums, their counts
+  const u64* tile_bytes = ctr + kSwWords;
+  const u32* tile_cnt = (const u32*)(tile_bytes + gridDim.x);
+  u64 rank0 = tile_cnt[blockIdx.x];
+  u64 byte0 = tile_bytes[blockIdx.x];
+  if (blockIdx.x == 0 && threadIdx.x == 0) out.offs[0] = 0;
+  if (rank0 > max_entries) return;
+  // (a tile the count pass found without an entry -- by its count, not its
+  // bytes -- holds nothing to write and not the first unwritten record; the
+  // last tile has no successor to tell by and always runs)
+  if (blockIdx.x + 1 < gridDim.x && tile_cnt[blockIdx.x + 1] == rank0) return;
+  const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (uniform in a wave)
+  const u32 t0 = blockIdx.x * kSweepTile + threadIdx.x;
+  for (u32 k = 0; k < kSweepTile / kSweepBlock; ++k) {
+    const u32 s = t0 + k * kSweepBlock;
+    const Rec r = load_rec(&win[s < nwin ? s : nwin - 1]);
+    Throttled v = throttle_eval(r, R, now, later);
+    v.q = v.q && s < nwin;
+    const u32 pk = v.q ? (1u << 19) | v.len : 0u;
+    const u32 sc = wave_incl_scan(pk);
+    if (__lane_id() == 63) wtot[k & 1][wv] = sc;
+    __syncthreads();   // (no thread leaves the loop early: every step has its barrier)
+    // (the waves before this one by a scalar loop: the unrolled form's eight
+    // lane masks would stay in scalar registers through the whole step)
+    u32 pre = 0, tot = 0;
+#pragma unroll 1
+    for (u32 w = 0; w < wv; ++w) pre += wtot[k & 1][w];
+#pragma unroll
+    for (u32 w = 0; w < kSweepBlock / 64; ++w) tot += wtot[k & 1][w];
+    const u32 ex = pre + sc - pk;
+    const u64 rank = rank0 + (ex >> 19);
+    const u64 start = byte0 + (ex & 0x7FFFFu);
+    rank0 += tot >> 19;
+    byte0 += tot & 0x7FFFFu;
+    if (!v.q) continue;
+    const u64 end = start + v.len;
+    if (rank >= max_entries || end > budget) {
+      // the first record not written: its predecessor was (or it has rank 0)
+      if (rank == 0 || (rank - 1 < max_entries && start <= budget)) {
+        ctr[kSwN] = rank;
+        ctr[kSwBytes] = start;
+        ctr[kSwNext] = s;
+      }
+      continue;
+    }
+    out.offs[rank + 1] = end;
+    put_name(out.names + start, r, v.len, arena, arena_used, &ctr[kSwErr]);
+    if (out.remaining) out.remaining[rank] = v.remaining;
+    if (out.rule) out.rule[rank] = (u8)v.rule;
+    if (out.retry_at) out.retry_at[rank] = (i64)s;
+  }
+}
+
+// The retry search of the written entries, one lane per entry, launched behind
+// k_throttle_write when the retry_at column is asked for: entry i < n (n: the
+// entries written, the counter word the write pass left) finds its slot in
+// retry_at[i] (counted from the window's first), reads that record again, derives its rule's clock-free parts
+// and replaces the slot by retry_search's answer.  A lane reads and writes its
+// own entry only.  Striding grid: the trip count is uniform across a wave, so
+// every lane of a wave reaches retry_search's vote (a lane past n searches
+// nothing and stores nothing).
+__global__ __launch_bounds__(kBlock) void k_throttle_retry(const Rec* __restrict__ win, u32 nwin,
+                                                           i64 now, i64* retry_at,
+                                                           const u64* __restrict__ ctr,
+                                                           ThrottleRules R) {
+  const u64 n = ctr[kSwN];
+  const u64 stride = (u64)gridDim.x * kBlock;
+  for (u64 base = (u64)blockIdx.x * kBlock; base < n; base += stride) {
+    const u64 i = base + threadIdx.x;
+    const u64 s = i < n ? (u64)retry_at[i] : 0ull;
+    const bool live = i < n && s < nwin;
+    const Rec r = load_rec(&win[live ? s : 0ull]);
+    const ThrottleParts p = throttle_parts(r, R);
+    const i64 at = retry_search(live, r.created, r.elapsed, now, p.hit.interval, p.fi, p.tokens,
+                                p.missing, p.hit.t, PeekVoteWave());
+    if (live) retry_at[i] = at;
+  }
+}
+
 }  // namespace phip
+

@@ -446,6 +446,78 @@ class GPURepo:
             if st["done"]:
                 return
 
+    # --------------------------------------------------------- throttled --
+    def _throttled_call(self, rules, cur, now, min_wait_ns, out, st, flags):
+        arr = _throttle_rules(rules)
+        rc = self.L.phip_export_throttled(self.h, C.byref(cur), arr, len(arr), int(now),
+                                          int(min_wait_ns), out, C.byref(st), flags)
+        self._queued = None   # a queued batch is finished (or failed)
+        self._check(rc)
+
+    def export_throttled(self, rules, now: int, min_wait_ns: int = 0, cursor=None,
+                         max_entries: int = 1 << 16, names_cap: int | None = None) -> dict:
+        """One call of the throttled sweep (phip_export_throttled): the buckets
+        of the next window of the table that their rule's rate denies at `now`
+        and still denies min_wait_ns later.  rules: a sequence of (prefix bytes
+        of at most 16, freq, per, count); the first rule whose prefix a name
+        starts with gives its query, and a bucket no rule matches is not
+        reported.  At most max_entries entries and names_cap name bytes
+        (default 231 each).  cursor: None to start, then the one the last call
+        returned.  -> dict(names list[bytes], retry_at int64 (the least later
+        clock reading that grants, or PEEK_NEVER), remaining uint64, rule
+        uint8, cursor, n, bytes, slots_scanned, done, restarted); loop until
+        done."""
+        if names_cap is None:
+            names_cap = _lib.MAX_NAME_LEN * max_entries
+        cur, st = self._sweep_cursor(cursor), _lib.phip_sweep_stats()
+        z = max(int(max_entries), 1)
+        names = np.zeros(max(int(names_cap), 1), np.uint8)
+        offs = np.zeros(z + 1, np.uint64)
+        at, rem, rule = np.zeros(z, np.int64), np.zeros(z, np.uint64), np.zeros(z, np.uint8)
+        out = _lib.phip_throttled_out(_ptr(names), int(names_cap), _ptr(offs), int(max_entries), 0,
+                                      _ptr(at), _ptr(rem), _ptr(rule))
+        self._throttled_call(rules, cur, now, min_wait_ns, C.byref(out), st, 0)
+        n = int(st.n)
+        raw = names[:int(st.bytes)].tobytes()
+        d = self._sweep_dict(st)
+        d.update(names=[raw[int(offs[i]):int(offs[i + 1])] for i in range(n)], retry_at=at[:n],
+                 remaining=rem[:n], rule=rule[:n], cursor=(int(cur.slot), int(cur.layout)))
+        return d
+
+    def export_throttled_device(self, rules, now: int, names, offs, cursor, max_entries: int,
+                                min_wait_ns: int = 0, retry_at=None, remaining=None, rule=None):
+        """phip_export_throttled with device pointers: names (uint8 CUDA tensor,
+        every byte of it is budget), offs (int64[max_entries + 1]) and the
+        columns wanted (retry_at / remaining int64[max_entries], rule
+        uint8[max_entries]); the rules stay host memory.
+        -> (n, cursor, stats dict)."""
+        cur, st = self._sweep_cursor(cursor), _lib.phip_sweep_stats()
+        cap = int(names.numel() * names.element_size())
+        out = _lib.phip_throttled_out(_ptr(names), cap, _ptr(offs), int(max_entries), 0,
+                                      _ptr(retry_at), _ptr(remaining), _ptr(rule))
+        self._throttled_call(rules, cur, now, min_wait_ns, C.byref(out), st, DEVICE_PTRS)
+        return int(st.n), (int(cur.slot), int(cur.layout)), self._sweep_dict(st)
+
+    def throttled_count(self, rules, now: int, min_wait_ns: int = 0) -> dict:
+        """What a whole throttled sweep would report (PHIP_SWEEP_COUNT):
+        dict(n, bytes (name bytes), ...), to size buffers by."""
+        cur, st = _lib.phip_sweep_cursor(), _lib.phip_sweep_stats()
+        self._throttled_call(rules, cur, now, min_wait_ns, None, st, _lib.SWEEP_COUNT)
+        return self._sweep_dict(st)
+
+    def throttled(self, rules, now: int, min_wait_ns: int = 0, max_entries: int = 1 << 16,
+                  names_cap: int | None = None):
+        """Generator over a whole throttled sweep: yields export_throttled's
+        dict per call until the cursor reaches the end of the table (a rebuild
+        in between starts it over, "restarted")."""
+        cursor = None
+        while True:
+            d = self.export_throttled(rules, now, min_wait_ns, cursor, max_entries, names_cap)
+            cursor = d["cursor"]
+            yield d
+            if d["done"]:
+                return
+
     # -------------------------------------------------------- change set --
     @staticmethod
     def _changes_dict(st) -> dict:
@@ -836,6 +908,32 @@ def peek_eval(state, now: int, freq: int, per: int, count: int):
     if st < 0:
         raise PatrolHipError(st, "phip_peek_eval")
     return st, int(rem.value), int(have.value), int(at.value)
+
+
+def _throttle_rules(rules):
+    """(prefix bytes, freq, per, count) rows -> a phip_throttle_rule array.  A
+    prefix over 16 bytes keeps its length (the library refuses it) and its
+    first 16 bytes."""
+    arr = (_lib.phip_throttle_rule * len(rules))()
+    for r, (prefix, freq, per, count) in zip(arr, rules):
+        prefix = bytes(prefix)
+        head = prefix[:_lib.THROTTLE_MAX_PREFIX]
+        r.prefix[:len(head)] = list(head)
+        r.prefix_len, r.freq, r.per, r.count = len(prefix), int(freq), int(per), int(count)
+    return arr
+
+
+def throttle_match(rules, name: bytes) -> int:
+    """phip_throttle_match (host only, no handle, no GPU): the index of the
+    first of the throttled sweep's rules ((prefix, freq, per, count) rows)
+    whose prefix `name` starts with, or -1 -- the function the sweep's kernels
+    call."""
+    arr = _throttle_rules(rules)
+    out = C.c_int32(-2)
+    rc = _lib.load().phip_throttle_match(arr, len(arr), bytes(name), len(name), C.byref(out))
+    if rc < 0:
+        raise PatrolHipError(rc, "phip_throttle_match")
+    return int(out.value)
 
 
 class GPUGroup:
