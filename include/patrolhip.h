@@ -1093,6 +1093,83 @@ int phip_incast_replies(const uint8_t* bytes, const uint64_t* offs, uint32_t n,
 int phip_udp_send_batch(int fd, const uint8_t* bytes, const uint64_t* offs, uint32_t n,
                         const uint8_t* peers, uint32_t peer_stride, uint32_t* sent_out);
 
+/* ---- Incast reply egress ----
+ * The unicast answers to a batch's incast requests (repo.go:86-90,160-169) as
+ * datagrams written on the device, ready for phip_udp_send_batch: the Receive
+ * counterpart of "Coalesced egress".  Each call below is the receive call it
+ * is named after -- the same statuses, results, table effects, stop rule,
+ * errors and checked-offset rule; res may be NULL, and so may any column of
+ * it -- and in addition fills rq.  No per-message reply column is needed
+ * anywhere: on a large device batch's common path (its dirty buckets run as a
+ * sub-batch of a few thousand entries) none exists even inside the library.
+ *
+ * Which messages.  Exactly those whose status is PHIP_ST_INCAST_REPLY: a zero
+ * remote state (Bucket.IsZero compares with ==, so a state of -0.0 fields is a
+ * request too) for a bucket that existed and was not zero at that point of the
+ * Go loop (repo.go:78-90).  Datagrams are in batch order.
+ *
+ * Datagram k is out[offs[k] .. offs[k+1]), offs[0] = 0: MarshalBinary
+ * (bucket.go:51-68), byte for byte, of the state phip_results.reply[i] holds
+ * for that message -- the local state at that message in loop order, not the
+ * state after the batch -- under the request's own name; src[k] = i, the
+ * message's batch index (src may be NULL).  With caps that do not cut and no
+ * name over PHIP_MAX_NAME_LEN, out / offs equal what phip_incast_replies
+ * writes from the same call's full status and reply columns, and
+ * phip_reply_peers(peers, src, n, ..) its out_peers.
+ *
+ * Left out and counted.  A reply under a name longer than PHIP_MAX_NAME_LEN
+ * (only a datagram brings one in; MarshalBinary refuses it, bucket.go:48) has
+ * no datagram: `skipped` counts them over the whole batch.  `replies` is the
+ * whole batch's reply count, whatever was written.
+ *
+ * Bounds.  The first datagrams in batch order that fit max_msgs and the byte
+ * budget are written, cut at a record; n < replies - skipped says some were
+ * cut, which is not an error (incast is best-effort UDP, and the caller can
+ * fetch those buckets with phip_export_datagrams).  max_msgs == 0, out == NULL,
+ * offs == NULL or out_cap < PHIP_BUCKET_PACKET_SIZE is PHIP_ERR_INVALID before
+ * anything is applied.
+ *
+ * Pointers.  rq is host memory; out, offs and src follow PHIP_DEVICE_PTRS like
+ * every other pointer of the call.  Device buffers follow phip_export_sweep's
+ * rules: out 8-byte aligned, out_cap a multiple of 8 and at least
+ * PHIP_BUCKET_PACKET_SIZE + 8, the byte budget out_cap - 8; out / offs then go
+ * unchanged into a peer handle's phip_receive_datagrams(..., PHIP_DEVICE_PTRS).
+ * A host-pointer call copies back only what was written.
+ *
+ * Stopped batches (a short datagram; a checked device batch's malformed offset
+ * entry): the replies of the messages before the stop are written and the out
+ * fields valid -- the Go loop had sent them before it returned -- and the
+ * return code is the stopped call's (PHIP_ERR_SHORT_BUFFER / PHIP_ERR_INVALID).
+ * On every other error the four out fields are zero.  A batch of no messages
+ * gives zeros and offs[0] = 0.
+ *
+ * Flags.  PHIP_RECV_ASYNC is PHIP_ERR_INVALID: a queued batch returns no
+ * replies.  PHIP_RECV_CLASSIFY is allowed.  Not covered either: the shard
+ * group (phip_group_receive returns no replies) and PHIP_OP_RECEIVE ops inside
+ * phip_apply_mixed.  phip_ring_receive_replies is phip_ring_receive with rq's
+ * buffers in host memory; res may leave out reply and status.
+ * phip_incast_replies stays for callers that hold the full columns. */
+typedef struct phip_reply_egress {   /* 56 bytes */
+  uint8_t*  out;       /* in:  datagram bytes                                  */
+  uint64_t  out_cap;   /* in                                                   */
+  uint64_t* offs;      /* in:  max_msgs + 1 entries                            */
+  uint32_t* src;       /* in:  max_msgs entries, may be NULL                   */
+  uint32_t  max_msgs;  /* in                                                   */
+  uint32_t  n;         /* out: datagrams written                               */
+  uint32_t  replies;   /* out: messages of the batch with PHIP_ST_INCAST_REPLY */
+  uint32_t  skipped;   /* out: of those, names over PHIP_MAX_NAME_LEN          */
+  uint64_t  bytes;     /* out: = offs[n]                                       */
+} phip_reply_egress;
+int phip_receive_soa_replies(phip_handle* h, const phip_msgs* m, int64_t now,
+                             const phip_results* res, phip_reply_egress* rq, uint32_t flags);
+int phip_receive_datagrams_replies(phip_handle* h, const uint8_t* bytes, const uint64_t* offs,
+                                   uint32_t n, int64_t now, const phip_results* res,
+                                   uint32_t* stop_index, phip_reply_egress* rq, uint32_t flags);
+int phip_ring_receive_replies(phip_ring* r, uint32_t slot, int64_t now, const phip_results* res,
+                              uint32_t* stop_index, phip_reply_egress* rq);
+/* host only: out_peers[k] = peers[src[k]] (PHIP_PEER_BYTES each), for phip_udp_send_batch */
+int phip_reply_peers(const uint8_t* peers, const uint32_t* src, uint32_t n, uint8_t* out_peers);
+
 /* ---- shard layer ---- */
 /* FNV-1a 64 of each name (the table's probe key; also the shard map:
  * owner = ((hash >> 32) * world) >> 32).  Host pointers need no GPU (h may be

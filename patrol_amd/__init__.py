@@ -10,6 +10,7 @@ from .engine import (BucketState, GPUGroup, GPURepo, PatrolHipError, Ring, TakeB
                      digest_diff, digest_fold, incast_replies, marshal, names_blob, parse_rate,
                      udp_recv_batch, udp_send_batch)
 from .engine import peek_eval, throttle_match  # noqa: F401
+from .engine import reply_peers  # noqa: F401
 
 __all__ = ["GPURepo", "GPUGroup", "BucketState", "PatrolHipError", "Ring", "TakeBatcher", "parse_rate", "marshal",
            "names_blob", "udp_recv_batch", "udp_send_batch", "incast_replies", "digest_diff",

@@ -39,6 +39,8 @@ EXPORTS = [
     "phip_export_changed",
     "phip_peek", "phip_peek_eval", "phip_api_peek",
     "phip_export_throttled", "phip_throttle_match",
+    "phip_receive_soa_replies", "phip_receive_datagrams_replies", "phip_ring_receive_replies",
+    "phip_reply_peers",
 ]
 
 PHIP_OK = 0
@@ -136,6 +138,12 @@ class phip_egress(C.Structure):
     _fields_ = [("out", C.c_void_p), ("out_cap", C.c_uint64), ("offs", C.c_void_p),
                 ("max_msgs", C.c_uint32), ("n_incast", C.c_uint32), ("n", C.c_uint32),
                 ("reserved", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+class phip_reply_egress(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("out_cap", C.c_uint64), ("offs", C.c_void_p),
+                ("src", C.c_void_p), ("max_msgs", C.c_uint32), ("n", C.c_uint32),
+                ("replies", C.c_uint32), ("skipped", C.c_uint32), ("bytes", C.c_uint64)]
 
 
 class phip_changes_stats(C.Structure):
@@ -327,5 +335,15 @@ def load(path: str = LIB_PATH):
                                             C.POINTER(phip_sweep_stats), u32]
         L.phip_throttle_match.argtypes = [C.POINTER(phip_throttle_rule), u32, C.c_char_p, u32,
                                           C.POINTER(C.c_int32)]
+    if hasattr(L, "phip_receive_soa_replies"):
+        L.phip_receive_soa_replies.argtypes = [vp, C.POINTER(phip_msgs), i64,
+                                               C.POINTER(phip_results),
+                                               C.POINTER(phip_reply_egress), u32]
+        L.phip_receive_datagrams_replies.argtypes = [vp, vp, vp, u32, i64, C.POINTER(phip_results),
+                                                     C.POINTER(u32), C.POINTER(phip_reply_egress),
+                                                     u32]
+        L.phip_ring_receive_replies.argtypes = [vp, u32, i64, C.POINTER(phip_results),
+                                                C.POINTER(u32), C.POINTER(phip_reply_egress)]
+        L.phip_reply_peers.argtypes = [vp, vp, u32, vp]
     _lib = L
     return L

@@ -65,6 +65,7 @@ enum BufId {
   B_EVICT, B_ULOG, B_ULCNT, B_SWEEP, B_DIGEST, B_DIGOUT,
   B_EGSZ, B_EGTILE, B_EGOUT, B_EGOFFS,
   B_PEEKAT, B_PEEKST,
+  B_RQCTR, B_RQSEL, B_RQTILE, B_RQOUT, B_RQOFFS, B_RQSRC, B_RQSTAT, B_RQREP,
   B_COUNT_
 };
 
@@ -1893,6 +1894,151 @@ inline OutView shifted(OutView o, u32 k) {
   return o;
 }
 
+// ------------------------------------------------ incast reply egress ----
+// phip_receive_*_replies (patrolhip.h "Incast reply egress"; kernels in
+// phip_kernels.hpp under the same heading).  A call's ReplyEg travels with the
+// batch to the path that holds its replies: run_deferred (reply_deferred) or
+// the ordered suffix (reply_suffix); a batch that reaches neither launched
+// nothing and reply_collect writes the zeros on the host.
+struct ReplyEg {
+  phip_reply_egress* rq;   // the caller's (host memory), out fields zeroed at entry
+  bool dev;                // out / offs / src are device memory
+  u64 budget;              // bytes the datagrams may take
+  ReplyOut R{};            // where the kernels write (reply_begin)
+  bool launched = false;
+};
+
+// The call's caps and buffers, checked before anything is applied.
+int reply_check(phip_handle* h, const phip_reply_egress* rq, bool dev, u64* budget) {
+  if (!rq->out || !rq->offs) return set_err(h, PHIP_ERR_INVALID, "replies: out and offs are required");
+  if (!rq->max_msgs) return set_err(h, PHIP_ERR_INVALID, "replies: max_msgs must be positive");
+  if (rq->out_cap < PHIP_BUCKET_PACKET_SIZE)
+    return set_err(h, PHIP_ERR_INVALID, "replies: out_cap below one datagram (%d bytes)",
+                   PHIP_BUCKET_PACKET_SIZE);
+  if (dev && ((reinterpret_cast<uintptr_t>(rq->out) & 7) || (rq->out_cap & 7) ||
+              rq->out_cap < PHIP_BUCKET_PACKET_SIZE + 8))
+    return set_err(h, PHIP_ERR_INVALID,
+                   "replies: a device buffer is 8-byte aligned, a multiple of 8 and >= %d bytes",
+                   PHIP_BUCKET_PACKET_SIZE + 8);
+  *budget = dev ? rq->out_cap - 8 : rq->out_cap;
+  return PHIP_OK;
+}
+
+// Output buffers for at most `bound` replies (the caller's, or the handle's
+// for a host-pointer call) and the cleared counter block.
+int reply_begin(phip_handle* h, ReplyEg* eg, u64 bound) {
+  int rc;
+  const phip_reply_egress& q = *eg->rq;
+  ReplyOut& R = eg->R;
+  R.out = q.out;
+  R.offs = reinterpret_cast<u64*>(q.offs);
+  R.src = q.src;
+  R.max_msgs = q.max_msgs;
+  R.budget = eg->budget;
+  if (!eg->dev) {
+    const u64 msgs = std::min<u64>(q.max_msgs, bound);
+    if ((rc = ensure(h, B_RQOUT, (size_t)std::min<u64>(eg->budget, msgs * PHIP_BUCKET_PACKET_SIZE),
+                     &R.out)) ||
+        (rc = ensure(h, B_RQOFFS, (size_t)msgs + 1, &R.offs)) ||
+        (rc = ensure(h, B_RQSRC, (size_t)msgs, &R.src)))
+      return rc;
+  }
+  if ((rc = ensure(h, B_RQCTR, kRqWords, &R.ctr))) return rc;
+  HIPCHK(h, hipMemsetAsync(R.ctr, 0, kRqWords * sizeof(u64), h->stream));
+  eg->launched = true;
+  return PHIP_OK;
+}
+
+// The deferred sub-batch's replies: selected and ordered by batch index in one
+// workgroup, written one lane per datagram.  No column of the batch's size.
+int reply_deferred(phip_handle* h, ReplyEg* eg, const SubBatch& sb, const u8* blob, const u8* st2,
+                   const phip_state* rep2, u32 nd) {
+  int rc;
+  u32* sel;
+  if ((rc = reply_begin(h, eg, kDirtyCap)) || (rc = ensure(h, B_RQSEL, kDirtyCap, &sel))) return rc;
+  const NamesPairs names{blob, sb.off, sb.len};
+  {
+    Launch l(h, "k_reply_select");
+    k_reply_select<<<1, kReplySelBlock, 0, h->stream>>>(sb.map, st2, nd, names, sel, eg->R);
+  }
+  {
+    Launch l(h, "k_reply_write");
+    const u32 most = std::min<u32>(std::min<u32>(nd, kDirtyCap), eg->R.max_msgs);
+    k_reply_write<<<grid_for(most), kBlock, 0, h->stream>>>(sel, rep2, names, eg->R);
+  }
+  HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
+}
+
+// The ordered suffix's replies from its status and reply columns (m messages
+// from batch index `first` on, already in batch order): count, scan, write.
+template <class Src>
+int reply_suffix(phip_handle* h, ReplyEg* eg, Src src, const u8* status, const phip_state* reply,
+                 u32 m, u32 first) {
+  int rc;
+  const u32 ntiles = grid_for(m);
+  u64* tile_bytes;
+  if ((rc = reply_begin(h, eg, m)) || (rc = ensure(h, B_RQTILE, 2 * (size_t)ntiles, &tile_bytes)))
+    return rc;
+  u32* tile_cnt = (u32*)(tile_bytes + ntiles);
+  {
+    Launch l(h, "k_reply_count");
+    k_reply_count<<<ntiles, kBlock, 0, h->stream>>>(src, status, m, tile_cnt, tile_bytes, eg->R.ctr);
+  }
+  {
+    Launch l(h, "k_reply_scan");
+    k_reply_scan<<<1, kSweepBlock, 0, h->stream>>>(tile_cnt, tile_bytes, ntiles, eg->R.ctr);
+  }
+  {
+    Launch l(h, "k_reply_place");
+    k_reply_place<<<ntiles, kBlock, 0, h->stream>>>(src, status, reply, m, first, tile_cnt,
+                                                     tile_bytes, eg->R);
+  }
+  HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
+}
+
+// The call's out fields; a host-pointer call gets back only what was written.
+// A batch whose replies no path was reached for has none: zeros, offs[0] = 0
+// (a device offs[0] is cleared on the stream; sync: the caller's own
+// synchronise does not follow).
+int reply_collect(phip_handle* h, ReplyEg* eg, bool sync = false) {
+  phip_reply_egress& q = *eg->rq;
+  if (!eg->launched) {
+    if (eg->dev) {
+      HIPCHK(h, hipMemsetAsync(q.offs, 0, sizeof(u64), h->stream));
+      if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else {
+      q.offs[0] = 0;
+    }
+    return PHIP_OK;
+  }
+  u64 c[kRqWords];
+  HIPCHK(h, hipMemcpyAsync(c, eg->R.ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (c[kRqErr] || c[kRqN] > q.max_msgs || c[kRqBytes] > eg->budget ||
+      c[kRqN] + c[kRqSkipped] > c[kRqReplies])
+    return set_err(h, PHIP_ERR_INVALID,
+                   "internal: reply egress wrote %llu datagrams, %llu bytes of %llu replies (flag %llu)",
+                   (unsigned long long)c[kRqN], (unsigned long long)c[kRqBytes],
+                   (unsigned long long)c[kRqReplies], (unsigned long long)c[kRqErr]);
+  if (!eg->dev) {
+    if (c[kRqBytes])
+      HIPCHK(h, hipMemcpyAsync(q.out, eg->R.out, c[kRqBytes], hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(q.offs, eg->R.offs, (c[kRqN] + 1) * sizeof(u64), hipMemcpyDeviceToHost,
+                             h->stream));
+    if (q.src && c[kRqN])
+      HIPCHK(h, hipMemcpyAsync(q.src, eg->R.src, c[kRqN] * sizeof(u32), hipMemcpyDeviceToHost,
+                               h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  q.n = (u32)c[kRqN];
+  q.bytes = c[kRqBytes];
+  q.replies = (u32)c[kRqReplies];
+  q.skipped = (u32)c[kRqSkipped];
+  return PHIP_OK;
+}
+
 // The last fast pass's ordered sub-batch (nd entries: its dirty buckets' dirty
 // messages and the merges of their cells, dirty_finish) through the ordered path,
 // its statuses and replies scattered back.  The dirty buckets' other
@@ -1900,8 +2046,11 @@ inline OutView shifted(OutView o, u32 k) {
 // message) or folded into the cells (after it); no other bucket is touched,
 // and Receive is per bucket (repo.go:77-106), so applying the sub-batch
 // after the rest of the batch gives each dirty bucket the Go loop's states.
+// eg: the batch's incast replies are written from the sub-batch's own statuses
+// and reply states (reply_deferred), whatever columns the caller asked for.
 template <class Src>
-int run_deferred(phip_handle* h, Src src, i64 now, const OutView& ow, u32 nd) {
+int run_deferred(phip_handle* h, Src src, i64 now, const OutView& ow, u32 nd,
+                 ReplyEg* eg = nullptr) {
   // (kSubBatchOver included: dirty_finish counted more entries than the
   // sub-batch holds and wrote none)
   if (nd > kSubBatchCap) {
@@ -1914,8 +2063,8 @@ int run_deferred(phip_handle* h, Src src, i64 now, const OutView& ow, u32 nd) {
   SubBatch sb;
   u8* st2 = nullptr;
   phip_state* rep2 = nullptr;
-  if ((rc = sub_batch(h, &sb)) || (ow.status && (rc = ensure(h, B_SSTAT, nd, &st2))) ||
-      (ow.reply && (rc = ensure(h, B_SREP, nd, &rep2))))
+  if ((rc = sub_batch(h, &sb)) || ((ow.status || eg) && (rc = ensure(h, B_SSTAT, nd, &st2))) ||
+      ((ow.reply || eg) && (rc = ensure(h, B_SREP, nd, &rep2))))
     return rc;
   if (rep2) HIPCHK(h, hipMemsetAsync(rep2, 0, (size_t)nd * sizeof(phip_state), h->stream));
   OpView ov{};
@@ -1925,10 +2074,11 @@ int run_deferred(phip_handle* h, Src src, i64 now, const OutView& ow, u32 nd) {
   if ((rc = ordered(h, NamesPairs{src.blob, sb.off, sb.len}, nd, ov,
                     OutView{st2, nullptr, nullptr, rep2})))
     return rc;
-  if (st2 || rep2) {
+  if (ow.status || ow.reply) {
     k_defer_scatter<<<grid_for(nd), kBlock, 0, h->stream>>>(sb.map, nd, st2, rep2, ow);
     HIPCHK(h, hipGetLastError());
   }
+  if (eg) return reply_deferred(h, eg, sb, src.blob, st2, rep2, nd);
   return PHIP_OK;
 }
 
@@ -1937,13 +2087,17 @@ int run_deferred(phip_handle* h, Src src, i64 now, const OutView& ow, u32 nd) {
 // which starts from the state the prefix left (the Go loop's state at that
 // message) -- or, when the fast pass deferred the dirty buckets
 // (first_dirty == n), over their messages (run_deferred).
+// eg: the batch's incast replies, from whichever of the two holds them (a
+// clean message is no request); the suffix's status and reply columns are the
+// caller's, or the handle's own for the suffix alone.
 template <class Src>
 int finish_receive(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t,
-                   const int64_t* e, i64 now, const OutView& ow, FastOutcome o) {
+                   const int64_t* e, i64 now, const OutView& ow, FastOutcome o,
+                   ReplyEg* eg = nullptr) {
   int rc;
   const bool deferred = o.ndef != 0;   // (the first pass's; finish_misses may run a second)
   if ((rc = finish_misses(h, src, a, t, e, now, ow.status, &o))) return rc;
-  if (deferred) return run_deferred(h, src, now, ow, o.ndef);
+  if (deferred) return run_deferred(h, src, now, ow, o.ndef, eg);
   const u32 stop = o.stop, k = o.first_dirty;
   h->stats.ordered = k < stop ? stop - k : 0;
   if (k >= stop) return PHIP_OK;
@@ -1951,7 +2105,12 @@ int finish_receive(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t
   ov.kind = nullptr; ov.kind0 = PHIP_OP_RECEIVE;
   ov.now = nullptr; ov.now0 = now;
   ov.a = a + k; ov.t = t + k; ov.e = e + k;
-  return ordered(h, shifted(src, k), stop - k, ov, shifted(ow, k));
+  OutView ow2 = shifted(ow, k);
+  if (eg && ((!ow2.status && (rc = ensure(h, B_RQSTAT, stop - k, &ow2.status))) ||
+             (!ow2.reply && (rc = ensure(h, B_RQREP, stop - k, &ow2.reply)))))
+    return rc;
+  if ((rc = ordered(h, shifted(src, k), stop - k, ov, ow2))) return rc;
+  return eg ? reply_suffix(h, eg, shifted(src, k), ow2.status, ow2.reply, stop - k, k) : PHIP_OK;
 }
 
 // Statuses of a batch that stopped at message `stop` (kCtrStop), as the Go
@@ -1980,12 +2139,15 @@ int stopped_at_bad_name(phip_handle* h, const OutView& ow, u32 n, u32 stop) {
 // ordered path from its first incast or -0.0 on.
 template <class Src>
 int receive_decoded(phip_handle* h, Src src, const uint64_t* a, const uint64_t* t,
-                    const int64_t* e, u32 n, i64 now, const OutView& ow, PassAsk ask) {
+                    const int64_t* e, u32 n, i64 now, const OutView& ow, PassAsk ask,
+                    ReplyEg* eg = nullptr) {
   int rc;
   FastOutcome o;
   if ((rc = fast_apply(h, SoaIn<Src>{src, a, t, e}, src, n, ow.status, ask, &o)) ||
-      (rc = finish_receive(h, src, a, t, e, now, ow, o)))
+      (rc = finish_receive(h, src, a, t, e, now, ow, o, eg)))
     return rc;
+  // (a batch that stopped had sent the replies before: they are collected first)
+  if (eg && (rc = reply_collect(h, eg))) return rc;
   return stopped_at_bad_name(h, ow, n, o.stop);   // (a checked batch's malformed entry)
 }
 
@@ -2216,12 +2378,60 @@ int small_uniform(phip_handle* h, const phip_msgs* m, u8 kind, int64_t now, cons
   return small_mixed(h, &ops, res, done);
 }
 
+// The incast replies of a small batch, marshalled on the host from the result
+// block its one launch copied back: the messages whose status is a reply, in
+// batch order, the first that fit both caps (the device paths' cut: nothing
+// is written behind a reply that did not fit).
+void marshal_replies(const uint8_t* names, const uint32_t* name_offs, const uint8_t* status,
+                     const phip_state* reply, u32 n, phip_reply_egress* rq) {
+  u64 pos = 0;
+  u32 m = 0;
+  bool cut = false;
+  rq->offs[0] = 0;
+  for (u32 i = 0; i < n; ++i) {
+    if ((status[i] & 0x7F) != PHIP_ST_INCAST_REPLY) continue;
+    ++rq->replies;
+    const u32 len = name_offs[i + 1] - name_offs[i];
+    if (len > PHIP_MAX_NAME_LEN) {   // (bucket.go:48: no datagram carries it)
+      ++rq->skipped;
+      continue;
+    }
+    cut = cut || m >= rq->max_msgs || pos + PHIP_BUCKET_FIXED_SIZE + len > rq->out_cap;
+    if (cut) continue;
+    pos += (u64)phip_marshal(names + name_offs[i], len, &reply[i], rq->out + pos);
+    if (rq->src) rq->src[m] = i;
+    rq->offs[++m] = pos;
+  }
+  rq->n = m;
+  rq->bytes = pos;
+}
+
+// small_uniform for a Receive batch whose replies are asked for (rq): the
+// same launch, with the status and reply columns in the block it copies back
+// whether or not the caller takes them.
+int small_uniform_replies(phip_handle* h, const phip_msgs* m, int64_t now, const phip_results* res,
+                          phip_reply_egress* rq, bool* done) {
+  *done = false;
+  if (!h->small || m->n > kSmallMax) return PHIP_OK;
+  std::vector<u8> st;
+  std::vector<phip_state> rp;
+  phip_results r{};
+  if (res) r = *res;
+  if (!r.status) { st.resize(m->n); r.status = st.data(); }
+  if (!r.reply) { rp.resize(m->n); r.reply = rp.data(); }
+  if (int rc = small_uniform(h, m, PHIP_OP_RECEIVE, now, &r, done)) return rc;
+  if (*done) marshal_replies(m->names, m->name_offs, r.status, r.reply, m->n, rq);
+  return PHIP_OK;
+}
+
 // ReplicatedRepo.Receive over at most kSmallMax host datagrams: decoded on
 // the host (UnmarshalBinary, bucket.go:71-91: a datagram under 25 bytes or
 // shorter than its name is io.ErrShortBuffer, where the Go loop stops), the
-// prefix before the first short one through small_mixed.
+// prefix before the first short one through small_mixed.  rq: that prefix's
+// incast replies (small_uniform_replies).
 int small_datagrams(phip_handle* h, const uint8_t* bytes, const uint64_t* offs, uint32_t n,
-                    int64_t now, const phip_results* res, uint32_t* stop_index, bool* done) {
+                    int64_t now, const phip_results* res, uint32_t* stop_index, bool* done,
+                    phip_reply_egress* rq = nullptr) {
   *done = false;
   if (!h->small || n > kSmallMax) return PHIP_OK;
   std::vector<uint64_t> a(n), t(n);
@@ -2257,8 +2467,12 @@ int small_datagrams(phip_handle* h, const uint8_t* bytes, const uint64_t* offs, 
     m.elapsed = e.data();
     bool ok = false;
     int rc;
-    if ((rc = small_uniform(h, &m, PHIP_OP_RECEIVE, now, res, &ok))) return rc;
+    if ((rc = rq ? small_uniform_replies(h, &m, now, res, rq, &ok)
+                 : small_uniform(h, &m, PHIP_OP_RECEIVE, now, res, &ok)))
+      return rc;
     if (!ok) return PHIP_OK;   // the large path takes the whole batch
+  } else if (rq) {
+    rq->offs[0] = 0;
   }
   if (res && res->status && stop < n) {   // the short datagram and everything after it
     std::memset(res->status + stop, PHIP_ST_NOT_PROCESSED, n - stop);
@@ -2951,13 +3165,32 @@ int phip_dump(phip_handle* h, uint8_t* names, uint64_t names_cap, uint64_t* name
   return PHIP_OK;
 }
 
-int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip_results* res,
-                     uint32_t flags) {
+// The incast-reply form of a receive call: its out fields read zero unless the
+// call gets as far as its replies (reply_zero, first thing in each entry
+// point), and reply_enter refuses its arguments before anything is applied.
+static void reply_zero(phip_reply_egress* rq) {
+  rq->n = rq->replies = rq->skipped = 0;
+  rq->bytes = 0;
+}
+static int reply_enter(phip_handle* h, phip_reply_egress* rq, uint32_t flags, ReplyEg* eg) {
+  if (flags & PHIP_RECV_ASYNC)
+    return set_err(h, PHIP_ERR_INVALID, "replies: PHIP_RECV_ASYNC batches return none");
+  eg->rq = rq;
+  eg->dev = flags & PHIP_DEVICE_PTRS;
+  return reply_check(h, rq, eg->dev, &eg->budget);
+}
+
+// phip_receive_soa, and with rq phip_receive_soa_replies (never queued).
+static int receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip_results* res,
+                       uint32_t flags, phip_reply_egress* rq) {
   if (!h || !m) return PHIP_ERR_INVALID;
   std::lock_guard<std::mutex> g(h->mu);
   bool dev = flags & PHIP_DEVICE_PTRS;
   u32 n = m->n;
   const PassAsk ask = (flags & PHIP_RECV_CLASSIFY) ? PassAsk::kPolicy : PassAsk::kMayUndo;
+  ReplyEg egs{}, *eg = rq ? &egs : nullptr;
+  if (rq)
+    if (int rc0 = reply_enter(h, rq, flags, eg)) return rc0;
   if ((flags & PHIP_RECV_ASYNC) && dev && n >= kHotMinBatch && m->names && m->name_offs &&
       m->added && m->taken && m->elapsed) {
     // Queue this batch's front (reset, directory with the status fill, or
@@ -3031,13 +3264,15 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
     return PHIP_OK;
   }
   if (int rc0 = begin_call(h)) return rc0;
-  if (n == 0) return PHIP_OK;
+  if (n == 0) return eg ? reply_collect(h, eg, true) : PHIP_OK;
   if (!m->names || !m->name_offs || !m->added || !m->taken || !m->elapsed) return PHIP_ERR_INVALID;
   if (!dev && !names_ok(m->name_offs, n)) return set_err(h, PHIP_ERR_NAME_TOO_LARGE, "name > 231 bytes");
   int rc;
   if (!dev) {
     bool done = false;
-    if ((rc = small_uniform(h, m, PHIP_OP_RECEIVE, now, res, &done))) return after_error(h, rc);
+    if ((rc = rq ? small_uniform_replies(h, m, now, res, rq, &done)
+                 : small_uniform(h, m, PHIP_OP_RECEIVE, now, res, &done)))
+      return after_error(h, rc);
     if (done) return PHIP_OK;
   }
   NamesOffs src;
@@ -3048,8 +3283,20 @@ int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip
       (rc = stage(h, B_A, m->added, n, dev, &a)) || (rc = stage(h, B_T, m->taken, n, dev, &t)) ||
       (rc = stage(h, B_E, m->elapsed, n, dev, &e)) || (rc = outputs(h, res, n, dev, &ow)))
     return rc;
-  if ((rc = receive_decoded(h, src, a, t, e, n, now, ow, ask))) return after_error(h, rc);
+  if ((rc = receive_decoded(h, src, a, t, e, n, now, ow, ask, eg))) return after_error(h, rc);
   return copy_outputs(h, res, n, dev, ow);
+}
+
+int phip_receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip_results* res,
+                     uint32_t flags) {
+  return receive_soa(h, m, now, res, flags, nullptr);
+}
+
+int phip_receive_soa_replies(phip_handle* h, const phip_msgs* m, int64_t now,
+                             const phip_results* res, phip_reply_egress* rq, uint32_t flags) {
+  if (!rq) return PHIP_ERR_INVALID;
+  reply_zero(rq);
+  return receive_soa(h, m, now, res, flags, rq);
 }
 
 }  // extern "C"
@@ -3059,7 +3306,8 @@ namespace {
 // caller's, the staging buffers, or a ring slot's copy); results go to
 // device (dev) or host buffers.  Called with the handle's mutex held.
 int receive_datagrams_dev(phip_handle* h, const u8* d_bytes, const uint64_t* d_offs, u32 n,
-                          int64_t now, const phip_results* res, uint32_t* stop_index, bool dev) {
+                          int64_t now, const phip_results* res, uint32_t* stop_index, bool dev,
+                          ReplyEg* eg = nullptr) {
   int rc;
   OutView ow{};
   if ((rc = outputs(h, res, n, dev, &ow))) return rc;
@@ -3091,10 +3339,13 @@ int receive_datagrams_dev(phip_handle* h, const u8* d_bytes, const uint64_t* d_o
                                                           h->ctr);
       HIPCHK(h, hipGetLastError());
     }
-    if ((rc = finish_receive(h, NamesPairs{d_bytes, no, nl}, a, t, e, now, ow, o)))
+    if ((rc = finish_receive(h, NamesPairs{d_bytes, no, nl}, a, t, e, now, ow, o, eg)))
       return after_error(h, rc);
   }
   if ((rc = copy_outputs(h, res, n, dev, ow))) return rc;
+  // (the replies of the messages before a short datagram were sent: collected
+  // before the stop is reported)
+  if (eg && (rc = reply_collect(h, eg))) return after_error(h, rc);
   if (dev) HIPCHK(h, hipStreamSynchronize(h->stream));
   if (stop_index) *stop_index = stop;
   if (stop < n) return set_err(h, PHIP_ERR_SHORT_BUFFER, "short buffer at datagram %u", stop);
@@ -3104,14 +3355,18 @@ int receive_datagrams_dev(phip_handle* h, const u8* d_bytes, const uint64_t* d_o
 
 extern "C" {
 
-int phip_receive_datagrams(phip_handle* h, const uint8_t* bytes, const uint64_t* offs, uint32_t n,
-                           int64_t now, const phip_results* res, uint32_t* stop_index,
-                           uint32_t flags) {
+// phip_receive_datagrams, and with rq phip_receive_datagrams_replies.
+static int receive_datagrams(phip_handle* h, const uint8_t* bytes, const uint64_t* offs, uint32_t n,
+                             int64_t now, const phip_results* res, uint32_t* stop_index,
+                             uint32_t flags, phip_reply_egress* rq) {
   if (!h || (n && (!bytes || !offs))) return PHIP_ERR_INVALID;
   std::lock_guard<std::mutex> g(h->mu);
+  ReplyEg egs{}, *eg = rq ? &egs : nullptr;
+  if (rq)
+    if (int rc0 = reply_enter(h, rq, flags, eg)) return rc0;
   if (int rc0 = begin_call(h)) return rc0;
   if (stop_index) *stop_index = n;
-  if (n == 0) return PHIP_OK;
+  if (n == 0) return eg ? reply_collect(h, eg, true) : PHIP_OK;
   bool dev = flags & PHIP_DEVICE_PTRS;
   int rc;
   const uint64_t* d_offs;
@@ -3120,13 +3375,27 @@ int phip_receive_datagrams(phip_handle* h, const uint8_t* bytes, const uint64_t*
     return set_err(h, PHIP_ERR_INVALID, "datagram offsets decrease");
   if (!dev) {
     bool done = false;
-    rc = small_datagrams(h, bytes, offs, n, now, res, stop_index, &done);
+    rc = small_datagrams(h, bytes, offs, n, now, res, stop_index, &done, rq);
     if (done || (rc && rc != PHIP_ERR_SHORT_BUFFER)) return rc == PHIP_ERR_SHORT_BUFFER ? rc : after_error(h, rc);
   }
   if ((rc = stage(h, B_DOFFS, offs, (size_t)n + 1, dev, &d_offs))) return rc;
   size_t nb = dev ? 0 : offs[n];
   if ((rc = stage(h, B_BYTES, bytes, nb, dev, &d_bytes))) return rc;
-  return receive_datagrams_dev(h, d_bytes, d_offs, n, now, res, stop_index, dev);
+  return receive_datagrams_dev(h, d_bytes, d_offs, n, now, res, stop_index, dev, eg);
+}
+
+int phip_receive_datagrams(phip_handle* h, const uint8_t* bytes, const uint64_t* offs, uint32_t n,
+                           int64_t now, const phip_results* res, uint32_t* stop_index,
+                           uint32_t flags) {
+  return receive_datagrams(h, bytes, offs, n, now, res, stop_index, flags, nullptr);
+}
+
+int phip_receive_datagrams_replies(phip_handle* h, const uint8_t* bytes, const uint64_t* offs,
+                                   uint32_t n, int64_t now, const phip_results* res,
+                                   uint32_t* stop_index, phip_reply_egress* rq, uint32_t flags) {
+  if (!rq) return PHIP_ERR_INVALID;
+  reply_zero(rq);
+  return receive_datagrams(h, bytes, offs, n, now, res, stop_index, flags, rq);
 }
 
 // ------------------------------------------------------------ ingest ring --
@@ -3242,8 +3511,9 @@ int phip_ring_submit(phip_ring* r, uint32_t slot, uint32_t n) {
   return PHIP_OK;
 }
 
-int phip_ring_receive(phip_ring* r, uint32_t slot, int64_t now, const phip_results* res,
-                      uint32_t* stop_index) {
+// phip_ring_receive, and with rq (host memory) phip_ring_receive_replies.
+static int ring_receive(phip_ring* r, uint32_t slot, int64_t now, const phip_results* res,
+                        uint32_t* stop_index, phip_reply_egress* rq) {
   if (!r || slot >= r->slots.size()) return PHIP_ERR_INVALID;
   phip_ring::Slot* s;
   {
@@ -3255,6 +3525,9 @@ int phip_ring_receive(phip_ring* r, uint32_t slot, int64_t now, const phip_resul
   int rc;
   {
     std::lock_guard<std::mutex> g(h->mu);
+    ReplyEg egs{}, *eg = rq ? &egs : nullptr;
+    // (refused arguments leave the slot submitted, as a busy slot does)
+    if (rq && (rc = reply_enter(h, rq, 0, eg))) return rc;
     if ((rc = begin_call(h))) return rc;
     if (stop_index) *stop_index = s->n;
     // A small slot is merged from its pinned host bytes in one launch (the
@@ -3262,7 +3535,7 @@ int phip_ring_receive(phip_ring* r, uint32_t slot, int64_t now, const phip_resul
     // finished, below); a larger one from the device copy.
     bool done = false;
     if (s->n && s->n <= kSmallMax) {
-      rc = small_datagrams(h, s->hbytes, s->hoffs, s->n, now, res, stop_index, &done);
+      rc = small_datagrams(h, s->hbytes, s->hoffs, s->n, now, res, stop_index, &done, rq);
       if (done || (rc && rc != PHIP_ERR_SHORT_BUFFER)) {
         if (rc && rc != PHIP_ERR_SHORT_BUFFER) rc = after_error(h, rc);
         done = true;
@@ -3276,9 +3549,9 @@ int phip_ring_receive(phip_ring* r, uint32_t slot, int64_t now, const phip_resul
       if (e != hipSuccess)
         rc = set_err(h, PHIP_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
       else if (s->n == 0)
-        rc = PHIP_OK;
+        rc = eg ? reply_collect(h, eg) : PHIP_OK;
       else
-        rc = receive_datagrams_dev(h, s->dbytes, s->doffs, s->n, now, res, stop_index, false);
+        rc = receive_datagrams_dev(h, s->dbytes, s->doffs, s->n, now, res, stop_index, false, eg);
     }
     // On success the stream has drained (results copied back), so the slot's
     // host and device buffers are free; after an error wait for them first.
@@ -3288,6 +3561,18 @@ int phip_ring_receive(phip_ring* r, uint32_t slot, int64_t now, const phip_resul
   s->state = phip_ring::kFree;
   r->next_receive = (r->next_receive + 1) % (u32)r->slots.size();
   return rc;
+}
+
+int phip_ring_receive(phip_ring* r, uint32_t slot, int64_t now, const phip_results* res,
+                      uint32_t* stop_index) {
+  return ring_receive(r, slot, now, res, stop_index, nullptr);
+}
+
+int phip_ring_receive_replies(phip_ring* r, uint32_t slot, int64_t now, const phip_results* res,
+                              uint32_t* stop_index, phip_reply_egress* rq) {
+  if (!rq) return PHIP_ERR_INVALID;
+  reply_zero(rq);
+  return ring_receive(r, slot, now, res, stop_index, rq);
 }
 
 int phip_upsert_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip_results* res,

@@ -7028,5 +7028,296 @@ __global__ __launch_bounds__(kBlock) void k_throttle_retry(const Rec* __restrict
   }
 }
 
+// ------------------------------------------------ incast reply egress ----
+// phip_receive_*_replies (patrolhip.h "Incast reply egress"): the unicast
+// answers of a Receive batch (repo.go:86-90,160-169) as MarshalBinary
+// datagrams in batch order, written from what the ordered path holds.
+//
+// Deferred path (run_deferred): the sub-batch's statuses and reply states
+// (st2 / rep2, at most kSubBatchCap entries, map2 their batch indices) never
+// become n-sized columns.
+//   k_reply_select  one workgroup: the entries whose status is a reply (at
+//                   most kDirtyCap: only a dirty message can be one) sorted by
+//                   batch index in LDS, their datagram sizes scanned and cut at
+//                   the caps; offs, src and the sub-batch entry of every
+//                   written datagram (sel);
+//   k_reply_write   one lane per written datagram.
+// Suffix path (finish_receive, messages [first_dirty, stop)): the suffix's
+// status and reply columns, already in batch order.
+//   k_reply_count   per tile of kBlock messages, the replies and their bytes;
+//   k_reply_scan    exclusive scans of the two tile arrays (one workgroup);
+//   k_reply_place   ranks a tile again and writes the datagrams that fit.
+// A reply under a name over PHIP_MAX_NAME_LEN (bucket.go:48; only a datagram
+// brings one in) has no datagram: counted in kRqSkipped, neither ranked nor
+// written.  Ranks and start bytes are monotone in batch order, so what fits
+// both caps is a prefix, cut at a record.
+//
+// Counters (u64 words of the call's device block, cleared in front).
+constexpr u32 kRqN = 0;        // datagrams written
+constexpr u32 kRqBytes = 1;    // their bytes (= offs[n])
+constexpr u32 kRqReplies = 2;  // messages with PHIP_ST_INCAST_REPLY
+constexpr u32 kRqSkipped = 3;  // of those, names over PHIP_MAX_NAME_LEN
+constexpr u32 kRqErr = 4;      // more replies than dirty messages (internal)
+constexpr u32 kRqWords = 8;
+constexpr u32 kReplySelBlock = 1024;
+
+struct ReplyOut {
+  u8* out;
+  u64* offs;     // max_msgs + 1
+  u32* src;      // max_msgs, or nullptr
+  u32 max_msgs;
+  u64 budget;
+  u64* ctr;      // kRqWords
+};
+
+__device__ inline bool is_reply(u8 st) { return (st & 0x7Fu) == PHIP_ST_INCAST_REPLY; }
+
+// One reply datagram at d: the three state words big-endian, the length byte,
+// the request's own name (k_sweep_write's stores: whole words while eight
+// bytes are left, single bytes after, nothing outside the datagram; the name
+// is read the same way, nothing outside the name).
+__device__ inline void put_reply(u8* d, const phip_state& s, const u8* __restrict__ name, u32 len) {
+  sweep_put8(d, __builtin_bswap64(s.added));
+  sweep_put8(d + 8, __builtin_bswap64(s.taken));
+  sweep_put8(d + 16, __builtin_bswap64((u64)s.elapsed));
+  d[24] = (u8)len;
+  d += PHIP_BUCKET_FIXED_SIZE;
+  u32 j = 0;
+  for (; j + 8 <= len; j += 8) {
+    u64 x;
+    __builtin_memcpy(&x, name + j, 8);
+    sweep_put8(d + j, x);
+  }
+  for (; j < len; ++j) d[j] = name[j];
+}
+
+// Exclusive scan of a packed (count << 19 | bytes) value over a workgroup of
+// kB threads (k_sweep_write's packing: a step of at most 1024 datagrams of at
+// most 256 bytes stays under 2^19 bytes); *tot: the workgroup's total.
+// Every thread of the workgroup calls it (two barriers).
+template <u32 kB>
+__device__ inline u32 block_excl_scan_packed(u32 v, u32* wtot, u32* tot) {
+  const u32 wv = threadIdx.x >> 6;
+  const u32 sc = wave_incl_scan(v);
+  __syncthreads();   // (wtot of the step before has been read)
+  if (__lane_id() == 63) wtot[wv] = sc;
+  __syncthreads();
+  u32 pre = 0, t = 0;
+#pragma unroll
+  for (u32 w = 0; w < kB / 64; ++w) {
+    const u32 x = wtot[w];
+    if (w < wv) pre += x;
+    t += x;
+  }
+  *tot = t;
+  return pre + sc - v;
+}
+
+// Whether the reply of rank `rank` that starts at byte `start` fits both caps;
+// one that does has its offs and src entries stored here.
+__device__ inline bool reply_fits(const ReplyOut& R, u64 rank, u64 start, u32 sz, u32 msg) {
+  if (rank >= R.max_msgs || start + sz > R.budget) return false;
+  R.offs[rank + 1] = start + sz;
+  if (R.src) R.src[rank] = msg;
+  return true;
+}
+
+// Deferred path, one workgroup.  sel[rank]: the sub-batch entry of written
+// datagram `rank` (k_reply_write reads it).  names: the sub-batch's
+// (NamesPairs over dirty_finish's off / len).
+__global__ __launch_bounds__(kReplySelBlock) void k_reply_select(
+    const u32* __restrict__ map2, const u8* __restrict__ st2, u32 nd, NamesPairs names,
+    u32* __restrict__ sel, ReplyOut R) {
+  __shared__ u64 key[kDirtyCap];   // batch index << 32 | sub-batch entry
+  __shared__ u32 cnt, skipped, nw;
+  __shared__ u64 bw;   // the written datagrams and their bytes (maxima: they are a prefix)
+  __shared__ u32 wtot[kReplySelBlock / 64];
+  const u32 tid = threadIdx.x;
+  if (tid == 0) { cnt = 0; skipped = 0; nw = 0; bw = 0; }
+  __syncthreads();
+  for (u32 j = tid; j < nd; j += kReplySelBlock) {
+    const u32 i = map2[j];
+    if (i == ~0u || !is_reply(st2[j])) continue;
+    if (names.len[j] > PHIP_MAX_NAME_LEN) {
+      atomicAdd(&skipped, 1u);
+      continue;
+    }
+    const u32 pos = atomicAdd(&cnt, 1u);
+    if (pos < kDirtyCap) key[pos] = ((u64)i << 32) | j;
+  }
+  __syncthreads();
+  const u32 m = cnt;
+  if (tid == 0) {
+    R.offs[0] = 0;
+    R.ctr[kRqReplies] = (u64)m + skipped;
+    R.ctr[kRqSkipped] = skipped;
+    if (m > kDirtyCap) R.ctr[kRqErr] = 1;
+  }
+  if (m == 0 || m > kDirtyCap) return;   // (uniform: the counters stay as cleared)
+  // bitonic sort of the keys, padded with ~0 to a power of two
+  u32 p2 = 1;
+  while (p2 < m) p2 <<= 1;
+  for (u32 x = m + tid; x < p2; x += kReplySelBlock) key[x] = ~0ull;
+  __syncthreads();
+  for (u32 k = 2; k <= p2; k <<= 1)
+    for (u32 s = k >> 1; s > 0; s >>= 1) {
+      for (u32 x = tid; x < p2; x += kReplySelBlock) {
+        const u32 y = x ^ s;
+        if (y > x) {
+          const u64 a = key[x], b = key[y];
+          if ((a > b) == ((x & k) == 0)) { key[x] = b; key[y] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  // sizes, scanned in steps of the workgroup's size with a running base
+  u64 rank0 = 0, byte0 = 0;
+  for (u32 base = 0; base < m; base += kReplySelBlock) {   // (uniform trip count)
+    const u32 x = base + tid;
+    u32 j = 0, sz = 0;
+    if (x < m) {
+      j = (u32)key[x];
+      sz = PHIP_BUCKET_FIXED_SIZE + names.len[j];
+    }
+    const u32 v = sz ? (1u << 19) | sz : 0u;
+    u32 tot;
+    const u32 ex = block_excl_scan_packed<kReplySelBlock>(v, wtot, &tot);
+    const u64 rank = rank0 + (ex >> 19), start = byte0 + (ex & 0x7FFFFu);
+    rank0 += tot >> 19;
+    byte0 += tot & 0x7FFFFu;
+    if (sz && reply_fits(R, rank, start, sz, (u32)(key[x] >> 32))) {
+      sel[rank] = j;
+      atomicMax(&nw, (u32)rank + 1);
+      atomicMax(&bw, start + sz);
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    R.ctr[kRqN] = nw;
+    R.ctr[kRqBytes] = bw;
+  }
+}
+
+// Deferred path: datagram k < ctr[kRqN] from sub-batch entry sel[k].
+__global__ __launch_bounds__(kBlock) void k_reply_write(const u32* __restrict__ sel,
+                                                        const phip_state* __restrict__ rep2,
+                                                        NamesPairs names, ReplyOut R) {
+  const u64 n = R.ctr[kRqN];
+  const u64 k = (u64)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= n) return;
+  const u32 j = sel[k];
+  const u64 start = R.offs[k];
+  const u32 len = (u32)(R.offs[k + 1] - start) - PHIP_BUCKET_FIXED_SIZE;
+  put_reply(R.out + start, rep2[j], names.blob + names.off[j], len);
+}
+
+// Datagram bytes of suffix message i (0: no reply, or a name MarshalBinary
+// refuses, which *skip reports).
+template <class Src>
+__device__ inline u32 reply_size(const Src& src, const u8* __restrict__ status, u32 i, u64& off,
+                                 bool* skip) {
+  *skip = false;
+  if (!is_reply(status[i])) return 0;
+  u32 len;
+  src.get(i, off, len);
+  if (len > PHIP_MAX_NAME_LEN) {
+    *skip = true;
+    return 0;
+  }
+  return PHIP_BUCKET_FIXED_SIZE + len;
+}
+
+// Suffix path, count pass: tile t = messages [t * kBlock, (t + 1) * kBlock).
+template <class Src>
+__global__ __launch_bounds__(kBlock) void k_reply_count(Src src, const u8* __restrict__ status, u32 m,
+                                                        u32* __restrict__ tile_cnt,
+                                                        u64* __restrict__ tile_bytes, u64* ctr) {
+  __shared__ u32 wtot[kBlock / 64];
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  u64 off;
+  bool skip = false;
+  const u32 sz = i < m ? reply_size(src, status, i, off, &skip) : 0u;
+  const u64 nskip = __popcll(__ballot(skip));
+  if (nskip && __lane_id() == 0) {
+    atomicAdd(&ctr[kRqSkipped], nskip);
+    atomicAdd(&ctr[kRqReplies], nskip);
+  }
+  u32 tot;
+  block_excl_scan_packed<kBlock>(sz ? (1u << 19) | sz : 0u, wtot, &tot);
+  if (threadIdx.x == 0) {
+    tile_cnt[blockIdx.x] = tot >> 19;
+    tile_bytes[blockIdx.x] = tot & 0x7FFFFu;
+  }
+}
+
+// Exclusive scans of the tile arrays in place (k_sweep_scan's walk); the
+// totals are what k_reply_place leaves standing when every reply fits.
+__global__ __launch_bounds__(kSweepBlock) void k_reply_scan(u32* __restrict__ tile_cnt,
+                                                            u64* __restrict__ tile_bytes,
+                                                            u32 ntiles, u64* ctr) {
+  __shared__ u32 wn[kSweepBlock / 64];
+  __shared__ u64 wb[kSweepBlock / 64];
+  const u32 wv = threadIdx.x >> 6;
+  u64 carry_n = 0, carry_b = 0;
+  for (u32 base = 0; base < ntiles; base += kSweepBlock) {
+    const u32 i = base + threadIdx.x;
+    const u32 c = i < ntiles ? tile_cnt[i] : 0u;
+    const u64 b = i < ntiles ? tile_bytes[i] : 0ull;
+    const u32 sc = wave_incl_scan(c);
+    const u64 sb = wave_incl_scan64(b);
+    if (__lane_id() == 63) { wn[wv] = sc; wb[wv] = sb; }
+    __syncthreads();
+    u64 pn = 0, pb = 0, tn = 0, tb = 0;
+    for (u32 w = 0; w < kSweepBlock / 64; ++w) {
+      if (w < wv) { pn += wn[w]; pb += wb[w]; }
+      tn += wn[w];
+      tb += wb[w];
+    }
+    if (i < ntiles) {
+      tile_cnt[i] = (u32)(carry_n + pn + sc - c);
+      tile_bytes[i] = carry_b + pb + sb - b;
+    }
+    carry_n += tn;
+    carry_b += tb;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    ctr[kRqN] = carry_n;
+    ctr[kRqBytes] = carry_b;
+    atomicAdd(&ctr[kRqReplies], carry_n);   // (beside the skipped ones k_reply_count added)
+  }
+}
+
+// Suffix path, write pass: one lane per message of the tile; `first` is the
+// suffix's first batch index (src[k] counts from the batch's start).
+template <class Src>
+__global__ __launch_bounds__(kBlock) void k_reply_place(Src src, const u8* __restrict__ status,
+                                                        const phip_state* __restrict__ reply, u32 m,
+                                                        u32 first, const u32* __restrict__ tile_cnt,
+                                                        const u64* __restrict__ tile_bytes,
+                                                        ReplyOut R) {
+  __shared__ u32 wtot[kBlock / 64];
+  const u64 rank0 = tile_cnt[blockIdx.x];
+  const u64 byte0 = tile_bytes[blockIdx.x];
+  if (blockIdx.x == 0 && threadIdx.x == 0) R.offs[0] = 0;
+  if (rank0 > R.max_msgs) return;   // (neither a written reply nor the first unwritten one)
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  u64 off = 0;
+  bool skip;
+  const u32 sz = i < m ? reply_size(src, status, i, off, &skip) : 0u;
+  u32 tot;
+  const u32 ex = block_excl_scan_packed<kBlock>(sz ? (1u << 19) | sz : 0u, wtot, &tot);
+  if (!sz) return;
+  const u64 rank = rank0 + (ex >> 19), start = byte0 + (ex & 0x7FFFFu);
+  if (reply_fits(R, rank, start, sz, first + i)) {
+    put_reply(R.out + start, reply[i], src.blob + off, sz - PHIP_BUCKET_FIXED_SIZE);
+  } else if (rank == 0 || (rank - 1 < R.max_msgs && start <= R.budget)) {
+    // the first reply not written (its predecessor was, or it has rank 0): n
+    // and bytes over the totals k_reply_scan left -- no atomics
+    R.ctr[kRqN] = rank;
+    R.ctr[kRqBytes] = start;
+  }
+}
+
 }  // namespace phip
 

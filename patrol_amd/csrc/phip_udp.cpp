@@ -124,6 +124,14 @@ int phip_incast_replies(const uint8_t* bytes, const uint64_t* offs, uint32_t n,
   return PHIP_OK;
 }
 
+int phip_reply_peers(const uint8_t* peers, const uint32_t* src, uint32_t n, uint8_t* out_peers) {
+  if (n && (!peers || !src || !out_peers)) return PHIP_ERR_INVALID;
+  for (uint32_t k = 0; k < n; ++k)
+    std::memcpy(out_peers + (uint64_t)k * PHIP_PEER_BYTES, peers + (uint64_t)src[k] * PHIP_PEER_BYTES,
+                PHIP_PEER_BYTES);
+  return PHIP_OK;
+}
+
 int phip_udp_send_batch(int fd, const uint8_t* bytes, const uint64_t* offs, uint32_t n,
                         const uint8_t* peers, uint32_t peer_stride, uint32_t* sent_out) {
   if (sent_out) *sent_out = 0;

@@ -711,6 +711,105 @@ class GPURepo:
         self._check(self.L.phip_receive_soa(self.h, C.byref(m), int(now), C.byref(res), fl))
         return dict(status=st[:n], reply=reply[:n])
 
+    # -- incast reply egress (patrolhip.h "Incast reply egress") --
+    @staticmethod
+    def _reply_host(n, max_msgs, out_cap):
+        """Host buffers of a phip_reply_egress for a batch of n messages (by
+        default caps no batch's replies reach)."""
+        max_msgs = max(n, 1) if max_msgs is None else int(max_msgs)
+        out_cap = _lib.PACKET_SIZE * max(max_msgs, 1) if out_cap is None else int(out_cap)
+        out = np.zeros(max(out_cap, 8), np.uint8)
+        offs = np.zeros(max_msgs + 1, np.uint64)
+        src = np.zeros(max(max_msgs, 1), np.uint32)
+        rq = _lib.phip_reply_egress(out.ctypes.data, out_cap, offs.ctypes.data, src.ctypes.data,
+                                    max_msgs, 0, 0, 0, 0)
+        return rq, out, offs, src
+
+    @staticmethod
+    def _reply_dict(rq, status, out, offs, src, rc=0, **more):
+        """dict(status, data, offs, src, n, replies, skipped, bytes[, stop]); host
+        buffers are cut to what was written, device tensors returned whole."""
+        k = int(rq.n)
+        if not _is_torch(out):
+            out, offs, src = out[:int(rq.bytes)], offs[:k + 1], src[:k]
+        return dict(status=status, data=out, offs=offs, src=src, n=k, replies=int(rq.replies),
+                    skipped=int(rq.skipped), bytes=int(rq.bytes), rc=rc, **more)
+
+    def receive_soa_replies(self, names, added, taken, elapsed, now: int, max_msgs=None,
+                            out_cap=None, want_status: bool = True, classify: bool = False):
+        """phip_receive_soa_replies over host arrays: the batch is received as
+        receive_soa receives it, and its incast replies come back as
+        datagrams (`data` / `offs`) with the batch index each one answers
+        (`src`).  No reply column is asked for; want_status=False asks for
+        no column at all."""
+        n = len(names)
+        blob, noffs = names_blob(names)
+        a, t, e = _np(added, np.uint64), _np(taken, np.uint64), _np(elapsed, np.int64)
+        m = phip_msgs(n, 0, blob.ctypes.data, noffs.ctypes.data, a.ctypes.data, t.ctypes.data,
+                      e.ctypes.data)
+        res, st, _, _, _ = self._results(n)
+        rq, out, offs, src = self._reply_host(n, max_msgs, out_cap)
+        self._check(self.L.phip_receive_soa_replies(
+            self.h, C.byref(m), int(now), C.byref(res) if want_status else None, C.byref(rq),
+            _lib.RECV_CLASSIFY if classify else 0))
+        return self._reply_dict(rq, st[:n] if want_status else None, out, offs, src)
+
+    def receive_soa_replies_device(self, n: int, names, name_offs, added, taken, elapsed, now: int,
+                                   out, offs, src, max_msgs: int, out_cap=None, status=None,
+                                   reply=None, names_len=None, flags: int = 0, allow=()):
+        """phip_receive_soa_replies with device pointers: the batch's columns
+        as receive_soa(device=True) takes them; out (uint8, 8-byte aligned),
+        offs (int64[max_msgs + 1]) and src (int32[max_msgs], or None) are CUDA
+        tensors.  status / reply: optional result columns.  `allow`: return
+        codes handed back in `rc` instead of raised (a stopped batch's)."""
+        m = phip_msgs(n, _names_len(names, names_len), _ptr(names), _ptr(name_offs),
+                      _ptr(added), _ptr(taken), _ptr(elapsed))
+        res = phip_results(_ptr(status), None, None, _ptr(reply))
+        cap = int(out.numel()) if out_cap is None else int(out_cap)
+        rq = _lib.phip_reply_egress(_ptr(out), cap, _ptr(offs), _ptr(src), int(max_msgs), 0, 0, 0, 0)
+        rc = self.L.phip_receive_soa_replies(
+            self.h, C.byref(m), int(now),
+            C.byref(res) if (status is not None or reply is not None) else None, C.byref(rq),
+            DEVICE_PTRS | flags)
+        self._check(rc, allow=allow)
+        return self._reply_dict(rq, status, out, offs, src, rc=rc)
+
+    def receive_datagrams_replies(self, datagrams: Sequence[bytes], now: int, max_msgs=None,
+                                  out_cap=None, want_status: bool = True):
+        """phip_receive_datagrams_replies over host datagrams -> the reply
+        dict of receive_soa_replies plus `stop` (receive_datagrams)."""
+        n = len(datagrams)
+        doffs = np.zeros(n + 1, np.uint64)
+        if n:
+            doffs[1:] = np.cumsum([len(d) for d in datagrams])
+        blob = np.zeros(int(doffs[-1]) + 8, np.uint8)
+        if doffs[-1]:
+            blob[:doffs[-1]] = np.frombuffer(b"".join(datagrams), np.uint8)
+        res, st, _, _, _ = self._results(n)
+        rq, out, offs, src = self._reply_host(n, max_msgs, out_cap)
+        stop = C.c_uint32()
+        rc = self.L.phip_receive_datagrams_replies(
+            self.h, blob.ctypes.data, doffs.ctypes.data, n, int(now),
+            C.byref(res) if want_status else None, C.byref(stop), C.byref(rq), 0)
+        self._check(rc, allow=(-5,))
+        return self._reply_dict(rq, st[:n] if want_status else None, out, offs, src, rc=rc,
+                                stop=stop.value)
+
+    def receive_datagrams_replies_device(self, data, doffs, n: int, now: int, out, offs, src,
+                                         max_msgs: int, out_cap=None, status=None):
+        """phip_receive_datagrams_replies with device pointers (data / doffs as
+        receive_datagrams_device takes them; out / offs / src as
+        receive_soa_replies_device)."""
+        res = phip_results(_ptr(status), None, None, None)
+        cap = int(out.numel()) if out_cap is None else int(out_cap)
+        rq = _lib.phip_reply_egress(_ptr(out), cap, _ptr(offs), _ptr(src), int(max_msgs), 0, 0, 0, 0)
+        stop = C.c_uint32(0)
+        rc = self.L.phip_receive_datagrams_replies(
+            self.h, _ptr(data), _ptr(doffs), n, int(now),
+            C.byref(res) if status is not None else None, C.byref(stop), C.byref(rq), DEVICE_PTRS)
+        self._check(rc, allow=(-5,))
+        return self._reply_dict(rq, status, out, offs, src, rc=rc, stop=stop.value)
+
     def upsert_soa(self, names, added, taken, elapsed, now: int):
         """LocalRepo.UpsertBucket for each state (repo.go:215-235)."""
         n = len(names)
@@ -1351,6 +1450,22 @@ class Ring:
         return dict(status=status[:n] if status is not None else None,
                     reply=reply[:n] if reply is not None else None, stop=stop.value)
 
+    def receive_replies(self, slot: int, n: int, now: int, max_msgs=None, out_cap=None,
+                        want_status: bool = False):
+        """phip_ring_receive_replies: receive the slot and return its incast
+        replies as datagrams -> GPURepo.receive_datagrams_replies' dict.  By
+        default no result column is asked for; reply_peers(peers, r["src"])
+        gives the addresses to send r["data"] / r["offs"] to."""
+        res, st, _, _, _ = GPURepo._results(n)
+        rq, out, offs, src = GPURepo._reply_host(n, max_msgs, out_cap)
+        stop = C.c_uint32()
+        rc = self.L.phip_ring_receive_replies(self.r, slot, int(now),
+                                              C.byref(res) if want_status else None,
+                                              C.byref(stop), C.byref(rq))
+        self.repo._check(rc, allow=(-5,))
+        return GPURepo._reply_dict(rq, st[:n] if want_status else None, out, offs, src, rc=rc,
+                                   stop=stop.value)
+
 
 def udp_send_batch(sock, data: bytes | np.ndarray, offs: np.ndarray, peers=None,
                    peer_stride: int = 0) -> int:
@@ -1401,6 +1516,20 @@ def incast_replies(data: np.ndarray, offs: np.ndarray, status, reply, peers=None
         raise PatrolHipError(rc, "incast replies")
     k = m.value
     return out[:int(oo[k])], oo[:k + 1], (op[:k] if op is not None else None)
+
+
+def reply_peers(peers: np.ndarray, src) -> np.ndarray:
+    """phip_reply_peers: peers[src[k]] for the datagrams of a *_replies call
+    (uint8[n, PEER_BYTES], the batch's senders in reply order)."""
+    L = _lib.load()
+    src = np.ascontiguousarray(src, np.uint32)
+    peers = np.ascontiguousarray(peers, np.uint8)
+    out = np.zeros((max(len(src), 1), _lib.PEER_BYTES), np.uint8)
+    rc = L.phip_reply_peers(peers.ctypes.data if peers.size else None,
+                            src.ctypes.data if src.size else None, len(src), out.ctypes.data)
+    if rc != 0:
+        raise PatrolHipError(rc, "reply peers")
+    return out[:len(src)]
 
 
 def parse_rate(s: bytes):
