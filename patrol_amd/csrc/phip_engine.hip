@@ -1446,47 +1446,80 @@ int resolve_all(phip_handle* h, Src src, u32 n, const int64_t* now_arr, i64 now0
   return PHIP_OK;
 }
 
-// phip_apply_mixed_egress' part of ordered(): where the batch's datagrams go
-// (device memory) and the caps its caller checked against the batch's worst
-// case.  uniform: every op has one kind, known to the host (wants: whether it
-// is TAKE or UPSERT), and the kernels read no kinds.
+// phip_apply_mixed_egress' part of ordered(): where the batch's datagrams go (device
+// memory) and the caps its caller checked against the batch's worst case.
 struct EgressOut {
   u8* out;
   u64* offs;
   u32 max_msgs;
   u64 budget;
-  bool uniform, wants;
 };
 
-// The batch egress behind the folds (phip_kernels.hpp "batch egress"), on the
-// main stream; the totals stay in the egress counter words for the caller.
-int egress_launches(phip_handle* h, const EgressOut& eg, u32 nseg, const u32* uslot,
-                    const u32* sstart, const u32* scnt, const u32* sidx, const u32* lng, u32 nlong,
-                    const u32* huge, u32 nhuge, const u8* status) {
-  const u32 ntiles = (nseg + kSweepTile - 1) / kSweepTile;
-  u32* esz;
-  u64* tile_bytes;
+// What runs behind an ordered batch's folds (behind_folds; ow.status is
+// required): the batch's egress into *eg, or, eg == nullptr, its marks in the
+// change set of a handle that keeps one.  uniform: every op has one kind,
+// known to the host, and the kernels read no kinds; wants: that kind is TAKE
+// or UPSERT (false unless uniform).
+struct Behind {
+  bool uniform, wants;
+  const EgressOut* eg;
+};
+
+// An ordered batch, sorted by slot and cut into one segment per bucket it
+// names (segment_batch): device pointers into the handle's buffers.
+struct Segs {
+  u32 n;              // ops of the batch
+  u32 nseg;           // segments (kCtrSegs, k_seg_finish)
+  u32 nlong;          // entries of lng (kCtrLongSegs, k_seg_finish)
+  u32 nhuge;          // entries of huge (kCtrHugeSegs, k_seg_finish)
+  const u32* uslot;   // by segment: the bucket's slot (k_seg_write)
+  const u32* sstart;  // by segment: its first position in the sorted order (k_seg_write)
+  const u32* scnt;    // by segment: its ops (k_seg_finish)
+  const u32* sidx;    // by sorted position: op index | kind << kOpIdxBits (the sort's values)
+  u32* lng;           // the segments of kLongSeg < ops <= kHugeSeg (k_seg_finish, fold_rest)
+  const u32* huge;    // the segments over kHugeSeg ops (k_seg_finish)
+  const OpRec* opr;   // by op index: the op records (k_pack_ops)
+};
+
+// What runs behind the folds, on the main stream: the batch egress
+// (phip_kernels.hpp "batch egress"; the totals stay in the egress counter
+// words for the caller) or the marks (phip_kernels.hpp "change set"), either
+// behind k_egress_wants when mixed kinds meet segments above kLongSeg ops.
+int behind_folds(phip_handle* h, const Behind& b, const Segs& sg, const u8* status) {
+  const u32 ntiles = (sg.nseg + kSweepTile - 1) / kSweepTile;
+  const bool ask = !b.uniform && (sg.nlong || sg.nhuge);
+  u32* esz = nullptr;
+  u64* tile_bytes = nullptr;
   int rc;
   // one buffer: the tiles' byte sums, then their counts (both sections each)
-  if ((rc = ensure(h, B_EGSZ, nseg, &esz)) ||
-      (rc = ensure(h, B_EGTILE, 3 * (size_t)ntiles, &tile_bytes)))
+  if (((b.eg || ask) && (rc = ensure(h, B_EGSZ, sg.nseg, &esz))) ||
+      (b.eg && (rc = ensure(h, B_EGTILE, 3 * (size_t)ntiles, &tile_bytes))))
     return rc;
-  u32* tile_cnt = (u32*)(tile_bytes + 2 * (size_t)ntiles);
-  if (!eg.uniform && (nlong || nhuge)) {
+  if (ask) {
     Launch l(h, "k_egress_wants");
-    k_egress_wants<<<(nlong + kBlock / 64 - 1) / (kBlock / 64) + nhuge, kBlock, 0, h->stream>>>(
-        lng, nlong, huge, nhuge, sstart, scnt, sidx, esz);
+    k_egress_wants<<<(sg.nlong + kBlock / 64 - 1) / (kBlock / 64) + sg.nhuge, kBlock, 0,
+                     h->stream>>>(sg.lng, sg.nlong, sg.huge, sg.nhuge, sg.sstart, sg.scnt, sg.sidx,
+                                  esz);
   }
+  if (!b.eg) {
+    Launch l(h, "k_changes_mark");
+#define PHIP_MARK(U)                                              \
+  k_changes_mark<U><<<grid_for(sg.nseg), kBlock, 0, h->stream>>>( \
+      sg.uslot, sg.sstart, sg.scnt, sg.sidx, sg.nseg, status, b.wants, esz, h->marks)
+    if (b.uniform) PHIP_MARK(true); else PHIP_MARK(false);
+#undef PHIP_MARK
+    HIPCHK(h, hipGetLastError());
+    return PHIP_OK;
+  }
+  u32* tile_cnt = (u32*)(tile_bytes + 2 * (size_t)ntiles);
   {
     Launch l(h, "k_egress_count");
-    if (eg.uniform)
-      k_egress_count<true><<<ntiles, kBlock, 0, h->stream>>>(h->recs, uslot, sstart, scnt, sidx, nseg,
-                                                            status, eg.wants, esz, ntiles, tile_cnt,
-                                                            tile_bytes);
-    else
-      k_egress_count<false><<<ntiles, kBlock, 0, h->stream>>>(h->recs, uslot, sstart, scnt, sidx,
-                                                             nseg, status, false, esz, ntiles,
-                                                             tile_cnt, tile_bytes);
+#define PHIP_COUNT(U)                                                                          \
+  k_egress_count<U><<<ntiles, kBlock, 0, h->stream>>>(h->recs, sg.uslot, sg.sstart, sg.scnt, \
+                                                      sg.sidx, sg.nseg, status, b.wants, esz, \
+                                                      ntiles, tile_cnt, tile_bytes)
+    if (b.uniform) PHIP_COUNT(true); else PHIP_COUNT(false);
+#undef PHIP_COUNT
   }
   {
     Launch l(h, "k_egress_scan");
@@ -1495,95 +1528,114 @@ int egress_launches(phip_handle* h, const EgressOut& eg, u32 nseg, const u32* us
   {
     // (long names are bounded by the arena's size, as in the sweep)
     Launch l(h, "k_egress_write");
-    k_egress_write<<<ntiles, kSweepBlock, 0, h->stream>>>(h->recs, h->arena, h->arena_cap, uslot, esz,
-                                                          nseg, ntiles, tile_cnt, tile_bytes,
-                                                          eg.max_msgs, eg.budget, eg.out, eg.offs,
-                                                          h->ctr);
+    k_egress_write<<<ntiles, kSweepBlock, 0, h->stream>>>(
+        h->recs, h->arena, h->arena_cap, sg.uslot, esz, sg.nseg, ntiles, tile_cnt, tile_bytes,
+        b.eg->max_msgs, b.eg->budget, b.eg->out, b.eg->offs, h->ctr);
   }
   HIPCHK(h, hipGetLastError());
   return PHIP_OK;
 }
 
-// phip_apply_mixed's part of ordered() on a handle that keeps a change set:
-// the batch's marks (phip_kernels.hpp "change set"), with the egress' uniform
-// form.
-struct MarkPlan {
-  bool uniform, wants;
+// A side stream's way back.  While armed (ev: the event that ends the side
+// stream's work), the main stream waits on ev when the Join goes out of scope:
+// no return from ordered() leaves a fork open.  join(): that wait, checked.
+struct Join {
+  phip_handle* h;
+  hipEvent_t ev = nullptr;
+  int join() {
+    hipEvent_t e = ev;
+    ev = nullptr;
+    if (e) HIPCHK(h, hipStreamWaitEvent(h->stream, e, 0));
+    return PHIP_OK;
+  }
+  ~Join() { if (ev) (void)hipStreamWaitEvent(h->stream, ev, 0); }
 };
 
-// The marks behind the folds, on the main stream: k_changes_mark, behind
-// k_egress_wants when mixed kinds meet segments above kLongSeg ops.
-int mark_launches(phip_handle* h, const MarkPlan& mp, u32 nseg, const u32* uslot, const u32* sstart,
-                  const u32* scnt, const u32* sidx, const u32* lng, u32 nlong, const u32* huge,
-                  u32 nhuge, const u8* status) {
-  u32* esz = nullptr;
-  if (!mp.uniform && (nlong || nhuge)) {
-    if (int rc = ensure(h, B_EGSZ, nseg, &esz)) return rc;
-    Launch l(h, "k_egress_wants");
-    k_egress_wants<<<(nlong + kBlock / 64 - 1) / (kBlock / 64) + nhuge, kBlock, 0, h->stream>>>(
-        lng, nlong, huge, nhuge, sstart, scnt, sidx, esz);
-  }
-  {
-    Launch l(h, "k_changes_mark");
-    if (mp.uniform)
-      k_changes_mark<true><<<grid_for(nseg), kBlock, 0, h->stream>>>(
-          uslot, sstart, scnt, sidx, nseg, status, mp.wants, esz, h->marks);
-    else
-      k_changes_mark<false><<<grid_for(nseg), kBlock, 0, h->stream>>>(
-          uslot, sstart, scnt, sidx, nseg, status, false, esz, h->marks);
-  }
-  HIPCHK(h, hipGetLastError());
+// stream4 and its events, on first use (phip_handle::stream4 says why not at open).
+int thread_stream(phip_handle* h) {
+  if (!h->ev_t4a) HIPCHK(h, hipEventCreateWithFlags(&h->ev_t4a, hipEventDisableTiming));
+  if (!h->ev_t4b) HIPCHK(h, hipEventCreateWithFlags(&h->ev_t4b, hipEventDisableTiming));
+  if (!h->stream4) HIPCHK(h, hipStreamCreateWithFlags(&h->stream4, hipStreamNonBlocking));
   return PHIP_OK;
 }
 
-// Apply a mixed op stream in seq order.  The NEW flag of created buckets is
-// consumed (cleared) by the fold itself.  eg: the batch's egress is written
-// behind the folds; mp: its marks are set there (ow.status is required by
-// either).
+// [schedule]
+// ordered()'s schedule: what each stream runs, in the order the host issues
+// it, and every event edge ("rec" records the event, "wait" waits on it).
+// Different segments touch different slots, so the three fold families
+// overlap.  [huge]: batches with segments over kHugeSeg ops only; [split]:
+// with more than PHIP_HUGE_FIRST of them only.
+//
+//   main (h->stream)       stream2                stream3 [split]    stream4
+//   ---------------------  ---------------------  -----------------  ---------------
+//   -- segment_batch --
+//   rec ev_fork            wait ev_fork
+//   resolve_all            k_pack_ops
+//   radix_sort_pairs       rec ev_pack
+//   segments, read_ctr
+//   wait ev_pack
+//   -- fold_huge [huge] --
+//   default fills
+//   rec ev_fork            wait ev_fork
+//                          [split] k_huge_order
+//                          k_huge_offsets
+//                          [split] rec ev_fork3   wait ev_fork3
+//                          k_gather_huge
+//   wait ev_gather         rec ev_gather
+//                          k_fold_block
+//                          k_huge_outputs
+//                                                 k_gather_huge2
+//   wait ev_gather3                               rec ev_gather3
+//                                                 k_fold_block2
+//                                                 k_huge_outputs2
+//                          wait ev_join3          rec ev_join3
+//                          rec ev_join
+//   -- fold_rest --
+//   rec ev_t4a                                                       wait ev_t4a
+//   rocprim::partition                                               k_fold_thread
+//   k_fold_wave                                                      rec ev_t4b
+//   wait ev_t4b
+//   [huge] wait ev_join
+//   behind_folds
+//
+// ev_pack: the op records are read by the folds only, so k_pack_ops runs
+// beside the resolve (bound by probe latency), the sort and the segmentation.
+// fold_huge: the largest huge segments (PHIP_HUGE_FIRST of them, moved to the
+// front of the list by k_huge_order) run gather -> fold -> outputs on stream2,
+// the others the same chain on stream3: the largest segments' folds are the
+// longest sequential chains, so they start as soon as their own (smaller)
+// gather is done.
+// ev_gather, ev_gather3: the wave and thread folds start behind the gathers;
+// the gathers alone, then the latency-bound block folds beside those
+// bandwidth-bound folds, is the shorter schedule.
+// fold_rest: the thread folds beside the wave folds, 6.37-6.38 against
+// 6.45-6.50 ms per C3 step.
+// ev_pack, ev_t4b, ev_join: waited on by ordered() itself, through a Join each.
+// [/schedule]
+
+// The batch's Segs: the buffers sized, k_pack_ops forked (*pack armed), every
+// op's slot resolved, the sort and the segmentation; one host round trip.
 template <class Src>
-int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow,
-            const EgressOut* eg = nullptr, const MarkPlan* mp = nullptr) {
-  if (n == 0) return PHIP_OK;
-  if (n > kMaxOrderedOps)
-    return set_err(h, PHIP_ERR_INVALID, "ordered batch of %u ops exceeds 2^30", n);
+int segment_batch(phip_handle* h, Src src, u32 n, const OpView& ov, Segs* sg, Join* pack) {
   int rc;
   u32 *idx, *sslot, *sidx, *uslot, *scnt, *sstart, *lng, *huge;
+  OpRec* opr;
   if ((rc = ensure(h, B_IDX, n, &idx)) || (rc = ensure(h, B_SSLOT, n, &sslot)) ||
       (rc = ensure(h, B_SIDX, n, &sidx)) || (rc = ensure(h, B_USLOT, n, &uslot)) ||
       (rc = ensure(h, B_SCNT, n, &scnt)) || (rc = ensure(h, B_SSTART, n, &sstart)) ||
-      (rc = ensure(h, B_LONG, n, &lng)) || (rc = ensure(h, B_HUGE, n, &huge)))
+      (rc = ensure(h, B_LONG, n, &lng)) || (rc = ensure(h, B_HUGE, n, &huge)) ||
+      (rc = ensure(h, B_OPS, n, &opr)))
     return rc;
-  OpRec* opr;
-  if ((rc = ensure(h, B_OPS, n, &opr))) return rc;
-  // The op records are read by the folds only: k_pack_ops runs on stream2
-  // beside the resolve, the sort and the segmentation (independent streams of
-  // the batch's columns; the resolve is bound by probe latency), and the main
-  // stream joins it before the first fold, or on any error return (PackJoin).
-  struct PackJoin {
-    phip_handle* h;
-    bool armed = true;
-    int join() {
-      armed = false;
-      return hipStreamWaitEvent(h->stream, h->ev_pack, 0) == hipSuccess
-                 ? PHIP_OK
-                 : set_err(h, PHIP_ERR_HIP, "hipStreamWaitEvent (op records)");
-    }
-    ~PackJoin() { if (armed) (void)hipStreamWaitEvent(h->stream, h->ev_pack, 0); }
-  } pack_join{h};
-  auto fork_pack = [&]() -> int {
-    HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-    {
-      Launch l(h, "k_pack_ops", h->stream2);
-      k_pack_ops<<<grid_for(n, kBlock * kPackPer), kBlock, 0, h->stream2>>>(ov, n, opr);
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev_pack, h->stream2));
-    return PHIP_OK;
-  };
-  if ((rc = fork_pack())) return rc;
-  u32* slot;
-  u32 n_claimed = 0;
+  HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
+  HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+  {
+    Launch l(h, "k_pack_ops", h->stream2);
+    k_pack_ops<<<grid_for(n, kBlock * kPackPer), kBlock, 0, h->stream2>>>(ov, n, opr);
+  }
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev_pack, h->stream2));
+  pack->ev = h->ev_pack;
+  u32 *slot, n_claimed = 0;   // (n_claimed unused: the folds' store_state clears the NEW flags)
   if ((rc = resolve_all(h, src, n, ov.now, ov.now0, &slot, &n_claimed,
                         SortVals{ov.kind, ov.kind0, idx})))
     return rc;
@@ -1597,10 +1649,10 @@ int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow,
   // segmentation buffers and scan temp sized before the sort is enqueued (a
   // larger B_TEMP must not replace the one the sort is using)
   const u32 ntiles = (u32)(((u64)n + kSegTile - 1) / kSegTile);
-  u32 *segt = nullptr, *segb = nullptr;
+  u32* segt;
   size_t tbs = 0;
   if ((rc = ensure(h, B_SEGT, 2 * ((size_t)ntiles + 1), &segt))) return rc;
-  segb = segt + ntiles + 1;
+  u32* const segb = segt + ntiles + 1;
   HIPCHK(h, rocprim::exclusive_scan(nullptr, tbs, segt, segb, 0u, (size_t)ntiles + 1,
                                     rocprim::plus<u32>(), h->stream));
   u8* temp;
@@ -1610,7 +1662,6 @@ int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow,
     HIPCHK(h, rocprim::radix_sort_pairs<SlotSortConfig>(temp, tb, slot, sslot, idx, sidx, n, 0u,
                                                          h->L, h->stream));
   }
-  u32 nseg = 0;
   {
     Launch l(h, "segments");
     k_seg_count<<<ntiles, 256, 0, h->stream>>>(sslot, n, segt, h->ctr);
@@ -1621,191 +1672,200 @@ int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow,
         segb, ntiles, sstart, n, scnt, lng, huge, h->ctr);
     HIPCHK(h, hipGetLastError());
     if ((rc = read_ctr(h))) return rc;
-    nseg = h->ctr_host[kCtrSegs];
   }
-  u32 nlong = h->ctr_host[kCtrLongSegs], nhuge = h->ctr_host[kCtrHugeSegs];
-  if ((rc = pack_join.join())) return rc;
-  // Different segments touch different slots, so the folds may overlap: the
-  // hot-bucket workgroups run on stream2 beside the wave and thread folds.
-  if (nhuge) {
-    // k_huge_outputs stores only results that differ from the defaults
-    // (write_out_nd): the defaults go in first, as streams
-    if (ow.status) HIPCHK(h, hipMemsetAsync(ow.status, PHIP_ST_MERGED, n, h->stream));
-    if (ow.remaining) HIPCHK(h, hipMemsetAsync(ow.remaining, 0, (size_t)n * 8, h->stream));
-    if (ow.have) HIPCHK(h, hipMemsetAsync(ow.have, 0, (size_t)n * 8, h->stream));
-    u64 *hoff, *woff;
-    OpRec* hop;
-    u32 *hval, *rpos, *runn, *wrun;
-    RunState* rst;
-    u8* segex;
-    WinSum* sums;
-    GMax* wing;
-    u32* segxf;
-    const size_t nwin_max = (size_t)n / kFoldWin + nhuge + 1;
-    if ((rc = ensure(h, B_WOFF, (size_t)nhuge + 1, &woff)) ||
-        (rc = ensure(h, B_SUMS, nwin_max, &sums)) || (rc = ensure(h, B_WRUN, nwin_max, &wrun)) ||
-        (rc = ensure(h, B_HOFF, nhuge, &hoff)) || (rc = ensure(h, B_HOP, n, &hop)) ||
-        (rc = ensure(h, B_HVAL, n, &hval)) || (rc = ensure(h, B_RPOS, (size_t)n + nhuge, &rpos)) ||
-        (rc = ensure(h, B_RST, (size_t)n + nhuge, &rst)) || (rc = ensure(h, B_RUNN, nhuge, &runn)) ||
-        (rc = ensure(h, B_SEGEX, nhuge, &segex)) || (rc = ensure(h, B_WING, nwin_max, &wing)) ||
-        (rc = ensure(h, B_SEGXF, nhuge, &segxf)))
-      return rc;
-    // The largest huge segments (kFirst of them, moved to the front of the
-    // list) run gather -> fold -> outputs on stream2, the other huge segments
-    // the same chain on stream3, beside the wave and thread folds on the
-    // main stream: the largest segments' folds are the longest sequential
-    // chains, so they start as soon as their own (smaller) gather is done.
-    const u32 kFirst = std::min<u32>(PHIP_HUGE_FIRST, kHugeFirstMax);
-    const bool split = kFirst > 0 && nhuge > kFirst;
-    const u32 hsplit = split ? kFirst : nhuge;
-    u32* hl = huge;
-    if (split && (rc = ensure(h, B_HUGE2, nhuge, &hl))) return rc;
-    HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-    if (split) {
-      k_huge_order<<<1, 1024, 0, h->stream2>>>(huge, nhuge, scnt, kFirst, hl);
-      HIPCHK(h, hipGetLastError());
-    }
-    k_huge_offsets<<<1, 1024, 0, h->stream2>>>(hl, nhuge, scnt, hoff, woff);
-    HIPCHK(h, hipGetLastError());
-    if (split) {
-      HIPCHK(h, hipEventRecord(h->ev_fork3, h->stream2));
-      HIPCHK(h, hipStreamWaitEvent(h->stream3, h->ev_fork3, 0));
-    }
-    // A diagnostics build (tools/build_variants.sh "stats:-DPHIP_FOLD_STATS")
-    // prints per hot segment ops / windows / windows folded / rounds / bursts
-    // / ops walked / runs / cycles to stderr.
-    u64* fold_dbg = nullptr;
+  const u32* c = h->ctr_host;
+  *sg = Segs{n,     c[kCtrSegs], c[kCtrLongSegs], c[kCtrHugeSegs],
+             uslot, sstart,      scnt,            sidx,            lng, huge, opr};
+  return PHIP_OK;
+}
+
 #ifdef PHIP_FOLD_STATS
-    if ((rc = ensure(h, B_FOLDDBG, (size_t)nhuge * 16, &fold_dbg))) return rc;
-#endif
-    // gather / outputs: window-striding grids of 8 workgroups per CU (the
-    // window count is known on the device only)
-    const unsigned hgrid = (unsigned)std::min<size_t>(nwin_max, (size_t)h->ncu * 8);
-    // one chain per group: segments [h0, h1) of the list on stream st; the
-    // main stream's wave and thread folds wait for the gathers (ev): the
-    // gathers alone, then the latency-bound block folds beside those
-    // bandwidth-bound folds, is the shorter schedule.
-    auto chain = [&](u32 h0, u32 h1, hipStream_t st, hipEvent_t ev, const char* ng,
-                     const char* nf, const char* no) -> int {
-      {
-        Launch l(h, ng, st);
-        k_gather_huge<<<hgrid, kBlock, 0, st>>>(hl, h1, hoff, woff, sstart, scnt, sidx, opr, hop,
-                                                 hval, sums, h0);
-      }
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipEventRecord(ev, st));
-      HIPCHK(h, hipStreamWaitEvent(h->stream, ev, 0));
-      {
-        Launch l(h, nf, st);
-        k_fold_block<<<h1 - h0, kFoldThreads, 0, st>>>(hl, h1, uslot, hoff, scnt, hval, hop,
-                                                       h->recs, rpos, rst, runn, segex, segxf,
-                                                       woff, sums, wrun, wing, fold_dbg, h0);
-      }
-      HIPCHK(h, hipGetLastError());
-      {
-        Launch l(h, no, st);
-#define PHIP_HUGE_OUT(M)                                                                      \
-  k_huge_outputs<M><<<hgrid, kBlock, 0, st>>>(hl, h1, hoff, woff, scnt, hval, hop, rpos, rst, \
-                                              runn, segex, segxf, wrun, wing, ow, h0)
-        PHIP_OUT_DISPATCH(out_mask(ow), PHIP_HUGE_OUT);
-#undef PHIP_HUGE_OUT
-      }
-      HIPCHK(h, hipGetLastError());
-      return PHIP_OK;
-    };
-    if ((rc = chain(0, hsplit, h->stream2, h->ev_gather, "k_gather_huge", "k_fold_block",
-                    "k_huge_outputs")))
-      return rc;
-    if (split) {
-      if ((rc = chain(hsplit, nhuge, h->stream3, h->ev_gather3, "k_gather_huge2", "k_fold_block2",
-                      "k_huge_outputs2")))
-        return rc;
-      HIPCHK(h, hipEventRecord(h->ev_join3, h->stream3));
-      HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_join3, 0));
-    }
-    if (fold_dbg) {
-      std::vector<u64> d((size_t)nhuge * 16);
-      HIPCHK(h, hipMemcpyAsync(d.data(), fold_dbg, d.size() * 8, hipMemcpyDeviceToHost, h->stream2));
-      HIPCHK(h, hipStreamSynchronize(h->stream2));
-      std::vector<u32> ord(nhuge);
-      for (u32 k = 0; k < nhuge; ++k) ord[k] = k;
-      std::sort(ord.begin(), ord.end(), [&](u32 x, u32 y) { return d[16 * x + 7] > d[16 * y + 7]; });
-      fprintf(stderr, "fold: %u huge segments\n", nhuge);
-      for (u32 i = 0; i < nhuge && i < 6; ++i) {
-        const u32 k = ord[i];
-        const u64* e = &d[16 * k];
-        fprintf(stderr, "fold[%u] ops %llu windows %llu folded %llu rounds %llu bursts %llu walked "
-                "%llu runs %llu us %.1f | scan %.1f stage %.1f prefix %.1f round %.1f burst %.1f "
-                "| burst iterations %llu (stopped at a merge %llu)\n",
-                k, e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7] / 100.0, e[8] / 100.0,
-                e[9] / 100.0, e[10] / 100.0, e[11] / 100.0, e[12] / 100.0, e[13], e[14]);
-      }
-    }
+// A diagnostics build (tools/build_variants.sh "stats:-DPHIP_FOLD_STATS")
+// prints per hot segment ops / windows / windows folded / rounds / bursts
+// / ops walked / runs / cycles to stderr, once stream2 has run the chains.
+int fold_stats_dump(phip_handle* h, const u64* fold_dbg, u32 nhuge) {
+  std::vector<u64> d((size_t)nhuge * 16);
+  HIPCHK(h, hipMemcpyAsync(d.data(), fold_dbg, d.size() * 8, hipMemcpyDeviceToHost, h->stream2));
+  HIPCHK(h, hipStreamSynchronize(h->stream2));
+  std::vector<u32> ord(nhuge);
+  for (u32 k = 0; k < nhuge; ++k) ord[k] = k;
+  std::sort(ord.begin(), ord.end(), [&](u32 x, u32 y) { return d[16 * x + 7] > d[16 * y + 7]; });
+  fprintf(stderr, "fold: %u huge segments\n", nhuge);
+  for (u32 i = 0; i < nhuge && i < 6; ++i) {
+    const u32 k = ord[i];
+    const u64* e = &d[16 * k];
+    fprintf(stderr, "fold[%u] ops %llu windows %llu folded %llu rounds %llu bursts %llu walked "
+            "%llu runs %llu us %.1f | scan %.1f stage %.1f prefix %.1f round %.1f burst %.1f "
+            "| burst iterations %llu (stopped at a merge %llu)\n",
+            k, e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7] / 100.0, e[8] / 100.0,
+            e[9] / 100.0, e[10] / 100.0, e[11] / 100.0, e[12] / 100.0, e[13], e[14]);
   }
-  // The thread folds (short segments, one thread each) run on stream4 beside
-  // the wave folds: different segments, different slots.  6.37-6.38 against
-  // 6.45-6.50 ms per C3 step.  The main stream joins them
-  // before returning, or on any error return (ThreadJoin).
-  struct ThreadJoin {
-    phip_handle* h;
-    bool armed = false;
-    ~ThreadJoin() { if (armed) (void)hipStreamWaitEvent(h->stream, h->ev_t4b, 0); }
-  } thread_join{h};
-  if (!h->ev_t4a) HIPCHK(h, hipEventCreateWithFlags(&h->ev_t4a, hipEventDisableTiming));
-  if (!h->ev_t4b) HIPCHK(h, hipEventCreateWithFlags(&h->ev_t4b, hipEventDisableTiming));
-  if (!h->stream4) HIPCHK(h, hipStreamCreateWithFlags(&h->stream4, hipStreamNonBlocking));
+  return PHIP_OK;
+}
+#endif
+
+// The huge segments' folds, one workgroup each, on stream2 and stream3 (the
+// schedule's fold_huge rows); *huge: armed with ev_join.
+int fold_huge(phip_handle* h, const Segs& sg, const OutView& ow, Join* huge) {
+  const u32 n = sg.n, nhuge = sg.nhuge;
+  int rc;
+  // k_huge_outputs stores only results that differ from the defaults
+  // (write_out_nd): the defaults go in first, as streams
+  if (ow.status) HIPCHK(h, hipMemsetAsync(ow.status, PHIP_ST_MERGED, n, h->stream));
+  if (ow.remaining) HIPCHK(h, hipMemsetAsync(ow.remaining, 0, (size_t)n * 8, h->stream));
+  if (ow.have) HIPCHK(h, hipMemsetAsync(ow.have, 0, (size_t)n * 8, h->stream));
+  u64 *hoff, *woff;
+  OpRec* hop;
+  u32 *hval, *rpos, *runn, *wrun, *segxf;
+  RunState* rst;
+  u8* segex;
+  WinSum* sums;
+  GMax* wing;
+  const size_t nwin_max = (size_t)n / kFoldWin + nhuge + 1;
+  if ((rc = ensure(h, B_WOFF, (size_t)nhuge + 1, &woff)) ||
+      (rc = ensure(h, B_SUMS, nwin_max, &sums)) || (rc = ensure(h, B_WRUN, nwin_max, &wrun)) ||
+      (rc = ensure(h, B_HOFF, nhuge, &hoff)) || (rc = ensure(h, B_HOP, n, &hop)) ||
+      (rc = ensure(h, B_HVAL, n, &hval)) || (rc = ensure(h, B_RPOS, (size_t)n + nhuge, &rpos)) ||
+      (rc = ensure(h, B_RST, (size_t)n + nhuge, &rst)) || (rc = ensure(h, B_RUNN, nhuge, &runn)) ||
+      (rc = ensure(h, B_SEGEX, nhuge, &segex)) || (rc = ensure(h, B_WING, nwin_max, &wing)) ||
+      (rc = ensure(h, B_SEGXF, nhuge, &segxf)))
+    return rc;
+  const u32 kFirst = std::min<u32>(PHIP_HUGE_FIRST, kHugeFirstMax);
+  const bool split = kFirst > 0 && nhuge > kFirst;
+  const u32 hsplit = split ? kFirst : nhuge;
+  u32* hl2 = nullptr;   // [split] the list with the largest in front
+  if (split && (rc = ensure(h, B_HUGE2, nhuge, &hl2))) return rc;
+  const u32* hl = split ? hl2 : sg.huge;
+  HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
+  HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+  if (split) {
+    k_huge_order<<<1, 1024, 0, h->stream2>>>(sg.huge, nhuge, sg.scnt, kFirst, hl2);
+    HIPCHK(h, hipGetLastError());
+  }
+  k_huge_offsets<<<1, 1024, 0, h->stream2>>>(hl, nhuge, sg.scnt, hoff, woff);
+  HIPCHK(h, hipGetLastError());
+  if (split) {
+    HIPCHK(h, hipEventRecord(h->ev_fork3, h->stream2));
+    HIPCHK(h, hipStreamWaitEvent(h->stream3, h->ev_fork3, 0));
+  }
+  u64* fold_dbg = nullptr;
+#ifdef PHIP_FOLD_STATS
+  if ((rc = ensure(h, B_FOLDDBG, (size_t)nhuge * 16, &fold_dbg))) return rc;
+#endif
+  // gather / outputs: window-striding grids of 8 workgroups per CU (the
+  // window count is known on the device only)
+  const unsigned hgrid = (unsigned)std::min<size_t>(nwin_max, (size_t)h->ncu * 8);
+  // one chain per group: segments [h0, h1) of the list on stream st, its
+  // gather's event ev waited on by the main stream
+  auto chain = [&](u32 h0, u32 h1, hipStream_t st, hipEvent_t ev, const char* ng,
+                   const char* nf, const char* no) -> int {
+    {
+      Launch l(h, ng, st);
+      k_gather_huge<<<hgrid, kBlock, 0, st>>>(hl, h1, hoff, woff, sg.sstart, sg.scnt, sg.sidx,
+                                               sg.opr, hop, hval, sums, h0);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(ev, st));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, ev, 0));
+    {
+      Launch l(h, nf, st);
+      k_fold_block<<<h1 - h0, kFoldThreads, 0, st>>>(hl, h1, sg.uslot, hoff, sg.scnt, hval, hop,
+                                                     h->recs, rpos, rst, runn, segex, segxf, woff,
+                                                     sums, wrun, wing, fold_dbg, h0);
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+      Launch l(h, no, st);
+#define PHIP_HUGE_OUT(M)                                                                         \
+  k_huge_outputs<M><<<hgrid, kBlock, 0, st>>>(hl, h1, hoff, woff, sg.scnt, hval, hop, rpos, rst, \
+                                              runn, segex, segxf, wrun, wing, ow, h0)
+      PHIP_OUT_DISPATCH(out_mask(ow), PHIP_HUGE_OUT);
+#undef PHIP_HUGE_OUT
+    }
+    HIPCHK(h, hipGetLastError());
+    return PHIP_OK;
+  };
+  if ((rc = chain(0, hsplit, h->stream2, h->ev_gather, "k_gather_huge", "k_fold_block",
+                  "k_huge_outputs")))
+    return rc;
+  if (split) {
+    if ((rc = chain(hsplit, nhuge, h->stream3, h->ev_gather3, "k_gather_huge2", "k_fold_block2",
+                    "k_huge_outputs2")))
+      return rc;
+    HIPCHK(h, hipEventRecord(h->ev_join3, h->stream3));
+    HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_join3, 0));
+  }
+  HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
+  huge->ev = h->ev_join;
+#ifdef PHIP_FOLD_STATS
+  if ((rc = fold_stats_dump(h, fold_dbg, nhuge))) return rc;
+#endif
+  return PHIP_OK;
+}
+
+// The other segments' folds: the short ones, one thread each, on stream4
+// (*threads: armed with ev_t4b), the long ones, one wave each, on the main
+// stream.  sg->lng: replaced by the list in the order the wave folds took it.
+int fold_rest(phip_handle* h, Segs* sg, const OutView& ow, Join* threads) {
+  int rc;
+  if ((rc = thread_stream(h))) return rc;
   hipStream_t ts = h->stream4;
   HIPCHK(h, hipEventRecord(h->ev_t4a, h->stream));
   HIPCHK(h, hipStreamWaitEvent(ts, h->ev_t4a, 0));
   {
     Launch l(h, "k_fold_thread", ts);
-#define PHIP_FOLD_THREAD(M)                                                            \
-  k_fold_thread<M><<<grid_for(nseg), kBlock, 0, ts>>>(uslot, sstart, scnt, nseg, sidx, \
-                                                      opr, h->recs, ow)
+#define PHIP_FOLD_THREAD(M)                                                                  \
+  k_fold_thread<M><<<grid_for(sg->nseg), kBlock, 0, ts>>>(sg->uslot, sg->sstart, sg->scnt, \
+                                                          sg->nseg, sg->sidx, sg->opr, h->recs, ow)
     PHIP_OUT_DISPATCH(out_mask(ow), PHIP_FOLD_THREAD);
 #undef PHIP_FOLD_THREAD
     HIPCHK(h, hipGetLastError());
   }
   HIPCHK(h, hipEventRecord(h->ev_t4b, ts));
-  thread_join.armed = true;
-  if (nlong) {
-    // the long segments over kBigLongSeg ops first (their sequential chains
-    // are the longest), then the rest
-    if (nlong > 1) {
-      u32* lng2;
-      if ((rc = ensure(h, B_LONG2, nlong, &lng2))) return rc;
-      size_t tb7 = 0;
-      HIPCHK(h, rocprim::partition(nullptr, tb7, lng, lng2, h->ctr + kCtrAux, (size_t)nlong,
-                                   BigLongSeg{scnt}, h->stream));
-      if ((rc = ensure(h, B_TEMP, tb7, &temp))) return rc;
-      HIPCHK(h, rocprim::partition(temp, tb7, lng, lng2, h->ctr + kCtrAux, (size_t)nlong,
-                                   BigLongSeg{scnt}, h->stream));
-      lng = lng2;
-    }
-    Launch l(h, "k_fold_wave");
-#define PHIP_FOLD_WAVE(M)                                                                  \
-  k_fold_wave<M><<<nlong, 64, 0, h->stream>>>(lng, nlong, uslot, sstart, scnt, sidx, opr, \
-                                              h->recs, ow)
-    PHIP_OUT_DISPATCH(out_mask(ow), PHIP_FOLD_WAVE);
+  threads->ev = h->ev_t4b;
+  const u32 nlong = sg->nlong;
+  if (!nlong) return PHIP_OK;
+  // the long segments over kBigLongSeg ops first (their sequential chains
+  // are the longest), then the rest
+  if (nlong > 1) {
+    u32* lng2;
+    u8* temp;
+    if ((rc = ensure(h, B_LONG2, nlong, &lng2))) return rc;
+    size_t tb = 0;
+    HIPCHK(h, rocprim::partition(nullptr, tb, sg->lng, lng2, h->ctr + kCtrAux, (size_t)nlong,
+                                 BigLongSeg{sg->scnt}, h->stream));
+    if ((rc = ensure(h, B_TEMP, tb, &temp))) return rc;
+    HIPCHK(h, rocprim::partition(temp, tb, sg->lng, lng2, h->ctr + kCtrAux, (size_t)nlong,
+                                 BigLongSeg{sg->scnt}, h->stream));
+    sg->lng = lng2;
+  }
+  Launch l(h, "k_fold_wave");
+#define PHIP_FOLD_WAVE(M)                                                                      \
+  k_fold_wave<M><<<nlong, 64, 0, h->stream>>>(sg->lng, nlong, sg->uslot, sg->sstart, sg->scnt, \
+                                              sg->sidx, sg->opr, h->recs, ow)
+  PHIP_OUT_DISPATCH(out_mask(ow), PHIP_FOLD_WAVE);
 #undef PHIP_FOLD_WAVE
-    HIPCHK(h, hipGetLastError());
-  }
-  thread_join.armed = false;
-  HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_t4b, 0));
-  if (nhuge) {
-    HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  }
-  (void)n_claimed;  // NEW flags cleared by store_state in the folds
-  // (every fold has joined the main stream: the records and statuses are final)
-  if (eg)
-    return egress_launches(h, *eg, nseg, uslot, sstart, scnt, sidx, lng, nlong, huge, nhuge,
-                           ow.status);
-  if (mp)
-    return mark_launches(h, *mp, nseg, uslot, sstart, scnt, sidx, lng, nlong, huge, nhuge,
-                         ow.status);
+  HIPCHK(h, hipGetLastError());
   return PHIP_OK;
+}
+
+// Apply a mixed op stream in seq order, by the schedule above.  The NEW flag
+// of created buckets is consumed (cleared) by the fold itself.  behind: what
+// runs once every fold has joined the main stream (ow.status is required).
+template <class Src>
+int ordered(phip_handle* h, Src src, u32 n, const OpView& ov, const OutView& ow,
+            const Behind* behind = nullptr) {
+  if (n == 0) return PHIP_OK;
+  if (n > kMaxOrderedOps)
+    return set_err(h, PHIP_ERR_INVALID, "ordered batch of %u ops exceeds 2^30", n);
+  int rc;
+  Segs sg{};
+  Join pack{h}, threads{h}, huge{h};
+  if ((rc = segment_batch(h, src, n, ov, &sg, &pack)) || (rc = pack.join())) return rc;
+  if (sg.nhuge && (rc = fold_huge(h, sg, ow, &huge))) return rc;
+  if ((rc = fold_rest(h, &sg, ow, &threads))) return rc;
+  if ((rc = threads.join()) || (rc = huge.join())) return rc;
+  return behind ? behind_folds(h, *behind, sg, ow.status) : PHIP_OK;
 }
 
 int stage_names(phip_handle* h, const uint8_t* names, const uint32_t* offs, u32 n, bool dev,
@@ -3690,9 +3750,9 @@ static int apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* 
                      (unsigned long long)need_cap);
     eo.max_msgs = (u32)need_msgs;
     eo.budget = dev ? need_cap - 8 : need_cap;
-    eo.uniform = uniform;
-    eo.wants = uniform && ops->kind[0] != PHIP_OP_RECEIVE;
   }
+  // what runs behind the ordered path's folds: the egress, or the marks
+  const Behind behind{uniform, uniform && ops->kind[0] != PHIP_OP_RECEIVE, eg ? &eo : nullptr};
   if (!dev && h->small) {
     bool done = false;
     if ((rc = small_mixed(h, ops, res, &done, eg, track))) {
@@ -3716,26 +3776,19 @@ static int apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* 
       (rc = stage(h, B_E, ops->elapsed, n, dev, &ov.e)) || (rc = outputs(h, res, n, dev, &ow)))
     return rc;
   ov.kind = kind;
-  if (track) {
-    // (as for the egress below: a status column of the library's own)
-    if (!ow.status && (rc = ensure(h, B_STATUS, n, &ow.status))) return rc;
-    const MarkPlan mp{uniform, uniform && ops->kind[0] != PHIP_OP_RECEIVE};
-    if ((rc = ordered(h, src, n, ov, ow, nullptr, &mp))) return after_error(h, rc);
-    return copy_outputs(h, res, n, dev, ow);
-  }
-  if (!eg) {
-    if ((rc = ordered(h, src, n, ov, ow))) return after_error(h, rc);
-    return copy_outputs(h, res, n, dev, ow);
-  }
   // the statuses say which buckets the batch created: a column of the
   // library's own when the caller asked for none
-  if (!ow.status && (rc = ensure(h, B_STATUS, n, &ow.status))) return rc;
+  if ((track || eg) && !ow.status && (rc = ensure(h, B_STATUS, n, &ow.status))) return rc;
+  if (!eg) {
+    if ((rc = ordered(h, src, n, ov, ow, track ? &behind : nullptr))) return after_error(h, rc);
+    return copy_outputs(h, res, n, dev, ow);
+  }
   eo.out = eg->out;
   eo.offs = reinterpret_cast<u64*>(eg->offs);
   if (!dev && ((rc = ensure(h, B_EGOUT, (size_t)need_cap + 8, &eo.out)) ||
                (rc = ensure(h, B_EGOFFS, 2 * (size_t)n + 1, &eo.offs))))
     return rc;
-  if ((rc = ordered(h, src, n, ov, ow, &eo))) return after_error(h, rc);
+  if ((rc = ordered(h, src, n, ov, ow, &behind))) return after_error(h, rc);
   if ((rc = read_ctr(h))) return rc;
   const u32* c = h->ctr_host;
   u64 bytes;
