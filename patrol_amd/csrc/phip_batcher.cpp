@@ -101,11 +101,14 @@ struct phip_batcher {
   uint64_t eg_batches = 0, eg_datagrams = 0, eg_wait_ns = 0;
 
   void run();
-  int dispatch(std::vector<Req*>& batch, EgressSlot* slot);
+  int dispatch(std::vector<Req*>& batch, EgressSlot* slot, uint64_t* ns);
 };
 
-// slot: where the batch's egress goes (nullptr: no egress).
-int phip_batcher::dispatch(std::vector<Req*>& batch, EgressSlot* slot) {
+// slot: where the batch's egress goes (nullptr: no egress).  Runs with mu
+// released, so it touches the dispatcher's scratch and its own batch only:
+// *ns receives the time of the engine call, which run() accounts under mu
+// (phip_batcher_stats reads the counters there).
+int phip_batcher::dispatch(std::vector<Req*>& batch, EgressSlot* slot, uint64_t* ns) {
   const uint32_t n = (uint32_t)batch.size();
   kind.assign(n, PHIP_OP_TAKE);
   offs.resize(n + 1);
@@ -150,14 +153,13 @@ int phip_batcher::dispatch(std::vector<Req*>& batch, EgressSlot* slot) {
   } else {
     rc = phip_apply_mixed(h, &ops, &res, 0);
   }
-  gpu_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t0).count();
+  *ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t0).count();
   for (uint32_t i = 0; i < n; ++i) {
     batch[i]->rc = rc;
     batch[i]->status = status[i];
     batch[i]->remaining = remaining[i];
     batch[i]->post = post[i];
   }
-  if (rc) ++errors;
   return rc;
 }
 
@@ -199,8 +201,11 @@ void phip_batcher::run() {
       if (s->state == EgressSlot::kFree) slot = s;
     }
     l.unlock();
-    const int rc = dispatch(batch, slot);
+    uint64_t ns = 0;
+    const int rc = dispatch(batch, slot, &ns);
     l.lock();
+    gpu_ns += ns;
+    if (rc) ++errors;
     if (slot && !rc && slot->n) {
       slot->batch = eg_tail++;
       slot->first_seq = batch[0]->seq;
