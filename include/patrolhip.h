@@ -1202,6 +1202,41 @@ int phip_route_pack(phip_handle* h, const phip_msgs* m, uint32_t world, uint8_t*
                     int64_t* send_elapsed, uint64_t* counts, uint64_t* name_bytes,
                     uint32_t flags);
 
+/* A batch of raw wire datagrams (MarshalBinary, bucket.go:51-68) in device
+ * memory: datagram i is bytes[offs[i] .. offs[i+1]).  32 bytes. */
+typedef struct phip_wire {
+  uint32_t n;
+  uint32_t reserved;
+  const uint8_t* bytes;   /* 8-byte aligned, readable to the next 8-byte boundary past offs[n] */
+  const uint64_t* offs;   /* n+1 entries */
+  uint64_t bytes_len;     /* 0: offsets trusted, as phip_receive_datagrams(PHIP_DEVICE_PTRS) trusts them */
+} phip_wire;
+
+/* phip_route_pack read straight from the wire: the same stable owner
+ * partition, into the same owner-major send buffers with the same counts /
+ * name_bytes, of the datagrams of w as they arrived (the name at offs[i] + 25
+ * with its length byte, added / taken / elapsed from the big-endian header,
+ * bucket.go:59-64); no decoded copy is written.  The field bits travel
+ * unchanged (-0.0, NaN payloads, zero states); bytes after the name are
+ * ignored (bucket.go:78-87).  send_* need n entries, send_names
+ * offs[n] - offs[0] - 25 * n bytes.  Device pointers only; world <= 64;
+ * PHIP_ROUTE_COMBINE as for phip_route_pack (the directory is sampled from the
+ * datagrams, the count pass classifies from the header fields).
+ *
+ * Stop rule (the Receive loop, repo.go:70-74, returns at the first datagram
+ * UnmarshalBinary rejects): only the datagrams before the first malformed one
+ * (size < 25, or a length byte larger than what is left of the datagram) are
+ * packed.  *stop (host memory, optional) receives that index, or n; when one
+ * was found the call returns PHIP_ERR_SHORT_BUFFER with [0, stop) packed and
+ * counts / name_bytes describing them.  A checked batch (w->bytes_len != 0)
+ * with an entry that is not offs[i] <= offs[i+1] <= bytes_len is
+ * PHIP_ERR_INVALID: nothing is packed, nothing is read at that entry.  Any
+ * flag besides PHIP_DEVICE_PTRS and PHIP_ROUTE_COMBINE is PHIP_ERR_INVALID. */
+int phip_route_pack_datagrams(phip_handle* h, const phip_wire* w, uint32_t world,
+                              uint8_t* send_names, uint32_t* send_lens, uint64_t* send_added,
+                              uint64_t* send_taken, int64_t* send_elapsed, uint64_t* counts,
+                              uint64_t* name_bytes, uint32_t* stop, uint32_t flags);
+
 /* Stable owner partition of an op stream (device pointers only, world <= 64):
  * op j of the send buffers is op send_src[j] of `ops`; owner-major, each owner's
  * ops in their batch order.  x0/x1/x2 carry the op's three operands by kind:
@@ -1303,6 +1338,66 @@ phip_handle* phip_group_handle(phip_group* g, uint32_t i);
  * is hashed or copied.  With names_len == 0 the offsets are trusted. */
 int phip_group_receive(phip_group* g, const phip_msgs* batches, int64_t now, uint64_t* sent,
                        uint64_t* merged, uint32_t flags);
+/* Owner-routed Receive from the wire: phip_group_receive over what a Patrol
+ * peer actually sends.  batches[i] holds the raw datagrams that arrived at
+ * member i (device memory of its GPU, e.g. a ring slot's copy); each member
+ * packs them by owner in place (phip_route_pack_datagrams), and the exchange
+ * and the owner's merge are phip_group_receive's in every respect: chunks of
+ * 2^24 datagrams (4096 with PHIP_GROUP_SMALL_CHUNKS), an owner merging chunk
+ * by chunk with the sources in rank order, PHIP_ROUTE_COMBINE,
+ * PHIP_GROUP_RCCL_SELF, shared-device groups, every member running the
+ * longest batch's number of rounds.
+ *
+ * Stop rule (repo.go:70-74).  One pre-pass per member over its whole batch
+ * (offsets and length bytes only) finds stop_i, the first malformed datagram
+ * (size < 25 or a length byte larger than what is left), before any chunk is
+ * packed.  Member i packs datagrams [0, stop_i), its round count comes from
+ * stop_i, and nothing at or past stop_i is hashed, copied or sent;
+ * stopped[i] (optional, one per local member) receives stop_i (n when there
+ * is none).  If any local member stopped, the call returns
+ * PHIP_ERR_SHORT_BUFFER after everything before the stops was exchanged and
+ * merged, and phip_group_last_error names the first such member and its
+ * index; the peers never wait.
+ *
+ * Checked batches (bytes_len != 0): the same pre-pass checks offs[i] <=
+ * offs[i+1] <= bytes_len; a violation is PHIP_ERR_INVALID under
+ * phip_group_receive's rule (none of this process's batches is applied, the
+ * process still runs the rounds with empty batches, stopped[] is 0), and
+ * nothing is read at the bad entry.
+ *
+ * A chunk's send buffers are sized from the datagram offsets at the chunk's
+ * boundaries (the sum of size - 25: an upper bound, trailing bytes count).
+ * A world of one without PHIP_GROUP_RCCL_SELF has nothing to route: datagrams
+ * [0, stop) go to the handle's own wire path (phip_receive_datagrams), sent =
+ * merged = stop, and PHIP_ROUTE_COMBINE is ignored.
+ *
+ * Flags: PHIP_DEVICE_PTRS is required; PHIP_ROUTE_COMBINE,
+ * PHIP_GROUP_RCCL_SELF and PHIP_GROUP_SMALL_CHUNKS are the others; any other
+ * bit is PHIP_ERR_INVALID.
+ *
+ * Out of scope: an incast request (the all-zero state) routed this way is
+ * merged at its owner (the bucket is created) but not answered, as
+ * phip_group_receive returns no per-message results either; replies over the
+ * group remain phip_group_apply_mixed with RECEIVE ops.  There is no batcher
+ * over the group. */
+int phip_group_receive_datagrams(phip_group* g, const phip_wire* batches, int64_t now,
+                                 uint64_t* sent, uint64_t* merged,
+                                 uint32_t* stopped /* per member */, uint32_t flags);
+/* The socket edge of a sharded node (the Receive goroutine, repo.go:54-92,
+ * over one ring per member): phip_group_receive_datagrams over the device
+ * copies of one submitted slot per local member.  rings[i] was opened on
+ * phip_group_handle(g, i) (a ring of any other handle is PHIP_ERR_INVALID;
+ * NULL is an empty batch for member i) and slots[i] must be that ring's next
+ * submitted slot, else PHIP_ERR_BUSY as phip_ring_receive reports it; a
+ * refused call leaves every slot submitted.  Member i's streams wait for its
+ * slot's copy, not the host.  A slot is freed only after the member's pack and
+ * exchange streams have finished reading it, after an error too, once they
+ * have drained.  The one-launch small-slot shortcut of phip_ring_receive does
+ * not apply.  sent, merged, stopped, flags and the return value are
+ * phip_group_receive_datagrams' (the slots' offsets were checked at submit). */
+int phip_group_ring_receive(phip_group* g, phip_ring* const* rings, const uint32_t* slots,
+                            int64_t now, uint64_t* sent, uint64_t* merged, uint32_t* stopped,
+                            uint32_t flags);
 /* Owner-routed phip_apply_mixed: batches[i] / results[i] belong to local member i
  * (device memory of its GPU; any results pointer may be NULL, results itself
  * too).  The sharded form of POST /take (api.go:51-86): an op that arrived at

@@ -41,6 +41,7 @@ EXPORTS = [
     "phip_export_throttled", "phip_throttle_match",
     "phip_receive_soa_replies", "phip_receive_datagrams_replies", "phip_ring_receive_replies",
     "phip_reply_peers",
+    "phip_route_pack_datagrams", "phip_group_receive_datagrams", "phip_group_ring_receive",
 ]
 
 PHIP_OK = 0
@@ -93,6 +94,12 @@ class phip_msgs(C.Structure):
     _fields_ = [("n", C.c_uint32), ("names_len", C.c_uint32), ("names", C.c_void_p),
                 ("name_offs", C.c_void_p), ("added", C.c_void_p), ("taken", C.c_void_p),
                 ("elapsed", C.c_void_p)]
+
+
+class phip_wire(C.Structure):
+    # raw datagrams in device memory; bytes_len 0 = offsets trusted (patrolhip.h)
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("bytes", C.c_void_p),
+                ("offs", C.c_void_p), ("bytes_len", C.c_uint64)]
 
 
 class phip_ops(C.Structure):
@@ -345,5 +352,12 @@ def load(path: str = LIB_PATH):
         L.phip_ring_receive_replies.argtypes = [vp, u32, i64, C.POINTER(phip_results),
                                                 C.POINTER(u32), C.POINTER(phip_reply_egress)]
         L.phip_reply_peers.argtypes = [vp, vp, u32, vp]
+    if hasattr(L, "phip_group_receive_datagrams"):
+        L.phip_route_pack_datagrams.argtypes = [vp, C.POINTER(phip_wire), u32, vp, vp, vp, vp, vp,
+                                                vp, vp, C.POINTER(u32), u32]
+        L.phip_group_receive_datagrams.argtypes = [vp, C.POINTER(phip_wire), i64, C.POINTER(u64),
+                                                   C.POINTER(u64), C.POINTER(u32), u32]
+        L.phip_group_ring_receive.argtypes = [vp, C.POINTER(vp), C.POINTER(u32), i64,
+                                              C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), u32]
     _lib = L
     return L

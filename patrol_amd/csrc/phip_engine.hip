@@ -2595,9 +2595,12 @@ static int route_scratch(phip_handle* h, u32 n, u32 world, u8** base, u32** pctr
 // Sender-side combine: the hot names of a strided sample of the
 // whole batch, counted by name hash (the buckets live on other ranks, so
 // there is no slot to count), as a directory for every pack of the batch.
-static int route_dir_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32 world, const void** out) {
+// Src: the batch's name source (NamesOffs: decoded messages; Datagrams: raw
+// datagrams, phip_route_pack_datagrams).
+template <class Src>
+static int route_dir_src(phip_handle* h, hipStream_t st, const Src& src, u32 n, u32 world,
+                         const void** out) {
   *out = nullptr;
-  const u32 n = m.n;
   if (n < kRouteMinBatch) return PHIP_OK;
   constexpr size_t kCnt = size_t(1) << kHotCntBits;
   const size_t zero_bytes = 3 * kCnt * sizeof(u32) + kHotHist * sizeof(u32) + sizeof(HotHdr);
@@ -2613,19 +2616,20 @@ static int route_dir_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32 
   HIPCHK(h, hipMemsetAsync(hb, 0, zero_bytes, st));
   const u32 stride = std::max<u32>(64, (n + kHotSampleMax - 1) / kHotSampleMax);
   const u32 nsample = (n + stride - 1) / stride;
-  NamesOffs src{m.names, m.name_offs, m.names_len};
   {
     Launch l(h, "k_route_sample", st);
-    k_route_sample<NamesOffs><<<grid_for(nsample, kHotSamplePerBlock), 256, 0, st>>>(
+    k_route_sample<Src><<<grid_for(nsample, kHotSamplePerBlock), 256, 0, st>>>(
         src, n, stride, nsample, ckeys, ccnt, cidx);
     k_hot_hist<<<grid_for(kCnt), kBlock, 0, st>>>(ccnt, hist);
     k_hot_select<<<1, 256, 0, st>>>(hist, hdr, kRouteHotMax);
-    k_route_dir_build<NamesOffs><<<grid_for(kCnt), kBlock, 0, st>>>(ckeys, ccnt, cidx, hdr, src,
-                                                                     world, d);
+    k_route_dir_build<Src><<<grid_for(kCnt), kBlock, 0, st>>>(ckeys, ccnt, cidx, hdr, src, world, d);
   }
   HIPCHK(h, hipGetLastError());
   *out = hdr;
   return PHIP_OK;
+}
+static int route_dir_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32 world, const void** out) {
+  return route_dir_src(h, st, NamesOffs{m.names, m.name_offs, m.names_len}, m.n, world, out);
 }
 
 // The skeleton of a stable owner partition of n entries, queued on `st` with
@@ -2677,33 +2681,43 @@ static int route_pack_with(phip_handle* h, hipStream_t st, u32 n, u32 world, uin
 // per-owner totals into counts / nbytes (device).  With a directory (dir) a
 // clean batch's hot names are max-combined (k_route_count classifies the
 // batch on the way; a dirty one is counted again without combining).
-static int route_pack_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32 world, const void* dir,
-                  uint8_t* send_names, uint32_t* send_lens, uint64_t* send_added,
-                  uint64_t* send_taken, int64_t* send_elapsed, uint64_t* counts,
-                  uint64_t* nbytes) {
-  const u32 n = m.n;
+// Src = Datagrams (the wire form): the kernels take the replica fields from
+// the datagrams' headers and a, t, e are not read (NULL).
+template <class Src>
+static int route_pack_src(phip_handle* h, hipStream_t st, const Src& src, const uint64_t* a,
+                          const uint64_t* t, const int64_t* e, u32 n, u32 world, const void* dir,
+                          uint8_t* send_names, uint32_t* send_lens, uint64_t* send_added,
+                          uint64_t* send_taken, int64_t* send_elapsed, uint64_t* counts,
+                          uint64_t* nbytes) {
   const HotHdr* hot = (const HotHdr*)dir;
   const RouteHot* rdir = hot ? (const RouteHot*)(hot + 1) : nullptr;
-  NamesOffs src{m.names, m.name_offs, m.names_len};
   return route_pack_with(
       h, st, n, world, counts, nbytes,
       [&](const RoutePlan& p, const RouteCells& c) {
         k_batch_reset<<<1, kShards, 0, st>>>(c.pctr, nullptr);
         Launch l(h, "k_route_count", st);
-        k_route_count<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
-            src, m.added, m.taken, m.elapsed, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
+        k_route_count<Src><<<p.nblk, kRouteBlock, 0, st>>>(
+            src, a, t, e, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
             c.cnt, c.bytes, hot ? kRouteCombine : kRoutePlain);
         if (hot)
-          k_route_count<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
-              src, m.added, m.taken, m.elapsed, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
+          k_route_count<Src><<<p.nblk, kRouteBlock, 0, st>>>(
+              src, a, t, e, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
               c.cnt, c.bytes, kRouteRecount);
       },
       [&](const RoutePlan& p, const RouteCells& c) {
         Launch l(h, "k_route_scatter", st);
-        k_route_scatter<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
-            src, m.added, m.taken, m.elapsed, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
+        k_route_scatter<Src><<<p.nblk, kRouteBlock, 0, st>>>(
+            src, a, t, e, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
             c.cbase, c.bbase, send_names, send_lens, send_added, send_taken, send_elapsed);
       });
+}
+static int route_pack_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32 world, const void* dir,
+                  uint8_t* send_names, uint32_t* send_lens, uint64_t* send_added,
+                  uint64_t* send_taken, int64_t* send_elapsed, uint64_t* counts,
+                  uint64_t* nbytes) {
+  return route_pack_src(h, st, NamesOffs{m.names, m.name_offs, m.names_len}, m.added, m.taken,
+                        m.elapsed, m.n, world, dir, send_names, send_lens, send_added, send_taken,
+                        send_elapsed, counts, nbytes);
 }
 
 // Stable owner partition of an op stream (phip_route_pack_ops, and the chunks
@@ -2753,6 +2767,32 @@ static int check_offsets_on(phip_handle* h, hipStream_t st, const uint8_t* names
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(first_bad, d, sizeof(u32), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
+  return PHIP_OK;
+}
+
+// The pre-pass of a routed wire batch on `st`, which it synchronises
+// (k_wire_scan): *stop is the first malformed datagram or n, *first_bad the
+// first entry whose offsets a checked batch (bytes_len != 0) rejects, ~0 when
+// there is none.
+static int wire_scan_on(phip_handle* h, hipStream_t st, const uint8_t* bytes, const uint64_t* offs,
+                        u64 bytes_len, u32 n, u32* stop, u32* first_bad) {
+  *stop = n;
+  *first_bad = ~0u;
+  if (n == 0) return PHIP_OK;
+  u32* d;
+  int rc;
+  if ((rc = ensure(h, B_NCHK, 2, &d))) return rc;
+  HIPCHK(h, hipMemsetAsync(d, 0xFF, 2 * sizeof(u32), st));
+  {
+    Launch l(h, "k_wire_scan", st);
+    k_wire_scan<<<grid_for(n), kBlock, 0, st>>>(bytes, offs, n, bytes_len, d);
+  }
+  HIPCHK(h, hipGetLastError());
+  u32 r[2];
+  HIPCHK(h, hipMemcpyAsync(r, d, sizeof r, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  *stop = std::min(r[0], n);
+  *first_bad = r[1];
   return PHIP_OK;
 }
 
@@ -3897,6 +3937,43 @@ int phip_route_pack(phip_handle* h, const phip_msgs* m, uint32_t world, uint8_t*
   return PHIP_OK;
 }
 
+int phip_route_pack_datagrams(phip_handle* h, const phip_wire* w, uint32_t world,
+                              uint8_t* send_names, uint32_t* send_lens, uint64_t* send_added,
+                              uint64_t* send_taken, int64_t* send_elapsed, uint64_t* counts,
+                              uint64_t* name_bytes, uint32_t* stop, uint32_t flags) {
+  if (!h || !w || !(flags & PHIP_DEVICE_PTRS) || (flags & ~(PHIP_DEVICE_PTRS | PHIP_ROUTE_COMBINE)) ||
+      world == 0 || world > kRouteMaxWorld || !counts || !name_bytes)
+    return PHIP_ERR_INVALID;
+  const u32 n = w->n;
+  if (n && (!w->bytes || !w->offs || !send_names || !send_lens || !send_added || !send_taken ||
+            !send_elapsed))
+    return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;
+  if (stop) *stop = n;
+  int rc;
+  // the Go loop's stop rule first (repo.go:70-74): the route kernels read
+  // well-formed datagrams only
+  u32 at, first_bad;
+  if ((rc = wire_scan_on(h, h->stream, w->bytes, w->offs, w->bytes_len, n, &at, &first_bad)))
+    return rc;
+  if (first_bad != ~0u)
+    return set_err(h, PHIP_ERR_INVALID,
+                   "malformed datagram offsets at datagram %u (bytes_len check): nothing packed",
+                   first_bad);
+  if (stop) *stop = at;
+  const Datagrams src{w->bytes, w->offs};
+  const void* dir = nullptr;
+  if ((flags & PHIP_ROUTE_COMBINE) && (rc = route_dir_src(h, h->stream, src, at, world, &dir)))
+    return rc;
+  if ((rc = route_pack_src(h, h->stream, src, nullptr, nullptr, nullptr, at, world, dir, send_names,
+                           send_lens, send_added, send_taken, send_elapsed, counts, name_bytes)))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (at < n) return set_err(h, PHIP_ERR_SHORT_BUFFER, "short buffer at datagram %u", at);
+  return PHIP_OK;
+}
+
 int phip_route_pack_ops(phip_handle* h, const phip_ops* ops, uint32_t world, uint8_t* send_names,
                         uint32_t* send_lens, uint8_t* send_kind, int64_t* send_now,
                         uint64_t* send_x0, uint64_t* send_x1, uint64_t* send_x2,
@@ -4760,6 +4837,38 @@ int check_offsets(phip_handle* h, void* stream, const uint8_t* names, const uint
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = finish_queued(h)) return rc0;
   return check_offsets_on(h, (hipStream_t)stream, names, name_offs, names_len, n, first_bad);
+}
+int wire_scan(phip_handle* h, void* stream, const phip_wire* w, uint32_t* stop, uint32_t* first_bad) {
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = finish_queued(h)) return rc0;
+  return wire_scan_on(h, (hipStream_t)stream, w->bytes, w->offs, w->bytes_len, w->n, stop, first_bad);
+}
+int route_dir_wire(phip_handle* h, void* stream, const phip_wire* w, uint32_t world, const void** dir) {
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = finish_queued(h)) return rc0;
+  return route_dir_src(h, (hipStream_t)stream, Datagrams{w->bytes, w->offs}, w->n, world, dir);
+}
+int route_pack_wire(phip_handle* h, void* stream, const phip_wire* w, uint32_t world, const void* dir,
+                    uint8_t* names, uint32_t* lens, uint64_t* a, uint64_t* t, int64_t* e,
+                    uint64_t* counts, uint64_t* nbytes) {
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = finish_queued(h)) return rc0;
+  return route_pack_src(h, (hipStream_t)stream, Datagrams{w->bytes, w->offs}, nullptr, nullptr,
+                        nullptr, w->n, world, dir, names, lens, a, t, e, counts, nbytes);
+}
+int ring_slot(phip_ring* r, uint32_t slot, const phip_handle* h, phip_wire* w, void** copied) {
+  if (!r || r->h != h || slot >= r->slots.size()) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(r->mu);
+  const phip_ring::Slot& s = r->slots[slot];
+  if (s.state != phip_ring::kSubmitted || slot != r->next_receive) return PHIP_ERR_BUSY;
+  *w = phip_wire{s.n, 0, s.dbytes, s.doffs, 0};
+  *copied = (void*)s.copied;
+  return PHIP_OK;
+}
+void ring_release(phip_ring* r, uint32_t slot) {
+  std::lock_guard<std::mutex> g(r->mu);
+  r->slots[slot].state = phip_ring::kFree;
+  r->next_receive = (r->next_receive + 1) % (u32)r->slots.size();
 }
 const char* last_error(phip_handle* h) { return h ? h->err.c_str() : ""; }
 int handle_device(const phip_handle* h) { return h ? h->device : -1; }

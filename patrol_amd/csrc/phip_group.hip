@@ -507,9 +507,11 @@ int round_totals(Member& mb, const std::vector<Seg>& plan, const char* round, co
   return PHIP_OK;
 }
 
-// name_offs at the chunk boundaries: out[k] = offs[min(k * chunk, n)].
-__global__ void k_chunk_bounds(const uint32_t* __restrict__ offs, u32 n, u64 chunk, u64 kc,
-                               u32* __restrict__ out) {
+// name_offs at the chunk boundaries: out[k] = offs[min(k * chunk, n)] (T =
+// u64: a wire batch's datagram offsets).
+template <class T>
+__global__ void k_chunk_bounds(const T* __restrict__ offs, u32 n, u64 chunk, u64 kc,
+                               T* __restrict__ out) {
   const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (k <= kc) out[k] = offs[k * chunk < n ? k * chunk : n];
 }
@@ -518,18 +520,19 @@ __global__ void k_chunk_bounds(const uint32_t* __restrict__ offs, u32 n, u64 chu
 // the split sizes carry it to the peers, and the name offsets at the round
 // boundaries ((*bnd)[k + 1] - (*bnd)[k]: the name bytes of round k), read
 // back on stream st, which it synchronises.
-int chunk_bounds(phip_group* g, Member& mb, hipStream_t st, const u32* offs, u32 n, u64 chunk,
-                 std::vector<u32>* bnd) {
+template <class T>
+int chunk_bounds(phip_group* g, Member& mb, hipStream_t st, const T* offs, u32 n, u64 chunk,
+                 std::vector<T>* bnd) {
   const u64 kc = ((u64)n + chunk - 1) / chunk;
   mb.k_local = kc;
   for (u32 p = 0; p < g->world; ++p) mb.host_k[p] = kc;
   bnd->assign(kc + 1, 0);
   if (n == 0) return PHIP_OK;
-  GHIP(mb, mb.bounds.ensure((kc + 1) * 4));
-  k_chunk_bounds<<<(unsigned)((kc + 1 + 255) / 256), 256, 0, st>>>(offs, n, chunk, kc,
-                                                                   (u32*)mb.bounds.p);
+  GHIP(mb, mb.bounds.ensure((kc + 1) * sizeof(T)));
+  k_chunk_bounds<T><<<(unsigned)((kc + 1 + 255) / 256), 256, 0, st>>>(offs, n, chunk, kc,
+                                                                      (T*)mb.bounds.p);
   GHIP(mb, hipGetLastError());
-  GHIP(mb, hipMemcpyAsync(bnd->data(), mb.bounds.p, (kc + 1) * 4, hipMemcpyDeviceToHost, st));
+  GHIP(mb, hipMemcpyAsync(bnd->data(), mb.bounds.p, (kc + 1) * sizeof(T), hipMemcpyDeviceToHost, st));
   GHIP(mb, hipStreamSynchronize(st));
   return PHIP_OK;
 }
@@ -585,10 +588,69 @@ phip_msgs chunk_of(const phip_msgs& in, u64 chunk, u64 k) {
   return c;
 }
 
-int member_receive(phip_group* g, Member& mb, const phip_msgs& in, int64_t now, uint64_t* sent,
+// What member_receive asks of a member's batch, decoded (MsgBatch) or raw
+// datagrams (WireBatch): its length, the merge of the whole of it where there
+// is nothing to route, its chunks' name bytes (bounds synchronises st and
+// sets the member's round count), the combine's directory and the pack of
+// chunk k into a send set.
+struct MsgBatch {
+  const phip_msgs& in;
+  std::vector<u32> bnd;   // name_offs at the chunk boundaries
+  u32 n() const { return in.n; }
+  int whole(Member& mb, int64_t now) {
+    GPHIP(mb, phip_receive_soa(mb.h, &in, now, nullptr, PHIP_DEVICE_PTRS | PHIP_RECV_CLASSIFY));
+    return PHIP_OK;
+  }
+  int bounds(phip_group* g, Member& mb, hipStream_t st, u64 chunk) {
+    return chunk_bounds(g, mb, st, in.name_offs, in.n, chunk, &bnd);
+  }
+  u64 chunk_bytes(u64, u64 k) const { return (u64)(bnd[k + 1] - bnd[k]); }
+  int dir(Member& mb, u32 W, const void** d) { return phip_host::route_dir(mb.h, mb.sp, &in, W, d); }
+  int pack(Member& mb, u64 chunk, u64 k, u32 W, const void* d, const ColSet& ss, u64* sz) {
+    const phip_msgs c = chunk_of(in, chunk, k);
+    return phip_host::route_pack(mb.h, mb.sp, &c, W, d, ss.at<uint8_t>(C_NAMES), ss.at<uint32_t>(C_LENS),
+                                 ss.at<uint64_t>(MSG_A), ss.at<uint64_t>(MSG_T), ss.at<int64_t>(MSG_E), sz,
+                                 sz + W);
+  }
+};
+
+// A wire batch cut at its stop: in.n datagrams, every one well formed (the
+// pre-pass of phip_group_receive_datagrams ran before).
+struct WireBatch {
+  phip_wire in;
+  std::vector<u64> bnd;   // the datagram offsets at the chunk boundaries
+  u32 n() const { return in.n; }
+  // one owner: the handle's own wire path reads the datagrams in place
+  int whole(Member& mb, int64_t now) {
+    GPHIP(mb, phip_receive_datagrams(mb.h, in.bytes, in.offs, in.n, now, nullptr, nullptr,
+                                     PHIP_DEVICE_PTRS));
+    return PHIP_OK;
+  }
+  int bounds(phip_group* g, Member& mb, hipStream_t st, u64 chunk) {
+    return chunk_bounds(g, mb, st, in.offs, in.n, chunk, &bnd);
+  }
+  // the sum of size - 25 over the chunk: its name bytes and any trailing ones
+  u64 chunk_bytes(u64 chunk, u64 k) const {
+    const u64 cnt = std::min<u64>(chunk, in.n - k * chunk);
+    return bnd[k + 1] - bnd[k] - cnt * PHIP_BUCKET_FIXED_SIZE;
+  }
+  int dir(Member& mb, u32 W, const void** d) { return phip_host::route_dir_wire(mb.h, mb.sp, &in, W, d); }
+  int pack(Member& mb, u64 chunk, u64 k, u32 W, const void* d, const ColSet& ss, u64* sz) {
+    phip_wire c = in;
+    const u64 lo = k * chunk;
+    c.n = lo < in.n ? (u32)std::min<u64>(chunk, in.n - lo) : 0u;
+    if (c.n) c.offs = in.offs + lo;   // absolute offsets into the same bytes
+    return phip_host::route_pack_wire(mb.h, mb.sp, &c, W, d, ss.at<uint8_t>(C_NAMES),
+                                      ss.at<uint32_t>(C_LENS), ss.at<uint64_t>(MSG_A),
+                                      ss.at<uint64_t>(MSG_T), ss.at<int64_t>(MSG_E), sz, sz + W);
+  }
+};
+
+template <class Batch>
+int member_receive(phip_group* g, Member& mb, Batch&& in, int64_t now, uint64_t* sent,
                    uint64_t* merged, uint32_t flags) {
   const u32 W = g->world;
-  const u32 n = in.n;
+  const u32 n = in.n();
   GHIP(mb, hipSetDevice(mb.device));
   hipStream_t st = (hipStream_t)phip_host::handle_stream(mb.h);
   // PHIP_GROUP_RCCL_SELF: the member's own segment goes through RCCL too (a
@@ -604,7 +666,7 @@ int member_receive(phip_group* g, Member& mb, const phip_msgs& in, int64_t now, 
     if (merged) *merged = n;
     if (n == 0) return PHIP_OK;
     GHIP(mb, mb.tm.mark(2, st));
-    GPHIP(mb, phip_receive_soa(mb.h, &in, now, nullptr, PHIP_DEVICE_PTRS | PHIP_RECV_CLASSIFY));
+    if (int r = in.whole(mb, now)) return r;
     GHIP(mb, mb.tm.mark(2, st));
     return PHIP_OK;
   }
@@ -618,12 +680,11 @@ int member_receive(phip_group* g, Member& mb, const phip_msgs& in, int64_t now, 
   const u64 cmax = std::max<u64>(1, std::min<u64>(n, chunk));
   int rc;
   // name bytes per chunk and lane: the offsets at the chunk boundaries
-  std::vector<u32> bnd;
-  if ((rc = chunk_bounds(g, mb, st, in.name_offs, n, chunk, &bnd))) return rc;
+  if ((rc = in.bounds(g, mb, st, chunk))) return rc;
   const u64 k_local = mb.k_local;
   u64 set_bytes[2] = {0, 0};
   for (u64 k = 0; k < k_local; ++k)
-    set_bytes[k & 1] = std::max<u64>(set_bytes[k & 1], (u64)(bnd[k + 1] - bnd[k]));
+    set_bytes[k & 1] = std::max<u64>(set_bytes[k & 1], in.chunk_bytes(chunk, k));
   for (u32 si = 0; si < 2; ++si) {
     GHIP(mb, mb.lane[si].send.ensure(cmax, set_bytes[si]));
     GHIP(mb, mb.sz[si].dev.ensure((size_t)6 * W * 8));
@@ -631,20 +692,16 @@ int member_receive(phip_group* g, Member& mb, const phip_msgs& in, int64_t now, 
   }
   // 1. the combine's directory, from a sample of the whole batch
   const void* dir = nullptr;
-  if ((flags & PHIP_ROUTE_COMBINE) && n &&
-      phip_host::route_dir(mb.h, mb.sp, &in, W, &dir) != PHIP_OK)
+  if ((flags & PHIP_ROUTE_COMBINE) && n && in.dir(mb, W, &dir) != PHIP_OK)
     return fail(mb, PHIP_ERR_HIP, "route directory: %s", phip_host::last_error(mb.h));
   // 2. pack chunk k into lane k & 1 (pack stream), once no exchange reads it
   auto pack = [&](u64 k) -> int {
     Lane& ln = mb.lane[k & 1];
     const ColSet& ss = ln.send;
     if (ln.x_pending) GHIP(mb, hipStreamWaitEvent(mb.sp, ln.ev_x, 0));
-    const phip_msgs c = chunk_of(in, chunk, k);
     u64* sz = (u64*)mb.sz[k & 1].dev.p;
     GHIP(mb, mb.tm.mark(0, mb.sp));
-    if (phip_host::route_pack(mb.h, mb.sp, &c, W, dir, ss.at<uint8_t>(C_NAMES), ss.at<uint32_t>(C_LENS),
-                              ss.at<uint64_t>(MSG_A), ss.at<uint64_t>(MSG_T), ss.at<int64_t>(MSG_E), sz,
-                              sz + W) != PHIP_OK)
+    if (in.pack(mb, chunk, k, W, dir, ss, sz) != PHIP_OK)
       return fail(mb, PHIP_ERR_HIP, "route pack: %s", phip_host::last_error(mb.h));
     GHIP(mb, hipMemcpyAsync(sz + 2 * W, mb.host_k, W * 8, hipMemcpyHostToDevice, mb.sp));
     GHIP(mb, mb.tm.mark(0, mb.sp));
@@ -1029,6 +1086,59 @@ int checked_call(phip_group* g, const Batch* batches, const char* what, Pre pre,
   return for_members(g, [&](size_t i) { return run(i, batches[i]); });
 }
 
+bool wire_flags_ok(uint32_t flags) {
+  constexpr uint32_t kAllowed =
+      PHIP_DEVICE_PTRS | PHIP_ROUTE_COMBINE | PHIP_GROUP_RCCL_SELF | PHIP_GROUP_SMALL_CHUNKS;
+  return (flags & PHIP_DEVICE_PTRS) && !(flags & ~kAllowed);
+}
+
+// phip_group_receive_datagrams over the local members' wire batches, behind
+// pre(member, its stream, i).  The pre-pass of every member first (the Go
+// loop's stop rule, repo.go:70-74, and a checked batch's offsets): member i
+// then runs the exchange over datagrams [0, stop_i), or over none when any
+// local batch's offsets were rejected (checked_call's rule: the peers of a
+// multi-rank group never wait for a rank that left early).
+template <class Pre>
+int receive_wire(phip_group* g, const phip_wire* batches, int64_t now, uint64_t* sent,
+                 uint64_t* merged, uint32_t* stopped, uint32_t flags, Pre pre) {
+  const size_t nl = g->m.size();
+  std::vector<uint32_t> stop(nl, 0), bad(nl, ~0u);
+  if (int rc = for_members(g, [&](size_t i) {
+        Member& mb = g->m[i];
+        GHIP(mb, hipSetDevice(mb.device));
+        hipStream_t st = (hipStream_t)phip_host::handle_stream(mb.h);
+        if (int r = pre(mb, st, i)) return r;
+        if (phip_host::wire_scan(mb.h, st, &batches[i], &stop[i], &bad[i]) != PHIP_OK)
+          return fail(mb, PHIP_ERR_HIP, "datagram pre-pass: %s", phip_host::last_error(mb.h));
+        return (int)PHIP_OK;
+      }))
+    return rc;
+  size_t ib = 0;
+  while (ib < nl && bad[ib] == ~0u) ++ib;
+  std::vector<phip_wire> cut(batches, batches + nl);
+  for (size_t i = 0; i < nl; ++i) {
+    cut[i].n = ib < nl ? 0 : stop[i];
+    if (stopped) stopped[i] = cut[i].n;
+  }
+  const int rc = for_members(g, [&](size_t i) {
+    return member_receive(g, g->m[i], WireBatch{cut[i], {}}, now, sent ? sent + i : nullptr,
+                          merged ? merged + i : nullptr, flags);
+  });
+  if (ib < nl) {
+    const std::string xerr = rc != PHIP_OK ? "; and the empty exchange failed: " + g->err : "";
+    g->err = "member " + std::to_string(ib) + ": malformed datagram offsets at datagram " +
+             std::to_string(bad[ib]) + " (bytes_len check): no local batch applied" + xerr;
+    return PHIP_ERR_INVALID;
+  }
+  if (rc != PHIP_OK) return rc;
+  for (size_t i = 0; i < nl; ++i)
+    if (stop[i] < batches[i].n) {
+      g->err = "member " + std::to_string(i) + ": short buffer at datagram " + std::to_string(stop[i]);
+      return PHIP_ERR_SHORT_BUFFER;
+    }
+  return PHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1132,9 +1242,55 @@ int phip_group_receive(phip_group* g, const phip_msgs* batches, int64_t now, uin
   return checked_call(
       g, batches, "message", [](Member&, hipStream_t, size_t) { return (int)PHIP_OK; },
       [&](size_t i, const phip_msgs& b) {
-        return member_receive(g, g->m[i], b, now, sent ? sent + i : nullptr,
+        return member_receive(g, g->m[i], MsgBatch{b, {}}, now, sent ? sent + i : nullptr,
                               merged ? merged + i : nullptr, flags);
       });
+}
+
+int phip_group_receive_datagrams(phip_group* g, const phip_wire* batches, int64_t now,
+                                 uint64_t* sent, uint64_t* merged, uint32_t* stopped,
+                                 uint32_t flags) {
+  if (!g || !batches || !wire_flags_ok(flags)) return PHIP_ERR_INVALID;
+  for (size_t i = 0; i < g->m.size(); ++i)
+    if (batches[i].n && (!batches[i].bytes || !batches[i].offs)) return PHIP_ERR_INVALID;
+  return receive_wire(g, batches, now, sent, merged, stopped, flags,
+                      [](Member&, hipStream_t, size_t) { return (int)PHIP_OK; });
+}
+
+int phip_group_ring_receive(phip_group* g, phip_ring* const* rings, const uint32_t* slots,
+                            int64_t now, uint64_t* sent, uint64_t* merged, uint32_t* stopped,
+                            uint32_t flags) {
+  if (!g || !rings || !slots || !wire_flags_ok(flags)) return PHIP_ERR_INVALID;
+  const size_t nl = g->m.size();
+  std::vector<phip_wire> batches(nl, phip_wire{});
+  std::vector<void*> copied(nl, nullptr);
+  // (refused before anything is queued: every slot stays submitted)
+  for (size_t i = 0; i < nl; ++i)
+    if (rings[i])
+      if (int rc = phip_host::ring_slot(rings[i], slots[i], g->m[i].h, &batches[i], &copied[i]))
+        return rc;
+  const int rc = receive_wire(g, batches.data(), now, sent, merged, stopped, flags,
+                              [&](Member& mb, hipStream_t st, size_t i) {
+                                // the member's streams all start behind st
+                                if (copied[i])
+                                  GHIP(mb, hipStreamWaitEvent(st, (hipEvent_t)copied[i], 0));
+                                return (int)PHIP_OK;
+                              });
+  // A slot is free once its member's streams have read it: the pack stream,
+  // the exchange behind it, and the handle's stream (the pre-pass; a world of
+  // one merges from the slot).  After an error they drain first.
+  int rc2 = PHIP_OK;
+  for (size_t i = 0; i < nl; ++i) {
+    if (!rings[i]) continue;
+    Member& mb = g->m[i];
+    if (hipSetDevice(mb.device) != hipSuccess || hipStreamSynchronize(mb.sp) != hipSuccess ||
+        hipStreamSynchronize(mb.sx) != hipSuccess ||
+        hipStreamSynchronize((hipStream_t)phip_host::handle_stream(mb.h)) != hipSuccess)
+      rc2 = PHIP_ERR_HIP;
+    phip_host::ring_release(rings[i], slots[i]);
+  }
+  if (rc == PHIP_OK && rc2 != PHIP_OK) g->err = "draining the members' streams failed";
+  return rc != PHIP_OK ? rc : rc2;
 }
 
 int phip_group_apply_mixed(phip_group* g, const phip_ops* batches, const phip_results* results,

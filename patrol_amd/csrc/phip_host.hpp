@@ -44,6 +44,26 @@ int results_scatter(phip_handle* h, void* stream, const uint32_t* src, uint32_t 
 // run it over every local batch before any pack.
 int check_offsets(phip_handle* h, void* stream, const uint8_t* names, const uint32_t* name_offs,
                   uint32_t names_len, uint32_t n, uint32_t* first_bad);
+// The wire forms (phip_group_receive_datagrams): w is a batch of raw
+// datagrams, or one chunk of it (offs advanced; the offsets stay absolute).
+//   wire_scan:  the pre-pass over offsets and length bytes on `stream`, which
+//               it synchronises: *stop is the first malformed datagram (or
+//               w->n), *first_bad the first entry a checked batch's offsets
+//               rule rejects (~0: none);
+//   route_dir_wire / route_pack_wire: route_dir / route_pack read from the
+//               datagrams in place; every datagram of w must be well formed.
+int wire_scan(phip_handle* h, void* stream, const phip_wire* w, uint32_t* stop, uint32_t* first_bad);
+int route_dir_wire(phip_handle* h, void* stream, const phip_wire* w, uint32_t world, const void** dir);
+int route_pack_wire(phip_handle* h, void* stream, const phip_wire* w, uint32_t world, const void* dir,
+                    uint8_t* names, uint32_t* lens, uint64_t* a, uint64_t* t, int64_t* e,
+                    uint64_t* counts, uint64_t* nbytes);
+// A ring's slot as a group member's batch (phip_group_ring_receive): the
+// slot's device copy as *w and its `copied` event (a hipEvent_t), when the
+// ring was opened on h (else PHIP_ERR_INVALID) and the slot is the ring's next
+// submitted one (else PHIP_ERR_BUSY; the slot stays submitted).  ring_release
+// frees the slot once nothing reads it any more.
+int ring_slot(phip_ring* r, uint32_t slot, const phip_handle* h, phip_wire* w, void** copied);
+void ring_release(phip_ring* r, uint32_t slot);
 const char* last_error(phip_handle* h);
 
 // The request parsing of API.takeBucket (api.go:55-65): the name-length check

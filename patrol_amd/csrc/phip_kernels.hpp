@@ -1331,6 +1331,48 @@ struct WireIn {
   }
 };
 
+// The replica fields of well-formed datagram i (at least PHIP_BUCKET_FIXED_SIZE
+// bytes) as WireIn::load takes them: the header's four aligned words, indices
+// clamped to the datagram's last word, funnel8 plus bswap.  The owner
+// routing's field source over raw datagrams (k_route_count / k_route_scatter
+// with Src = Datagrams); the bits pass unchanged.
+template <bool NT = false>
+__device__ inline void wire_fields(const Datagrams& d, u32 i, u64& ra, u64& rt, i64& re) {
+  const u64 o = ld<NT>(d.offs + i), end = ld<NT>(d.offs + i + 1);
+  const u64* p = reinterpret_cast<const u64*>(d.blob);
+  const u64 last = (end > o ? end - 1 : o) >> 3, hb = o >> 3;
+  u64 h[4];
+#pragma unroll
+  for (u32 k = 0; k < 4; ++k) h[k] = ld<false>(p + (hb + k < last ? hb + k : last));
+  const u32 sb = (u32)(o & 7);
+  ra = __builtin_bswap64(funnel8(h[0], h[1], sb));
+  rt = __builtin_bswap64(funnel8(h[1], h[2], sb));
+  re = (i64)__builtin_bswap64(funnel8(h[2], h[3], sb));
+}
+
+// The pre-pass of a routed wire batch (phip_route_pack_datagrams,
+// phip_group_receive_datagrams): offsets and length bytes only.  out[0]: the
+// first malformed datagram (size < PHIP_BUCKET_FIXED_SIZE, or a length byte
+// larger than what is left: repo.go:70-74 stops there); out[1], checked
+// batches (lim != 0): the first entry that is not offs[i] <= offs[i+1] <= lim,
+// at which nothing is read.  Both min-reduced; the caller sets them to ~0.
+__global__ __launch_bounds__(kBlock) void k_wire_scan(const u8* __restrict__ bytes,
+                                                      const uint64_t* __restrict__ offs, u32 n,
+                                                      u64 lim, u32* __restrict__ out) {
+  const u64 i = (u64)blockIdx.x * kBlock + threadIdx.x;
+  bool bad = false, stop = false;
+  if (i < n) {
+    const u64 o = offs[i], end = offs[i + 1];
+    bad = lim != 0 && (end < o || end > lim);
+    if (!bad) {
+      const u64 sz = end >= o ? end - o : 0;
+      stop = sz < PHIP_BUCKET_FIXED_SIZE || sz - PHIP_BUCKET_FIXED_SIZE < bytes[o + 24];
+    }
+  }
+  note_min(stop, (u32)i, &out[0]);
+  note_min(bad, (u32)i, &out[1]);
+}
+
 // Classification of a fast batch: the first dirty message into
 // ctr[kCtrDirty], the first malformed datagram into ctr[kCtrStop].  One atomic per
 // wave that finds one, none on a clean batch.
@@ -4680,6 +4722,9 @@ __global__ __launch_bounds__(kRouteBlock) void k_route_count(
   // kRouteRecount: count again without combining if that found a dirty
   // message (nothing to do on a clean batch); mode kRoutePlain: no combine.
   if (mode == kRouteRecount && ctr[kCtrDirty] == ~0u) return;
+  // Src = Datagrams: the wire form (phip_route_pack_datagrams); a, t and e
+  // are unused and the fields come from the datagram's header (wire_fields)
+  constexpr bool kWire = std::is_same<Src, Datagrams>::value;
   const bool comb = mode == kRouteCombine;
   const u32 nh = comb ? route_hot_n(hot, ctr) : 0u;
   for (u32 j = threadIdx.x; j < kRouteWaves * kRouteMaxWorld; j += kRouteBlock) {
@@ -4709,13 +4754,17 @@ __global__ __launch_bounds__(kRouteBlock) void k_route_count(
     bool valid[kRUC];
     u64 off[kRUC], w0[kRUC], w1[kRUC], w2[kRUC];
     u64 ra[kRUC], rt[kRUC];
+    [[maybe_unused]] i64 re[kRUC];   // (the wire form's elapsed comes with the header)
 #pragma unroll
     for (u32 u = 0; u < kRUC; ++u) {
       const u64 i = b0 + u * 64 + lane;
       valid[u] = i < wend;   // (the last step of a wave's range may reach past it)
       const u32 ic = (u32)(valid[u] ? i : t0);
       src.template get<true>(ic, off[u], len[u]);
-      if (comb) { ra[u] = ld<true>(a + ic); rt[u] = ld<true>(t + ic); }
+      if (comb) {
+        if constexpr (kWire) wire_fields<true>(src, ic, ra[u], rt[u], re[u]);
+        else { ra[u] = ld<true>(a + ic); rt[u] = ld<true>(t + ic); }
+      }
     }
 #pragma unroll
     for (u32 u = 0; u < kRUC; ++u) load_words3<true>(src.blob, off[u], len[u], w0[u], w1[u], w2[u]);
@@ -4732,7 +4781,9 @@ __global__ __launch_bounds__(kRouteBlock) void k_route_count(
         const bool fpos = as_f64(ra[u]) > 0.0 || as_f64(rt[u]) > 0.0;
         bool dirty = ra[u] == kSign || rt[u] == kSign;
         if (valid[u] && !fpos) {
-          const i64 ev = e[i];
+          i64 ev;
+          if constexpr (kWire) ev = re[u];
+          else ev = e[i];
           ok = ev > 0;
           dirty |= replica_dirty(ra[u], rt[u], ev);
         }
@@ -4977,6 +5028,7 @@ __global__ __launch_bounds__(kRouteBlock) __attribute__((amdgpu_waves_per_eu(6, 
   __shared__ u64 hmax[3][kRouteHotMax];
   __shared__ u32 hit[kRouteHotMax];
   __shared__ u32 nstage[kRouteWaves][kStageWords];
+  constexpr bool kWire = std::is_same<Src, Datagrams>::value;   // as k_route_count
   const u32 nh = route_hot_n(hot, ctr);
   const u32 wave = threadIdx.x / 64, lane = threadIdx.x & 63;
   const u32 tile = blockIdx.x;
@@ -5013,7 +5065,8 @@ __global__ __launch_bounds__(kRouteBlock) __attribute__((amdgpu_waves_per_eu(6, 
       const u32 ic = (u32)(valid[u] ? i : t0);
       c[u] = code[ic];
       src.get(ic, off[u], len[u]);
-      va[u] = a[ic]; vt[u] = t[ic]; ve[u] = e[ic];
+      if constexpr (kWire) wire_fields(src, ic, va[u], vt[u], ve[u]);
+      else { va[u] = a[ic]; vt[u] = t[ic]; ve[u] = e[ic]; }
     }
     // the name as three aligned words (all of a name of <= 16 bytes)
 #pragma unroll

@@ -24,7 +24,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (DEVICE_PTRS, phip_config, phip_msgs, phip_ops, phip_results, phip_state,
-                   phip_take_reply)
+                   phip_take_reply, phip_wire)
 
 
 class PatrolHipError(RuntimeError):
@@ -922,6 +922,36 @@ class GPURepo:
             _ptr(out["counts"]), _ptr(out["name_bytes"]), DEVICE_PTRS))
         return out
 
+    def route_pack_datagrams_device(self, data, offs, n: int, world: int, combine: bool = False,
+                                    bytes_len: int = 0):
+        """phip_route_pack_datagrams: the stable owner partition of n raw
+        datagrams read in place (data: uint8 CUDA tensor of back-to-back
+        datagrams with 8 bytes of slack, offs: int64[n+1]) -> dict of CUDA
+        tensors names (packed back to back), lens, added, taken, elapsed (bit
+        patterns), counts and name_bytes per owner, and stop: the first
+        malformed datagram (the Go loop stops there, repo.go:70-74; only the
+        datagrams before it are packed) or n.  bytes_len != 0 has the offsets
+        checked against it (a violation raises, code -1)."""
+        import torch
+        dev = data.device
+        z = max(n, 1)
+        out = dict(names=torch.zeros(int(data.numel()) + 64, dtype=torch.uint8, device=dev),
+                   lens=torch.zeros(z, dtype=torch.int32, device=dev),
+                   added=torch.zeros(z, dtype=torch.int64, device=dev),
+                   taken=torch.zeros(z, dtype=torch.int64, device=dev),
+                   elapsed=torch.zeros(z, dtype=torch.int64, device=dev),
+                   counts=torch.zeros(max(world, 1), dtype=torch.int64, device=dev),
+                   name_bytes=torch.zeros(max(world, 1), dtype=torch.int64, device=dev))
+        w = phip_wire(n, 0, _ptr(data), _ptr(offs), int(bytes_len))
+        stop = C.c_uint32(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.L.phip_route_pack_datagrams(
+            self.h, C.byref(w), world, _ptr(out["names"]), _ptr(out["lens"]), _ptr(out["added"]),
+            _ptr(out["taken"]), _ptr(out["elapsed"]), _ptr(out["counts"]), _ptr(out["name_bytes"]),
+            C.byref(stop), DEVICE_PTRS | (_lib.ROUTE_COMBINE if combine else 0)), allow=(-5,))
+        out["stop"] = stop.value
+        return out
+
     def take(self, names, now, freq, per, count):
         """Batched Bucket.Take via GetBucket (create) then Take: (remaining, ok)."""
         n = len(names)
@@ -1117,6 +1147,74 @@ class GPUGroup:
             (_lib.GROUP_SMALL_CHUNKS if small_chunks else 0)
         self._check(self.L.phip_group_receive(self.g, msgs, int(now), sent, merged, flags))
         return [int(x) for x in sent], [int(x) for x in merged]
+
+    def _wire_flags(self, combine, rccl_self, small_chunks):
+        return DEVICE_PTRS | (_lib.ROUTE_COMBINE if combine else 0) | \
+            (_lib.GROUP_RCCL_SELF if rccl_self else 0) | \
+            (_lib.GROUP_SMALL_CHUNKS if small_chunks else 0)
+
+    def _wire_call(self, rc, sent, merged, stopped):
+        """A stop (PHIP_ERR_SHORT_BUFFER, the Go loop's io.ErrShortBuffer) does
+        not raise: `stopped` tells where each member's batch ended."""
+        if rc not in (0, -5):
+            self._check(rc)
+        self.last_rc = rc
+        return [int(x) for x in sent], [int(x) for x in merged], [int(x) for x in stopped]
+
+    def receive_datagrams(self, batches, now: int, combine: bool = True, rccl_self: bool = False,
+                          small_chunks: bool = False, checked: bool = True):
+        """Owner-routed Receive straight from the wire
+        (phip_group_receive_datagrams): batches holds, per local member, the
+        raw datagrams that arrived there, as a (bytes uint8, offs int64[n+1])
+        pair of CUDA tensors (8-byte aligned, 8 bytes of slack past the last
+        datagram) or as a list of `bytes` objects that is packed and uploaded
+        to the member's GPU.  -> (sent, merged, stopped) lists.
+
+        Member i's datagrams before its first malformed one (repo.go:70-74)
+        are routed and merged; stopped[i] is that index, or its n.  A stop
+        does not raise: last_rc is then -5 (PHIP_ERR_SHORT_BUFFER), else 0.
+        checked: the offsets are verified against the bytes tensor's length
+        before anything is read through them; a violation raises
+        PatrolHipError (code -1) and no batch is applied.  combine,
+        rccl_self, small_chunks: as receive()."""
+        import torch
+        k = len(batches)
+        ws = (phip_wire * k)()
+        keep = []
+        for i, b in enumerate(batches):
+            if isinstance(b, (list, tuple)) and (len(b) != 2 or not _is_torch(b[0])):
+                dev = torch.device("cuda", self.repos[i].device)
+                offs = np.zeros(len(b) + 1, np.int64)
+                if len(b):
+                    offs[1:] = np.cumsum(np.fromiter((len(d) for d in b), np.int64, len(b)))
+                blob = np.zeros((int(offs[-1]) + 15) // 8 * 8, np.uint8)
+                blob[:int(offs[-1])] = np.frombuffer(b"".join(b), np.uint8)
+                b = (torch.from_numpy(blob).to(dev), torch.from_numpy(offs).to(dev))
+                torch.cuda.synchronize(dev)
+            data, offs = b
+            keep.append(b)
+            ws[i] = phip_wire(offs.numel() - 1, 0, _ptr(data), _ptr(offs),
+                              int(data.numel()) if checked else 0)
+        sent, merged, stopped = (C.c_uint64 * k)(), (C.c_uint64 * k)(), (C.c_uint32 * k)()
+        rc = self.L.phip_group_receive_datagrams(self.g, ws, int(now), sent, merged, stopped,
+                                                 self._wire_flags(combine, rccl_self, small_chunks))
+        return self._wire_call(rc, sent, merged, stopped)
+
+    def ring_receive(self, rings, slots, now: int, combine: bool = True, rccl_self: bool = False,
+                     small_chunks: bool = False):
+        """The socket edge (phip_group_ring_receive): rings[i] is a Ring over
+        repos[i] (None: an empty batch for member i), slots[i] its next
+        submitted slot.  -> (sent, merged, stopped) as receive_datagrams; the
+        slots are free again when the call returns.  An out-of-order slot
+        raises PatrolHipError (code -9, PHIP_ERR_BUSY) and a ring of another
+        handle code -1; both leave every slot submitted."""
+        k = len(rings)
+        rs = (C.c_void_p * k)(*[r.r.value if r is not None else None for r in rings])
+        sl = (C.c_uint32 * k)(*[int(s) for s in slots])
+        sent, merged, stopped = (C.c_uint64 * k)(), (C.c_uint64 * k)(), (C.c_uint32 * k)()
+        rc = self.L.phip_group_ring_receive(self.g, rs, sl, int(now), sent, merged, stopped,
+                                            self._wire_flags(combine, rccl_self, small_chunks))
+        return self._wire_call(rc, sent, merged, stopped)
 
     _OPS_KEYS = ("kind", "names", "name_offs", "now", "freq", "per", "count", "added", "taken",
                  "elapsed")
