@@ -1144,9 +1144,9 @@ int phip_udp_send_batch(int fd, const uint8_t* bytes, const uint64_t* offs, uint
  * gives zeros and offs[0] = 0.
  *
  * Flags.  PHIP_RECV_ASYNC is PHIP_ERR_INVALID: a queued batch returns no
- * replies.  PHIP_RECV_CLASSIFY is allowed.  Not covered either: the shard
- * group (phip_group_receive returns no replies) and PHIP_OP_RECEIVE ops inside
- * phip_apply_mixed.  phip_ring_receive_replies is phip_ring_receive with rq's
+ * replies.  PHIP_RECV_CLASSIFY is allowed.  Not covered either:
+ * PHIP_OP_RECEIVE ops inside phip_apply_mixed.  The shard group has its own
+ * forms ("Group reply egress").  phip_ring_receive_replies is phip_ring_receive with rq's
  * buffers in host memory; res may leave out reply and status.
  * phip_incast_replies stays for callers that hold the full columns. */
 typedef struct phip_reply_egress {   /* 56 bytes */
@@ -1375,11 +1375,10 @@ int phip_group_receive(phip_group* g, const phip_msgs* batches, int64_t now, uin
  * PHIP_GROUP_RCCL_SELF and PHIP_GROUP_SMALL_CHUNKS are the others; any other
  * bit is PHIP_ERR_INVALID.
  *
- * Out of scope: an incast request (the all-zero state) routed this way is
- * merged at its owner (the bucket is created) but not answered, as
- * phip_group_receive returns no per-message results either; replies over the
- * group remain phip_group_apply_mixed with RECEIVE ops.  There is no batcher
- * over the group. */
+ * An incast request (the all-zero state) routed this way is merged at its
+ * owner (the bucket is created); its answer comes from the replies form,
+ * phip_group_receive_datagrams_replies ("Group reply egress").  There is no
+ * batcher over the group. */
 int phip_group_receive_datagrams(phip_group* g, const phip_wire* batches, int64_t now,
                                  uint64_t* sent, uint64_t* merged,
                                  uint32_t* stopped /* per member */, uint32_t flags);
@@ -1398,6 +1397,96 @@ int phip_group_receive_datagrams(phip_group* g, const phip_wire* batches, int64_
 int phip_group_ring_receive(phip_group* g, phip_ring* const* rings, const uint32_t* slots,
                             int64_t now, uint64_t* sent, uint64_t* merged, uint32_t* stopped,
                             uint32_t flags);
+/* ---- Group reply egress ----
+ * The shard group's answers to incast requests (repo.go:86-90,160-169): the
+ * other half of the protocol for a sharded node.  Each of the three calls
+ * below is the group receive call it is named after -- the same tables, sent /
+ * merged / stopped, stop rule, checked-offset rule, flags and return codes --
+ * and in addition fills rq[i] (a phip_reply_egress, "Incast reply egress")
+ * for every local member i with the answers to the requests that arrived in
+ * member i's batch, wherever their buckets live.
+ *
+ * Which messages.  Exactly the messages of member i's batch whose Receive at
+ * their owner has status PHIP_ST_INCAST_REPLY, in the order the group defines:
+ * a bucket sees its messages in the order (round, source rank, index in the
+ * source's batch), and an answer carries the bucket's state at that point,
+ * not the state after the call.
+ *
+ * Layout.  Datagram k is out[offs[k] .. offs[k+1]), offs[0] = 0: MarshalBinary
+ * (bucket.go:51-68), byte for byte, of that state under the request's own
+ * name.  src[k] is the message's index in member i's batch (src may be NULL),
+ * so phip_reply_peers(peers_i, src, n, ..) works unchanged.  Datagrams are in
+ * batch order across all rounds and all owners.
+ *
+ * Bounds are phip_reply_egress': the first datagrams in batch order that fit
+ * max_msgs and the byte budget are written, cut at a record.  max_msgs == 0, a
+ * NULL out / offs or an out_cap below one datagram in any rq[i], or a NULL
+ * rq, is PHIP_ERR_INVALID before anything of any member is applied.
+ *
+ * Counters.  They differ from the single-handle form:
+ *   n        datagrams written;
+ *   replies  the answers that came back for member i's requests, whatever the
+ *            caps let through: n < replies says some were cut;
+ *   skipped  counted where it is known: the answers member i left out AS AN
+ *            OWNER because the name is over PHIP_MAX_NAME_LEN, whoever asked
+ *            (they never travel, so `replies` of the asking member excludes
+ *            them);
+ *   bytes    = offs[n].
+ * A world of one without PHIP_GROUP_RCCL_SELF has nothing to route: the batch
+ * goes to phip_receive_datagrams_replies / phip_receive_soa_replies, and its
+ * counters are reported in the same terms (replies excludes skipped).
+ *
+ * Pointers.  phip_group_receive_datagrams_replies and
+ * phip_group_receive_replies require PHIP_DEVICE_PTRS; out / offs / src are
+ * device memory of member i's GPU under phip_export_sweep's rules (8-byte
+ * aligned, out_cap a multiple of 8 and at least PHIP_BUCKET_PACKET_SIZE + 8,
+ * the byte budget out_cap - 8).  phip_group_ring_receive_replies takes host
+ * buffers in rq, as phip_ring_receive_replies does, and copies back only
+ * what was written; its byte budget is out_cap rounded down to a multiple of
+ * 8.
+ *
+ * Stops and errors.  A member stopped at a malformed datagram: the answers to
+ * its requests before the stop are returned, the out fields are valid and the
+ * call returns PHIP_ERR_SHORT_BUFFER as phip_group_receive_datagrams does.  A
+ * refused checked batch, or any other error: the four out fields of every
+ * local rq are zero.
+ *
+ * Flags: the receive call's own set (phip_group_receive_replies refuses
+ * unknown bits too).  PHIP_ROUTE_COMBINE is accepted: a pack that combined is
+ * a clean pack and holds no request (a zero state never combines), and a
+ * chunk that holds a request packs plain.
+ *
+ * How.  Every member counts the zero-state messages of each chunk it packs
+ * (one pass over the replica fields) and sends the count with the split
+ * sizes; a round in which every count is 0 runs exactly the path of the call
+ * without replies, and no return exchange.  In a round with requests every
+ * owner merges its chunk with phip_receive_soa_replies into buffers sized from
+ * the requests it can have received (sum over sources p of min(zero states of
+ * p, messages p sent here)), and only the answers travel back: their
+ * per-source counts as split sizes, then lengths, bytes and positions along
+ * that plan.  The source turns positions into batch indices, sorts the
+ * round's answers by index and appends what fits; once a round is cut, later
+ * rounds only count.  Such a round finishes before the next round's exchange
+ * starts.
+ *
+ * Out of scope: PHIP_RECV_ASYNC with replies, answers to PHIP_OP_RECEIVE ops
+ * inside phip_apply_mixed (its reply column stays), and a batcher over the
+ * group. */
+int phip_group_receive_datagrams_replies(phip_group* g, const phip_wire* batches, int64_t now,
+                                         uint64_t* sent, uint64_t* merged, uint32_t* stopped,
+                                         phip_reply_egress* rq /* one per local member */,
+                                         uint32_t flags);
+int phip_group_receive_replies(phip_group* g, const phip_msgs* batches, int64_t now,
+                               uint64_t* sent, uint64_t* merged,
+                               phip_reply_egress* rq /* one per local member */, uint32_t flags);
+int phip_group_ring_receive_replies(phip_group* g, phip_ring* const* rings, const uint32_t* slots,
+                                    int64_t now, uint64_t* sent, uint64_t* merged,
+                                    uint32_t* stopped, phip_reply_egress* rq, uint32_t flags);
+/* The last *_replies call of member i: out[0] rounds run, out[1] rounds that
+ * ran a return exchange, out[2] the request bound the member received as an
+ * owner, summed over rounds, out[3] the answers it wrote as an owner.
+ * Returns the number written (<= 4). */
+int phip_group_reply_stats(phip_group* g, uint32_t i, uint64_t* out, int max);
 /* Owner-routed phip_apply_mixed: batches[i] / results[i] belong to local member i
  * (device memory of its GPU; any results pointer may be NULL, results itself
  * too).  The sharded form of POST /take (api.go:51-86): an op that arrived at

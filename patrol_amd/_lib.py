@@ -42,6 +42,8 @@ EXPORTS = [
     "phip_receive_soa_replies", "phip_receive_datagrams_replies", "phip_ring_receive_replies",
     "phip_reply_peers",
     "phip_route_pack_datagrams", "phip_group_receive_datagrams", "phip_group_ring_receive",
+    "phip_group_receive_datagrams_replies", "phip_group_receive_replies",
+    "phip_group_ring_receive_replies", "phip_group_reply_stats",
 ]
 
 PHIP_OK = 0
@@ -359,5 +361,15 @@ def load(path: str = LIB_PATH):
                                                    C.POINTER(u64), C.POINTER(u32), u32]
         L.phip_group_ring_receive.argtypes = [vp, C.POINTER(vp), C.POINTER(u32), i64,
                                               C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), u32]
+    if hasattr(L, "phip_group_reply_stats"):
+        rqp = C.POINTER(phip_reply_egress)
+        L.phip_group_receive_datagrams_replies.argtypes = [
+            vp, C.POINTER(phip_wire), i64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), rqp, u32]
+        L.phip_group_receive_replies.argtypes = [vp, C.POINTER(phip_msgs), i64, C.POINTER(u64),
+                                                 C.POINTER(u64), rqp, u32]
+        L.phip_group_ring_receive_replies.argtypes = [vp, C.POINTER(vp), C.POINTER(u32), i64,
+                                                      C.POINTER(u64), C.POINTER(u64),
+                                                      C.POINTER(u32), rqp, u32]
+        L.phip_group_reply_stats.argtypes = [vp, u32, C.POINTER(u64), C.c_int]
     _lib = L
     return L

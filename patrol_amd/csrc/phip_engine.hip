@@ -2688,7 +2688,7 @@ static int route_pack_src(phip_handle* h, hipStream_t st, const Src& src, const 
                           const uint64_t* t, const int64_t* e, u32 n, u32 world, const void* dir,
                           uint8_t* send_names, uint32_t* send_lens, uint64_t* send_added,
                           uint64_t* send_taken, int64_t* send_elapsed, uint64_t* counts,
-                          uint64_t* nbytes) {
+                          uint64_t* nbytes, uint32_t* send_src = nullptr) {
   const HotHdr* hot = (const HotHdr*)dir;
   const RouteHot* rdir = hot ? (const RouteHot*)(hot + 1) : nullptr;
   return route_pack_with(
@@ -2705,19 +2705,24 @@ static int route_pack_src(phip_handle* h, hipStream_t st, const Src& src, const 
               c.cnt, c.bytes, kRouteRecount);
       },
       [&](const RoutePlan& p, const RouteCells& c) {
-        Launch l(h, "k_route_scatter", st);
-        k_route_scatter<Src><<<p.nblk, kRouteBlock, 0, st>>>(
-            src, a, t, e, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
-            c.cbase, c.bbase, send_names, send_lens, send_added, send_taken, send_elapsed);
+        Launch l(h, send_src ? "k_route_scatter_src" : "k_route_scatter", st);
+        if (send_src)   // (the replies forms of the group: the same pack, keeping every message's index)
+          k_route_scatter<WithSrcIdx<Src>><<<p.nblk, kRouteBlock, 0, st>>>(
+              WithSrcIdx<Src>{src, send_src}, a, t, e, n, p.span, world, p.ntile, hot, rdir, c.pctr,
+              c.code, c.cbase, c.bbase, send_names, send_lens, send_added, send_taken, send_elapsed);
+        else
+          k_route_scatter<Src><<<p.nblk, kRouteBlock, 0, st>>>(
+              src, a, t, e, n, p.span, world, p.ntile, hot, rdir, c.pctr, c.code,
+              c.cbase, c.bbase, send_names, send_lens, send_added, send_taken, send_elapsed);
       });
 }
 static int route_pack_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32 world, const void* dir,
                   uint8_t* send_names, uint32_t* send_lens, uint64_t* send_added,
                   uint64_t* send_taken, int64_t* send_elapsed, uint64_t* counts,
-                  uint64_t* nbytes) {
+                  uint64_t* nbytes, uint32_t* send_src = nullptr) {
   return route_pack_src(h, st, NamesOffs{m.names, m.name_offs, m.names_len}, m.added, m.taken,
                         m.elapsed, m.n, world, dir, send_names, send_lens, send_added, send_taken,
-                        send_elapsed, counts, nbytes);
+                        send_elapsed, counts, nbytes, send_src);
 }
 
 // Stable owner partition of an op stream (phip_route_pack_ops, and the chunks
@@ -4808,10 +4813,30 @@ int route_dir(phip_handle* h, void* stream, const phip_msgs* m, uint32_t world, 
 }
 int route_pack(phip_handle* h, void* stream, const phip_msgs* m, uint32_t world, const void* dir,
                uint8_t* names, uint32_t* lens, uint64_t* a, uint64_t* t, int64_t* e,
-               uint64_t* counts, uint64_t* nbytes) {
+               uint64_t* counts, uint64_t* nbytes, uint32_t* src) {
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = finish_queued(h)) return rc0;
-  return route_pack_on(h, (hipStream_t)stream, *m, world, dir, names, lens, a, t, e, counts, nbytes);
+  return route_pack_on(h, (hipStream_t)stream, *m, world, dir, names, lens, a, t, e, counts, nbytes,
+                       src);
+}
+// The chunk's zero-state count (k_zero_count) on `stream`, added into the high
+// halves of out[0 .. nout).
+template <class Fields>
+static int count_zero_on(phip_handle* h, hipStream_t st, const Fields& f, u32 n, u32 nout, uint64_t* out) {
+  if (!n) return PHIP_OK;
+  const u32 grid = (u32)std::min<u64>(grid_for(n), (u64)h->ncu * 8);
+  Launch l(h, "k_zero_count", st);
+  k_zero_count<Fields><<<grid, kBlock, 0, st>>>(f, n, nout, (unsigned long long*)out);
+  HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
+}
+int count_zero(phip_handle* h, void* stream, const phip_msgs* m, uint32_t nout, uint64_t* out) {
+  std::lock_guard<std::mutex> g(h->mu);
+  return count_zero_on(h, (hipStream_t)stream, SoaFields{m->added, m->taken, m->elapsed}, m->n, nout, out);
+}
+int count_zero_wire(phip_handle* h, void* stream, const phip_wire* w, uint32_t nout, uint64_t* out) {
+  std::lock_guard<std::mutex> g(h->mu);
+  return count_zero_on(h, (hipStream_t)stream, WireFields{Datagrams{w->bytes, w->offs}}, w->n, nout, out);
 }
 int route_pack_ops(phip_handle* h, void* stream, const phip_ops* ops, uint32_t world,
                    uint8_t* names, uint32_t* lens, uint8_t* kind, int64_t* now, uint64_t* x0,
@@ -4850,11 +4875,11 @@ int route_dir_wire(phip_handle* h, void* stream, const phip_wire* w, uint32_t wo
 }
 int route_pack_wire(phip_handle* h, void* stream, const phip_wire* w, uint32_t world, const void* dir,
                     uint8_t* names, uint32_t* lens, uint64_t* a, uint64_t* t, int64_t* e,
-                    uint64_t* counts, uint64_t* nbytes) {
+                    uint64_t* counts, uint64_t* nbytes, uint32_t* src) {
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = finish_queued(h)) return rc0;
   return route_pack_src(h, (hipStream_t)stream, Datagrams{w->bytes, w->offs}, nullptr, nullptr,
-                        nullptr, w->n, world, dir, names, lens, a, t, e, counts, nbytes);
+                        nullptr, w->n, world, dir, names, lens, a, t, e, counts, nbytes, src);
 }
 int ring_slot(phip_ring* r, uint32_t slot, const phip_handle* h, phip_wire* w, void** copied) {
   if (!r || r->h != h || slot >= r->slots.size()) return PHIP_ERR_INVALID;

@@ -24,6 +24,15 @@
 // its peers' buffers with device copies; the all-reduce is an element-wise
 // max over the members' joins.  The packing, segment offsets, source order
 // and merge are the same code as the RCCL path.
+//
+// The *_replies forms of Receive also answer the incast requests (zero
+// states, repo.go:86-90) that arrived at each member.  Every chunk's split
+// sizes carry the number of zero-state messages its member holds, so all
+// members know alike whether a round has requests; such a round leaves the
+// pipeline (reply_round): its owners merge with phip_receive_soa_replies, the
+// answers alone travel back along a plan made of their per-source counts, and
+// the source appends them to the caller's buffers in batch order.  A round
+// without requests runs the path of the call without replies.
 #include <dlfcn.h>
 
 #include <cstdarg>
@@ -104,9 +113,15 @@ constexpr Col kLens = {4, false, ncclUint32, 1, 4}, kNames = {1, true, ncclUint8
 constexpr Cols kMsgCols = {5, {kLens, kNames, kWord, kWord, kWord}};
 constexpr Cols kOpCols = {7, {kLens, kNames, kByte, kWord, kWord, kWord, kWord}};
 constexpr Cols kResCols = {4, {kByte, kWord, kWord, kReply}};
+// The answers to a round's incast requests on their way back (the *_replies
+// forms): every datagram's length, the datagrams' bytes back to back (a
+// segment of them is addressed by byte, as names are) and the request's
+// position in the segment its source sent.
+constexpr Cols kBackCols = {3, {kLens, kNames, kLens}};
 enum { C_LENS, C_NAMES, MSG_A, MSG_T, MSG_E };
 enum { O_KIND = C_NAMES + 1, O_NOW, O_X0, O_X1, O_X2 };
 enum { R_STATUS, R_REM, R_HAVE, R_REPLY };
+enum { B_LENS, B_BYTES, B_POS };
 
 // The buffers of one column set, sized and moved by its table.
 struct ColSet {
@@ -133,7 +148,11 @@ struct ColSet {
 // One chunk's split sizes: dev (device) and host (pinned) hold [6 * world] u64:
 //   send counts | send name bytes | send chunk totals | recv counts | recv name bytes | recv chunk totals
 // (the chunk totals: every member's chunk count K, so that all members run
-// the same number of exchange rounds).
+// the same number of exchange rounds).  A chunk total's low half is K; its
+// high half is the number of zero-state messages the member's chunk holds
+// (the *_replies forms count them; 0 otherwise), so that every member knows
+// from exchanged values alone whether the round has requests to answer.
+constexpr u64 kRoundMask = 0xFFFFFFFFull;
 struct Sizes {
   Buf dev;
   uint64_t* host = nullptr;
@@ -152,6 +171,28 @@ struct Lane {
   hipEvent_t ev_recv = nullptr;   // its exchange (exchange stream)
   hipEvent_t ev_merged = nullptr; // its merge (handle stream)
   bool merge_pending = false;     // ev_merged recorded for a merge reading `recv`
+  bool to_merge = false;          // `recv` holds a chunk no merge was queued for yet
+  // The *_replies forms: where every packed message of the chunk stood in it
+  // (send position -> chunk index), and the owner's answers to the chunk's
+  // requests as phip_receive_soa_replies writes them (their datagrams into
+  // rsend's byte column), split by source for the way back.
+  Buf src, roffs, rsrc;
+  ColSet rsend{kBackCols};
+};
+
+// One member's part of a *_replies call: the caller's buffers and how far
+// they are filled (the rounds append), and phip_group_reply_stats' words.
+struct Replies {
+  phip_reply_egress* rq = nullptr;
+  u64 budget = 0;
+  u64 n = 0, bytes = 0, replies = 0, skipped = 0;
+  bool cut = false;               // a round did not fit: later rounds only count
+};
+enum { RS_ROUNDS, RS_RETURNS, RS_BOUND, RS_WRITTEN, RS_WORDS };
+
+// Segment boundaries by peer, as a kernel argument (world <= 64).
+struct SegBounds {
+  u32 at[65];
 };
 
 // Busy spans of one group call per stage (0 pack, 1 exchange, 2 merge):
@@ -191,6 +232,7 @@ struct StageTimer {
 };
 
 constexpr u32 kOpsSizes = 2;   // Member::sz of the ops path (0, 1: Receive's lanes)
+constexpr u32 kBackSizes = 3;  // ... and of the answers' way back (the *_replies forms)
 
 struct Member {
   phip_handle* h = nullptr;
@@ -209,8 +251,17 @@ struct Member {
   // results the owners returned to this source, in send order.
   ColSet osend{kOpCols}, orecv{kOpCols}, ores{kResCols}, oback{kResCols};
   Buf osrc, ooffs;
-  Sizes sz[3];
+  Sizes sz[4];
   Buf scan_tmp, ae, bounds;
+  // The *_replies forms, source side: the answers the owners returned (owners
+  // in rank order), the sort by batch index and the gather's scratch; the
+  // ring form's device copies of the caller's host buffers; the last call's
+  // phip_group_reply_stats.
+  ColSet rback{kBackCols};
+  Buf gkey_in, gval_in, gkey, gval, gaoff, gslen, gsend, gctr;
+  Buf ring_out, ring_offs, ring_src;
+  hipEvent_t ev_rep = nullptr;
+  u64 rstats[RS_WORDS] = {0, 0, 0, 0};
   u64* host_k = nullptr;       // pinned [world]: this member's chunk count, to every peer
   u64 k_local = 0;             // (shared-device groups read each other's)
   StageTimer tm;
@@ -479,15 +530,19 @@ int adopt_sizes(phip_group* g, Member& mb, u32 si, bool first, u64* K) {
       const u64* ps = g->m[p].sz[si].host;
       hs[3 * W + p] = ps[mb.rank];
       hs[4 * W + p] = ps[W + mb.rank];
-      hs[5 * W + p] = g->m[p].k_local;
+      hs[5 * W + p] = g->m[p].k_local | (ps[2 * W + mb.rank] & ~kRoundMask);
     }
   }
   if (first) {
-    for (u32 p = 0; p < W; ++p) *K = std::max<u64>(*K, hs[5 * W + p]);
+    for (u32 p = 0; p < W; ++p) *K = std::max<u64>(*K, hs[5 * W + p] & kRoundMask);
     *K = std::max<u64>(*K, 1);
   }
   return PHIP_OK;
 }
+
+// The zero-state messages source p holds in this round (the *_replies forms;
+// 0 from every other call): the chunk total's high half.
+u64 zero_states_of(const u64* hs, u32 W, u32 p) { return hs[5 * W + p] >> 32; }
 
 // What one round sends and receives; a receive side past 2^32 is refused.
 struct Totals {
@@ -553,6 +608,7 @@ int offsets_from_lens(Member& mb, const u32* lens, u64 n, u32* offs, hipStream_t
 // the names' offsets, then phip_receive_soa (sources in rank order, each in
 // its order), on the handle's stream behind the chunk's exchange.
 int merge_chunk(Member& mb, Lane& ln, hipStream_t st, int64_t now) {
+  ln.to_merge = false;
   if (ln.n) {
     GHIP(mb, hipStreamWaitEvent(st, ln.ev_recv, 0));
     GHIP(mb, mb.tm.mark(2, st));
@@ -606,11 +662,21 @@ struct MsgBatch {
   }
   u64 chunk_bytes(u64, u64 k) const { return (u64)(bnd[k + 1] - bnd[k]); }
   int dir(Member& mb, u32 W, const void** d) { return phip_host::route_dir(mb.h, mb.sp, &in, W, d); }
-  int pack(Member& mb, u64 chunk, u64 k, u32 W, const void* d, const ColSet& ss, u64* sz) {
+  int pack(Member& mb, u64 chunk, u64 k, u32 W, const void* d, const ColSet& ss, u64* sz, u32* src) {
     const phip_msgs c = chunk_of(in, chunk, k);
     return phip_host::route_pack(mb.h, mb.sp, &c, W, d, ss.at<uint8_t>(C_NAMES), ss.at<uint32_t>(C_LENS),
                                  ss.at<uint64_t>(MSG_A), ss.at<uint64_t>(MSG_T), ss.at<int64_t>(MSG_E), sz,
-                                 sz + W);
+                                 sz + W, src);
+  }
+  // the *_replies forms: chunk k's zero-state count into the chunk totals,
+  // and the whole batch with its answers where there is nothing to route
+  int count_zero(Member& mb, u64 chunk, u64 k, u32 W, u64* totals) {
+    const phip_msgs c = chunk_of(in, chunk, k);
+    return phip_host::count_zero(mb.h, mb.sp, &c, W, totals);
+  }
+  int whole_replies(Member& mb, int64_t now, phip_reply_egress* rq) {
+    GPHIP(mb, phip_receive_soa_replies(mb.h, &in, now, nullptr, rq, PHIP_DEVICE_PTRS | PHIP_RECV_CLASSIFY));
+    return PHIP_OK;
   }
 };
 
@@ -635,20 +701,251 @@ struct WireBatch {
     return bnd[k + 1] - bnd[k] - cnt * PHIP_BUCKET_FIXED_SIZE;
   }
   int dir(Member& mb, u32 W, const void** d) { return phip_host::route_dir_wire(mb.h, mb.sp, &in, W, d); }
-  int pack(Member& mb, u64 chunk, u64 k, u32 W, const void* d, const ColSet& ss, u64* sz) {
+  phip_wire chunk_of(u64 chunk, u64 k) const {
     phip_wire c = in;
     const u64 lo = k * chunk;
     c.n = lo < in.n ? (u32)std::min<u64>(chunk, in.n - lo) : 0u;
     if (c.n) c.offs = in.offs + lo;   // absolute offsets into the same bytes
+    return c;
+  }
+  int pack(Member& mb, u64 chunk, u64 k, u32 W, const void* d, const ColSet& ss, u64* sz, u32* src) {
+    const phip_wire c = chunk_of(chunk, k);
     return phip_host::route_pack_wire(mb.h, mb.sp, &c, W, d, ss.at<uint8_t>(C_NAMES),
                                       ss.at<uint32_t>(C_LENS), ss.at<uint64_t>(MSG_A),
-                                      ss.at<uint64_t>(MSG_T), ss.at<int64_t>(MSG_E), sz, sz + W);
+                                      ss.at<uint64_t>(MSG_T), ss.at<int64_t>(MSG_E), sz, sz + W, src);
+  }
+  // (as MsgBatch's: the three header words of every datagram of the chunk)
+  int count_zero(Member& mb, u64 chunk, u64 k, u32 W, u64* totals) {
+    const phip_wire c = chunk_of(chunk, k);
+    return phip_host::count_zero_wire(mb.h, mb.sp, &c, W, totals);
+  }
+  int whole_replies(Member& mb, int64_t now, phip_reply_egress* rq) {
+    GPHIP(mb, phip_receive_datagrams_replies(mb.h, in.bytes, in.offs, in.n, now, nullptr, nullptr, rq,
+                                             PHIP_DEVICE_PTRS));
+    return PHIP_OK;
   }
 };
 
+// ---- the answers of a round with incast requests (the *_replies forms) ----
+// The peer whose segment [at[p], at[p + 1]) holds entry x (empty segments are
+// passed over).
+__device__ inline u32 seg_of(const SegBounds& b, u32 W, u32 x) {
+  u32 p = 0;
+  while (p + 1 < W && x >= b.at[p + 1]) ++p;
+  return p;
+}
+
+// Owner: the chunk's n answers (src: the request's place in the received
+// chunk, sources in rank order, so the list is grouped by source already;
+// offs: the datagrams' offsets) split at the received segments' boundaries
+// `at`: every answer's length and its request's position within its source's
+// segment, and per source the answers and their bytes, the way back's split
+// sizes.
+__global__ void k_reply_split(const u32* __restrict__ src, const u64* __restrict__ offs, u32 n,
+                              SegBounds at, u32 W, u32* __restrict__ lens, u32* __restrict__ pos,
+                              unsigned long long* __restrict__ counts,
+                              unsigned long long* __restrict__ bytes) {
+  const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const u32 x = src[k], p = seg_of(at, W, x);
+  const u32 len = (u32)(offs[k + 1] - offs[k]);
+  lens[k] = len;
+  pos[k] = x - at.at[p];
+  atomicAdd(&counts[p], 1ull);
+  atomicAdd(&bytes[p], (unsigned long long)len);
+}
+
+// Source: returned answer j (owners in rank order, `from` their segments'
+// boundaries) answers the message this member packed at position pos[j] of
+// its send segment for that owner (starting at so.at[owner]); send_src turns
+// the send position into the chunk index, base the chunk's first batch index.
+__global__ void k_back_keys(const u32* __restrict__ pos, u32 n, SegBounds from, SegBounds so, u32 W,
+                            const u32* __restrict__ send_src, u32 base, u32* __restrict__ keys,
+                            u32* __restrict__ vals) {
+  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const u32 p = seg_of(from, W, j);
+  keys[j] = base + send_src[so.at[p] + pos[j]];
+  vals[j] = j;
+}
+
+__global__ void k_gather_lens(const u32* __restrict__ vals, const u32* __restrict__ lens, u32 n,
+                              u64* __restrict__ out) {
+  const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) out[k] = lens[vals[k]];
+}
+
+// Source: the round's answers in batch order (answer k of the round: returned
+// answer vals[k], for batch index keys[k], its bytes at aoff[.] of the
+// returned bytes, ending at end[k] of the round's output) appended behind
+// the n0 datagrams / b0 bytes the rounds before wrote, as far as max_msgs and
+// the byte budget allow (a prefix: end[] grows).  One wave a datagram: a
+// byte run of any length and alignment, byte by byte.  ctr[0]: datagrams
+// written, ctr[1]: the output's end.
+__global__ __launch_bounds__(256) void k_reply_gather(
+    const u32* __restrict__ vals, const u32* __restrict__ keys, const u32* __restrict__ lens,
+    const u32* __restrict__ aoff, const u64* __restrict__ end, u32 n, const uint8_t* __restrict__ in,
+    u64 n0, u64 b0, u64 max_msgs, u64 budget, uint8_t* __restrict__ out, u64* __restrict__ offs,
+    u32* __restrict__ src, unsigned long long* __restrict__ ctr) {
+  const u32 k = (blockIdx.x * blockDim.x + threadIdx.x) / 64, lane = threadIdx.x & 63;
+  if (k >= n) return;
+  const u64 e = b0 + end[k];
+  if (n0 + k >= max_msgs || e > budget) return;
+  const u32 j = vals[k], len = lens[j];
+  const uint8_t* from = in + aoff[j];
+  uint8_t* to = out + (e - len);
+  for (u32 x = lane; x < len; x += 64) to[x] = from[x];
+  if (lane == 0) {
+    offs[n0 + k + 1] = e;
+    if (src) src[n0 + k] = keys[k];
+    atomicMax(&ctr[0], (unsigned long long)k + 1);
+    atomicMax(&ctr[1], (unsigned long long)e);
+  }
+}
+
+// Round k of a *_replies call in which some member holds a zero-state message
+// (every member takes this path: the decision comes from exchanged values).
+// The owner merges its received chunk with phip_receive_soa_replies into
+// lane-owned buffers sized from `bound` (the requests it can have received),
+// splits the answers by source and returns them: the per-source counts as
+// split sizes, then lengths, bytes and positions along that plan on the
+// exchange stream (RCCL calls stay in one order: behind this round's exchange,
+// before the next round's sizes).  The source sorts what came back by batch
+// index and appends what fits to the caller's buffers.  The round is finished
+// when this returns.
+int reply_round(phip_group* g, Member& mb, u32 si, u64 k, u64 chunk, const std::vector<Seg>& plan,
+                u64 bound, int64_t now, bool rccl_self, Replies& rp, hipStream_t st) {
+  const u32 W = g->world;
+  Lane& ln = mb.lane[si];
+  Sizes& zs = mb.sz[kBackSizes];
+  int rc;
+  GHIP(mb, zs.dev.ensure((size_t)6 * W * 8));
+  u64* sz = (u64*)zs.dev.p;
+  GHIP(mb, ln.rsend.ensure(bound, bound ? bound * PHIP_BUCKET_PACKET_SIZE + 8 : 0));
+  GHIP(mb, hipMemsetAsync(sz, 0, (size_t)6 * W * 8, st));
+  u64 wrote = 0;
+  if (ln.n && bound) {
+    ln.to_merge = false;
+    GHIP(mb, hipStreamWaitEvent(st, ln.ev_recv, 0));
+    GHIP(mb, mb.tm.mark(2, st));
+    GHIP(mb, ln.offs.ensure(ln.n * 4 + 8));
+    GHIP(mb, ln.roffs.ensure((bound + 1) * 8));
+    GHIP(mb, ln.rsrc.ensure(bound * 4));
+    if ((rc = offsets_from_lens(mb, ln.recv.at<u32>(C_LENS), ln.n, (u32*)ln.offs.p, st))) return rc;
+    phip_msgs rm{};
+    rm.n = (u32)ln.n;
+    rm.names = ln.recv.at<uint8_t>(C_NAMES);
+    rm.name_offs = (const u32*)ln.offs.p;
+    rm.added = ln.recv.at<u64>(MSG_A);
+    rm.taken = ln.recv.at<u64>(MSG_T);
+    rm.elapsed = ln.recv.at<int64_t>(MSG_E);
+    phip_reply_egress q{};
+    q.out = ln.rsend.at<uint8_t>(B_BYTES);
+    q.out_cap = bound * PHIP_BUCKET_PACKET_SIZE + 8;
+    q.offs = (u64*)ln.roffs.p;
+    q.src = (u32*)ln.rsrc.p;
+    q.max_msgs = (u32)bound;
+    GPHIP(mb, phip_receive_soa_replies(mb.h, &rm, now, nullptr, &q, PHIP_DEVICE_PTRS | PHIP_RECV_CLASSIFY));
+    if ((u64)q.n + q.skipped != q.replies)
+      return fail(mb, PHIP_ERR_INVALID, "internal: %u answers for a bound of %llu requests", q.replies,
+                  (unsigned long long)bound);
+    wrote = q.n;
+    rp.skipped += q.skipped;
+    if (wrote) {
+      SegBounds at{};
+      for (u32 p = 0; p < W; ++p) at.at[p] = (u32)plan[p].ro;
+      k_reply_split<<<(unsigned)((wrote + 255) / 256), 256, 0, st>>>(
+          q.src, q.offs, (u32)wrote, at, W, ln.rsend.at<u32>(B_LENS), ln.rsend.at<u32>(B_POS),
+          (unsigned long long*)sz, (unsigned long long*)(sz + W));
+      GHIP(mb, hipGetLastError());
+    }
+    GHIP(mb, mb.tm.mark(2, st));
+    GHIP(mb, hipEventRecord(ln.ev_merged, st));
+    ln.merge_pending = true;
+  } else if ((rc = merge_chunk(mb, ln, st, now))) {
+    return rc;
+  }
+  mb.rstats[RS_RETURNS] += 1;
+  mb.rstats[RS_BOUND] += bound;
+  mb.rstats[RS_WRITTEN] += wrote;
+  // the way back: its split sizes behind the owner's split, then the segments
+  GHIP(mb, hipEventRecord(mb.ev_rep, st));
+  GHIP(mb, hipStreamWaitEvent(mb.sx, mb.ev_rep, 0));
+  if ((rc = exchange_sizes(g, mb, zs, mb.sx))) return rc;
+  GHIP(mb, hipStreamSynchronize(mb.sx));
+  u64 unused = 0;
+  if ((rc = adopt_sizes(g, mb, kBackSizes, false, &unused))) return rc;
+  std::vector<Seg> back;
+  segment_plan(zs.host, W, &back);
+  Totals tb;
+  if ((rc = round_totals(mb, back, "round", "answers", &tb))) return rc;
+  if (tb.c_send != wrote)
+    return fail(mb, PHIP_ERR_INVALID, "internal: split %llu of %llu answers",
+                (unsigned long long)tb.c_send, (unsigned long long)wrote);
+  GHIP(mb, mb.rback.ensure(tb.c_recv, tb.b_recv));
+  GHIP(mb, mb.tm.mark(1, mb.sx));
+  if ((rc = move_segments(g, mb, back, ln.rsend, mb.rback, mb.sx, rccl_self,
+                          peers_of(g, mb, kBackSizes, 0, [&](const Member& m) -> const ColSet& {
+                            return m.lane[si].rsend;
+                          }))))
+    return rc;
+  GHIP(mb, mb.tm.mark(1, mb.sx));
+  // every source holds its answers before an owner's next round rewrites them
+  GHIP(mb, hipStreamSynchronize(mb.sx));
+  if (g->shared && !g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
+  // the source: into the caller's buffers, in batch order
+  const u64 R = tb.c_recv;
+  rp.replies += R;
+  if (!R || rp.cut) return PHIP_OK;
+  for (Buf* b : {&mb.gkey_in, &mb.gval_in, &mb.gkey, &mb.gval, &mb.gaoff}) GHIP(mb, b->ensure(R * 4));
+  for (Buf* b : {&mb.gslen, &mb.gsend}) GHIP(mb, b->ensure(R * 8));
+  GHIP(mb, mb.gctr.ensure(16));
+  SegBounds from{}, so{};
+  for (u32 p = 0; p < W; ++p) {
+    from.at[p] = (u32)back[p].ro;
+    so.at[p] = (u32)plan[p].so;
+  }
+  u32 *kin = (u32*)mb.gkey_in.p, *vin = (u32*)mb.gval_in.p, *keys = (u32*)mb.gkey.p,
+      *vals = (u32*)mb.gval.p, *aoff = (u32*)mb.gaoff.p;
+  const u32* lens = mb.rback.at<u32>(B_LENS);
+  const unsigned grid = (unsigned)((R + 255) / 256);
+  size_t t1 = 0, t2 = 0, t3 = 0;
+  GHIP(mb, rocprim::exclusive_scan(nullptr, t1, lens, aoff, 0u, (size_t)R, rocprim::plus<u32>(), st));
+  GHIP(mb, rocprim::radix_sort_pairs(nullptr, t2, kin, keys, vin, vals, (size_t)R, 0, 32, st));
+  GHIP(mb, rocprim::inclusive_scan(nullptr, t3, (u64*)mb.gslen.p, (u64*)mb.gsend.p, (size_t)R,
+                                   rocprim::plus<u64>(), st));
+  GHIP(mb, mb.scan_tmp.ensure(std::max(t1, std::max(t2, t3))));
+  GHIP(mb, mb.tm.mark(2, st));
+  GHIP(mb, hipMemsetAsync(mb.gctr.p, 0, 16, st));
+  k_back_keys<<<grid, 256, 0, st>>>(mb.rback.at<u32>(B_POS), (u32)R, from, so, W, (const u32*)ln.src.p,
+                                    (u32)(k * chunk), kin, vin);
+  GHIP(mb, hipGetLastError());
+  GHIP(mb, rocprim::exclusive_scan(mb.scan_tmp.p, t1, lens, aoff, 0u, (size_t)R, rocprim::plus<u32>(), st));
+  GHIP(mb, rocprim::radix_sort_pairs(mb.scan_tmp.p, t2, kin, keys, vin, vals, (size_t)R, 0, 32, st));
+  k_gather_lens<<<grid, 256, 0, st>>>(vals, lens, (u32)R, (u64*)mb.gslen.p);
+  GHIP(mb, hipGetLastError());
+  GHIP(mb, rocprim::inclusive_scan(mb.scan_tmp.p, t3, (u64*)mb.gslen.p, (u64*)mb.gsend.p, (size_t)R,
+                                   rocprim::plus<u64>(), st));
+  k_reply_gather<<<(unsigned)((R * 64 + 255) / 256), 256, 0, st>>>(
+      vals, keys, lens, aoff, (const u64*)mb.gsend.p, (u32)R, mb.rback.at<uint8_t>(B_BYTES), rp.n,
+      rp.bytes, rp.rq->max_msgs, rp.budget, rp.rq->out, rp.rq->offs, rp.rq->src,
+      (unsigned long long*)mb.gctr.p);
+  GHIP(mb, hipGetLastError());
+  GHIP(mb, mb.tm.mark(2, st));
+  u64 c[2] = {0, 0};
+  GHIP(mb, hipMemcpyAsync(c, mb.gctr.p, sizeof c, hipMemcpyDeviceToHost, st));
+  GHIP(mb, hipStreamSynchronize(st));
+  if (c[0]) {
+    rp.n += c[0];
+    rp.bytes = c[1];
+  }
+  rp.cut = c[0] < R;
+  return PHIP_OK;
+}
+
 template <class Batch>
 int member_receive(phip_group* g, Member& mb, Batch&& in, int64_t now, uint64_t* sent,
-                   uint64_t* merged, uint32_t flags) {
+                   uint64_t* merged, uint32_t flags, Replies* rp = nullptr) {
   const u32 W = g->world;
   const u32 n = in.n();
   GHIP(mb, hipSetDevice(mb.device));
@@ -658,18 +955,36 @@ int member_receive(phip_group* g, Member& mb, Batch&& in, int64_t now, uint64_t*
   // world 1, on one GPU, with the plan the multi-GPU group uses
   const bool rccl_self = (flags & PHIP_GROUP_RCCL_SELF) && !g->shared;
   mb.tm.reset();
+  if (rp) std::fill(mb.rstats, mb.rstats + RS_WORDS, 0);
   if (W == 1 && !rccl_self) {
     // One owner: every message is this member's, so there is nothing to
     // pack or exchange; the batch is merged as it came (the sender-side
     // combine is subsumed by the fast path's hot directory).
     if (sent) *sent = n;
     if (merged) *merged = n;
+    if (rp) {
+      // ... with its answers, the handle's own reply egress writing straight
+      // into the caller's buffers (an empty batch too: offs[0] = 0); the
+      // counters in the group's terms
+      phip_reply_egress q = *rp->rq;
+      GHIP(mb, mb.tm.mark(2, st));
+      if (int r = in.whole_replies(mb, now, &q)) return r;
+      GHIP(mb, mb.tm.mark(2, st));
+      rp->n = q.n;
+      rp->bytes = q.bytes;
+      rp->skipped = q.skipped;
+      rp->replies = q.replies - q.skipped;
+      mb.rstats[RS_ROUNDS] = 1;
+      mb.rstats[RS_WRITTEN] = q.n;
+      return PHIP_OK;
+    }
     if (n == 0) return PHIP_OK;
     GHIP(mb, mb.tm.mark(2, st));
     if (int r = in.whole(mb, now)) return r;
     GHIP(mb, mb.tm.mark(2, st));
     return PHIP_OK;
   }
+  if (rp) GHIP(mb, hipMemsetAsync(rp->rq->offs, 0, sizeof(u64), st));   // (no answer: offs[0] = 0)
   // The batch's producers are on the handle's stream: both pipeline streams
   // start behind it.
   GHIP(mb, hipEventRecord(mb.ev_done, st));
@@ -688,7 +1003,9 @@ int member_receive(phip_group* g, Member& mb, Batch&& in, int64_t now, uint64_t*
   for (u32 si = 0; si < 2; ++si) {
     GHIP(mb, mb.lane[si].send.ensure(cmax, set_bytes[si]));
     GHIP(mb, mb.sz[si].dev.ensure((size_t)6 * W * 8));
+    if (rp) GHIP(mb, mb.lane[si].src.ensure(cmax * 4 + 4));
     mb.lane[si].x_pending = false;
+    mb.lane[si].to_merge = false;
   }
   // 1. the combine's directory, from a sample of the whole batch
   const void* dir = nullptr;
@@ -701,9 +1018,12 @@ int member_receive(phip_group* g, Member& mb, Batch&& in, int64_t now, uint64_t*
     if (ln.x_pending) GHIP(mb, hipStreamWaitEvent(mb.sp, ln.ev_x, 0));
     u64* sz = (u64*)mb.sz[k & 1].dev.p;
     GHIP(mb, mb.tm.mark(0, mb.sp));
-    if (in.pack(mb, chunk, k, W, dir, ss, sz) != PHIP_OK)
+    if (in.pack(mb, chunk, k, W, dir, ss, sz, rp ? (u32*)ln.src.p : nullptr) != PHIP_OK)
       return fail(mb, PHIP_ERR_HIP, "route pack: %s", phip_host::last_error(mb.h));
     GHIP(mb, hipMemcpyAsync(sz + 2 * W, mb.host_k, W * 8, hipMemcpyHostToDevice, mb.sp));
+    // the *_replies forms: the chunk's zero-state messages, to every owner
+    if (rp && in.count_zero(mb, chunk, k, W, sz + 2 * W) != PHIP_OK)
+      return fail(mb, PHIP_ERR_HIP, "zero-state count: %s", phip_host::last_error(mb.h));
     GHIP(mb, mb.tm.mark(0, mb.sp));
     GHIP(mb, hipEventRecord(ln.ev_pack, mb.sp));
     return PHIP_OK;
@@ -746,18 +1066,36 @@ int member_receive(phip_group* g, Member& mb, Batch&& in, int64_t now, uint64_t*
     GHIP(mb, hipEventRecord(ln.ev_recv, mb.sx));
     ln.x_pending = true;
     ln.n = t.c_recv;
+    ln.to_merge = true;
     n_send += t.c_send;
     recv_msgs += t.c_recv;
+    // the *_replies forms: does any member's chunk hold a zero-state message,
+    // and how many requests can have reached this owner (never the chunk size)
+    bool requests = false;
+    u64 bound = 0;
+    if (rp)
+      for (u32 p = 0; p < W; ++p) {
+        const u64 z = zero_states_of(mb.sz[si].host, W, p);
+        requests |= z != 0;
+        bound += std::min<u64>(z, plan[p].rc);
+      }
     // 6. the owner's merge of chunk k-1 beside chunk k's exchange (chunk
     //    order: the merges queue on the handle's stream; a shared-device
     //    member merges before it waits for its copies)
-    const bool merge_prev = k >= 1;
+    const bool merge_prev = k >= 1 && mb.lane[(k - 1) & 1].to_merge;
     if (g->shared) {
       if (merge_prev && (rc = merge_chunk(mb, mb.lane[(k - 1) & 1], st, now))) return rc;
       // every member has copied chunk k out of every lane k & 1 before any
       // packs chunk k + 2 into it
       GHIP(mb, hipEventSynchronize(ln.ev_x));
       if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
+    }
+    // A round with requests is finished here -- the merges in chunk order,
+    // the answers' way back, the gather -- before the next round's sizes are
+    // queued; a round without runs the path it always did.
+    if (requests) {
+      if (!g->shared && merge_prev && (rc = merge_chunk(mb, mb.lane[(k - 1) & 1], st, now))) return rc;
+      if ((rc = reply_round(g, mb, si, k, chunk, plan, bound, now, rccl_self, *rp, st))) return rc;
     }
     // 5. next: chunk k+1's sizes behind chunk k's exchange (RCCL keeps one
     //    order per communicator), chunk k+2's pack into the lane just sent
@@ -772,14 +1110,17 @@ int member_receive(phip_group* g, Member& mb, Batch&& in, int64_t now, uint64_t*
         packed = k + 3;
       }
     }
-    if (!g->shared && merge_prev && (rc = merge_chunk(mb, mb.lane[(k - 1) & 1], st, now)))
+    // (a round with requests has merged chunk k-1 already)
+    if (!g->shared && k >= 1 && mb.lane[(k - 1) & 1].to_merge &&
+        (rc = merge_chunk(mb, mb.lane[(k - 1) & 1], st, now)))
       return rc;
   }
   if (sent) *sent = n_send;
   if (merged) *merged = recv_msgs;
+  if (rp) mb.rstats[RS_ROUNDS] = K;
   // the last chunk's merge; the handle's stream ends behind every exchange
   // (the next call's packs reuse the send sets)
-  if ((rc = merge_chunk(mb, mb.lane[(K - 1) & 1], st, now))) return rc;
+  if (mb.lane[(K - 1) & 1].to_merge && (rc = merge_chunk(mb, mb.lane[(K - 1) & 1], st, now))) return rc;
   GHIP(mb, hipEventRecord(mb.ev_done, mb.sx));
   GHIP(mb, hipStreamWaitEvent(st, mb.ev_done, 0));
   return PHIP_OK;
@@ -1010,6 +1351,8 @@ void destroy(phip_group* g) {
       ln.send.release();
       ln.recv.release();
       ln.offs.release();
+      for (Buf* b : {&ln.src, &ln.roffs, &ln.rsrc}) b->release();
+      ln.rsend.release();
       for (hipEvent_t ev : {ln.ev_pack, ln.ev_sz, ln.ev_x, ln.ev_recv, ln.ev_merged})
         if (ev) (void)hipEventDestroy(ev);
     }
@@ -1018,7 +1361,12 @@ void destroy(phip_group* g) {
       s.dev.release();
       if (s.host) (void)hipHostFree(s.host);
     }
-    for (Buf* b : {&mb.osrc, &mb.ooffs, &mb.scan_tmp, &mb.ae, &mb.bounds}) b->release();
+    for (Buf* b : {&mb.osrc, &mb.ooffs, &mb.scan_tmp, &mb.ae, &mb.bounds, &mb.gkey_in, &mb.gval_in,
+                   &mb.gkey, &mb.gval, &mb.gaoff, &mb.gslen, &mb.gsend, &mb.gctr, &mb.ring_out,
+                   &mb.ring_offs, &mb.ring_src})
+      b->release();
+    mb.rback.release();
+    if (mb.ev_rep) (void)hipEventDestroy(mb.ev_rep);
     mb.tm.release();
     if (mb.host_k) (void)hipHostFree(mb.host_k);
     if (mb.ev_done) (void)hipEventDestroy(mb.ev_done);
@@ -1037,6 +1385,7 @@ int alloc_member_state(phip_group* g) {
         hipStreamCreateWithFlags(&mb.sp, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&mb.sx, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&mb.ev_done, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&mb.ev_rep, hipEventDisableTiming) != hipSuccess ||
         hipHostMalloc(&mb.host_k, (size_t)g->world * sizeof(u64), 0) != hipSuccess)
       return PHIP_ERR_HIP;
     for (Sizes& s : mb.sz)
@@ -1100,7 +1449,8 @@ bool wire_flags_ok(uint32_t flags) {
 // multi-rank group never wait for a rank that left early).
 template <class Pre>
 int receive_wire(phip_group* g, const phip_wire* batches, int64_t now, uint64_t* sent,
-                 uint64_t* merged, uint32_t* stopped, uint32_t flags, Pre pre) {
+                 uint64_t* merged, uint32_t* stopped, uint32_t flags, Pre pre,
+                 std::vector<Replies>* reps = nullptr) {
   const size_t nl = g->m.size();
   std::vector<uint32_t> stop(nl, 0), bad(nl, ~0u);
   if (int rc = for_members(g, [&](size_t i) {
@@ -1122,7 +1472,7 @@ int receive_wire(phip_group* g, const phip_wire* batches, int64_t now, uint64_t*
   }
   const int rc = for_members(g, [&](size_t i) {
     return member_receive(g, g->m[i], WireBatch{cut[i], {}}, now, sent ? sent + i : nullptr,
-                          merged ? merged + i : nullptr, flags);
+                          merged ? merged + i : nullptr, flags, reps ? &(*reps)[i] : nullptr);
   });
   if (ib < nl) {
     const std::string xerr = rc != PHIP_OK ? "; and the empty exchange failed: " + g->err : "";
@@ -1137,6 +1487,135 @@ int receive_wire(phip_group* g, const phip_wire* batches, int64_t now, uint64_t*
       return PHIP_ERR_SHORT_BUFFER;
     }
   return PHIP_OK;
+}
+
+// ---- the *_replies forms' entry ----
+void replies_zero(phip_reply_egress* rq, size_t nl) {
+  for (size_t i = 0; i < nl; ++i) {
+    rq[i].n = rq[i].replies = rq[i].skipped = 0;
+    rq[i].bytes = 0;
+  }
+}
+
+// phip_reply_egress' bounds for every local member, before anything of any
+// member is applied; dev: the buffers are device memory (phip_export_sweep's
+// rules).
+bool replies_ok(const phip_reply_egress* rq, size_t nl, bool dev) {
+  for (size_t i = 0; i < nl; ++i) {
+    const phip_reply_egress& q = rq[i];
+    if (!q.out || !q.offs || !q.max_msgs || q.out_cap < PHIP_BUCKET_PACKET_SIZE) return false;
+    if (dev && ((reinterpret_cast<uintptr_t>(q.out) & 7) || (q.out_cap & 7) ||
+                q.out_cap < PHIP_BUCKET_PACKET_SIZE + 8))
+      return false;
+  }
+  return true;
+}
+
+std::vector<Replies> replies_of(phip_reply_egress* rq, size_t nl) {
+  std::vector<Replies> v(nl);
+  for (size_t i = 0; i < nl; ++i) {
+    v[i].rq = &rq[i];
+    v[i].budget = rq[i].out_cap - 8;
+  }
+  return v;
+}
+
+// The call's out fields: what the rounds wrote (a stopped member's answers
+// before its stop included), zeros after any other error.
+int replies_done(int rc, const std::vector<Replies>& reps, phip_reply_egress* rq) {
+  replies_zero(rq, reps.size());
+  if (rc != PHIP_OK && rc != PHIP_ERR_SHORT_BUFFER) return rc;
+  for (size_t i = 0; i < reps.size(); ++i) {
+    rq[i].n = (u32)reps[i].n;
+    rq[i].replies = (u32)reps[i].replies;
+    rq[i].skipped = (u32)reps[i].skipped;
+    rq[i].bytes = reps[i].bytes;
+  }
+  return rc;
+}
+
+// phip_group_ring_receive, and with rq (host buffers) its replies form: the
+// members write into device copies the group keeps, and what was written is
+// copied back.
+int ring_receive(phip_group* g, phip_ring* const* rings, const uint32_t* slots, int64_t now,
+                 uint64_t* sent, uint64_t* merged, uint32_t* stopped, uint32_t flags,
+                 phip_reply_egress* rq) {
+  const size_t nl = g->m.size();
+  std::vector<phip_wire> batches(nl, phip_wire{});
+  std::vector<void*> copied(nl, nullptr);
+  // (refused before anything is queued: every slot stays submitted)
+  for (size_t i = 0; i < nl; ++i)
+    if (rings[i])
+      if (int rc = phip_host::ring_slot(rings[i], slots[i], g->m[i].h, &batches[i], &copied[i]))
+        return rc;
+  // the device form of the caller's caps: a byte budget of out_cap rounded
+  // down to a multiple of 8
+  std::vector<phip_reply_egress> dq;
+  std::vector<Replies> reps;
+  int rc0 = PHIP_OK;
+  if (rq) {
+    dq.assign(rq, rq + nl);
+    for (size_t i = 0; i < nl && rc0 == PHIP_OK; ++i) {
+      Member& mb = g->m[i];
+      dq[i].out_cap = (rq[i].out_cap & ~7ull) + 8;
+      if (hipSetDevice(mb.device) != hipSuccess || mb.ring_out.ensure(dq[i].out_cap) != hipSuccess ||
+          mb.ring_offs.ensure(((size_t)rq[i].max_msgs + 1) * 8) != hipSuccess ||
+          mb.ring_src.ensure((size_t)rq[i].max_msgs * 4) != hipSuccess) {
+        g->err = "member " + std::to_string(i) + ": no device memory for the reply buffers";
+        rc0 = PHIP_ERR_HIP;
+      }
+      dq[i].out = (uint8_t*)mb.ring_out.p;
+      dq[i].offs = (uint64_t*)mb.ring_offs.p;
+      dq[i].src = (uint32_t*)mb.ring_src.p;
+    }
+    if (rc0 != PHIP_OK) return rc0;   // (nothing queued: every slot stays submitted)
+    reps = replies_of(dq.data(), nl);
+  }
+  int rc = receive_wire(g, batches.data(), now, sent, merged, stopped, flags,
+                        [&](Member& mb, hipStream_t st, size_t i) {
+                          // the member's streams all start behind st
+                          if (copied[i])
+                            GHIP(mb, hipStreamWaitEvent(st, (hipEvent_t)copied[i], 0));
+                          return (int)PHIP_OK;
+                        },
+                        rq ? &reps : nullptr);
+  // A slot is free once its member's streams have read it: the pack stream,
+  // the exchange behind it, and the handle's stream (the pre-pass; a world of
+  // one merges from the slot).  After an error they drain first.
+  int rc2 = PHIP_OK;
+  for (size_t i = 0; i < nl; ++i) {
+    Member& mb = g->m[i];
+    if (!rings[i] && !rq) continue;
+    if (hipSetDevice(mb.device) != hipSuccess || hipStreamSynchronize(mb.sp) != hipSuccess ||
+        hipStreamSynchronize(mb.sx) != hipSuccess ||
+        hipStreamSynchronize((hipStream_t)phip_host::handle_stream(mb.h)) != hipSuccess)
+      rc2 = PHIP_ERR_HIP;
+    if (rings[i]) phip_host::ring_release(rings[i], slots[i]);
+  }
+  if (rc == PHIP_OK && rc2 != PHIP_OK) g->err = "draining the members' streams failed";
+  if (rc == PHIP_OK) rc = rc2;
+  if (!rq) return rc;
+  replies_done(rc, reps, dq.data());
+  for (size_t i = 0; i < nl; ++i) {
+    rq[i].n = dq[i].n;
+    rq[i].replies = dq[i].replies;
+    rq[i].skipped = dq[i].skipped;
+    rq[i].bytes = dq[i].bytes;
+    if (rc != PHIP_OK && rc != PHIP_ERR_SHORT_BUFFER) continue;
+    const Member& mb = g->m[i];
+    bool ok = hipSetDevice(mb.device) == hipSuccess &&
+              hipMemcpy(rq[i].offs, dq[i].offs, ((size_t)dq[i].n + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok && dq[i].bytes)
+      ok = hipMemcpy(rq[i].out, dq[i].out, dq[i].bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok && dq[i].n && rq[i].src)
+      ok = hipMemcpy(rq[i].src, dq[i].src, (size_t)dq[i].n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) {
+      g->err = "member " + std::to_string(i) + ": copying the answers back failed";
+      replies_zero(rq, nl);
+      return PHIP_ERR_HIP;
+    }
+  }
+  return rc;
 }
 
 }  // namespace
@@ -1261,36 +1740,56 @@ int phip_group_ring_receive(phip_group* g, phip_ring* const* rings, const uint32
                             int64_t now, uint64_t* sent, uint64_t* merged, uint32_t* stopped,
                             uint32_t flags) {
   if (!g || !rings || !slots || !wire_flags_ok(flags)) return PHIP_ERR_INVALID;
+  return ring_receive(g, rings, slots, now, sent, merged, stopped, flags, nullptr);
+}
+
+// The replies forms (patrolhip.h "Group reply egress"): the call each is named
+// after, with one Replies per local member travelling through member_receive.
+int phip_group_receive_datagrams_replies(phip_group* g, const phip_wire* batches, int64_t now,
+                                         uint64_t* sent, uint64_t* merged, uint32_t* stopped,
+                                         phip_reply_egress* rq, uint32_t flags) {
+  if (!g || !batches || !rq || !wire_flags_ok(flags)) return PHIP_ERR_INVALID;
   const size_t nl = g->m.size();
-  std::vector<phip_wire> batches(nl, phip_wire{});
-  std::vector<void*> copied(nl, nullptr);
-  // (refused before anything is queued: every slot stays submitted)
+  replies_zero(rq, nl);
   for (size_t i = 0; i < nl; ++i)
-    if (rings[i])
-      if (int rc = phip_host::ring_slot(rings[i], slots[i], g->m[i].h, &batches[i], &copied[i]))
-        return rc;
-  const int rc = receive_wire(g, batches.data(), now, sent, merged, stopped, flags,
-                              [&](Member& mb, hipStream_t st, size_t i) {
-                                // the member's streams all start behind st
-                                if (copied[i])
-                                  GHIP(mb, hipStreamWaitEvent(st, (hipEvent_t)copied[i], 0));
-                                return (int)PHIP_OK;
-                              });
-  // A slot is free once its member's streams have read it: the pack stream,
-  // the exchange behind it, and the handle's stream (the pre-pass; a world of
-  // one merges from the slot).  After an error they drain first.
-  int rc2 = PHIP_OK;
-  for (size_t i = 0; i < nl; ++i) {
-    if (!rings[i]) continue;
-    Member& mb = g->m[i];
-    if (hipSetDevice(mb.device) != hipSuccess || hipStreamSynchronize(mb.sp) != hipSuccess ||
-        hipStreamSynchronize(mb.sx) != hipSuccess ||
-        hipStreamSynchronize((hipStream_t)phip_host::handle_stream(mb.h)) != hipSuccess)
-      rc2 = PHIP_ERR_HIP;
-    phip_host::ring_release(rings[i], slots[i]);
-  }
-  if (rc == PHIP_OK && rc2 != PHIP_OK) g->err = "draining the members' streams failed";
-  return rc != PHIP_OK ? rc : rc2;
+    if (batches[i].n && (!batches[i].bytes || !batches[i].offs)) return PHIP_ERR_INVALID;
+  if (!replies_ok(rq, nl, true)) return PHIP_ERR_INVALID;
+  std::vector<Replies> reps = replies_of(rq, nl);
+  const int rc = receive_wire(g, batches, now, sent, merged, stopped, flags,
+                              [](Member&, hipStream_t, size_t) { return (int)PHIP_OK; }, &reps);
+  return replies_done(rc, reps, rq);
+}
+
+int phip_group_receive_replies(phip_group* g, const phip_msgs* batches, int64_t now, uint64_t* sent,
+                               uint64_t* merged, phip_reply_egress* rq, uint32_t flags) {
+  if (!g || !batches || !rq || !wire_flags_ok(flags)) return PHIP_ERR_INVALID;
+  const size_t nl = g->m.size();
+  replies_zero(rq, nl);
+  if (!replies_ok(rq, nl, true)) return PHIP_ERR_INVALID;
+  std::vector<Replies> reps = replies_of(rq, nl);
+  const int rc = checked_call(
+      g, batches, "message", [](Member&, hipStream_t, size_t) { return (int)PHIP_OK; },
+      [&](size_t i, const phip_msgs& b) {
+        return member_receive(g, g->m[i], MsgBatch{b, {}}, now, sent ? sent + i : nullptr,
+                              merged ? merged + i : nullptr, flags, &reps[i]);
+      });
+  return replies_done(rc, reps, rq);
+}
+
+int phip_group_ring_receive_replies(phip_group* g, phip_ring* const* rings, const uint32_t* slots,
+                                    int64_t now, uint64_t* sent, uint64_t* merged,
+                                    uint32_t* stopped, phip_reply_egress* rq, uint32_t flags) {
+  if (!g || !rings || !slots || !rq || !wire_flags_ok(flags)) return PHIP_ERR_INVALID;
+  replies_zero(rq, g->m.size());
+  if (!replies_ok(rq, g->m.size(), false)) return PHIP_ERR_INVALID;
+  return ring_receive(g, rings, slots, now, sent, merged, stopped, flags, rq);
+}
+
+int phip_group_reply_stats(phip_group* g, uint32_t i, uint64_t* out, int max) {
+  if (!g || !out || i >= g->m.size()) return 0;
+  const int n = std::min<int>(std::max(max, 0), RS_WORDS);
+  for (int k = 0; k < n; ++k) out[k] = g->m[i].rstats[k];
+  return n;
 }
 
 int phip_group_apply_mixed(phip_group* g, const phip_ops* batches, const phip_results* results,

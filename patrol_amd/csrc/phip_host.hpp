@@ -24,7 +24,7 @@ int handle_device(const phip_handle* h);
 int route_dir(phip_handle* h, void* stream, const phip_msgs* m, uint32_t world, const void** dir);
 int route_pack(phip_handle* h, void* stream, const phip_msgs* m, uint32_t world, const void* dir,
                uint8_t* names, uint32_t* lens, uint64_t* a, uint64_t* t, int64_t* e,
-               uint64_t* counts, uint64_t* nbytes);
+               uint64_t* counts, uint64_t* nbytes, uint32_t* src = nullptr);
 // The same for an ordered op stream (phip_route_pack_ops' pack of one chunk,
 // no combine), and the results' way back: entry j of the returned columns
 // (send order) into out's columns at src[j]; a NULL column of out is skipped.
@@ -56,7 +56,16 @@ int wire_scan(phip_handle* h, void* stream, const phip_wire* w, uint32_t* stop, 
 int route_dir_wire(phip_handle* h, void* stream, const phip_wire* w, uint32_t world, const void** dir);
 int route_pack_wire(phip_handle* h, void* stream, const phip_wire* w, uint32_t world, const void* dir,
                     uint8_t* names, uint32_t* lens, uint64_t* a, uint64_t* t, int64_t* e,
-                    uint64_t* counts, uint64_t* nbytes);
+                    uint64_t* counts, uint64_t* nbytes, uint32_t* src = nullptr);
+// What the replies forms of the group add at the source (phip_group_*_replies).
+// route_pack / route_pack_wire with src != nullptr also write src[j], the
+// chunk index of the message packed at send position j (~0 for a combined
+// message, which stands for many and is never a request); without it they
+// launch the kernels they always did.  count_zero / count_zero_wire: one pass
+// over the chunk's replica fields on `stream` that adds its zero-state count
+// (Bucket.IsZero's ==) << 32 to out[0 .. nout) (device), no synchronisation.
+int count_zero(phip_handle* h, void* stream, const phip_msgs* m, uint32_t nout, uint64_t* out);
+int count_zero_wire(phip_handle* h, void* stream, const phip_wire* w, uint32_t nout, uint64_t* out);
 // A ring's slot as a group member's batch (phip_group_ring_receive): the
 // slot's device copy as *w and its `copied` event (a hipEvent_t), when the
 // ring was opened on h (else PHIP_ERR_INVALID) and the slot is the ring's next

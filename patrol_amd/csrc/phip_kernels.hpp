@@ -5012,6 +5012,21 @@ __device__ inline void route_names_staged(u8* __restrict__ out, u32* stg, u32 wo
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// A name source that also keeps where every packed message stood in the chunk
+// (k_route_ops_scatter's send_src, for phip_group_*_replies: an answer finds
+// its request's batch index through it).  A compile-time variant of the
+// source, so k_route_scatter<NamesOffs> and <Datagrams> stay the kernels they
+// were; a combined message stands for many and keeps ~0 (it is never a
+// request: a zero state does not combine).
+template <class Base>
+struct WithSrcIdx : Base {
+  u32* out_src;
+};
+template <class S>
+struct route_keeps_src : std::false_type {};
+template <class B>
+struct route_keeps_src<WithSrcIdx<B>> : std::true_type {};
+
 template <class Src>
 __global__ __launch_bounds__(kRouteBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_route_scatter(
     Src src, const uint64_t* __restrict__ a, const uint64_t* __restrict__ t,
@@ -5028,7 +5043,8 @@ __global__ __launch_bounds__(kRouteBlock) __attribute__((amdgpu_waves_per_eu(6, 
   __shared__ u64 hmax[3][kRouteHotMax];
   __shared__ u32 hit[kRouteHotMax];
   __shared__ u32 nstage[kRouteWaves][kStageWords];
-  constexpr bool kWire = std::is_same<Src, Datagrams>::value;   // as k_route_count
+  constexpr bool kWire = std::is_base_of<Datagrams, Src>::value;   // as k_route_count
+  constexpr bool kKeepSrc = route_keeps_src<Src>::value;
   const u32 nh = route_hot_n(hot, ctr);
   const u32 wave = threadIdx.x / 64, lane = threadIdx.x & 63;
   const u32 tile = blockIdx.x;
@@ -5130,6 +5146,7 @@ __global__ __launch_bounds__(kRouteBlock) __attribute__((amdgpu_waves_per_eu(6, 
         out_a[d] = va[u];
         out_t[d] = vt[u];
         out_e[d] = ve[u];
+        if constexpr (kKeepSrc) src.out_src[d] = (u32)(s0 + (u64)(wave * kRU + u) * 64 + lane);
       }
       // owner runs of this chunk [bo, be) (lane o), in the send buffer
       const u32 bo = pb + bo_l[u], be = pb + be_l[u];
@@ -5172,6 +5189,7 @@ __global__ __launch_bounds__(kRouteBlock) __attribute__((amdgpu_waves_per_eu(6, 
     out_a[d] = ma ? dec_f64(ma) : kNaN;
     out_t[d] = mt ? dec_f64(mt) : kNaN;
     out_e[d] = (i64)(hmax[2][j] ^ kSign);
+    if constexpr (kKeepSrc) src.out_src[d] = ~0u;
     for (u32 k = 0; k < ln; ++k) {   // name byte k is canonical byte k + 2
       const u32 cb = k + 2;
       out_names[db + k] = (u8)((cb < 8 ? L.w0[j] >> (8 * cb) : L.w1[j] >> (8 * (cb - 8))) & 0xFFu);
@@ -5192,6 +5210,51 @@ __global__ void k_route_totals(const u32* __restrict__ cnt, const u32* __restric
   const u32 b1 = o + 1 < world ? bbase[(u64)(o + 1) * nblk] : bbase[last] + bytes[last];
   counts[o] = c1 - c0;
   nbytes[o] = b1 - b0;
+}
+
+// The zero-state messages of a chunk (phip_group_*_replies): one streaming
+// pass over the replica fields alone, Bucket.IsZero's == (bucket.go:165-170:
+// a field of -0.0 is zero), no name read.  Only such a message can be
+// answered (repo.go:86-90), so a round whose count is zero on every member
+// needs no return exchange.  The count goes into the high half of out[0 ..
+// nout): the chunk-total words of the split sizes, whose low half carries the
+// member's round count.
+struct SoaFields {
+  const uint64_t* a;
+  const uint64_t* t;
+  const int64_t* e;
+  __device__ inline void get(u32 i, u64& ra, u64& rt, i64& re) const {
+    ra = ld<true>(a + i); rt = ld<true>(t + i); re = ld<true>(e + i);
+  }
+};
+struct WireFields {
+  Datagrams d;
+  __device__ inline void get(u32 i, u64& ra, u64& rt, i64& re) const { wire_fields<true>(d, i, ra, rt, re); }
+};
+template <class Fields>
+__global__ __launch_bounds__(kBlock) void k_zero_count(Fields f, u32 n, u32 nout,
+                                                       unsigned long long* __restrict__ out) {
+  __shared__ u32 total;
+  if (threadIdx.x == 0) total = 0;
+  __syncthreads();
+  u32 mine = 0;
+  const u64 stride = (u64)gridDim.x * kBlock;
+  for (u64 b0 = (u64)blockIdx.x * kBlock; b0 < n; b0 += stride) {   // b0: uniform over the workgroup
+    const u64 i = b0 + threadIdx.x;
+    bool z = false;
+    if (i < n) {
+      u64 ra, rt;
+      i64 re;
+      f.get((u32)i, ra, rt, re);
+      z = state_is_zero(ra, rt, re);
+    }
+    mine += (u32)__popcll(__ballot(z));
+  }
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&total, mine);
+  __syncthreads();
+  const u32 tot = total;
+  if (tot)
+    for (u32 p = threadIdx.x; p < nout; p += kBlock) atomicAdd(&out[p], (unsigned long long)tot << 32);
 }
 
 // ------------------------------------------------- owner routing of ops ----

@@ -1120,8 +1120,57 @@ class GPUGroup:
         if rc != 0:
             raise PatrolHipError(rc, self.L.phip_group_last_error(self.g).decode(errors="replace"))
 
+    def _group_rq(self, replies, host: bool = False):
+        """One phip_reply_egress per local member from replies=dict(max_msgs=,
+        out_cap=) -> (the ctypes array, the buffers per member): CUDA tensors on
+        the member's GPU (out_cap: a multiple of 8, 8 bytes past the byte
+        budget), or numpy arrays for the ring form."""
+        k = len(self.repos)
+        max_msgs = int(replies["max_msgs"])
+        out_cap = int(replies.get("out_cap") or _lib.PACKET_SIZE * max(max_msgs, 1) + 8)
+        rq = (_lib.phip_reply_egress * k)()
+        bufs = []
+        for i in range(k):
+            if host:
+                out = np.zeros(max(out_cap, 8), np.uint8)
+                offs = np.zeros(max_msgs + 1, np.uint64)
+                src = np.zeros(max(max_msgs, 1), np.uint32)
+                ptrs = (out.ctypes.data, offs.ctypes.data, src.ctypes.data)
+            else:
+                import torch
+                dev = torch.device("cuda", self.repos[i].device)
+                out = torch.zeros(max(out_cap, 8), dtype=torch.uint8, device=dev)
+                offs = torch.zeros(max_msgs + 1, dtype=torch.int64, device=dev)
+                src = torch.zeros(max(max_msgs, 1), dtype=torch.int32, device=dev)
+                torch.cuda.synchronize(dev)
+                ptrs = (_ptr(out), _ptr(offs), _ptr(src))
+            rq[i] = _lib.phip_reply_egress(ptrs[0], out_cap, ptrs[1], ptrs[2], max_msgs, 0, 0, 0, 0)
+            bufs.append((out, offs, src))
+        return rq, bufs
+
+    @staticmethod
+    def _group_replies(rq, bufs):
+        """-> one dict(data, offs, src, n, replies, skipped, bytes) per member
+        (the group form's counters: patrolhip.h "Group reply egress"); host
+        buffers are cut to what was written, device tensors returned whole."""
+        out = []
+        for q, (data, offs, src) in zip(rq, bufs):
+            n = int(q.n)
+            if not _is_torch(data):
+                data, offs, src = data[:int(q.bytes)], offs[:n + 1], src[:n]
+            out.append(dict(data=data, offs=offs, src=src, n=n, replies=int(q.replies),
+                            skipped=int(q.skipped), bytes=int(q.bytes)))
+        return out
+
+    def reply_stats(self, i: int = 0) -> dict:
+        """phip_group_reply_stats of member i's last replies call."""
+        v = (C.c_uint64 * 4)()
+        k = self.L.phip_group_reply_stats(self.g, i, v, 4)
+        names = ("rounds", "return_rounds", "bound", "written")
+        return {nm: int(v[j]) for j, nm in enumerate(names[:k])}
+
     def receive(self, batches, now: int, combine: bool = True, rccl_self: bool = False,
-                small_chunks: bool = False):
+                small_chunks: bool = False, replies=None):
         """batches: one (names uint8, name_offs int32[n+1], added, taken, elapsed)
         tuple of CUDA tensors per local member -> (sent, merged) lists.
         rccl_self (PHIP_GROUP_RCCL_SELF, testing): every segment, the
@@ -1135,7 +1184,10 @@ class GPUGroup:
         PatrolHipError (code -1, PHIP_ERR_INVALID; the message names the
         member and the message index) and none of the batches is applied;
         the members still run the exchange with empty batches, so peer
-        ranks are not left waiting."""
+        ranks are not left waiting.
+
+        replies=dict(max_msgs=, out_cap=): phip_group_receive_replies; the
+        result then ends with one reply dict per member (device tensors)."""
         k = len(batches)
         msgs = (phip_msgs * k)()
         for i, (names, offs, a, t, e) in enumerate(batches):
@@ -1145,6 +1197,11 @@ class GPUGroup:
         flags = DEVICE_PTRS | (_lib.ROUTE_COMBINE if combine else 0) | \
             (_lib.GROUP_RCCL_SELF if rccl_self else 0) | \
             (_lib.GROUP_SMALL_CHUNKS if small_chunks else 0)
+        if replies is not None:
+            rq, bufs = self._group_rq(replies)
+            self._check(self.L.phip_group_receive_replies(self.g, msgs, int(now), sent, merged, rq,
+                                                          flags))
+            return [int(x) for x in sent], [int(x) for x in merged], self._group_replies(rq, bufs)
         self._check(self.L.phip_group_receive(self.g, msgs, int(now), sent, merged, flags))
         return [int(x) for x in sent], [int(x) for x in merged]
 
@@ -1162,7 +1219,7 @@ class GPUGroup:
         return [int(x) for x in sent], [int(x) for x in merged], [int(x) for x in stopped]
 
     def receive_datagrams(self, batches, now: int, combine: bool = True, rccl_self: bool = False,
-                          small_chunks: bool = False, checked: bool = True):
+                          small_chunks: bool = False, checked: bool = True, replies=None):
         """Owner-routed Receive straight from the wire
         (phip_group_receive_datagrams): batches holds, per local member, the
         raw datagrams that arrived there, as a (bytes uint8, offs int64[n+1])
@@ -1176,7 +1233,11 @@ class GPUGroup:
         checked: the offsets are verified against the bytes tensor's length
         before anything is read through them; a violation raises
         PatrolHipError (code -1) and no batch is applied.  combine,
-        rccl_self, small_chunks: as receive()."""
+        rccl_self, small_chunks: as receive().
+
+        replies=dict(max_msgs=, out_cap=): phip_group_receive_datagrams_replies;
+        the result then ends with one reply dict per member (device tensors:
+        the answers to the incast requests of that member's batch)."""
         import torch
         k = len(batches)
         ws = (phip_wire * k)()
@@ -1196,24 +1257,38 @@ class GPUGroup:
             ws[i] = phip_wire(offs.numel() - 1, 0, _ptr(data), _ptr(offs),
                               int(data.numel()) if checked else 0)
         sent, merged, stopped = (C.c_uint64 * k)(), (C.c_uint64 * k)(), (C.c_uint32 * k)()
-        rc = self.L.phip_group_receive_datagrams(self.g, ws, int(now), sent, merged, stopped,
-                                                 self._wire_flags(combine, rccl_self, small_chunks))
+        flags = self._wire_flags(combine, rccl_self, small_chunks)
+        if replies is not None:
+            rq, bufs = self._group_rq(replies)
+            rc = self.L.phip_group_receive_datagrams_replies(self.g, ws, int(now), sent, merged,
+                                                             stopped, rq, flags)
+            return self._wire_call(rc, sent, merged, stopped) + (self._group_replies(rq, bufs),)
+        rc = self.L.phip_group_receive_datagrams(self.g, ws, int(now), sent, merged, stopped, flags)
         return self._wire_call(rc, sent, merged, stopped)
 
     def ring_receive(self, rings, slots, now: int, combine: bool = True, rccl_self: bool = False,
-                     small_chunks: bool = False):
+                     small_chunks: bool = False, replies=None):
         """The socket edge (phip_group_ring_receive): rings[i] is a Ring over
         repos[i] (None: an empty batch for member i), slots[i] its next
         submitted slot.  -> (sent, merged, stopped) as receive_datagrams; the
         slots are free again when the call returns.  An out-of-order slot
         raises PatrolHipError (code -9, PHIP_ERR_BUSY) and a ring of another
-        handle code -1; both leave every slot submitted."""
+        handle code -1; both leave every slot submitted.
+
+        replies=dict(max_msgs=, out_cap=): phip_group_ring_receive_replies; the
+        result then ends with one reply dict per member (numpy arrays, cut to
+        what was written; reply_peers(peers_i, src) gives their peers)."""
         k = len(rings)
         rs = (C.c_void_p * k)(*[r.r.value if r is not None else None for r in rings])
         sl = (C.c_uint32 * k)(*[int(s) for s in slots])
         sent, merged, stopped = (C.c_uint64 * k)(), (C.c_uint64 * k)(), (C.c_uint32 * k)()
-        rc = self.L.phip_group_ring_receive(self.g, rs, sl, int(now), sent, merged, stopped,
-                                            self._wire_flags(combine, rccl_self, small_chunks))
+        flags = self._wire_flags(combine, rccl_self, small_chunks)
+        if replies is not None:
+            rq, bufs = self._group_rq(replies, host=True)
+            rc = self.L.phip_group_ring_receive_replies(self.g, rs, sl, int(now), sent, merged,
+                                                        stopped, rq, flags)
+            return self._wire_call(rc, sent, merged, stopped) + (self._group_replies(rq, bufs),)
+        rc = self.L.phip_group_ring_receive(self.g, rs, sl, int(now), sent, merged, stopped, flags)
         return self._wire_call(rc, sent, merged, stopped)
 
     _OPS_KEYS = ("kind", "names", "name_offs", "now", "freq", "per", "count", "added", "taken",
