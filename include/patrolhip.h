@@ -243,7 +243,33 @@ typedef struct phip_ops {
   const int64_t* elapsed;    /* (RECEIVE/UPSERT)                                */
 } phip_ops;
 
-/* Per-op results (any pointer may be NULL). */
+/* Per-op results (any pointer may be NULL).
+ *
+ * Result columns.  Each pointer is a column of n entries, n the batch's size
+ * (phip_msgs.n, phip_ops.n, the datagram count), in host memory or, with
+ * PHIP_DEVICE_PTRS, device memory; a column needs its entry type's alignment
+ * and no more.  After a call that returns PHIP_OK, and after one that stopped
+ * (below), a column that was passed is written in all n entries and nowhere
+ * else, whatever other columns were passed with it and whatever path the
+ * batch took.  An entry the column does not apply to reads zero:
+ *   - remaining and have of a RECEIVE or UPSERT op, and so every entry of
+ *     them after phip_receive_soa, phip_receive_datagrams, phip_ring_receive,
+ *     their _replies forms and phip_upsert_soa;
+ *   - reply of a merged replica (PHIP_ST_MERGED of a RECEIVE op);
+ *   - remaining, have and reply of every message at or after a Receive
+ *     batch's stop, a short datagram (PHIP_ERR_SHORT_BUFFER) or a checked
+ *     batch's malformed entry (PHIP_ERR_INVALID from phip_receive_soa with
+ *     names_len, phip_msgs): status reads PHIP_ST_SHORT there and
+ *     PHIP_ST_NOT_PROCESSED after it, and the columns of the messages before
+ *     it are those of a batch that ended there.
+ * Nothing the caller passes in (names, offsets, operands, datagrams) is ever
+ * written.  A batch queued with PHIP_RECV_ASYNC has its columns written by
+ * the call that finishes it.
+ * A call refused with any other error (PHIP_ERR_INVALID for bad arguments, a
+ * checked phip_upsert_soa / phip_apply_mixed batch or egress caps too small;
+ * PHIP_ERR_FULL for a table that may not grow; ...) leaves the columns
+ * undefined: untouched, partly written, or, from host memory, not copied
+ * back. */
 typedef struct phip_results {
   uint8_t* status;           /* PHIP_ST_* (| PHIP_ST_CREATED)                   */
   uint64_t* remaining;       /* TAKE: uint64(remaining) as Go returns it        */

@@ -1921,6 +1921,18 @@ int outputs(phip_handle* h, const phip_results* res, u32 n, bool dev, OutView* o
   return PHIP_OK;
 }
 
+// outputs() of a Receive batch.  It holds no TAKE op, and no receive path
+// stores a remaining or have: a column of those the caller passed all the
+// same reads zero in every entry (patrolhip.h "Result columns"), here as on
+// the one-launch small path, instead of the caller's bytes (device form) or an
+// earlier call's staged results (host form).  No cost unless they are passed.
+int receive_outputs(phip_handle* h, const phip_results* res, u32 n, bool dev, OutView* ow) {
+  if (int rc = outputs(h, res, n, dev, ow)) return rc;
+  if (ow->remaining) HIPCHK(h, hipMemsetAsync(ow->remaining, 0, (size_t)n * 8, h->stream));
+  if (ow->have) HIPCHK(h, hipMemsetAsync(ow->have, 0, (size_t)n * 8, h->stream));
+  return PHIP_OK;
+}
+
 int copy_outputs(phip_handle* h, const phip_results* res, u32 n, bool dev, const OutView& ow) {
   if (!res || dev) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2336,8 +2348,9 @@ int small_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, bo
   phip_results r{};
   if (res) r = *res;
   OutView ow{};
-  // (the egress and the marks read who created what)
-  ow.status = (r.status || eg || track) ? dout + o_st : nullptr;
+  // (the egress and the marks read who created what; the reply column's
+  // filter below reads which RECEIVE ops were incast requests)
+  ow.status = (r.status || r.reply || eg || track) ? dout + o_st : nullptr;
   ow.remaining = r.remaining ? (uint64_t*)(dout + o_rem) : nullptr;
   ow.have = r.have ? (uint64_t*)(dout + o_have) : nullptr;
   ow.reply = r.reply ? (phip_state*)(dout + o_reply) : nullptr;
@@ -2400,13 +2413,9 @@ int small_mixed(phip_handle* h, const phip_ops* ops, const phip_results* res, bo
     // reply states are defined for Takes, Upserts and incasts (step_sop);
     // the other entries read as zeros, as on the large path (outputs())
     const phip_state* src_r = (const phip_state*)(pout + o_reply);
-    std::vector<u8> st;
-    const u8* stp = r.status;
-    if (!stp) {
-      st.assign(n, 0);
-      HIPCHK(h, hipMemcpy(st.data(), dout + o_st, n, hipMemcpyDeviceToHost));
-      stp = st.data();
-    }
+    // (the statuses came back in the same copy: ow.status is set whenever
+    // the reply column is asked for)
+    const u8* stp = pout + o_st;
     for (u32 i = 0; i < n; ++i)
       r.reply[i] = has_reply_state(stp[i], ops->kind ? ops->kind[i] : (u8)PHIP_OP_RECEIVE)
                        ? src_r[i] : phip_state{};
@@ -2534,9 +2543,15 @@ int small_datagrams(phip_handle* h, const uint8_t* bytes, const uint64_t* offs, 
   } else if (rq) {
     rq->offs[0] = 0;
   }
-  if (res && res->status && stop < n) {   // the short datagram and everything after it
-    std::memset(res->status + stop, PHIP_ST_NOT_PROCESSED, n - stop);
-    res->status[stop] = PHIP_ST_SHORT;
+  if (res && stop < n) {   // the short datagram and everything after it
+    if (res->status) {
+      std::memset(res->status + stop, PHIP_ST_NOT_PROCESSED, n - stop);
+      res->status[stop] = PHIP_ST_SHORT;
+    }
+    // (the other columns read zero from the stop on, as on the large path)
+    if (res->remaining) std::memset(res->remaining + stop, 0, 8 * (size_t)(n - stop));
+    if (res->have) std::memset(res->have + stop, 0, 8 * (size_t)(n - stop));
+    if (res->reply) std::memset(res->reply + stop, 0, sizeof(phip_state) * (size_t)(n - stop));
   }
   if (stop_index) *stop_index = stop;
   *done = true;
@@ -3311,7 +3326,7 @@ static int receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const ph
     FastPass pass;
     int rc;
     bool worked = false;
-    if ((rc = outputs(h, res, n, true, &ow))) return rc;
+    if ((rc = receive_outputs(h, res, n, true, &ow))) return rc;
     const bool prev = h->pend.active;
     const phip_handle::HotKeep keep0 = h->keep;
     if ((rc = fast_begin(h, in, src, n, ow.status, ask, !prev, &pass)))
@@ -3386,7 +3401,7 @@ static int receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const ph
   OutView ow{};
   if ((rc = stage_names(h, m->names, m->name_offs, n, dev, &src, m->names_len)) ||
       (rc = stage(h, B_A, m->added, n, dev, &a)) || (rc = stage(h, B_T, m->taken, n, dev, &t)) ||
-      (rc = stage(h, B_E, m->elapsed, n, dev, &e)) || (rc = outputs(h, res, n, dev, &ow)))
+      (rc = stage(h, B_E, m->elapsed, n, dev, &e)) || (rc = receive_outputs(h, res, n, dev, &ow)))
     return rc;
   if ((rc = receive_decoded(h, src, a, t, e, n, now, ow, ask, eg))) return after_error(h, rc);
   return copy_outputs(h, res, n, dev, ow);
@@ -3415,7 +3430,7 @@ int receive_datagrams_dev(phip_handle* h, const u8* d_bytes, const uint64_t* d_o
                           ReplyEg* eg = nullptr) {
   int rc;
   OutView ow{};
-  if ((rc = outputs(h, res, n, dev, &ow))) return rc;
+  if ((rc = receive_outputs(h, res, n, dev, &ow))) return rc;
   // Fast path straight from the wire bytes: k_classify reads the headers
   // (and finds the first malformed datagram), k_receive_fast reads every
   // datagram in place; no decoded copy is written.

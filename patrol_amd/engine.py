@@ -863,13 +863,14 @@ class GPURepo:
 
     def apply_mixed_device(self, n, kind, names, name_offs, now, freq=None, per=None, count=None,
                            added=None, taken=None, elapsed=None, status=None, remaining=None,
-                           have=None, names_len=None):
+                           have=None, names_len=None, reply=None):
         """apply_mixed with every array a torch CUDA tensor (PHIP_DEVICE_PTRS);
-        names_len as receive_soa's."""
+        names_len as receive_soa's; reply: an int64 [n, 4] tensor for the
+        phip_state replies."""
         ops = phip_ops(n, _names_len(names, names_len), _ptr(kind), _ptr(names), _ptr(name_offs),
                        _ptr(now), _ptr(freq),
                        _ptr(per), _ptr(count), _ptr(added), _ptr(taken), _ptr(elapsed))
-        res = phip_results(_ptr(status), _ptr(remaining), _ptr(have), None)
+        res = phip_results(_ptr(status), _ptr(remaining), _ptr(have), _ptr(reply))
         self._check(self.L.phip_apply_mixed(self.h, C.byref(ops), C.byref(res), DEVICE_PTRS))
 
     def apply_mixed_egress_device(self, n, kind, names, name_offs, now, out, offs, max_msgs,
@@ -1295,7 +1296,7 @@ class GPUGroup:
                  "elapsed")
 
     def apply_mixed(self, batches, rccl_self: bool = False, small_chunks: bool = False,
-                    want_reply: bool = True):
+                    want_reply: bool = True, results=None):
         """Owner-routed phip_apply_mixed (phip_group_apply_mixed): batches holds,
         per local member, the ops that arrived there as a dict (or a tuple in
         this order) of CUDA tensors: kind uint8, names uint8 blob, name_offs
@@ -1312,7 +1313,13 @@ class GPUGroup:
         small_chunks).  The batches are checked (names_len = the names
         tensor's length) as receive()'s are: a malformed name_offs entry
         raises PatrolHipError (code -1, naming the member and the op) and no
-        batch is applied."""
+        batch is applied.
+
+        results (optional): per member, a dict of the caller's own CUDA
+        tensors for the columns (status, remaining, have, reply; a missing
+        key or None leaves that column out, want_reply is then ignored), or
+        None for that member's default columns.  They are handed to the
+        library as they are and returned as results[i]."""
         import torch
         k = len(batches)
         ops = (phip_ops * k)()
@@ -1323,6 +1330,11 @@ class GPUGroup:
                 b = dict(zip(self._OPS_KEYS, b))
             n = b["name_offs"].numel() - 1
             ops[i] = phip_ops(n, _names_len(b["names"]), *[_ptr(b.get(key)) for key in self._OPS_KEYS])
+            if results is not None and results[i] is not None:
+                r = {key: results[i].get(key) for key in ("status", "remaining", "have", "reply")}
+                res[i] = phip_results(*[_ptr(v) for v in r.values()])
+                out.append(r)
+                continue
             dev, z = b["names"].device, max(n, 1)
             r = dict(status=torch.zeros(z, dtype=torch.uint8, device=dev),
                      remaining=torch.zeros(z, dtype=torch.int64, device=dev),

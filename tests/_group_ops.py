@@ -96,6 +96,24 @@ def oracle_results(o, batches, order):
     return per
 
 
+_HASH = {}
+
+
+def owners(names, world):
+    """The owner rank of each name in a group of `world` members
+    (patrol_amd.shard.owner_of over the names' FNV-1a hashes)."""
+    import torch
+    from oracle import go_semantics as G
+    from patrol_amd import shard
+    for nm in names:
+        if nm not in _HASH:
+            _HASH[nm] = G.fnv1a64(nm)
+    if not len(names):
+        return np.zeros(0, np.int64)
+    h = np.array([_HASH[nm] for nm in names], np.uint64).view(np.int64)
+    return shard.owner_of(torch.from_numpy(h), world).numpy().astype(np.int64)
+
+
 def reply_mask(kind, status):
     """Ops whose reply state is defined (patrolhip.h phip_results.reply): TAKE,
     UPSERT and incast RECEIVEs; a merged replica's entry is all zeros."""

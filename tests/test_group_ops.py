@@ -30,18 +30,7 @@ def pa():
 
 DEV = torch.device("cuda", 0)
 POOL = GO.name_pool(400)
-_HASH = {}
-
-
-def _owners(names, world):
-    from patrol_amd import shard
-    for nm in names:
-        if nm not in _HASH:
-            _HASH[nm] = G.fnv1a64(nm)
-    h = np.array([_HASH[nm] for nm in names], np.uint64).view(np.int64)
-    if not len(names):
-        return np.zeros(0, np.int64)
-    return shard.owner_of(torch.from_numpy(h), world).numpy().astype(np.int64)
+_owners = GO.owners
 
 
 def _dev(b, drop=()):
