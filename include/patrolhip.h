@@ -112,6 +112,8 @@ enum {
 #define PHIP_GROUP_SMALL_CHUNKS 0x8u /* phip_group_receive (testing): pipeline the exchange in
                                         chunks of 4096 messages instead of 2^24, so that small
                                         batches run many pack / exchange rounds */
+#define PHIP_GROUP_PEEK_STATE 0x10u /* phip_group_peek: the 32-byte state column returns over the
+                                       exchange too (every process of the group passes it alike) */
 #define PHIP_RECV_ASYNC 0x20u /* phip_receive_soa with PHIP_DEVICE_PTRS, >= 2^16 messages: the
                                  call queues the batch and returns; the batch is finished
                                  (misses created, its dirty buckets through the ordered path,
@@ -817,10 +819,10 @@ int phip_take(phip_handle* h, const uint8_t* names, const uint32_t* name_offs, u
  * NULL): 0 with 200; with 429 retry_at - now, saturating at INT64_MAX, or -1
  * for never; untouched otherwise.
  *
- * Not here: a PEEK kind inside ordered streams, peeks through the Take
- * batcher, and an owner-routed phip_group_peek (a single-process group can
- * peek each member's phip_group_handle by the shard map meanwhile).  The
- * reverse question -- which buckets are denied now -- is "Throttled sweep"
+ * The sharded form is phip_group_peek ("Owner-routed phip_peek" below): every
+ * query is answered by the handle that owns its name.  Not here: a PEEK kind
+ * inside ordered streams and peeks through the Take batcher.  The reverse
+ * question -- which buckets are denied now -- is "Throttled sweep"
  * below. */
 #define PHIP_PEEK_NEVER INT64_MIN
 typedef struct phip_peek_results { /* any pointer may be NULL */
@@ -1274,7 +1276,11 @@ int phip_route_pack_datagrams(phip_handle* h, const phip_wire* w, uint32_t world
  * other bit is PHIP_ERR_INVALID).  A checked batch (ops->names_len != 0) with
  * a malformed offset entry is PHIP_ERR_INVALID and nothing is packed.  The
  * `kind` values of a device batch are the producer's to guarantee, as for
- * phip_apply_mixed. */
+ * phip_apply_mixed.
+ * The query pack (phip_group_peek's): with ops->kind and send_kind both NULL
+ * the batch is a batch of peek queries: no kind column is read or written,
+ * x0/x1/x2 are always freq/per/count, and everything else is as above.  One
+ * of the two NULL alone is PHIP_ERR_INVALID. */
 int phip_route_pack_ops(phip_handle* h, const phip_ops* ops, uint32_t world,
                         uint8_t* send_names, uint32_t* send_lens, uint8_t* send_kind,
                         int64_t* send_now, uint64_t* send_x0, uint64_t* send_x1,
@@ -1561,6 +1567,69 @@ int phip_group_reply_stats(phip_group* g, uint32_t i, uint64_t* out, int max);
 int phip_group_apply_mixed(phip_group* g, const phip_ops* batches,
                            const phip_results* results, uint64_t* sent,
                            uint64_t* applied, uint32_t flags);
+/* Owner-routed phip_peek: batches[i] / results[i] belong to local member i
+ * (device memory of its GPU; any results pointer may be NULL, results itself
+ * too).  The sharded form of a read-only quota query (X-RateLimit-Remaining,
+ * Retry-After, a per-user and a per-org limit checked before taking from
+ * either): a query that arrived at member i for a bucket of member j is
+ * evaluated at j, and its answer comes back to i.
+ *
+ * Queries.  Of each batch the call reads what phip_peek reads: n, names,
+ * name_offs, names_len, now, freq, per and count.  names, name_offs and now
+ * are required when n != 0; a NULL freq, per or count column reads as zeros.
+ * kind, added, taken and elapsed are ignored and may be NULL (kind is never
+ * read).
+ *
+ * Results.  results[i] entry j is exactly what phip_peek reports for query j
+ * of batches[i] on the handle that owns its name (the owner of a name among w
+ * shards: phip_route_pack): status, with PHIP_ST_ABSENT or-ed in when the
+ * owner does not hold the bucket, remaining, have, retry_at, and state under
+ * PHIP_GROUP_PEEK_STATE.  An absent bucket is evaluated with created = the
+ * query's own now, as on one handle.  All n entries of every column passed
+ * are written and nothing outside them ("Result columns" at phip_results).
+ *
+ * Nothing is written on any member: tables, arenas, change sets, layout
+ * counts, hot directories and phip_len stay as they are.  Each owner's step
+ * is one phip_peek with PHIP_DEVICE_PTRS on its handle, so "Peek" item 4
+ * holds per member (a batch queued with PHIP_RECV_ASYNC is finished first).
+ *
+ * Rounds.  Queries are read-only, so their order cannot show and there is no
+ * order rule.  The call still runs phip_group_apply_mixed's rounds: K is the
+ * largest ceil(n / chunk) over the members of the group, chunk is 2^24, or
+ * 4096 with PHIP_GROUP_SMALL_CHUNKS, and a member whose batch has ended sends
+ * empty rounds.  The rounds bound the scratch buffers and keep every member's
+ * collective calls alike; they run one after another on the handle's stream.
+ *
+ * What travels.  Forward, per query: its name bytes, their length, now and
+ * the three operand words (no kind byte).  Back: status, remaining, have and
+ * retry_at, 25 bytes a query, always (the members of a multi-process group
+ * cannot see each other's NULL pointers).  The 32-byte state column returns
+ * only under PHIP_GROUP_PEEK_STATE, which every process of the group must
+ * pass alike; a non-NULL results[i].state without the flag is
+ * PHIP_ERR_INVALID before any exchange, and with the flag a NULL state
+ * pointer is skipped at the scatter, as any column the caller passed as NULL.
+ * sent[i] / answered[i] (optional) receive the queries member i sent and the
+ * queries it answered as an owner.
+ *
+ * Flags.  PHIP_DEVICE_PTRS is required; PHIP_GROUP_RCCL_SELF and
+ * PHIP_GROUP_SMALL_CHUNKS as for phip_group_receive, PHIP_GROUP_PEEK_STATE as
+ * above; any other bit is PHIP_ERR_INVALID, with nothing exchanged and the
+ * result columns untouched.  A world of one without PHIP_GROUP_RCCL_SELF has
+ * nothing to route: the batch goes straight to phip_peek with the caller's
+ * buffers.
+ *
+ * Checked batches (phip_ops.names_len != 0), errors, the barriers of a
+ * shared-device group and phip_group_last_error: phip_group_apply_mixed's
+ * rules.  Every local batch's offset column is checked in full before any
+ * pack; if any holds a malformed entry, the process still runs every round
+ * with empty batches (so peers do not wait), the call returns
+ * PHIP_ERR_INVALID and phip_group_last_error names the member and the query.
+ * Every status column the caller passed is zeroed first, so a query that was
+ * not answered (a failed call, a rejected batch) reports status 0, which no
+ * answered query has. */
+int phip_group_peek(phip_group* g, const phip_ops* batches /* one per local member */,
+                    const phip_peek_results* results /* one per local member, may be NULL */,
+                    uint64_t* sent, uint64_t* answered, uint32_t flags);
 /* Anti-entropy round over simulated replicas (BASELINE configs[4]):
  * replicas[i] holds member i's nrep replicas in phip_ae_local_max's layout
  * (device memory).  Local join (phip_ae_local_max), RCCL all-reduce(MAX) of
@@ -1584,7 +1653,9 @@ int phip_group_evict_idle(phip_group* g, int64_t now, int64_t idle_ns, uint64_t 
  * or device copies; the all-reduce), ms[2] the owner's merges (the apply).
  * phip_group_apply_mixed: ms[0] the pack (phip_route_pack_ops), ms[1] both
  * exchanges (ops out, results back), ms[2] the owner's phip_apply_mixed plus
- * the results scatter.
+ * the results scatter.  phip_group_peek: ms[0] the query pack, ms[1] both
+ * exchanges (queries out, answers back), ms[2] the owner's phip_peek plus the
+ * answers' scatter.
  * The stages overlap, so their sum can exceed the call.  The read
  * synchronises on the events. */
 int phip_group_set_timing(phip_group* g, int on);

@@ -44,6 +44,7 @@ EXPORTS = [
     "phip_route_pack_datagrams", "phip_group_receive_datagrams", "phip_group_ring_receive",
     "phip_group_receive_datagrams_replies", "phip_group_receive_replies",
     "phip_group_ring_receive_replies", "phip_group_reply_stats",
+    "phip_group_peek",
 ]
 
 PHIP_OK = 0
@@ -66,6 +67,7 @@ CFG_TRACK_CHANGES = 0x20
 ROUTE_COMBINE = 0x2
 GROUP_RCCL_SELF = 0x4
 GROUP_SMALL_CHUNKS = 0x8
+GROUP_PEEK_STATE = 0x10      # PHIP_GROUP_PEEK_STATE (phip_group_peek): the state column returns too
 RECV_ASYNC = 0x20
 RECV_CLASSIFY = 0x100
 EVICT_SHRINK = 0x40
@@ -371,5 +373,8 @@ def load(path: str = LIB_PATH):
                                                       C.POINTER(u64), C.POINTER(u64),
                                                       C.POINTER(u32), rqp, u32]
         L.phip_group_reply_stats.argtypes = [vp, u32, C.POINTER(u64), C.c_int]
+    if hasattr(L, "phip_group_peek"):
+        L.phip_group_peek.argtypes = [vp, C.POINTER(phip_ops), C.POINTER(phip_peek_results),
+                                      C.POINTER(u64), C.POINTER(u64), u32]
     _lib = L
     return L

@@ -2743,7 +2743,10 @@ static int route_pack_on(phip_handle* h, hipStream_t st, const phip_msgs& m, u32
 // Stable owner partition of an op stream (phip_route_pack_ops, and the chunks
 // of phip_group_apply_mixed) into owner-major send buffers: route_pack_on's
 // skeleton (B_ROUTE, which nothing of ordered() touches); ordered ops never
-// combine.
+// combine.  Peek: the query pack of phip_group_peek (k_route_ops_scatter's
+// peek form: no kind column is read or written, the operands are the TAKE
+// ones); the count pass reads only names and serves both.
+template <bool Peek = false>
 static int route_pack_ops_on(phip_handle* h, hipStream_t st, const phip_ops& ops, u32 world,
                              uint8_t* send_names, uint32_t* send_lens, uint8_t* send_kind,
                              int64_t* send_now, uint64_t* send_x0, uint64_t* send_x1,
@@ -2761,8 +2764,8 @@ static int route_pack_ops_on(phip_handle* h, hipStream_t st, const phip_ops& ops
                                                                       c.code, c.cnt, c.bytes);
       },
       [&](const RoutePlan& p, const RouteCells& c) {
-        Launch l(h, "k_route_ops_scatter", st);
-        k_route_ops_scatter<NamesOffs><<<p.nblk, kRouteBlock, 0, st>>>(
+        Launch l(h, Peek ? "k_route_ops_scatter_peek" : "k_route_ops_scatter", st);
+        k_route_ops_scatter<NamesOffs, Peek><<<p.nblk, kRouteBlock, 0, st>>>(
             src, ro, n, p.span, world, p.ntile, c.code, c.cbase, c.bbase, send_names, send_lens,
             send_kind, send_now, send_x0, send_x1, send_x2, send_src);
       });
@@ -4003,8 +4006,9 @@ int phip_route_pack_ops(phip_handle* h, const phip_ops* ops, uint32_t world, uin
       !counts || !name_bytes)
     return PHIP_ERR_INVALID;
   const u32 n = ops->n;
-  if (n && (!ops->kind || !ops->names || !ops->name_offs || !ops->now || !send_names ||
-            !send_lens || !send_kind || !send_now || !send_x0 || !send_x1 || !send_x2 || !send_src))
+  const bool peek = !ops->kind && !send_kind;   // the query pack: no kind column on either side
+  if (n && ((!peek && (!ops->kind || !send_kind)) || !ops->names || !ops->name_offs || !ops->now ||
+            !send_names || !send_lens || !send_now || !send_x0 || !send_x1 || !send_x2 || !send_src))
     return PHIP_ERR_INVALID;
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = begin_call(h)) return rc0;
@@ -4016,9 +4020,12 @@ int phip_route_pack_ops(phip_handle* h, const phip_ops* ops, uint32_t world, uin
   if (first_bad != ~0u)
     return set_err(h, PHIP_ERR_INVALID,
                    "malformed name offsets at op %u (names_len check): nothing packed", first_bad);
-  if ((rc = route_pack_ops_on(h, h->stream, *ops, world, send_names, send_lens, send_kind,
-                              send_now, send_x0, send_x1, send_x2, send_src, counts, name_bytes)))
-    return rc;
+  rc = peek ? route_pack_ops_on<true>(h, h->stream, *ops, world, send_names, send_lens, nullptr,
+                                      send_now, send_x0, send_x1, send_x2, send_src, counts,
+                                      name_bytes)
+            : route_pack_ops_on(h, h->stream, *ops, world, send_names, send_lens, send_kind,
+                                send_now, send_x0, send_x1, send_x2, send_src, counts, name_bytes);
+  if (rc) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return PHIP_OK;
 }
@@ -4860,6 +4867,26 @@ int route_pack_ops(phip_handle* h, void* stream, const phip_ops* ops, uint32_t w
   if (int rc0 = finish_queued(h)) return rc0;
   return route_pack_ops_on(h, (hipStream_t)stream, *ops, world, names, lens, kind, now, x0, x1, x2,
                            src, counts, nbytes);
+}
+int route_pack_queries(phip_handle* h, void* stream, const phip_ops* q, uint32_t world,
+                       uint8_t* names, uint32_t* lens, int64_t* now, uint64_t* x0, uint64_t* x1,
+                       uint64_t* x2, uint32_t* src, uint64_t* counts, uint64_t* nbytes) {
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = finish_queued(h)) return rc0;
+  return route_pack_ops_on<true>(h, (hipStream_t)stream, *q, world, names, lens, nullptr, now, x0,
+                                 x1, x2, src, counts, nbytes);
+}
+int peek_results_scatter(phip_handle* h, void* stream, const uint32_t* src, uint32_t n,
+                         const uint8_t* status, const uint64_t* remaining, const uint64_t* have,
+                         const int64_t* retry_at, const phip_state* state,
+                         const phip_peek_results* out) {
+  if (!n || !out) return PHIP_OK;
+  const PeekOut po{out->status, out->remaining, out->have, out->retry_at, state ? out->state : nullptr};
+  if (!po.status && !po.remaining && !po.have && !po.retry_at && !po.state) return PHIP_OK;
+  k_peek_results_scatter<<<grid_for(n), kBlock, 0, (hipStream_t)stream>>>(
+      src, n, status, remaining, have, retry_at, state, po);
+  HIPCHK(h, hipGetLastError());
+  return PHIP_OK;
 }
 int results_scatter(phip_handle* h, void* stream, const uint32_t* src, uint32_t n,
                     const uint8_t* status, const uint64_t* remaining, const uint64_t* have,

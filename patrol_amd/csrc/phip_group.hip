@@ -113,6 +113,12 @@ constexpr Col kLens = {4, false, ncclUint32, 1, 4}, kNames = {1, true, ncclUint8
 constexpr Cols kMsgCols = {5, {kLens, kNames, kWord, kWord, kWord}};
 constexpr Cols kOpCols = {7, {kLens, kNames, kByte, kWord, kWord, kWord, kWord}};
 constexpr Cols kResCols = {4, {kByte, kWord, kWord, kReply}};
+// phip_group_peek's: a query is an op without its kind byte, an answer is
+// status, remaining, have and retry_at (25 bytes), and the state evaluated
+// behind them under PHIP_GROUP_PEEK_STATE.
+constexpr Cols kQryCols = {6, {kLens, kNames, kWord, kWord, kWord, kWord}};
+constexpr Cols kPeekCols = {4, {kByte, kWord, kWord, kWord}};
+constexpr Cols kPeekStateCols = {5, {kByte, kWord, kWord, kWord, kReply}};
 // The answers to a round's incast requests on their way back (the *_replies
 // forms): every datagram's length, the datagrams' bytes back to back (a
 // segment of them is addressed by byte, as names are) and the request's
@@ -121,6 +127,8 @@ constexpr Cols kBackCols = {3, {kLens, kNames, kLens}};
 enum { C_LENS, C_NAMES, MSG_A, MSG_T, MSG_E };
 enum { O_KIND = C_NAMES + 1, O_NOW, O_X0, O_X1, O_X2 };
 enum { R_STATUS, R_REM, R_HAVE, R_REPLY };
+enum { Q_NOW = C_NAMES + 1, Q_X0, Q_X1, Q_X2 };
+enum { P_STATUS, P_REM, P_HAVE, P_AT, P_STATE };
 enum { B_LENS, B_BYTES, B_POS };
 
 // The buffers of one column set, sized and moved by its table.
@@ -251,6 +259,10 @@ struct Member {
   // results the owners returned to this source, in send order.
   ColSet osend{kOpCols}, orecv{kOpCols}, ores{kResCols}, oback{kResCols};
   Buf osrc, ooffs;
+  // phip_group_peek's, in the same roles (osrc, ooffs and the ops path's split
+  // sizes serve both: a group runs one call at a time).  pres / pback take the
+  // call's answer columns, with or without the state (PeekPath::begin).
+  ColSet qsend{kQryCols}, qrecv{kQryCols}, pres{kPeekCols}, pback{kPeekCols};
   Sizes sz[4];
   Buf scan_tmp, ae, bounds;
   // The *_replies forms, source side: the answers the owners returned (owners
@@ -1132,7 +1144,7 @@ phip_ops ops_chunk_of(const phip_ops& in, u64 chunk, u64 k) {
   const u64 lo = k * chunk;
   c.n = lo < in.n ? (u32)std::min<u64>(chunk, in.n - lo) : 0u;
   if (c.n) {
-    c.kind = in.kind + lo;
+    if (in.kind) c.kind = in.kind + lo;   // (a query batch has none)
     c.name_offs = in.name_offs + lo;   // absolute offsets into the same blob
     c.now = in.now + lo;
     if (in.freq) c.freq = in.freq + lo;
@@ -1154,14 +1166,151 @@ phip_results results_from(const phip_results& r, u64 lo) {
   return c;
 }
 
-// Owner-routed phip_apply_mixed of one member (the order rule: patrolhip.h).
+phip_peek_results peek_results_from(const phip_peek_results& r, u64 lo) {
+  phip_peek_results c = r;
+  if (c.status) c.status += lo;
+  if (c.remaining) c.remaining += lo;
+  if (c.have) c.have += lo;
+  if (c.retry_at) c.retry_at += lo;
+  if (c.state) c.state += lo;
+  return c;
+}
+
+// What member_routed asks of a routed call over an op batch: the member's
+// four column sets of the call (a round packed owner-major, as the owner
+// received it, the owner's results, the results returned to this source),
+// what an entry is called in an error, the call on the one handle where there
+// is nothing to route, the pack of one round (split sizes into sz), the
+// owner's step over the n entries it received (their names' offsets in
+// mb.ooffs) and the scatter of a round's n returned results into the caller's
+// columns from entry lo on.
+//
+// phip_group_apply_mixed: the ops with their kind byte forward, one
+// phip_apply_mixed at the owner, the four result columns back.
+struct OpsPath {
+  const phip_results& res;
+  static constexpr ColSet Member::*kSend = &Member::osend, Member::*kRecv = &Member::orecv,
+                          Member::*kRes = &Member::ores, Member::*kBack = &Member::oback;
+  static constexpr const char* kItems = "ops";
+  void begin(Member&) const {}
+  int direct(Member& mb, const phip_ops& in) const {
+    GPHIP(mb, phip_apply_mixed(mb.h, &in, &res, PHIP_DEVICE_PTRS));
+    return PHIP_OK;
+  }
+  int pack(Member& mb, hipStream_t st, const phip_ops& c, u32 W, u64* sz) const {
+    const ColSet& ss = mb.osend;
+    if (phip_host::route_pack_ops(mb.h, st, &c, W, ss.at<uint8_t>(C_NAMES), ss.at<uint32_t>(C_LENS),
+                                  ss.at<uint8_t>(O_KIND), ss.at<int64_t>(O_NOW), ss.at<uint64_t>(O_X0),
+                                  ss.at<uint64_t>(O_X1), ss.at<uint64_t>(O_X2), (uint32_t*)mb.osrc.p,
+                                  sz, sz + W) != PHIP_OK)
+      return fail(mb, PHIP_ERR_HIP, "route pack ops: %s", phip_host::last_error(mb.h));
+    return PHIP_OK;
+  }
+  // One phip_apply_mixed over the round (sources in rank order, each in its
+  // order).  The three operand words serve both kinds: k_pack_ops reads
+  // freq/per/count under TAKE and added/taken/elapsed otherwise.
+  int owner(Member& mb, u64 n) const {
+    const ColSet& rs = mb.orecv;
+    phip_ops ro{};
+    ro.n = (u32)n;
+    ro.kind = rs.at<uint8_t>(O_KIND);
+    ro.names = rs.at<uint8_t>(C_NAMES);
+    ro.name_offs = (const u32*)mb.ooffs.p;
+    ro.now = rs.at<int64_t>(O_NOW);
+    ro.freq = rs.at<int64_t>(O_X0);
+    ro.per = rs.at<int64_t>(O_X1);
+    ro.count = rs.at<uint64_t>(O_X2);
+    ro.added = rs.at<uint64_t>(O_X0);
+    ro.taken = rs.at<uint64_t>(O_X1);
+    ro.elapsed = rs.at<int64_t>(O_X2);
+    phip_results rr{};
+    rr.status = mb.ores.at<uint8_t>(R_STATUS);
+    rr.remaining = mb.ores.at<uint64_t>(R_REM);
+    rr.have = mb.ores.at<uint64_t>(R_HAVE);
+    rr.reply = mb.ores.at<phip_state>(R_REPLY);
+    GPHIP(mb, phip_apply_mixed(mb.h, &ro, &rr, PHIP_DEVICE_PTRS));
+    return PHIP_OK;
+  }
+  int scatter(Member& mb, hipStream_t st, u32 n, u64 lo) const {
+    const phip_results out = results_from(res, lo);
+    if (phip_host::results_scatter(mb.h, st, (const uint32_t*)mb.osrc.p, n,
+                                   mb.oback.at<uint8_t>(R_STATUS), mb.oback.at<uint64_t>(R_REM),
+                                   mb.oback.at<uint64_t>(R_HAVE), mb.oback.at<phip_state>(R_REPLY),
+                                   &out) != PHIP_OK)
+      return fail(mb, PHIP_ERR_HIP, "results scatter: %s", phip_host::last_error(mb.h));
+    return PHIP_OK;
+  }
+};
+
+// phip_group_peek: the queries without a kind byte forward, one read-only
+// phip_peek at the owner, the peek columns back, with the evaluated state
+// only when the call asked for it (every process alike).  Nothing of any
+// handle is written.
+struct PeekPath {
+  const phip_peek_results& res;
+  bool with_state;
+  static constexpr ColSet Member::*kSend = &Member::qsend, Member::*kRecv = &Member::qrecv,
+                          Member::*kRes = &Member::pres, Member::*kBack = &Member::pback;
+  static constexpr const char* kItems = "queries";
+  void begin(Member& mb) const {   // the answer columns of this call
+    mb.pres.cols = mb.pback.cols = with_state ? &kPeekStateCols : &kPeekCols;
+  }
+  int direct(Member& mb, const phip_ops& in) const {
+    GPHIP(mb, phip_peek(mb.h, &in, &res, PHIP_DEVICE_PTRS));
+    return PHIP_OK;
+  }
+  int pack(Member& mb, hipStream_t st, const phip_ops& c, u32 W, u64* sz) const {
+    const ColSet& ss = mb.qsend;
+    if (phip_host::route_pack_queries(mb.h, st, &c, W, ss.at<uint8_t>(C_NAMES), ss.at<uint32_t>(C_LENS),
+                                      ss.at<int64_t>(Q_NOW), ss.at<uint64_t>(Q_X0),
+                                      ss.at<uint64_t>(Q_X1), ss.at<uint64_t>(Q_X2),
+                                      (uint32_t*)mb.osrc.p, sz, sz + W) != PHIP_OK)
+      return fail(mb, PHIP_ERR_HIP, "route pack queries: %s", phip_host::last_error(mb.h));
+    return PHIP_OK;
+  }
+  int owner(Member& mb, u64 n) const {
+    const ColSet& rs = mb.qrecv;
+    phip_ops rq{};
+    rq.n = (u32)n;
+    rq.names = rs.at<uint8_t>(C_NAMES);
+    rq.name_offs = (const u32*)mb.ooffs.p;
+    rq.now = rs.at<int64_t>(Q_NOW);
+    rq.freq = rs.at<int64_t>(Q_X0);
+    rq.per = rs.at<int64_t>(Q_X1);
+    rq.count = rs.at<uint64_t>(Q_X2);
+    phip_peek_results rr{};
+    rr.status = mb.pres.at<uint8_t>(P_STATUS);
+    rr.remaining = mb.pres.at<uint64_t>(P_REM);
+    rr.have = mb.pres.at<uint64_t>(P_HAVE);
+    rr.retry_at = mb.pres.at<int64_t>(P_AT);
+    if (with_state) rr.state = mb.pres.at<phip_state>(P_STATE);
+    GPHIP(mb, phip_peek(mb.h, &rq, &rr, PHIP_DEVICE_PTRS));
+    return PHIP_OK;
+  }
+  int scatter(Member& mb, hipStream_t st, u32 n, u64 lo) const {
+    const phip_peek_results out = peek_results_from(res, lo);
+    if (phip_host::peek_results_scatter(
+            mb.h, st, (const uint32_t*)mb.osrc.p, n, mb.pback.at<uint8_t>(P_STATUS),
+            mb.pback.at<uint64_t>(P_REM), mb.pback.at<uint64_t>(P_HAVE), mb.pback.at<int64_t>(P_AT),
+            with_state ? mb.pback.at<phip_state>(P_STATE) : nullptr, &out) != PHIP_OK)
+      return fail(mb, PHIP_ERR_HIP, "peek results scatter: %s", phip_host::last_error(mb.h));
+    return PHIP_OK;
+  }
+};
+
+// One member's part of an owner-routed call over an op batch (OpsPath: the
+// order rule in patrolhip.h; PeekPath: read-only, so no order shows and the
+// rounds only bound the scratch and keep the members' collective calls alike).
 // The rounds run one after another on the handle's stream: pack, split
-// sizes, the ops to their owners, the owner's phip_apply_mixed, the results
-// back to their sources, the scatter into the caller's columns.  An ordered
-// round cannot start before the one before it was applied, and a Take's
-// caller waits for its result, so there is nothing to overlap across rounds.
-int member_apply_mixed(phip_group* g, Member& mb, const phip_ops& in, const phip_results& res,
-                       uint64_t* sent, uint64_t* applied, uint32_t flags) {
+// sizes, the entries to their owners, the owner's step, the results back to
+// their sources, the scatter into the caller's columns.  An ordered round
+// cannot start before the one before it was applied, and a Take's caller
+// waits for its result, so there is nothing to overlap across rounds.
+// osrc, ooffs and the split sizes serve both paths: a group runs one call at
+// a time.
+template <class Path>
+int member_routed(phip_group* g, Member& mb, const phip_ops& in, const Path& path, uint64_t* sent,
+                  uint64_t* done, uint32_t flags) {
   const u32 W = g->world;
   const u32 n = in.n;
   GHIP(mb, hipSetDevice(mb.device));
@@ -1170,10 +1319,10 @@ int member_apply_mixed(phip_group* g, Member& mb, const phip_ops& in, const phip
   mb.tm.reset();
   if (W == 1 && !rccl_self) {   // one owner: nothing to route
     if (sent) *sent = n;
-    if (applied) *applied = n;
+    if (done) *done = n;
     if (n == 0) return PHIP_OK;
     GHIP(mb, mb.tm.mark(2, st));
-    GPHIP(mb, phip_apply_mixed(mb.h, &in, &res, PHIP_DEVICE_PTRS));
+    if (int r = path.direct(mb, in)) return r;
     GHIP(mb, mb.tm.mark(2, st));
     return PHIP_OK;
   }
@@ -1185,12 +1334,12 @@ int member_apply_mixed(phip_group* g, Member& mb, const phip_ops& in, const phip
   if ((rc = chunk_bounds(g, mb, st, in.name_offs, n, chunk, &bnd))) return rc;
   u64 max_bytes = 0;
   for (u64 k = 0; k < mb.k_local; ++k) max_bytes = std::max<u64>(max_bytes, (u64)(bnd[k + 1] - bnd[k]));
+  path.begin(mb);
   Sizes& zs = mb.sz[kOpsSizes];
-  const ColSet& ss = mb.osend;
-  ColSet& rs = mb.orecv;
-  GHIP(mb, mb.osend.ensure(cmax, max_bytes));
+  ColSet &ss = mb.*Path::kSend, &rs = mb.*Path::kRecv, &res = mb.*Path::kRes, &bk = mb.*Path::kBack;
+  GHIP(mb, ss.ensure(cmax, max_bytes));
   GHIP(mb, mb.osrc.ensure(cmax * 4 + 4));
-  GHIP(mb, mb.oback.ensure(cmax, 0));
+  GHIP(mb, bk.ensure(cmax, 0));
   GHIP(mb, zs.dev.ensure((size_t)6 * W * 8));
   u64* sz = (u64*)zs.dev.p;
   u64 K = 1, n_send = 0, n_recv = 0;
@@ -1199,11 +1348,7 @@ int member_apply_mixed(phip_group* g, Member& mb, const phip_ops& in, const phip
     // 1. the pack of round k
     const phip_ops c = ops_chunk_of(in, chunk, k);
     GHIP(mb, mb.tm.mark(0, st));
-    if (phip_host::route_pack_ops(mb.h, st, &c, W, ss.at<uint8_t>(C_NAMES), ss.at<uint32_t>(C_LENS),
-                                  ss.at<uint8_t>(O_KIND), ss.at<int64_t>(O_NOW), ss.at<uint64_t>(O_X0),
-                                  ss.at<uint64_t>(O_X1), ss.at<uint64_t>(O_X2), (uint32_t*)mb.osrc.p,
-                                  sz, sz + W) != PHIP_OK)
-      return fail(mb, PHIP_ERR_HIP, "route pack ops: %s", phip_host::last_error(mb.h));
+    if ((rc = path.pack(mb, st, c, W, sz))) return rc;
     GHIP(mb, hipMemcpyAsync(sz + 2 * W, mb.host_k, W * 8, hipMemcpyHostToDevice, st));
     GHIP(mb, mb.tm.mark(0, st));
     // 2. the split sizes
@@ -1212,46 +1357,26 @@ int member_apply_mixed(phip_group* g, Member& mb, const phip_ops& in, const phip
     if ((rc = adopt_sizes(g, mb, kOpsSizes, k == 0, &K))) return rc;
     segment_plan(zs.host, W, &plan);
     Totals t;
-    if ((rc = round_totals(mb, plan, "round", "ops", &t))) return rc;
+    if ((rc = round_totals(mb, plan, "round", Path::kItems, &t))) return rc;
     if (t.c_send != c.n)
-      return fail(mb, PHIP_ERR_INVALID, "internal: packed %llu of %u ops", (unsigned long long)t.c_send,
-                  c.n);
+      return fail(mb, PHIP_ERR_INVALID, "internal: packed %llu of %u %s", (unsigned long long)t.c_send,
+                  c.n, Path::kItems);
     GHIP(mb, rs.ensure(t.c_recv, t.b_recv));
     GHIP(mb, mb.ooffs.ensure(t.c_recv * 4 + 8));
-    GHIP(mb, mb.ores.ensure(t.c_recv, 0));
-    // 3. the ops to their owners
+    GHIP(mb, res.ensure(t.c_recv, 0));
+    // 3. the entries to their owners
     GHIP(mb, mb.tm.mark(1, st));
     if ((rc = move_segments(g, mb, plan, ss, rs, st, rccl_self,
                             peers_of(g, mb, kOpsSizes, 0, [](const Member& m) -> const ColSet& {
-                              return m.osend;
+                              return m.*Path::kSend;
                             }))))
       return rc;
     GHIP(mb, mb.tm.mark(1, st));
-    // 4. the owner's apply: the names' offsets, then one phip_apply_mixed over
-    //    the round (sources in rank order, each in its order).  The three
-    //    operand words serve both kinds: k_pack_ops reads freq/per/count under
-    //    TAKE and added/taken/elapsed otherwise.
+    // 4. the owner's step: the names' offsets, then one call over the round
     if (t.c_recv) {
       GHIP(mb, mb.tm.mark(2, st));
       if ((rc = offsets_from_lens(mb, rs.at<u32>(C_LENS), t.c_recv, (u32*)mb.ooffs.p, st))) return rc;
-      phip_ops ro{};
-      ro.n = (u32)t.c_recv;
-      ro.kind = rs.at<uint8_t>(O_KIND);
-      ro.names = rs.at<uint8_t>(C_NAMES);
-      ro.name_offs = (const u32*)mb.ooffs.p;
-      ro.now = rs.at<int64_t>(O_NOW);
-      ro.freq = rs.at<int64_t>(O_X0);
-      ro.per = rs.at<int64_t>(O_X1);
-      ro.count = rs.at<uint64_t>(O_X2);
-      ro.added = rs.at<uint64_t>(O_X0);
-      ro.taken = rs.at<uint64_t>(O_X1);
-      ro.elapsed = rs.at<int64_t>(O_X2);
-      phip_results rr{};
-      rr.status = mb.ores.at<uint8_t>(R_STATUS);
-      rr.remaining = mb.ores.at<uint64_t>(R_REM);
-      rr.have = mb.ores.at<uint64_t>(R_HAVE);
-      rr.reply = mb.ores.at<phip_state>(R_REPLY);
-      GPHIP(mb, phip_apply_mixed(mb.h, &ro, &rr, PHIP_DEVICE_PTRS));
+      if ((rc = path.owner(mb, t.c_recv))) return rc;
       GHIP(mb, mb.tm.mark(2, st));
     }
     // 5. the results back to their sources: source p's segment [ro, ro + rc)
@@ -1265,9 +1390,9 @@ int member_apply_mixed(phip_group* g, Member& mb, const phip_ops& in, const phip
     }
     for (u32 p = 0; p < W; ++p) back[p] = swapped(plan[p]);
     GHIP(mb, mb.tm.mark(1, st));
-    if ((rc = move_segments(g, mb, back, mb.ores, mb.oback, st, rccl_self,
+    if ((rc = move_segments(g, mb, back, res, bk, st, rccl_self,
                             peers_of(g, mb, kOpsSizes, 3 * W, [](const Member& m) -> const ColSet& {
-                              return m.ores;
+                              return m.*Path::kRes;
                             }))))
       return rc;
     GHIP(mb, mb.tm.mark(1, st));
@@ -1275,22 +1400,17 @@ int member_apply_mixed(phip_group* g, Member& mb, const phip_ops& in, const phip
       GHIP(mb, hipStreamSynchronize(st));
       if (!g->bar.wait()) return fail(mb, PHIP_ERR_INVALID, "another member failed");
     }
-    // 6. into the caller's columns, at the ops' places in the batch
+    // 6. into the caller's columns, at the entries' places in the batch
     if (c.n) {
-      const phip_results out = results_from(res, k * chunk);
       GHIP(mb, mb.tm.mark(2, st));
-      if (phip_host::results_scatter(mb.h, st, (const uint32_t*)mb.osrc.p, c.n,
-                                     mb.oback.at<uint8_t>(R_STATUS), mb.oback.at<uint64_t>(R_REM),
-                                     mb.oback.at<uint64_t>(R_HAVE), mb.oback.at<phip_state>(R_REPLY),
-                                     &out) != PHIP_OK)
-        return fail(mb, PHIP_ERR_HIP, "results scatter: %s", phip_host::last_error(mb.h));
+      if ((rc = path.scatter(mb, st, c.n, k * chunk))) return rc;
       GHIP(mb, mb.tm.mark(2, st));
     }
     n_send += t.c_send;
     n_recv += t.c_recv;
   }
   if (sent) *sent = n_send;
-  if (applied) *applied = n_recv;
+  if (done) *done = n_recv;
   GHIP(mb, hipStreamSynchronize(st));   // the results are the caller's to read
   return PHIP_OK;
 }
@@ -1356,7 +1476,9 @@ void destroy(phip_group* g) {
       for (hipEvent_t ev : {ln.ev_pack, ln.ev_sz, ln.ev_x, ln.ev_recv, ln.ev_merged})
         if (ev) (void)hipEventDestroy(ev);
     }
-    for (ColSet* s : {&mb.osend, &mb.orecv, &mb.ores, &mb.oback}) s->release();
+    for (ColSet* s : {&mb.osend, &mb.orecv, &mb.ores, &mb.oback, &mb.qsend, &mb.qrecv, &mb.pres,
+                      &mb.pback})
+      s->release();
     for (Sizes& s : mb.sz) {
       s.dev.release();
       if (s.host) (void)hipHostFree(s.host);
@@ -1813,8 +1935,36 @@ int phip_group_apply_mixed(phip_group* g, const phip_ops* batches, const phip_re
         return (int)PHIP_OK;
       },
       [&](size_t i, const phip_ops& b) {
-        return member_apply_mixed(g, g->m[i], b, res[i], sent ? sent + i : nullptr,
-                                  applied ? applied + i : nullptr, flags);
+        return member_routed(g, g->m[i], b, OpsPath{res[i]}, sent ? sent + i : nullptr,
+                             applied ? applied + i : nullptr, flags);
+      });
+}
+
+int phip_group_peek(phip_group* g, const phip_ops* batches, const phip_peek_results* results,
+                    uint64_t* sent, uint64_t* answered, uint32_t flags) {
+  constexpr uint32_t kAllowed =
+      PHIP_DEVICE_PTRS | PHIP_GROUP_RCCL_SELF | PHIP_GROUP_SMALL_CHUNKS | PHIP_GROUP_PEEK_STATE;
+  if (!g || !batches || !(flags & PHIP_DEVICE_PTRS) || (flags & ~kAllowed)) return PHIP_ERR_INVALID;
+  const size_t nl = g->m.size();
+  std::vector<phip_peek_results> res(nl);   // (a NULL results: no column wanted)
+  for (size_t i = 0; i < nl; ++i) {
+    const phip_ops& b = batches[i];
+    if (b.n && (!b.names || !b.name_offs || !b.now)) return PHIP_ERR_INVALID;
+    res[i] = results ? results[i] : phip_peek_results{};
+    // the state column travels only when every process asked for it
+    if (res[i].state && !(flags & PHIP_GROUP_PEEK_STATE)) return PHIP_ERR_INVALID;
+  }
+  // Queries that are not answered report status 0 (phip_group_apply_mixed's rule).
+  return checked_call(
+      g, batches, "query",
+      [&](Member& mb, hipStream_t st, size_t i) {
+        if (res[i].status && batches[i].n)
+          GHIP(mb, hipMemsetAsync(res[i].status, 0, batches[i].n, st));
+        return (int)PHIP_OK;
+      },
+      [&](size_t i, const phip_ops& b) {
+        return member_routed(g, g->m[i], b, PeekPath{res[i], (flags & PHIP_GROUP_PEEK_STATE) != 0},
+                             sent ? sent + i : nullptr, answered ? answered + i : nullptr, flags);
       });
 }
 

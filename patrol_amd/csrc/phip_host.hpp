@@ -35,6 +35,17 @@ int route_pack_ops(phip_handle* h, void* stream, const phip_ops* ops, uint32_t w
 int results_scatter(phip_handle* h, void* stream, const uint32_t* src, uint32_t n,
                     const uint8_t* status, const uint64_t* remaining, const uint64_t* have,
                     const phip_state* reply, const phip_results* out);
+// The read side (phip_group_peek): the query pack is route_pack_ops without a
+// kind column on either side (q->kind is not read; the operand words are
+// always freq, per, count), and the answers' way back is results_scatter over
+// the peek columns (state == NULL: the call did not return that column).
+int route_pack_queries(phip_handle* h, void* stream, const phip_ops* q, uint32_t world,
+                       uint8_t* names, uint32_t* lens, int64_t* now, uint64_t* x0, uint64_t* x1,
+                       uint64_t* x2, uint32_t* src, uint64_t* counts, uint64_t* nbytes);
+int peek_results_scatter(phip_handle* h, void* stream, const uint32_t* src, uint32_t n,
+                         const uint8_t* status, const uint64_t* remaining, const uint64_t* have,
+                         const int64_t* retry_at, const phip_state* state,
+                         const phip_peek_results* out);
 // The route kernels do not check a batch's name offsets as they go.
 // check_offsets: one pass over a checked batch's offset column (names_len !=
 // 0; NamesOffs::bad's rule) on `stream`, which it synchronises: *first_bad is

@@ -5325,7 +5325,10 @@ __global__ __launch_bounds__(kRouteBlock) void k_route_ops_count(
   }
 }
 
-template <class Src>
+// Peek (phip_group_peek's query pack): a query has no kind.  Its operand
+// words are always freq, per, count, and neither op.kind nor out_kind is
+// touched (both may be NULL); everything else is the op pack's.
+template <class Src, bool Peek = false>
 __global__ __launch_bounds__(kRouteBlock) void k_route_ops_scatter(
     Src src, RouteOps op, u32 n, u32 span, u32 world, u32 ntile, const u16* __restrict__ code,
     const u32* __restrict__ cbase, const u32* __restrict__ bbase, u8* __restrict__ out_names,
@@ -5367,11 +5370,11 @@ __global__ __launch_bounds__(kRouteBlock) void k_route_ops_scatter(
       idx[u] = ic;
       c[u] = code[ic];
       src.get(ic, off[u], len[u]);
-      kd[u] = op.kind[ic];
+      if constexpr (!Peek) kd[u] = op.kind[ic];
       nw[u] = op.now[ic];
       // the operand words of the op's kind; a column the batch does not have
       // reads as zeros
-      const bool take = kd[u] == PHIP_OP_TAKE;
+      const bool take = Peek || kd[u] == PHIP_OP_TAKE;
       const u64* p0 = take ? (const u64*)op.freq : (const u64*)op.a;
       const u64* p1 = take ? (const u64*)op.per : (const u64*)op.t;
       const u64* p2 = take ? (const u64*)op.count : (const u64*)op.e;
@@ -5428,7 +5431,7 @@ __global__ __launch_bounds__(kRouteBlock) void k_route_ops_scatter(
       const u32 db = (u32)__shfl((int)pb, (int)oo) + dby[u];
       if (plain) {
         out_lens[d] = len[u];
-        out_kind[d] = (u8)kd[u];
+        if constexpr (!Peek) out_kind[d] = (u8)kd[u];
         out_now[d] = nw[u];
         out_x0[d] = x0[u];
         out_x1[d] = x1[u];
@@ -5475,6 +5478,9 @@ __global__ __launch_bounds__(kBlock) void k_route_results_scatter(
   if (ow.have) ow.have[i] = have[j];
   if (ow.reply) ow.reply[i] = reply[j];
 }
+
+// (phip_group_peek's answers take the same way home: k_peek_results_scatter,
+// beside k_peek.)
 
 // ------------------------------------------------------------ shard layer --
 // Anti-entropy over simulated cluster replicas (BASELINE configs[4], SURVEY
@@ -6888,6 +6894,26 @@ __global__ __launch_bounds__(kBlock) void k_peek(NamesOffs src, OpView ov, u32 n
   if (po.have) po.have[i] = pr.have_bits;
   if (po.retry_at) po.retry_at[i] = pr.retry_at;
   if (po.state) po.state[i] = st;
+}
+
+// phip_group_peek's answers on their way home (k_route_results_scatter's walk
+// over the peek columns): the owners' results, returned in send order (entry
+// j answers the query that stood at src[j] of the batch), into the caller's
+// columns.  One lane a query; the returned columns are read coalesced.  A
+// column the caller did not ask for is skipped; `state` is NULL when the call
+// did not return that column.
+__global__ __launch_bounds__(kBlock) void k_peek_results_scatter(
+    const u32* __restrict__ src, u32 n, const u8* __restrict__ status,
+    const uint64_t* __restrict__ remaining, const uint64_t* __restrict__ have,
+    const int64_t* __restrict__ retry_at, const phip_state* __restrict__ state, PeekOut po) {
+  const u32 j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= n) return;
+  const u32 i = src[j];
+  if (po.status) po.status[i] = status[j];
+  if (po.remaining) po.remaining[i] = remaining[j];
+  if (po.have) po.have[i] = have[j];
+  if (po.retry_at) po.retry_at[i] = retry_at[j];
+  if (po.state && state) po.state[i] = state[j];
 }
 
 // ----------------------------------------------------- throttled sweep ----

@@ -898,14 +898,16 @@ class GPURepo:
         as torch CUDA tensors (a missing operand column reads as zeros) ->
         dict of CUDA tensors: names (uint8, packed back to back), lens, kind,
         now, x0, x1, x2 (the operand words by kind), src (op j of the send
-        buffers is op src[j] of the batch), counts and name_bytes per owner."""
+        buffers is op src[j] of the batch), counts and name_bytes per owner.
+        kind=None: the query pack of phip_group_peek (no kind column on either
+        side: out["kind"] is None; x0, x1, x2 are freq, per, count)."""
         import torch
         dev = names.device
         nb = int(names.numel())
         z = max(n, 1)
         out = dict(names=torch.zeros(nb + 64, dtype=torch.uint8, device=dev),
                    lens=torch.zeros(z, dtype=torch.int32, device=dev),
-                   kind=torch.zeros(z, dtype=torch.uint8, device=dev),
+                   kind=torch.zeros(z, dtype=torch.uint8, device=dev) if kind is not None else None,
                    now=torch.zeros(z, dtype=torch.int64, device=dev),
                    x0=torch.zeros(z, dtype=torch.int64, device=dev),
                    x1=torch.zeros(z, dtype=torch.int64, device=dev),
@@ -1350,6 +1352,60 @@ class GPUGroup:
             (_lib.GROUP_SMALL_CHUNKS if small_chunks else 0)
         self._check(self.L.phip_group_apply_mixed(self.g, ops, res, sent, applied, flags))
         return out, [int(x) for x in sent], [int(x) for x in applied]
+
+    _PEEK_KEYS = ("status", "remaining", "have", "retry_at", "state")
+
+    def peek(self, batches, rccl_self: bool = False, small_chunks: bool = False,
+             want_state: bool = False, results=None):
+        """Owner-routed phip_peek (phip_group_peek): batches holds, per local
+        member, the queries that arrived there as a dict of CUDA tensors:
+        names uint8 blob, name_offs int32[n+1], now int64, and the operand
+        columns freq, per, count (any of which may be None: zeros).  ->
+        (results, sent, answered): results[i] is a dict of CUDA tensors status
+        uint8[n] (ST_TAKE_OK / ST_TAKE_DENIED, | ST_ABSENT), remaining / have /
+        retry_at int64[n], state int64[n, 4] (None without want_state), entry
+        j what phip_peek reports for query j of batches[i] on the member that
+        owns its name; sent[i] / answered[i] the queries member i sent and
+        answered as an owner.  Nothing is written on any member.
+
+        The batches are checked as apply_mixed()'s are.  want_state sets
+        PHIP_GROUP_PEEK_STATE (the state column returns over the exchange).
+
+        results (optional): per member, a dict of the caller's own CUDA
+        tensors for the columns (a missing key or None leaves that column
+        out), or None for that member's default columns.  They are handed to
+        the library as they are and returned as results[i]."""
+        import torch
+        k = len(batches)
+        ops = (phip_ops * k)()
+        res = (_lib.phip_peek_results * k)()
+        out = []
+        for i, b in enumerate(batches):
+            n = b["name_offs"].numel() - 1
+            ops[i] = phip_ops(n, _names_len(b["names"]), None, _ptr(b["names"]),
+                              _ptr(b["name_offs"]), _ptr(b.get("now")), _ptr(b.get("freq")),
+                              _ptr(b.get("per")), _ptr(b.get("count")), None, None, None)
+            if results is not None and results[i] is not None:
+                r = {key: results[i].get(key) for key in self._PEEK_KEYS}
+                res[i] = _lib.phip_peek_results(*[_ptr(v) for v in r.values()])
+                out.append(r)
+                continue
+            dev, z = b["names"].device, max(n, 1)
+            r = {key: torch.zeros(z, dtype=torch.int64, device=dev)
+                 for key in ("remaining", "have", "retry_at")}
+            r["status"] = torch.zeros(z, dtype=torch.uint8, device=dev)
+            r["state"] = torch.zeros((z, 4), dtype=torch.int64, device=dev) if want_state else None
+            res[i] = _lib.phip_peek_results(*[_ptr(r[key]) for key in self._PEEK_KEYS])
+            out.append({key: (r[key][:n] if r[key] is not None else None)
+                        for key in self._PEEK_KEYS})
+        for r in self.repos:
+            torch.cuda.synchronize(r.device)
+        sent, answered = (C.c_uint64 * k)(), (C.c_uint64 * k)()
+        flags = DEVICE_PTRS | (_lib.GROUP_RCCL_SELF if rccl_self else 0) | \
+            (_lib.GROUP_SMALL_CHUNKS if small_chunks else 0) | \
+            (_lib.GROUP_PEEK_STATE if want_state else 0)
+        self._check(self.L.phip_group_peek(self.g, ops, res, sent, answered, flags))
+        return out, [int(x) for x in sent], [int(x) for x in answered]
 
     def set_timing(self, on: bool = True):
         """phip_group_set_timing: per-stage event timing of later calls."""
