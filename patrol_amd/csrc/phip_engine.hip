@@ -92,6 +92,7 @@ struct FastPass {
   bool hot_join = false;      // the directory was built on stream2 (fast_back joins it)
   bool built = false;         // its front launched k_hot_dir
   u32 hot_age = 0;            // passes its directory served before this one (0: built for it)
+  u32 hot_nw = 0;             // a kept directory's layout in the kernel (k_receive_fast's NW; 0: today's)
   // optimistic, queued behind a pass not settled yet: that pass's counter
   // set, the kernel's gate (nullptr: none); and whether the host, reading the
   // same words in that pass's mirror, found it shut (receive_queued)
@@ -139,6 +140,7 @@ struct phip_handle {
     u32 served = 0;         // passes that took it, the one it was built for included
     // from the passes collected so far
     bool agree = false;     // the latest build collected: kept * 8 >= own * 7, own > 0
+    u32 maxlen = ~0u;       // that build's longest selected name (kCtrHotMaxLen), in bytes
     u64 ref_hits = 0, ref_n = 0;   // that build's batch: messages folded, messages
     bool sagged = false;    // a pass collected since folded < 7/8 of ref_hits / ref_n
   } keep;
@@ -658,26 +660,28 @@ int after_error(phip_handle* h, int rc) {
 // tables and sync words, which have to be zero at its next launch: the fast
 // kernel that takes the directory clears them (fast_back).  Only a buffer just
 // created, or one whose directory no fast kernel took, is cleared in front.
-// B_HOT: those tables, the candidate list, then two {HotHdr, HotEntry[kHotMax]}
+// B_HOT: those tables, the candidate list, then two {HotHdr, HotEntry[kHotMaxExt]}
 // slots built into alternately (HotKeep), so that the kernel's last workgroup
 // reads the directory before while it writes the new one.
 // status: nothing runs beside the kernel (an optimistic batch): one sample
-// per lane, and further workgroups fill the batch's status column; nullptr:
-// it shares the chip with k_classify, which writes the statuses.
+// per lane, up to kHotSampleMaxAlone of them, and further workgroups fill the
+// batch's status column; nullptr: it shares the chip with k_classify, which
+// writes the statuses, and takes up to kHotSampleMax.
+constexpr size_t kHotSlotBytes = sizeof(HotHdr) + kHotMaxExt * sizeof(HotEntry);
+constexpr size_t kHotSlotsAt = kHotZeroBytes + kHotDirCandMax * sizeof(u32);
 template <class Src>
 int build_hot(phip_handle* h, Src src, u32 n, hipStream_t st, u8* status, FastPass* p) {
   if (n < kHotMinBatch) return PHIP_OK;
-  constexpr size_t kCnt = size_t(1) << kHotCntBits;
-  constexpr size_t kSlot = sizeof(HotHdr) + kHotMax * sizeof(HotEntry);
+  constexpr size_t kCnt = size_t(1) << kHotDirCntBits;
   u8* base;
   int rc;
-  if ((rc = ensure(h, B_HOT, kHotZeroBytes + kHotCandMax * sizeof(u32) + 2 * kSlot, &base)))
-    return rc;
+  if ((rc = ensure(h, B_HOT, kHotSlotsAt + 2 * kHotSlotBytes, &base))) return rc;
   u32* ckeys = (u32*)base;
   u32* ccnt = ckeys + kCnt;
   u32* sync = ccnt + kCnt;
   u32* cand = sync + kHotSyncWords;
-  u8* slots = (u8*)(cand + kHotCandMax);
+  u8* slots = base + kHotSlotsAt;
+  constexpr size_t kSlot = kHotSlotBytes;
   // The slot not built last; the one built last, while it still describes the
   // table, is the directory the kernel's agreement sums compare with.
   phip_handle::HotKeep& kp = h->keep;
@@ -694,7 +698,8 @@ int build_hot(phip_handle* h, Src src, u32 n, hipStream_t st, u8* status, FastPa
   HotEntry* dir = (HotEntry*)(hdr + 1);
   if (h->hot_clean != base) HIPCHK(h, hipMemsetAsync(base, 0, kHotZeroBytes, st));
   h->hot_clean = nullptr;
-  const u32 stride = std::max<u32>(64, (n + kHotSampleMax - 1) / kHotSampleMax);
+  const u32 smax = status ? kHotSampleMaxAlone : kHotSampleMax;
+  const u32 stride = std::max<u32>(64, (n + smax - 1) / smax);
   const u32 nsample = (n + stride - 1) / stride;
   {
     Launch l(h, "k_hot_dir", st);
@@ -1040,7 +1045,11 @@ int fast_back(phip_handle* h, In in, FastPass& p, bool queued) {
         u8* kstatus = PHIP_STATUS_IN_KERNEL ? p.fill : nullptr;
         if (p.fill && !kstatus) HIPCHK(h, hipMemsetAsync(p.fill, PHIP_ST_MERGED, n, h->stream));
         Launch l(h, "k_receive_fast");
-        k_receive_fast<In, true><<<ul.grid, kFastBlock, 0, h->stream>>>(
+        // (hot_nw: a kept directory in a compact layout, keep_take)
+        auto* kern = p.hot_nw == 2   ? k_receive_fast<In, true, 2>
+                     : p.hot_nw == 3 ? k_receive_fast<In, true, 3>
+                                     : k_receive_fast<In, true, 0>;
+        kern<<<ul.grid, kFastBlock, 0, h->stream>>>(
             in, 0, n, table(h), msh, p.c, p.hot, p.dir, nullptr, nullptr, p.log,
             (uint4*)p.hot_zero, p.hot_age != 0, p.gate, kstatus);
       }
@@ -1121,14 +1130,23 @@ bool keep_take(phip_handle* h, FastPass* p) {
   if (p->n < kHotMinBatch || !k.have || !k.agree || k.sagged || k.served >= kHotKeepPasses ||
       k.gen != h->layout_gen || k.base != h->buf[B_HOT].p)
     return false;
-  constexpr size_t kSlot = sizeof(HotHdr) + kHotMax * sizeof(HotEntry);
-  p->hot = (const HotHdr*)((u8*)k.base + kHotZeroBytes + kHotCandMax * sizeof(u32) + k.slot * kSlot);
+  p->hot = (const HotHdr*)((u8*)k.base + kHotSlotsAt + k.slot * kHotSlotBytes);
   p->dir = (const HotEntry*)(p->hot + 1);
   p->hot_age = k.served++;
+  // The layout the kernel holds it in, from the longest name the latest build
+  // collected selected: two name words an entry and the whole extended
+  // selection, three words and its first kHotMax3 entries (the better part:
+  // k_hot_dir orders them by count), or today's and the first HotHdr::n.  A
+  // queued pass may take a slot built after that build, not collected yet; the
+  // kernel leaves out any entry whose name its layout does not hold, so the
+  // choice costs hits at worst.
+  p->hot_nw = k.maxlen <= kShortName ? 2u : k.maxlen <= kInlineName ? 3u : 0u;
   return true;
 }
 // (a pass served by the kept directory folded less than 7/8 of the fraction
-// the latest build's batch folded)
+// the latest build's batch folded; the reference is a built pass, which folds
+// through the first HotHdr::n entries only, so a kept pass in a compact layout
+// of more entries folds more than its build did and cannot sag for that reason)
 bool keep_sagged(const phip_handle* h, const FastPass& p, const u32* c) {
   const phip_handle::HotKeep& k = h->keep;
   return p.hot_age != 0 && (unsigned __int128)c[kCtrHotHits] * k.ref_n * 8 <
@@ -1142,6 +1160,7 @@ void keep_collect(phip_handle* h, const FastPass& p, const u32* c) {
   }
   if (p.built) {
     k.agree = c[kCtrHotOwn] > 0 && (u64)c[kCtrHotKept] * 8 >= (u64)c[kCtrHotOwn] * 7;
+    k.maxlen = c[kCtrHotMaxLen];
     k.ref_hits = c[kCtrHotHits];
     k.ref_n = p.n;
     k.sagged = false;
@@ -3356,6 +3375,7 @@ static int receive_soa(phip_handle* h, const phip_msgs* m, int64_t now, const ph
           // generation go back; what collecting that batch learned stays)
           phip_handle::HotKeep k = keep0;
           k.agree = h->keep.agree;
+          k.maxlen = h->keep.maxlen;
           k.ref_hits = h->keep.ref_hits;
           k.ref_n = h->keep.ref_n;
           k.sagged = h->keep.sagged;

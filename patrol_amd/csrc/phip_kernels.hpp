@@ -311,6 +311,14 @@ constexpr u32 kCtrNSorted = 19;
 // R: apply_policy (keep_collect), only after a pass whose front built.
 constexpr u32 kCtrHotOwn = 20;
 constexpr u32 kCtrHotKept = 21;
+// A directory build's extended selection (F): its entries (HotHdr::n_ext; the
+// two sums above run over them) and the longest name among them, in bytes.
+// W: k_hot_dir's last workgroup, in every launch.  R: apply_policy
+// (keep_collect), only after a pass whose front built: the layout a later
+// pass takes the kept directory in.  They share the first two egress words:
+// those kernels run on G only, this one on F only.
+constexpr u32 kCtrHotExt = 23;
+constexpr u32 kCtrHotMaxLen = 24;
 // 1: the optimistic kernel found its gate shut -- the pass before it, whose
 // counter set it was given, left work -- and returned with nothing written; 0:
 // it ran (F).  W: k_receive_fast<Opt>, one lane, in every launch.
@@ -322,8 +330,8 @@ constexpr u32 kCtrGateShut = 22;
 // whose long name lies outside the arena.  W: k_egress_scan (the totals, the
 // flag's zero), k_egress_write (the flag).  R: apply_mixed (phip_engine.hip),
 // once, after the write.
-constexpr u32 kCtrEgIncast = 23;
-constexpr u32 kCtrEgN = 24;
+constexpr u32 kCtrEgIncast = kCtrHotExt;
+constexpr u32 kCtrEgN = kCtrHotMaxLen;
 constexpr u32 kCtrEgErr = 25;
 // Two u64: the requests' bytes and all the datagrams' (= offs[n]) (G).
 // W: k_egress_scan.  R: apply_mixed.
@@ -780,10 +788,12 @@ __device__ inline u64 enc_replica_nz(u64 b) {
 // (PHIP_HOT_MAX / PHIP_HOT_LDS / PHIP_FAST_BLOCK / PHIP_FAST_PER_CU override
 // the defaults for tuning builds, tools/build_variants.sh.)
 // 736 entries in a 4096-slot lookup (18% load) with two 1024-lane
-// workgroups a CU fill its 160 KB of LDS; against 384 in 1024 slots with
-// four 512-lane workgroups: k_receive_fast 1.78-1.79 vs 1.85 ms on C2
-// (DESIGN.md §4 round 5).  The lookup's load matters as much as the size:
-// 640 entries in 1024 slots ran 2.06 ms.
+// workgroups a CU fill its 160 KiB of LDS -- 16,384 B of lookup and 88 B an
+// entry (tag, three name words, three tail words, slot, arena offset, three
+// maxima): 16,384 + 736 * 88 = 81,152 B, and 12 B of counters, a workgroup;
+// against 384 in 1024 slots with four 512-lane workgroups: k_receive_fast
+// 1.78-1.79 vs 1.85 ms on C2.  The lookup's load
+// matters as much as the size: 640 entries in 1024 slots ran 2.06 ms.
 #ifndef PHIP_HOT_MAX
 #define PHIP_HOT_MAX 736
 #endif
@@ -792,6 +802,32 @@ __device__ inline u64 enc_replica_nz(u64 b) {
 #endif
 constexpr u32 kHotMax = PHIP_HOT_MAX;     // directory entries
 constexpr u32 kHotLds = PHIP_HOT_LDS;     // LDS lookup slots (power of 2, >= 1.5 * kHotMax)
+// The compact layouts of a kept directory (k_receive_fast's NW, DESIGN.md
+// §3.4): a name of <= kShortName bytes is its first two record words, one of
+// <= kInlineName bytes its first three, so an entry is NW name words, the
+// slot and three maxima -- 44 or 52 B -- behind a 16-bit lookup (entry + 1 in
+// 11 bits, 5 bits of the tag beside it).  In the LDS of today's 736:
+//   two words    16,384 + 1472 * 44 = 81,152 B
+//   three words  16,384 + 1216 * 52 = 79,616 B   (1216: the largest multiple
+//                                                 of 64 that fits)
+// k_hot_dir selects up to kHotMaxExt entries, today's kHotMax first.
+// (PHIP_HOT_MAX_EXT / PHIP_HOT_IDX: tools/build_variants.sh)
+#ifndef PHIP_HOT_MAX_EXT
+#define PHIP_HOT_MAX_EXT 1472
+#endif
+#ifndef PHIP_HOT_IDX
+#define PHIP_HOT_IDX 8192
+#endif
+constexpr u32 kHotMaxExt = PHIP_HOT_MAX_EXT;   // entries of the extended selection (two-word class)
+constexpr u32 kHotIdx = PHIP_HOT_IDX;          // 16-bit lookup slots of the compact layouts
+__host__ __device__ constexpr u32 hot_compact_bytes(u32 nw, u32 entries) {
+  return kHotIdx * 2 + entries * (nw * 8 + 4 + 24);
+}
+// (three words: what the two-word class's bytes hold, in multiples of 64)
+constexpr u32 kHotMax3 = (hot_compact_bytes(2, kHotMaxExt) - kHotIdx * 2) / 52 / 64 * 64;
+static_assert(kHotMaxExt >= kHotMax && kHotMaxExt < 2047 && (kHotIdx & (kHotIdx - 1)) == 0 &&
+                  kHotIdx * 2 >= kHotMaxExt * 3,
+              "the compact lookup: 11 bits of entry + 1, at most 2/3 full");
 // The sender-side combine's directory (phip_route_pack): its own size, as its
 // kernels hold less per entry in LDS than k_receive_fast.
 constexpr u32 kRouteHotMax = 512;
@@ -811,10 +847,20 @@ constexpr u32 kHotAloneThreads = PHIP_HOT_ALONE;
 constexpr u32 kHotHist = 4096;        // histogram bins of sample counts
 constexpr u32 kHotMinCount = 8;       // sample hits for a bucket to qualify
 constexpr u32 kHotCandMax = kHotSampleMax / kHotMinCount;   // count-table entries that can qualify
+// k_hot_dir's own sample where nothing runs beside it (an optimistic build):
+// 2^18.  With 2^17 samples of the C2 headline about 1077 buckets reach
+// kHotMinCount, fewer than the extended selection takes; with 2^18 about 2023
+// do.  Beside k_classify (the classified and wire paths) it stays 2^17.
+// Batches below 2^23 messages are sampled at stride 64 either way.  Its
+// count table holds twice the larger sample.
+constexpr u32 kHotSampleMaxAlone = 1u << 18;
+constexpr u32 kHotDirCntBits = 19;
+constexpr u32 kHotDirCandMax = kHotSampleMaxAlone / kHotMinCount;
+static_assert(kHotSampleMaxAlone * 2 <= (1u << kHotDirCntBits), "samples <= half the count table");
 // k_hot_dir's words that must be zero at launch: the two count tables, then
 // its sync words {ticket, candidates} on a line of their own.
 constexpr u32 kHotSyncWords = 16;
-constexpr size_t kHotZeroBytes = (2 * (size_t(1) << kHotCntBits) + kHotSyncWords) * sizeof(u32);
+constexpr size_t kHotZeroBytes = (2 * (size_t(1) << kHotDirCntBits) + kHotSyncWords) * sizeof(u32);
 // Smaller batches skip the directory.  2^16, not larger: a skewed batch of a
 // few 100k messages (C1: 1M into 100k buckets, 13% of them on one bucket)
 // otherwise sends every message of its hottest bucket to one record as a
@@ -841,10 +887,19 @@ struct HotEntry {
 struct HotHdr {
   u32 n;             // directory entries
   u32 thresh;        // sample count threshold that selected them
-  u32 pad[14];
+  // k_hot_dir's extended selection (k_hot_select leaves these 0): entries
+  // [0, n_ext) by descending sample count, the first n today's set; the
+  // longest name among them, in bytes
+  u32 n_ext;
+  u32 maxlen;
+  u32 pad[12];
 };
 
 __device__ inline u32 hot_home(u64 tag) { return (u32)(tag ^ (tag >> 29)) & (kHotLds - 1); }
+// The compact layouts' lookup: the home slot, and the 5 tag bits kept beside
+// the entry index (bits the home slot does not use).
+__device__ inline u32 hot_home_idx(u64 tag) { return (u32)(tag ^ (tag >> 29)) & (kHotIdx - 1); }
+__device__ inline u32 hot_fp(u64 tag) { return (u32)(tag >> 48) & 31u; }
 
 // One record as a directory entry (tail words of a short arena name included).
 __device__ inline HotEntry hot_entry(const Table& T, u32 s) {
@@ -919,10 +974,10 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
   constexpr u32 kWords = 2 * kL > kHotHist ? 2 * kL : kHotHist;
   __shared__ u32 lds[kWords];
   __shared__ u32 part[kThreads];
-  __shared__ u32 sel[kHotMax], selcnt[kHotMax];
-  __shared__ u32 best, nsel, last, own, kept;
+  __shared__ u32 sel[kHotMaxExt], selcnt[kHotMaxExt];
+  __shared__ u32 best, best_ext, nsel, nsel_ext, last, own, kept, maxlen;
   constexpr u32 kPrevSet = 4096;   // the previous directory's slots, looked up in `lds`
-  static_assert(kWords >= kPrevSet && kPrevSet * 2 >= kHotMax * 3, "the previous directory's set");
+  static_assert(kWords >= kPrevSet && kPrevSet * 2 >= kHotMaxExt * 3, "the previous directory's set");
   if (blockIdx.x >= nblk) {
     // The workgroups behind the nblk sampling ones fill the batch's status
     // column with PHIP_ST_MERGED (an optimistic batch: front_optimistic), in the
@@ -965,7 +1020,7 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
     }
   }
   __syncthreads();
-  constexpr u32 mask = (1u << kHotCntBits) - 1;
+  constexpr u32 mask = (1u << kHotDirCntBits) - 1;
   // A lane's LDS entries to the global table with their atomics in flight
   // together (each is a round trip to memory: a CAS on the key, the add on
   // the count, and for the entries that cross kHotMinCount one add on the
@@ -976,7 +1031,7 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
   for (u32 k = 0; k < kE; ++k) {
     key[k] = lkey[k * kThreads + threadIdx.x];
     cnt[k] = lcnt[k * kThreads + threadIdx.x];
-    hh[k] = ((key[k] - 1) * 2654435761u) >> (32 - kHotCntBits);
+    hh[k] = ((key[k] - 1) * 2654435761u) >> (32 - kHotDirCntBits);
     before[k] = ~0u;   // (not counted yet)
   }
   for (u32 tries = 0; tries <= mask; ++tries) {
@@ -1005,7 +1060,7 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
     u32 at = atomicAdd(&sync[1], ncross);
 #pragma unroll
     for (u32 k = 0; k < kE; ++k)
-      if (key[k] && at < kHotCandMax) st_co32(&cand[at++], hh[k]);
+      if (key[k] && at < kHotDirCandMax) st_co32(&cand[at++], hh[k]);
   }
   // the ticket, behind every wave's stores and atomics
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1028,16 +1083,18 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
   // histogram to the selection.  Any beyond are read again.  The first 4096
   // list entries are read along with the list's length, not behind it.
   constexpr u32 kU = 4096 / kThreads;
-  static_assert(4096 <= kHotCandMax, "the list entries read before its length");
+  static_assert(4096 <= kHotDirCandMax, "the list entries read before its length");
   u32 hh0[kU];
 #pragma unroll
   for (u32 k = 0; k < kU; ++k) hh0[k] = ld_co32(&cand[k * kThreads + threadIdx.x]);
-  const u32 ncand = min(ld_co32(&sync[1]), kHotCandMax);
+  const u32 ncand = min(ld_co32(&sync[1]), kHotDirCandMax);
 #pragma unroll
   for (u32 k = 0; k < kU; ++k) hh0[k] = k * kThreads + threadIdx.x < ncand ? hh0[k] & mask : ~0u;
   u32* hist = lds;
   for (u32 e = threadIdx.x; e < kHotHist; e += kThreads) hist[e] = 0;
-  if (threadIdx.x == 0) { best = kHotHist; nsel = 0; own = 0; kept = 0; }
+  if (threadIdx.x == 0) {
+    best = kHotHist; best_ext = kHotHist; nsel = 0; nsel_ext = 0; own = 0; kept = 0; maxlen = 0;
+  }
   __syncthreads();
   auto counts = [&](const u32 (&hh)[kU], u32 (&cc)[kU], u32 (&kk)[kU]) {
 #pragma unroll
@@ -1069,7 +1126,8 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
     count(cc);
   }
   __syncthreads();
-  {   // (k_hot_select's rule, on the LDS histogram)
+  {   // (k_hot_select's rule, on the LDS histogram, for both sizes: the
+      // directory's kHotMax and the extended selection's kHotMaxExt)
     constexpr u32 kBins = kHotHist / kThreads;
     const u32 t = threadIdx.x;
     u32 s = 0;
@@ -1078,23 +1136,34 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
     __syncthreads();
     u32 run = 0;   // slots counted in later chunks
     for (u32 u = t + 1; u < kThreads; ++u) run += part[u];
-    u32 lo = kHotHist;
+    u32 lo = kHotHist, lo_ext = kHotHist;
     for (int b = (int)kBins - 1; b >= 0; --b) {
+      // A bin becomes the candidates counted more often than it: where the
+      // first candidate of its count goes in the directory, which is thereby
+      // ordered by descending count (pick's add hands out the places).  Only
+      // this lane reads its bins.
+      const u32 above = run;
       run += hist[t * kBins + b];
+      hist[t * kBins + b] = above;
       if (run <= kHotMax) lo = t * kBins + b;
+      if (run <= kHotMaxExt) lo_ext = t * kBins + b;
     }
     atomicMin(&best, lo);
+    atomicMin(&best_ext, lo_ext);
     __syncthreads();
   }
   const u32 thresh = best > kHotMinCount ? best : kHotMinCount;
+  const u32 thresh_ext = best_ext > kHotMinCount ? best_ext : kHotMinCount;   // (<= thresh)
   // the selected slots, packed in LDS: every lane then builds its share of
   // the entries, their record reads in flight together
   auto pick = [&](const u32 (&cc)[kU], const u32 (&kk)[kU]) {
 #pragma unroll
     for (u32 k = 0; k < kU; ++k) {
-      if (cc[k] < thresh) continue;
-      const u32 idx = atomicAdd(&nsel, 1u);
-      if (idx < kHotMax) {   // (always: the threshold bounds the count)
+      if (cc[k] < thresh_ext) continue;
+      const u32 idx = atomicAdd(&hist[cc[k] < kHotHist ? cc[k] : kHotHist - 1], 1u);
+      atomicAdd(&nsel_ext, 1u);
+      if (cc[k] >= thresh) atomicAdd(&nsel, 1u);
+      if (idx < kHotMaxExt) {   // (always: the threshold bounds the count)
         sel[idx] = kk[k] - 1;
         selcnt[idx] = cc[k];
       }
@@ -1107,44 +1176,51 @@ __global__ __launch_bounds__(kThreads) void k_hot_dir(Src src, u32 n, u32 stride
     pick(cc, kk);
   }
   __syncthreads();
-  const u32 ns = min(nsel, kHotMax);
+  const u32 ns = min(nsel_ext, kHotMaxExt);
   // Agreement with the directory built before this one (prev_hdr, prev_dir:
   // the other slot of the pair; nullptr: none): its slots into a set in `lds`
   // (the histogram is done with), then own = the selected entries' sample
   // counts and kept = the counts of those the set holds.  The host keeps a
   // directory for later batches while consecutive builds agree (keep_collect).
-  const u32 np = prev_hdr ? min(prev_hdr->n, kHotMax) : 0u;
+  const u32 np = prev_hdr ? min(prev_hdr->n_ext, kHotMaxExt) : 0u;
   for (u32 e = threadIdx.x; e < kPrevSet; e += kThreads) lds[e] = 0;
   __syncthreads();
   for (u32 j = threadIdx.x; j < np; j += kThreads) {
     const u32 s = prev_dir[j].slot;
     u32 ph = (s * 2654435761u) & (kPrevSet - 1);
-    for (;;) {   // at most kHotMax keys in kPrevSet entries
+    for (;;) {   // at most kHotMaxExt keys in kPrevSet entries
       const u32 old = atomicCAS(&lds[ph], 0u, s + 1);
       if (old == 0 || old == s + 1) break;
       ph = (ph + 1) & (kPrevSet - 1);
     }
   }
   __syncthreads();
-  u32 o = 0, kp = 0;
+  u32 o = 0, kp = 0, ml = 0;
 #pragma unroll
-  for (u32 k = 0; k < (kHotMax + kThreads - 1) / kThreads; ++k) {
+  for (u32 k = 0; k < (kHotMaxExt + kThreads - 1) / kThreads; ++k) {
     const u32 j = k * kThreads + threadIdx.x;
     if (j >= ns) continue;
     const u32 s = sel[j];
-    dir[j] = hot_entry(T, s);
+    const HotEntry d = hot_entry(T, s);
+    dir[j] = d;
+    ml = max(ml, (u32)(d.w0 & 0xFFu));
     o += selcnt[j];
     for (u32 ph = (s * 2654435761u) & (kPrevSet - 1); lds[ph]; ph = (ph + 1) & (kPrevSet - 1))
       if (lds[ph] == s + 1) { kp += selcnt[j]; break; }
   }
   if (o) atomicAdd(&own, o);
   if (kp) atomicAdd(&kept, kp);
+  if (ml) atomicMax(&maxlen, ml);
   __syncthreads();
   if (threadIdx.x == 0) {
     ctr[kCtrHotOwn] = own;
     ctr[kCtrHotKept] = kept;
+    ctr[kCtrHotExt] = ns;
+    ctr[kCtrHotMaxLen] = maxlen;
     hdr->n = nsel;
     hdr->thresh = thresh;
+    hdr->n_ext = ns;
+    hdr->maxlen = maxlen;
     st_co32(&sync[0], 0u);
     st_co32(&sync[1], 0u);
   }
@@ -1211,6 +1287,12 @@ __global__ __launch_bounds__(256) void k_hot_select(const u32* __restrict__ hist
 #endif
 constexpr u32 kFastBlock = PHIP_FAST_BLOCK;
 constexpr u32 kFastPerCU = PHIP_FAST_PER_CU;   // resident workgroups per CU (LDS-bound)
+// Static LDS a fast workgroup may take: its share of the CU's 160 KiB (81,920 B
+// at two a CU), the directory and 64 B for the kernel's counters.
+constexpr u32 kHotLdsBudget = 160 * 1024 / kFastPerCU;
+static_assert(hot_compact_bytes(2, kHotMaxExt) + 64 <= kHotLdsBudget &&
+                  hot_compact_bytes(3, kHotMax3) + 64 <= kHotLdsBudget,
+              "the compact layouts in a workgroup's share of the LDS");
 
 // Batch inputs of the fast kernel.  load() issues a message's loads in two
 // dependent rounds (offsets, then everything they address) and returns the
@@ -1697,7 +1779,24 @@ __device__ inline void undo_store(u64x2* p, u32 slot, u64 a, u64 t, i64 e) {
 
 // Messages [lo, n) of the batch (lo a multiple of 64: a segment of a batch
 // classified segment by segment, or 0).
-template <class In, bool Opt = false>
+// NW: the directory's layout in LDS.  0: today's, any name, kHotMax entries
+// (the first of the extended selection).  2, 3: a compact layout (HotCompact)
+// for a kept directory whose build reported no name longer than kShortName /
+// kInlineName bytes, of kHotMaxExt / kHotMax3 entries; an entry with a longer
+// name stays out of the lookup, and messages with longer names take the table
+// path.  Only the optimistic decoded instantiation has them.
+template <u32 NW>
+struct HotCompact {
+  static constexpr u32 kMax = NW == 2 ? kHotMaxExt : kHotMax3;
+  static constexpr u32 kNameMax = NW == 2 ? kShortName : kInlineName;
+  u16 hidx[kHotIdx];      // entry + 1 (0 = empty) | hot_fp << 11
+  u64 hw[NW][kMax];       // canonical name words
+  u64 hmax[3][kMax];      // per-workgroup maxima, as today's
+  u32 hrec[kMax];         // record slot
+};
+static_assert(sizeof(HotCompact<2>) == hot_compact_bytes(2, kHotMaxExt) &&
+              sizeof(HotCompact<3>) == hot_compact_bytes(3, kHotMax3), "the layouts' arithmetic");
+template <class In, bool Opt = false, u32 NW = 0>
 __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_receive_fast(
     In in, u32 lo, u32 n, Table T, Sharded miss, u32* ctr,
     const HotHdr* __restrict__ hot, const HotEntry* __restrict__ hot_dir, const u64* dtab,
@@ -1740,6 +1839,14 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   __shared__ u32 hrec[kHotMax], haoff[kHotMax];
   __shared__ u64 htail[kHotTailWords][kHotMax];
   __shared__ u64 hmax[3][kHotMax];      // per-workgroup maxima (elapsed biased by 2^63)
+  // (NW: the compact layout instead of the arrays above, which such an
+  // instantiation never touches and so does not allocate)
+  static_assert(NW == 0 || (Opt && In::kSoa && (NW == 2 || NW == 3)), "compact: optimistic, decoded");
+  using Compact = HotCompact<NW ? NW : 2>;
+  __shared__ Compact hc;
+  static_assert(NW != 0 || sizeof(hslot) + sizeof(htag) * 4 + sizeof(hrec) * 2 + sizeof(htail) +
+                                   sizeof(hmax) + 64 <= kHotLdsBudget,
+                "today's layout in half a CU's LDS");
   __shared__ u32 hhits;
   __shared__ u32 hlog[2];               // Opt: the workgroup's log entries, overflowed messages
 
@@ -1763,14 +1870,48 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   const bool iso = !Opt && ndr != 0 && ndr <= kDirtyCap;
   if constexpr (!Opt) n = min(n, iso ? ctr[kCtrStop] : min(ctr[kCtrStop], ctr[kCtrDirty]));
   if (n <= lo) return;
-  const u32 nh = hot ? min(hot->n, kHotMax) : 0u;
-  for (u32 j = threadIdx.x; j < kHotLds; j += kFastBlock) hslot[j] = 0;
-  for (u32 j = threadIdx.x; j < kHotMax; j += kFastBlock) {
-    hmax[0][j] = 0; hmax[1][j] = 0; hmax[2][j] = 0;
+  const u32 nh = !hot ? 0u : NW ? min(hot->n_ext, Compact::kMax) : min(hot->n, kHotMax);
+  if constexpr (NW != 0) {
+    u32* const hidx32 = reinterpret_cast<u32*>(hc.hidx);   // (two slots a word)
+    for (u32 j = threadIdx.x; j < kHotIdx / 2; j += kFastBlock) hidx32[j] = 0;
+    for (u32 j = threadIdx.x; j < Compact::kMax; j += kFastBlock) {
+      hc.hmax[0][j] = 0; hc.hmax[1][j] = 0; hc.hmax[2][j] = 0;
+    }
+  } else {
+    for (u32 j = threadIdx.x; j < kHotLds; j += kFastBlock) hslot[j] = 0;
+    for (u32 j = threadIdx.x; j < kHotMax; j += kFastBlock) {
+      hmax[0][j] = 0; hmax[1][j] = 0; hmax[2][j] = 0;
+    }
   }
   if (threadIdx.x == 0) hhits = 0;
   if (Opt && threadIdx.x < 2) hlog[threadIdx.x] = 0;
   __syncthreads();
+  if constexpr (NW != 0) {
+    u32* const hidx32 = reinterpret_cast<u32*>(hc.hidx);
+    for (u32 j = threadIdx.x; j < nh; j += kFastBlock) {
+      const HotEntry d = hot_dir[j];
+      hc.hw[0][j] = d.w0; hc.hw[1][j] = d.w1;
+      if constexpr (NW == 3) hc.hw[2][j] = d.w2;
+      hc.hrec[j] = d.slot;
+      // Validated on load as below (such a directory is always a kept one);
+      // an entry whose name the layout's words do not hold stays out as well.
+      bool same = (u32)(d.w0 & 0xFFu) <= Compact::kNameMax && d.slot <= T.mask();
+      if (same) {
+        const Rec r = load_rec(&T.recs[d.slot]);
+        same = r.tag == d.tag && (rec_flags(r) & kRecPublished) && (r.name0 & ~0xFF00ull) == d.w0 &&
+               r.name1 == d.w1 && r.name2 == d.w2;
+      }
+      if (!same) continue;
+      const u32 val = (j + 1) | (hot_fp(d.tag) << 11);
+      for (u32 hs = hot_home_idx(d.tag);;) {
+        const u32 sh = (hs & 1) * 16;
+        const u32 old = __hip_atomic_load(&hidx32[hs >> 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if ((old >> sh) & 0xFFFFu) { hs = (hs + 1) & (kHotIdx - 1); continue; }
+        // (lost to the word's other slot: the same slot again)
+        if (atomicCAS(&hidx32[hs >> 1], old, old | (val << sh)) == old) break;
+      }
+    }
+  } else
   for (u32 j = threadIdx.x; j < nh; j += kFastBlock) {
     const HotEntry d = hot_dir[j];
     htag[j] = d.tag; hw0[j] = d.w0; hw1[j] = d.w1; hw2[j] = d.w2;
@@ -1891,9 +2032,9 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
         const u64* bw = reinterpret_cast<const u64*>(in.blob());
         const u64 last = (off + len - 1) >> 3, w3i = (off >> 3) + 3;
         inline_name(w0, w1, w2, bw[w3i < last ? w3i : last], off, len, nm);
-      } else if (In::kSoa && len <= kHotTailName) {
+      } else if (In::kSoa && NW == 0 && len <= kHotTailName) {
         // (decoded batches only: the datagram form keeps its registers
-        // for the wire decode)
+        // for the wire decode; a compact directory holds no such name)
         load_name_tail(in.blob(), off, len, nm, tail);
       } else {
         load_name_wide<true>(in.blob(), off, len, nm);
@@ -1911,6 +2052,25 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     i64 ge = 0;
     if (valid) {
       int hidx = -1;
+      if constexpr (NW != 0) {
+        // The name words are the whole name (the length byte in w0): no tag
+        // compare.  The 5 tag bits beside the index turn most strangers away
+        // before their words are read.
+        if (nh && len <= Compact::kNameMax) {
+          const u32 fp = hot_fp(tag);
+          for (u32 hs = hot_home_idx(tag);; hs = (hs + 1) & (kHotIdx - 1)) {
+            const u32 e = hc.hidx[hs];
+            if (!e) break;
+            if ((e >> 11) != fp) continue;
+            const u32 j = (e & 0x7FFu) - 1;
+            if (hc.hw[0][j] == nm.w0 && hc.hw[1][j] == nm.w1 &&
+                (NW == 2 || shortname || hc.hw[2][j] == nm.w2)) {
+              hidx = (int)j;
+              break;
+            }
+          }
+        }
+      } else
       if (nh) {
         for (u32 hs = hot_home(tag);; hs = (hs + 1) & (kHotLds - 1)) {
           const u32 e = hslot[hs];
@@ -1931,7 +2091,12 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
       // to k_dirty_pass (a byte store; doing that work here cost this kernel
       // its registers: 11 spilled, 1.78 -> 2.54 ms on a clean C2 batch).
       if (hidx >= 0) {
-        if (iso && (hrec[hidx] >> 31)) {
+        if constexpr (NW != 0) {
+          ++hits;
+          if (ea > hc.hmax[0][hidx]) atomicMax(&hc.hmax[0][hidx], ea);
+          if (et > hc.hmax[1][hidx]) atomicMax(&hc.hmax[1][hidx], et);
+          if (ee > hc.hmax[2][hidx]) atomicMax(&hc.hmax[2][hidx], ee);
+        } else if (iso && (hrec[hidx] >> 31)) {
           mark[i] = kMarkDirty;
         } else {
           ++hits;
@@ -2003,6 +2168,50 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   // Directory flush: the workgroup's maxima, skipping fields already beaten.
   // (Opt: logged like a cold merge, in the region's reserve -- at most 64
   // entries per wave and round, so the flush always finds room)
+  if constexpr (NW != 0) {
+    // A compact directory has more entries than lanes, so a wave's flush can
+    // log more than the kUndoFlushReserve entries kept for it: what the
+    // wave's loop left of its region takes the rest (the cursor runs on to
+    // the region's end, ulog.cap).  Past that a lane issues no atomic and the
+    // pass counts it in ctr[kCtrLogOver], as the loop does: nothing changes a
+    // record without an entry, and ulog.cnt stays <= cap.
+    for (u32 jb = wave * 64; jb < nh; jb += kFastBlock) {   // (wave-uniform bounds)
+      const u32 j = jb + lane;
+      bool lg = false;
+      u64 xa = 0, xt = 0, xe = 0, ca = 0, ct = 0, ce = 0;
+      Rec* r = nullptr;
+      if (j < nh) {
+        xa = hc.hmax[0][j]; xt = hc.hmax[1][j]; xe = hc.hmax[2][j];
+        if (xa | xt | xe) {
+          r = &T.recs[hc.hrec[j]];
+          ca = r->added; ct = r->taken; ce = (u64)r->elapsed ^ kSign;
+          lg = xa > ca || xt > ct || xe > ce;
+        }
+      }
+      const u64 gm = __ballot(lg);
+      const u32 pos = lcur + lane_rank(gm);
+      if (lg && pos < ulog.cap) {
+        undo_store(lbase + 2 * (size_t)pos, hc.hrec[j], ca, ct, (i64)(ce ^ kSign));
+        if (xa > ca) atomicMax(&r->added, xa);
+        if (xt > ct) atomicMax(&r->taken, xt);
+        if (xe > ce) atomicMax(&r->elapsed, (i64)(xe ^ kSign));
+      }
+      const u32 want = lcur + (u32)__popcll(gm);
+      lover += want > ulog.cap ? want - ulog.cap : 0u;
+      lcur = min(want, ulog.cap);
+    }
+    if (lane == 0) {
+      ulog.cnt[blockIdx.x * kWaves + wave] = lcur;
+      if (lcur) atomicAdd(&hlog[0], lcur);
+      if (lover) atomicAdd(&hlog[1], lover);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      if (hlog[0]) atomicAdd(&ctr[kCtrLogCount], hlog[0]);
+      if (hlog[1]) atomicAdd(&ctr[kCtrLogOver], hlog[1]);
+    }
+    return;
+  } else
   if constexpr (Opt) {
     for (u32 jb = wave * 64; jb < nh; jb += kFastBlock) {   // (wave-uniform bounds)
       const u32 j = jb + lane;
@@ -2042,6 +2251,7 @@ __global__ __launch_bounds__(kFastBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     }
     return;
   }
+  if constexpr (!Opt)
   for (u32 j = threadIdx.x; j < nh; j += kFastBlock) {
     const u64 xa = hmax[0][j], xt = hmax[1][j], xe = hmax[2][j];
     if (!(xa | xt | xe)) continue;

@@ -5,6 +5,11 @@
 # (the status column of a pass on a kept directory, DESIGN.md §4 round 9:
 #  "st0:-DPHIP_STATUS_IN_KERNEL=0" a fill in front of the fast kernel,
 #  "st2:-DPHIP_STATUS_IN_KERNEL=2" stored chunk by chunk in its loop)
+# (the two-word compact layout of a kept directory, DESIGN.md §4 round 10:
+#  the default is 1472 entries behind 8192 16-bit slots, 18% load;
+#  "v1664:-DPHIP_HOT_MAX_EXT=1664 -DPHIP_HOT_IDX=4096" 1664 entries behind 4096
+#  slots, 41% load -- both fill the same LDS; the three-word layout's size
+#  follows from them, kHotMax3)
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/var
