@@ -397,6 +397,49 @@ int copy_back(phip_handle* h, T* user, const T* dev_buf, size_t count, bool dev)
   return PHIP_OK;
 }
 
+// ---- datagram outputs (sweep, change set, reply egress, batch egress) ----
+// The output arguments of a call that writes datagrams and an offsets column,
+// checked before anything is applied; `what` starts the message.  *budget:
+// the bytes the datagrams may take (a device buffer keeps 8 bytes of slack for
+// the whole-word stores).
+int datagram_args(phip_handle* h, const char* what, const uint8_t* out, uint64_t out_cap,
+                  const uint64_t* offs, uint32_t max_msgs, bool dev, u64* budget) {
+  if (!out || !offs) return set_err(h, PHIP_ERR_INVALID, "%s: out and offs are required", what);
+  if (!max_msgs) return set_err(h, PHIP_ERR_INVALID, "%s: max_msgs must be positive", what);
+  if (out_cap < PHIP_BUCKET_PACKET_SIZE)
+    return set_err(h, PHIP_ERR_INVALID, "%s: out_cap below one datagram (%d bytes)", what,
+                   PHIP_BUCKET_PACKET_SIZE);
+  if (dev && ((reinterpret_cast<uintptr_t>(out) & 7) || (out_cap & 7) ||
+              out_cap < PHIP_BUCKET_PACKET_SIZE + 8))
+    return set_err(h, PHIP_ERR_INVALID,
+                   "%s: a device buffer is 8-byte aligned, a multiple of 8 and >= %d bytes", what,
+                   PHIP_BUCKET_PACKET_SIZE + 8);
+  *budget = dev ? out_cap - 8 : out_cap;
+  return PHIP_OK;
+}
+
+// A host-pointer call gets back only what was written: `bytes` bytes of
+// datagrams and n + 1 offsets, staging to caller, on the handle's stream (the
+// caller synchronises).
+int datagrams_back(phip_handle* h, uint8_t* out, const u8* d_out, u64 bytes, uint64_t* offs,
+                   const u64* d_offs, u64 n) {
+  if (bytes) HIPCHK(h, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(offs, d_offs, (n + 1) * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+  return PHIP_OK;
+}
+
+// No datagrams: offs[0] = 0, a device pointer's on the stream (sync: no
+// synchronise of the caller's follows).
+int datagrams_none(phip_handle* h, uint64_t* offs, bool dev, bool sync) {
+  if (!dev) {
+    offs[0] = 0;
+    return PHIP_OK;
+  }
+  HIPCHK(h, hipMemsetAsync(offs, 0, sizeof(u64), h->stream));
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PHIP_OK;
+}
+
 // ----------------------------------------------------------- inserts -----
 inline u64 load_limit(u64 cap, u32 pct) { return cap * pct / 100; }
 
@@ -1999,22 +2042,6 @@ struct ReplyEg {
   bool launched = false;
 };
 
-// The call's caps and buffers, checked before anything is applied.
-int reply_check(phip_handle* h, const phip_reply_egress* rq, bool dev, u64* budget) {
-  if (!rq->out || !rq->offs) return set_err(h, PHIP_ERR_INVALID, "replies: out and offs are required");
-  if (!rq->max_msgs) return set_err(h, PHIP_ERR_INVALID, "replies: max_msgs must be positive");
-  if (rq->out_cap < PHIP_BUCKET_PACKET_SIZE)
-    return set_err(h, PHIP_ERR_INVALID, "replies: out_cap below one datagram (%d bytes)",
-                   PHIP_BUCKET_PACKET_SIZE);
-  if (dev && ((reinterpret_cast<uintptr_t>(rq->out) & 7) || (rq->out_cap & 7) ||
-              rq->out_cap < PHIP_BUCKET_PACKET_SIZE + 8))
-    return set_err(h, PHIP_ERR_INVALID,
-                   "replies: a device buffer is 8-byte aligned, a multiple of 8 and >= %d bytes",
-                   PHIP_BUCKET_PACKET_SIZE + 8);
-  *budget = dev ? rq->out_cap - 8 : rq->out_cap;
-  return PHIP_OK;
-}
-
 // Output buffers for at most `bound` replies (the caller's, or the handle's
 // for a host-pointer call) and the cleared counter block.
 int reply_begin(phip_handle* h, ReplyEg* eg, u64 bound) {
@@ -2095,15 +2122,8 @@ int reply_suffix(phip_handle* h, ReplyEg* eg, Src src, const u8* status, const p
 // synchronise does not follow).
 int reply_collect(phip_handle* h, ReplyEg* eg, bool sync = false) {
   phip_reply_egress& q = *eg->rq;
-  if (!eg->launched) {
-    if (eg->dev) {
-      HIPCHK(h, hipMemsetAsync(q.offs, 0, sizeof(u64), h->stream));
-      if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
-    } else {
-      q.offs[0] = 0;
-    }
-    return PHIP_OK;
-  }
+  if (!eg->launched) return datagrams_none(h, q.offs, eg->dev, sync);
+  int rc;
   u64 c[kRqWords];
   HIPCHK(h, hipMemcpyAsync(c, eg->R.ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2114,10 +2134,8 @@ int reply_collect(phip_handle* h, ReplyEg* eg, bool sync = false) {
                    (unsigned long long)c[kRqN], (unsigned long long)c[kRqBytes],
                    (unsigned long long)c[kRqReplies], (unsigned long long)c[kRqErr]);
   if (!eg->dev) {
-    if (c[kRqBytes])
-      HIPCHK(h, hipMemcpyAsync(q.out, eg->R.out, c[kRqBytes], hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(q.offs, eg->R.offs, (c[kRqN] + 1) * sizeof(u64), hipMemcpyDeviceToHost,
-                             h->stream));
+    if ((rc = datagrams_back(h, q.out, eg->R.out, c[kRqBytes], q.offs, eg->R.offs, c[kRqN])))
+      return rc;
     if (q.src && c[kRqN])
       HIPCHK(h, hipMemcpyAsync(q.src, eg->R.src, c[kRqN] * sizeof(u32), hipMemcpyDeviceToHost,
                                h->stream));
@@ -3319,7 +3337,8 @@ static int reply_enter(phip_handle* h, phip_reply_egress* rq, uint32_t flags, Re
     return set_err(h, PHIP_ERR_INVALID, "replies: PHIP_RECV_ASYNC batches return none");
   eg->rq = rq;
   eg->dev = flags & PHIP_DEVICE_PTRS;
-  return reply_check(h, rq, eg->dev, &eg->budget);
+  return datagram_args(h, "replies", rq->out, rq->out_cap, rq->offs, rq->max_msgs, eg->dev,
+                       &eg->budget);
 }
 
 // phip_receive_soa, and with rq phip_receive_soa_replies (never queued).
@@ -3786,16 +3805,7 @@ static int apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* 
   bool dev = flags & PHIP_DEVICE_PTRS;
   if (eg && (!eg->out || !eg->offs))
     return set_err(h, PHIP_ERR_INVALID, "egress: out and offs are required");
-  if (n == 0) {
-    if (!eg) return PHIP_OK;
-    if (dev) {
-      HIPCHK(h, hipMemsetAsync(eg->offs, 0, sizeof(u64), h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-    } else {
-      eg->offs[0] = 0;
-    }
-    return PHIP_OK;
-  }
+  if (n == 0) return eg ? datagrams_none(h, eg->offs, dev, true) : PHIP_OK;
   if (!ops->kind || !ops->names || !ops->name_offs || !ops->now) return PHIP_ERR_INVALID;
   if (!dev && !names_ok(ops->name_offs, n)) return set_err(h, PHIP_ERR_NAME_TOO_LARGE, "name > 231 bytes");
   bool uniform = false;
@@ -3879,12 +3889,9 @@ static int apply_mixed(phip_handle* h, const phip_ops* ops, const phip_results* 
   if (c[kCtrEgErr] || c[kCtrEgN] > eo.max_msgs || bytes > eo.budget || c[kCtrEgIncast] > c[kCtrEgN])
     return set_err(h, PHIP_ERR_INVALID, "internal: egress of %u datagrams, %llu bytes (flag %u)",
                    c[kCtrEgN], (unsigned long long)bytes, c[kCtrEgErr]);
-  if (!dev) {
-    // only what was written travels back
-    if (bytes) HIPCHK(h, hipMemcpyAsync(eg->out, eo.out, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(eg->offs, eo.offs, ((size_t)c[kCtrEgN] + 1) * sizeof(u64),
-                             hipMemcpyDeviceToHost, h->stream));
-  }
+  // (the copies wait for copy_outputs' synchronise)
+  if (!dev && (rc = datagrams_back(h, eg->out, eo.out, bytes, eg->offs, eo.offs, c[kCtrEgN])))
+    return rc;
   if ((rc = copy_outputs(h, res, n, dev, ow))) return rc;
   eg->n_incast = c[kCtrEgIncast];
   eg->n = c[kCtrEgN];
@@ -4284,6 +4291,94 @@ int phip_evict_idle(phip_handle* h, int64_t now, int64_t idle_ns, uint64_t min_e
   return evict_idle(h, now, idle_ns, min_evict, out, flags);
 }
 
+}  // extern "C"
+
+namespace {
+// ---- the sweep window (export sweep, throttled sweep) ----
+// One call's window of slots: [s0, s_end), ntiles tiles of PHIP_SWEEP_TILE.
+struct SweepWindow {
+  u64 s0, s_end;
+  u32 ntiles;
+  bool restarted;   // the cursor was another layout's: the window begins at slot 0
+};
+
+// The window at the cursor: W slots, rounded up to whole tiles (one at least)
+// and cut at the table's end.  empty: the call asks for nothing (an empty
+// partition mask), reads no slot and is done.
+SweepWindow sweep_open(const phip_handle* h, const phip_sweep_cursor* cur, u64 W,
+                       bool empty = false) {
+  SweepWindow w{};
+  w.s0 = cur->slot;
+  if ((cur->slot || cur->layout) && cur->layout != h->layout_gen) {
+    w.s0 = 0;
+    w.restarted = true;
+  }
+  w.s0 = empty ? h->cap : std::min<u64>(w.s0, h->cap);
+  W = std::max<u64>(W, PHIP_SWEEP_TILE);
+  W = (W + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE * PHIP_SWEEP_TILE;
+  w.s_end = std::min<u64>(w.s0 + W, h->cap);
+  w.ntiles = (u32)((w.s_end - w.s0 + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE);
+  return w;
+}
+
+// The sweep's counter words, read back: one synchronise.
+int sweep_read(phip_handle* h, const u64* ctr, u64 (&c)[kSwWords]) {
+  HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PHIP_OK;
+}
+
+// The end of a window call.  c: the counters behind the write pass (zeros for
+// a window without tiles, which launched nothing), checked against the call's
+// caps; what / unit name the sweep and its entries in the messages.  The
+// cursor moves to the first record not written -- kSwNext counts from
+// next_base -- or to the window's end.
+int sweep_close(phip_handle* h, const SweepWindow& w, const u64 (&c)[kSwWords], const char* what,
+                const char* unit, u64 max_n, u64 budget, u64 next_base, phip_sweep_cursor* cur,
+                phip_sweep_stats* st) {
+  if (c[kSwErr])
+    return set_err(h, PHIP_ERR_INVALID, "internal: %s met a long name outside the arena", what);
+  if (c[kSwN] > max_n || c[kSwBytes] > budget)
+    return set_err(h, PHIP_ERR_INVALID, "internal: %s wrote %llu %s, %llu bytes", what,
+                   (unsigned long long)c[kSwN], unit, (unsigned long long)c[kSwBytes]);
+  const u64 next = w.ntiles && c[kSwNext] != ~0ull ? next_base + c[kSwNext] : w.s_end;
+  cur->slot = next;
+  cur->layout = h->layout_gen;
+  phip_sweep_stats s{};
+  s.n = c[kSwN];
+  s.bytes = c[kSwBytes];
+  s.slots_scanned = w.s_end - w.s0;
+  s.restarted = w.restarted;
+  s.done = next >= h->cap;
+  *st = s;
+  return PHIP_OK;
+}
+
+// Count mode: the counters cleared, launch(grid, buffer) over the whole table
+// on the striding grid (a few workgroups per compute unit), the two sums read
+// back.  mw: the words of a mask behind the counters.
+template <class F>
+int sweep_count_mode(phip_handle* h, size_t mw, F launch, phip_sweep_stats* st) {
+  int rc;
+  u64* ctr;
+  u64 c[kSwWords];
+  if ((rc = ensure(h, B_SWEEP, SweepBuf::words(mw, 0), &ctr))) return rc;
+  HIPCHK(h, hipMemsetAsync(ctr, 0, kSwWords * sizeof(u64), h->stream));
+  if ((rc = launch(std::min<unsigned>(grid_for(h->cap), 8u * (unsigned)h->ncu),
+                   SweepBuf(ctr, mw, 0))))
+    return rc;
+  HIPCHK(h, hipGetLastError());
+  if ((rc = sweep_read(h, ctr, c))) return rc;
+  phip_sweep_stats s{};
+  s.n = c[kSwN];
+  s.bytes = c[kSwBytes];
+  s.slots_scanned = h->cap;
+  *st = s;
+  return PHIP_OK;
+}
+}  // namespace
+
+extern "C" {
 // Export sweep (patrolhip.h "Anti-entropy sweep"; kernels in phip_kernels.hpp
 // "export sweep").  One window of slots per call: count per tile, scan, write.
 // A device-pointer call reads the four counters back once, at its end; a
@@ -4316,101 +4411,64 @@ static int export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int
                                                : part_mask[w]);
   const bool none = parts && !m;
   int rc;
-  u64 c[kSwWords] = {};
-  phip_sweep_stats s{};
   if (flags & PHIP_SWEEP_COUNT) {
     if (out) return set_err(h, PHIP_ERR_INVALID, "sweep: count mode takes no output buffer");
     if (none) {
-      *st = s;
+      *st = phip_sweep_stats{};
       return PHIP_OK;
     }
-    u64* ctr;
-    if ((rc = ensure(h, B_SWEEP, kSwWords + mw, &ctr))) return rc;
-    HIPCHK(h, hipMemsetAsync(ctr, 0, kSwWords * sizeof(u64), h->stream));
-    if (parts)
-      HIPCHK(h, hipMemcpyAsync(ctr + kSwWords, part_mask, mw * sizeof(u64), hipMemcpyHostToDevice,
-                               h->stream));
-    {
+    return sweep_count_mode(h, mw, [&](unsigned grid, const SweepBuf& b) -> int {
+      if (parts)
+        HIPCHK(h, hipMemcpyAsync(b.mask, part_mask, mw * sizeof(u64), hipMemcpyHostToDevice,
+                                 h->stream));
       Launch l(h, "k_sweep_count");
-      const unsigned grid = std::min<unsigned>(grid_for(h->cap), 8u * (unsigned)h->ncu);
       if (parts)
         k_sweep_count<false, true><<<grid, kBlock, 0, h->stream>>>(
-            h->recs, 0, h->cap, now, idle_ns, nullptr, nullptr, ctr,
-            SweepParts<true>{ctr + kSwWords, log2_parts});
+            h->recs, 0, h->cap, now, idle_ns, nullptr, nullptr, b.ctr,
+            SweepParts<true>{b.mask, log2_parts});
       else
         k_sweep_count<false, false><<<grid, kBlock, 0, h->stream>>>(
-            h->recs, 0, h->cap, now, idle_ns, nullptr, nullptr, ctr, SweepParts<false>{});
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    s.n = c[kSwN];
-    s.bytes = c[kSwBytes];
-    s.slots_scanned = h->cap;
-    *st = s;
-    return PHIP_OK;
+            h->recs, 0, h->cap, now, idle_ns, nullptr, nullptr, b.ctr, SweepParts<false>{});
+      return PHIP_OK;
+    }, st);
   }
-  if (!out || !offs) return set_err(h, PHIP_ERR_INVALID, "sweep: out and offs are required");
-  if (!max_msgs) return set_err(h, PHIP_ERR_INVALID, "sweep: max_msgs must be positive");
-  if (out_cap < PHIP_BUCKET_PACKET_SIZE)
-    return set_err(h, PHIP_ERR_INVALID, "sweep: out_cap below one datagram (%d bytes)",
-                   PHIP_BUCKET_PACKET_SIZE);
-  if (dev && ((reinterpret_cast<uintptr_t>(out) & 7) || (out_cap & 7) ||
-              out_cap < PHIP_BUCKET_PACKET_SIZE + 8))
-    return set_err(h, PHIP_ERR_INVALID,
-                   "sweep: a device buffer is 8-byte aligned, a multiple of 8 and >= %d bytes",
-                   PHIP_BUCKET_PACKET_SIZE + 8);
-  const u64 budget = dev ? out_cap - 8 : out_cap;
-
-  u64 s0 = cur->slot;
-  if (cur->slot || cur->layout) {
-    if (cur->layout != h->layout_gen) {
-      s0 = 0;
-      s.restarted = 1;
-    }
-  }
-  s0 = std::min<u64>(s0, h->cap);
-  if (none) s0 = h->cap;   // (an empty mask reads no slot and is done)
-  // (4 * 2^32 * 2^20 < 2^64: the product cannot wrap)
-  u64 W = std::max<u64>(4ull * max_msgs * ((nparts + std::max<u64>(m, 1) - 1) / std::max<u64>(m, 1)),
-                        PHIP_SWEEP_TILE);
-  W = (W + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE * PHIP_SWEEP_TILE;
-  const u64 s_end = std::min<u64>(s0 + W, h->cap);
-  s.slots_scanned = s_end - s0;
-  const u32 ntiles = (u32)((s_end - s0 + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE);
-  u64 next = s_end;
-  if (ntiles) {
-    // one buffer: the counters, the mask, the tiles' byte sums, the tiles' counts
+  u64 budget;
+  if ((rc = datagram_args(h, "sweep", out, out_cap, offs, max_msgs, dev, &budget))) return rc;
+  // four slots per datagram asked for, times the partitions per partition
+  // asked for (4 * 2^32 * 2^20 < 2^64: the product cannot wrap); an empty
+  // mask reads no slot and is done
+  const u64 share = (nparts + std::max<u64>(m, 1) - 1) / std::max<u64>(m, 1);
+  const SweepWindow w = sweep_open(h, cur, 4ull * max_msgs * share, none);
+  u64 c[kSwWords] = {};
+  u8* d_out = out;
+  u64* d_offs = reinterpret_cast<u64*>(offs);
+  if (w.ntiles) {
     u64* ctr;
-    if ((rc = ensure(h, B_SWEEP, kSwWords + mw + (size_t)ntiles + ((size_t)ntiles + 1) / 2, &ctr)))
-      return rc;
-    u64* d_mask = ctr + kSwWords;
-    u64* tile_bytes = d_mask + mw;
-    u32* tile_cnt = (u32*)(tile_bytes + ntiles);
-    const SweepParts<true> sp{d_mask, log2_parts};
+    if ((rc = ensure(h, B_SWEEP, SweepBuf::words(mw, w.ntiles), &ctr))) return rc;
+    const SweepBuf b(ctr, mw, w.ntiles);
+    const SweepParts<true> sp{b.mask, log2_parts};
     if (parts)
-      HIPCHK(h, hipMemcpyAsync(d_mask, part_mask, mw * sizeof(u64), hipMemcpyHostToDevice,
+      HIPCHK(h, hipMemcpyAsync(b.mask, part_mask, mw * sizeof(u64), hipMemcpyHostToDevice,
                                h->stream));
     {
       Launch l(h, "k_sweep_count");
       if (parts)
-        k_sweep_count<true, true><<<ntiles, kBlock, 0, h->stream>>>(h->recs, s0, s_end, now, idle_ns,
-                                                                    tile_cnt, tile_bytes, ctr, sp);
+        k_sweep_count<true, true><<<w.ntiles, kBlock, 0, h->stream>>>(
+            h->recs, w.s0, w.s_end, now, idle_ns, b.tile_cnt, b.tile_bytes, ctr, sp);
       else
-        k_sweep_count<true, false><<<ntiles, kBlock, 0, h->stream>>>(
-            h->recs, s0, s_end, now, idle_ns, tile_cnt, tile_bytes, ctr, SweepParts<false>{});
+        k_sweep_count<true, false><<<w.ntiles, kBlock, 0, h->stream>>>(
+            h->recs, w.s0, w.s_end, now, idle_ns, b.tile_cnt, b.tile_bytes, ctr,
+            SweepParts<false>{});
     }
     {
       Launch l(h, "k_sweep_scan");
-      k_sweep_scan<<<1, kSweepBlock, 0, h->stream>>>(tile_cnt, tile_bytes, ntiles, ctr);
+      k_sweep_scan<<<1, kSweepBlock, 0, h->stream>>>(b.tile_cnt, b.tile_bytes, w.ntiles, ctr);
     }
     HIPCHK(h, hipGetLastError());
-    u8* d_out = out;
-    u64* d_offs = reinterpret_cast<u64*>(offs);
     if (!dev) {
-      HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      if ((rc = ensure(h, B_EXPORT, (size_t)std::min<u64>(out_cap, c[kSwBytes]), &d_out)) ||
+      // staging sized by what the window holds, not by the caller's caps
+      if ((rc = sweep_read(h, ctr, c)) ||
+          (rc = ensure(h, B_EXPORT, (size_t)std::min<u64>(out_cap, c[kSwBytes]), &d_out)) ||
           (rc = ensure(h, B_OFFS, (size_t)std::min<u64>(max_msgs, c[kSwN]) + 1, &d_offs)))
         return rc;
     }
@@ -4419,41 +4477,23 @@ static int export_sweep(phip_handle* h, phip_sweep_cursor* cur, int64_t now, int
       // the cursor would cost a device-pointer call a second round trip)
       Launch l(h, "k_sweep_write");
       if (parts)
-        k_sweep_write<true><<<ntiles, kSweepBlock, 0, h->stream>>>(
-            h->recs, h->arena, h->arena_cap, s0, s_end, now, idle_ns, tile_cnt, tile_bytes,
+        k_sweep_write<true><<<w.ntiles, kSweepBlock, 0, h->stream>>>(
+            h->recs, h->arena, h->arena_cap, w.s0, w.s_end, now, idle_ns, b.tile_cnt, b.tile_bytes,
             max_msgs, budget, d_out, d_offs, ctr, sp);
       else
-        k_sweep_write<false><<<ntiles, kSweepBlock, 0, h->stream>>>(
-            h->recs, h->arena, h->arena_cap, s0, s_end, now, idle_ns, tile_cnt, tile_bytes,
+        k_sweep_write<false><<<w.ntiles, kSweepBlock, 0, h->stream>>>(
+            h->recs, h->arena, h->arena_cap, w.s0, w.s_end, now, idle_ns, b.tile_cnt, b.tile_bytes,
             max_msgs, budget, d_out, d_offs, ctr, SweepParts<false>{});
     }
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (c[kSwErr]) return set_err(h, PHIP_ERR_INVALID, "internal: sweep met a long name outside the arena");
-    if (c[kSwN] > max_msgs || c[kSwBytes] > budget)
-      return set_err(h, PHIP_ERR_INVALID, "internal: sweep wrote %llu datagrams, %llu bytes",
-                     (unsigned long long)c[kSwN], (unsigned long long)c[kSwBytes]);
-    s.n = c[kSwN];
-    s.bytes = c[kSwBytes];
-    if (c[kSwNext] != ~0ull) next = c[kSwNext];
-    if (!dev) {
-      // only what was written travels back
-      if (s.bytes) HIPCHK(h, hipMemcpyAsync(out, d_out, s.bytes, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipMemcpyAsync(offs, d_offs, (s.n + 1) * sizeof(u64), hipMemcpyDeviceToHost,
-                               h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-  } else if (dev) {
-    HIPCHK(h, hipMemsetAsync(offs, 0, sizeof(u64), h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  } else {
-    offs[0] = 0;
+    if ((rc = sweep_read(h, ctr, c))) return rc;
   }
-  cur->slot = next;
-  cur->layout = h->layout_gen;
-  s.done = next >= h->cap;
-  *st = s;
+  if ((rc = sweep_close(h, w, c, "sweep", "datagrams", max_msgs, budget, 0, cur, st))) return rc;
+  if (!w.ntiles) return datagrams_none(h, offs, dev, true);
+  if (!dev) {
+    if ((rc = datagrams_back(h, out, d_out, st->bytes, offs, d_offs, st->n))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
   return PHIP_OK;
 }
 
@@ -4473,9 +4513,9 @@ int phip_export_sweep_parts(phip_handle* h, phip_sweep_cursor* cur, int64_t now,
 }
 
 // Throttled sweep (patrolhip.h "Throttled sweep"; kernels in phip_kernels.hpp
-// "throttled sweep"): export_sweep's window, cursor, tile arrays, scan and
-// read-backs, with the rule table -- rates derived here, once -- as a kernel
-// argument.  Nothing of the handle changes but its scratch buffers.
+// "throttled sweep"): the sweep's window, tile arrays and scan, with the rule
+// table -- rates derived here, once -- as a kernel argument.  Nothing of the
+// handle changes but its scratch buffers.
 int phip_export_throttled(phip_handle* h, phip_sweep_cursor* cur, const phip_throttle_rule* rules,
                           uint32_t n_rules, int64_t now, int64_t min_wait_ns,
                           const phip_throttled_out* out, phip_sweep_stats* st, uint32_t flags) {
@@ -4500,27 +4540,14 @@ int phip_export_throttled(phip_handle* h, phip_sweep_cursor* cur, const phip_thr
   if (__builtin_add_overflow((i64)now, (i64)min_wait_ns, &later)) later = INT64_MAX;
   const bool dev = flags & PHIP_DEVICE_PTRS;
   int rc;
-  u64 c[kSwWords] = {};
-  phip_sweep_stats s{};
   if (flags & PHIP_SWEEP_COUNT) {
     if (out) return set_err(h, PHIP_ERR_INVALID, "throttled: count mode takes no output");
-    u64* ctr;
-    if ((rc = ensure(h, B_SWEEP, kSwWords, &ctr))) return rc;
-    HIPCHK(h, hipMemsetAsync(ctr, 0, kSwWords * sizeof(u64), h->stream));
-    {
+    return sweep_count_mode(h, 0, [&](unsigned grid, const SweepBuf& b) -> int {
       Launch l(h, "k_throttle_count");
-      const unsigned grid = std::min<unsigned>(grid_for(h->cap), 8u * (unsigned)h->ncu);
       k_throttle_count<false><<<grid, kBlock, 0, h->stream>>>(h->recs, 0, h->cap, now, later, nullptr,
-                                                              nullptr, ctr, R);
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    s.n = c[kSwN];
-    s.bytes = c[kSwBytes];
-    s.slots_scanned = h->cap;
-    *st = s;
-    return PHIP_OK;
+                                                              nullptr, b.ctr, R);
+      return PHIP_OK;
+    }, st);
   }
   if (!out || !out->names || !out->offs)
     return set_err(h, PHIP_ERR_INVALID, "throttled: out, its names and its offs are required");
@@ -4530,42 +4557,28 @@ int phip_export_throttled(phip_handle* h, phip_sweep_cursor* cur, const phip_thr
     return set_err(h, PHIP_ERR_INVALID, "throttled: names_cap below one name (%d bytes)",
                    PHIP_MAX_NAME_LEN);
   const u64 budget = o.names_cap;
-
-  u64 s0 = cur->slot;
-  if ((cur->slot || cur->layout) && cur->layout != h->layout_gen) {
-    s0 = 0;
-    s.restarted = 1;
-  }
-  s0 = std::min<u64>(s0, h->cap);
-  u64 W = std::max<u64>(4ull * o.max_entries, PHIP_SWEEP_TILE);
-  W = (W + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE * PHIP_SWEEP_TILE;
-  const u64 s_end = std::min<u64>(s0 + W, h->cap);
-  s.slots_scanned = s_end - s0;
-  const u32 ntiles = (u32)((s_end - s0 + PHIP_SWEEP_TILE - 1) / PHIP_SWEEP_TILE);
-  u64 next = s_end;
-  if (ntiles) {
-    // one buffer: the counters, the tiles' byte sums, the tiles' counts
+  const SweepWindow w = sweep_open(h, cur, 4ull * o.max_entries);
+  const u32 nwin = (u32)(w.s_end - w.s0);
+  u64 c[kSwWords] = {};
+  ThrottledOut d{o.names, reinterpret_cast<u64*>(o.offs), reinterpret_cast<i64*>(o.retry_at),
+                 reinterpret_cast<u64*>(o.remaining), o.rule};
+  if (w.ntiles) {
     u64* ctr;
-    if ((rc = ensure(h, B_SWEEP, kSwWords + (size_t)ntiles + ((size_t)ntiles + 1) / 2, &ctr)))
-      return rc;
-    u64* tile_bytes = ctr + kSwWords;
-    u32* tile_cnt = (u32*)(tile_bytes + ntiles);
+    if ((rc = ensure(h, B_SWEEP, SweepBuf::words(0, w.ntiles), &ctr))) return rc;
+    const SweepBuf b(ctr, 0, w.ntiles);
     {
       Launch l(h, "k_throttle_count");
-      k_throttle_count<true><<<ntiles, kBlock, 0, h->stream>>>(h->recs, s0, s_end, now, later,
-                                                               tile_cnt, tile_bytes, ctr, R);
+      k_throttle_count<true><<<w.ntiles, kBlock, 0, h->stream>>>(h->recs, w.s0, w.s_end, now, later,
+                                                                 b.tile_cnt, b.tile_bytes, ctr, R);
     }
     {
       Launch l(h, "k_sweep_scan");
-      k_sweep_scan<<<1, kSweepBlock, 0, h->stream>>>(tile_cnt, tile_bytes, ntiles, ctr);
+      k_sweep_scan<<<1, kSweepBlock, 0, h->stream>>>(b.tile_cnt, b.tile_bytes, w.ntiles, ctr);
     }
     HIPCHK(h, hipGetLastError());
-    ThrottledOut d{o.names, reinterpret_cast<u64*>(o.offs), reinterpret_cast<i64*>(o.retry_at),
-                   reinterpret_cast<u64*>(o.remaining), o.rule};
     if (!dev) {
       // staging sized by what the window holds, not by the caller's caps
-      HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
+      if ((rc = sweep_read(h, ctr, c))) return rc;
       const size_t ne = (size_t)std::min<u64>(o.max_entries, c[kSwN]);
       if ((rc = ensure(h, B_EXPORT, (size_t)std::min<u64>(o.names_cap, c[kSwBytes]), &d.names)) ||
           (rc = ensure(h, B_OFFS, ne + 1, &d.offs)) ||
@@ -4575,55 +4588,36 @@ int phip_export_throttled(phip_handle* h, phip_sweep_cursor* cur, const phip_thr
         return rc;
     }
     {
-      // (long names are bounded by the arena's size, as in export_sweep)
+      // (long names are bounded by the arena's size, as in export_sweep; the
+      // kernel finds the tile arrays behind ctr by SweepBuf)
       Launch l(h, "k_throttle_write");
-      k_throttle_write<<<ntiles, kSweepBlock, 0, h->stream>>>(
-          h->recs + s0, (u32)(s_end - s0), h->arena, h->arena_cap, now, later, o.max_entries, budget,
-          d, ctr, R);   // (the tile arrays: behind ctr, by the layout above)
+      k_throttle_write<<<w.ntiles, kSweepBlock, 0, h->stream>>>(
+          h->recs + w.s0, nwin, h->arena, h->arena_cap, now, later, o.max_entries, budget, d, ctr, R);
     }
     // the retry search, one lane per written entry; their number is on the
     // device (the counter word), the grid goes by what the host knows of it:
     // the window's total after the scan, or (device pointers) the window
-    const u64 most = std::min<u64>(o.max_entries, dev ? s_end - s0 : c[kSwN]);
+    const u64 most = std::min<u64>(o.max_entries, dev ? nwin : c[kSwN]);
     if (d.retry_at && most) {
       Launch l(h, "k_throttle_retry");
       const unsigned grid = std::min<unsigned>(grid_for(most), 16u * (unsigned)h->ncu);
-      k_throttle_retry<<<grid, kBlock, 0, h->stream>>>(h->recs + s0, (u32)(s_end - s0), now,
-                                                       d.retry_at, ctr, R);
+      k_throttle_retry<<<grid, kBlock, 0, h->stream>>>(h->recs + w.s0, nwin, now, d.retry_at, ctr, R);
     }
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (c[kSwErr])
-      return set_err(h, PHIP_ERR_INVALID, "internal: throttled sweep met a long name outside the arena");
-    if (c[kSwN] > o.max_entries || c[kSwBytes] > budget)
-      return set_err(h, PHIP_ERR_INVALID, "internal: throttled sweep wrote %llu entries, %llu bytes",
-                     (unsigned long long)c[kSwN], (unsigned long long)c[kSwBytes]);
-    s.n = c[kSwN];
-    s.bytes = c[kSwBytes];
-    if (c[kSwNext] != ~0ull) next = s0 + c[kSwNext];   // (the kernel counts from the window's first)
-    if (!dev) {
-      // only what was written travels back
-      if (s.bytes)
-        HIPCHK(h, hipMemcpyAsync(o.names, d.names, s.bytes, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipMemcpyAsync(o.offs, d.offs, (s.n + 1) * sizeof(u64), hipMemcpyDeviceToHost,
-                               h->stream));
-      if ((rc = copy_back(h, reinterpret_cast<i64*>(o.retry_at), d.retry_at, s.n, false)) ||
-          (rc = copy_back(h, reinterpret_cast<u64*>(o.remaining), d.remaining, s.n, false)) ||
-          (rc = copy_back(h, o.rule, d.rule, s.n, false)))
-        return rc;
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-  } else if (dev) {
-    HIPCHK(h, hipMemsetAsync(o.offs, 0, sizeof(u64), h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  } else {
-    o.offs[0] = 0;
+    if ((rc = sweep_read(h, ctr, c))) return rc;
   }
-  cur->slot = next;
-  cur->layout = h->layout_gen;
-  s.done = next >= h->cap;
-  *st = s;
+  // (k_throttle_write counts slots from the window's first)
+  if ((rc = sweep_close(h, w, c, "throttled sweep", "entries", o.max_entries, budget, w.s0, cur, st)))
+    return rc;
+  if (!w.ntiles) return datagrams_none(h, o.offs, dev, true);
+  if (!dev) {
+    if ((rc = datagrams_back(h, o.names, d.names, st->bytes, o.offs, d.offs, st->n)) ||
+        (rc = copy_back(h, reinterpret_cast<i64*>(o.retry_at), d.retry_at, st->n, false)) ||
+        (rc = copy_back(h, reinterpret_cast<u64*>(o.remaining), d.remaining, st->n, false)) ||
+        (rc = copy_back(h, o.rule, d.rule, st->n, false)))
+      return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
   return PHIP_OK;
 }
 
@@ -4643,24 +4637,15 @@ int phip_export_changed(phip_handle* h, uint8_t* out, uint64_t out_cap, uint64_t
   if (flags & ~(PHIP_DEVICE_PTRS | PHIP_SWEEP_COUNT))
     return set_err(h, PHIP_ERR_INVALID, "changes: unknown flag bits 0x%x", flags);
   const bool dev = flags & PHIP_DEVICE_PTRS, count = flags & PHIP_SWEEP_COUNT;
+  int rc;
+  u64 budget = 0;
   if (count) {
     if (out) return set_err(h, PHIP_ERR_INVALID, "changes: count mode takes no output buffer");
-  } else {
-    if (!out || !offs) return set_err(h, PHIP_ERR_INVALID, "changes: out and offs are required");
-    if (!max_msgs) return set_err(h, PHIP_ERR_INVALID, "changes: max_msgs must be positive");
-    if (out_cap < PHIP_BUCKET_PACKET_SIZE)
-      return set_err(h, PHIP_ERR_INVALID, "changes: out_cap below one datagram (%d bytes)",
-                     PHIP_BUCKET_PACKET_SIZE);
-    if (dev && ((reinterpret_cast<uintptr_t>(out) & 7) || (out_cap & 7) ||
-                out_cap < PHIP_BUCKET_PACKET_SIZE + 8))
-      return set_err(h, PHIP_ERR_INVALID,
-                     "changes: a device buffer is 8-byte aligned, a multiple of 8 and >= %d bytes",
-                     PHIP_BUCKET_PACKET_SIZE + 8);
+  } else if ((rc = datagram_args(h, "changes", out, out_cap, offs, max_msgs, dev, &budget))) {
+    return rc;
   }
-  const u64 budget = dev ? out_cap - 8 : out_cap;
   const u64 nwords = mark_words(h->cap);
   const u32 ntiles = (u32)((h->cap + kSweepTile - 1) / kSweepTile);
-  int rc;
   // one buffer: the tiles' byte sums, then their counts (both sections each)
   u64* tile_bytes;
   if ((rc = ensure(h, B_EGTILE, 3 * (size_t)ntiles, &tile_bytes))) return rc;
@@ -4721,10 +4706,7 @@ int phip_export_changed(phip_handle* h, uint8_t* out, uint64_t out_cap, uint64_t
   s.pending = c[kCtrChgMarks] - c[kCtrChgCleared];
   s.done = s.pending == 0;
   if (!dev) {
-    // only what was written travels back
-    if (s.bytes) HIPCHK(h, hipMemcpyAsync(out, d_out, s.bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(offs, d_offs, (s.n + 1) * sizeof(u64), hipMemcpyDeviceToHost,
-                             h->stream));
+    if ((rc = datagrams_back(h, out, d_out, s.bytes, offs, d_offs, s.n))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
   *st = s;

@@ -6083,6 +6083,117 @@ __device__ inline u32 sweep_size(const Rec& r, i64 now, i64 idle_ns,
   return PHIP_BUCKET_FIXED_SIZE + len;
 }
 
+// ---- what the ranked exports share (sweep, throttled sweep, batch egress,
+// change set, reply egress) ----
+//
+// The sweep's device buffer in u64 words, stated once for the host and for
+// k_throttle_write: the kSwWords counters, the partition mask's mw words (none
+// for the unfiltered and the throttled sweep), the tiles' byte sums, the
+// tiles' counts (u32).  Count mode has no tiles.
+struct SweepBuf {
+  u64* ctr;
+  u64* mask;
+  u64* tile_bytes;
+  u32* tile_cnt;
+  __host__ __device__ SweepBuf(u64* c, size_t mw, u32 ntiles)
+      : ctr(c), mask(c + kSwWords), tile_bytes(mask + mw), tile_cnt((u32*)(tile_bytes + ntiles)) {}
+  static size_t words(size_t mw, u32 ntiles) {
+    return kSwWords + mw + (size_t)ntiles + ((size_t)ntiles + 1) / 2;
+  }
+};
+
+// The end of a count pass.  wave_sum: every lane's (n, b) becomes its wave's.
+// tile_sum: a workgroup of kBlock sums them; true for thread 0 alone, whose n
+// and b are then the workgroup's.  count_finish: the tile's sums into its slot
+// of the tile arrays (plain stores), or (count mode) one add per wave and
+// counter word.
+__device__ inline void wave_sum(u32& n, u64& b) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    n += __shfl_xor(n, d);
+    b += __shfl_xor(b, d);
+  }
+}
+
+__device__ inline bool tile_sum(u32& n, u64& b) {
+  __shared__ u32 wn[kBlock / 64];
+  __shared__ u64 wb[kBlock / 64];
+  wave_sum(n, b);
+  if (__lane_id() == 0) { wn[threadIdx.x >> 6] = n; wb[threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x != 0) return false;
+  n = 0;
+  b = 0;
+  for (u32 i = 0; i < kBlock / 64; ++i) { n += wn[i]; b += wb[i]; }
+  return true;
+}
+
+template <bool kTiles>
+__device__ inline void count_finish(u32 n, u64 b, u32* __restrict__ tile_cnt,
+                                    u64* __restrict__ tile_bytes, u64* ctr) {
+  if (kTiles) {
+    if (tile_sum(n, b)) {
+      tile_cnt[blockIdx.x] = n;
+      tile_bytes[blockIdx.x] = b;
+    }
+  } else {
+    wave_sum(n, b);
+    if (__lane_id() == 0) {
+      if (n) atomicAdd(&ctr[kSwN], (u64)n);
+      if (b) atomicAdd(&ctr[kSwBytes], b);
+    }
+  }
+}
+
+__device__ inline u64 wave_incl_scan64(u64 v) {
+  const u32 lane = __lane_id();
+#pragma unroll
+  for (u32 d = 1; d < 64; d <<= 1) {
+    const u64 o = __shfl_up(v, d);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+// The tile scan: exclusive scans of cnt[0..n) / bytes[0..n) in place, one
+// workgroup of kSweepBlock walking the entries in chunks of its size with a
+// running carry.  Every thread returns the two totals, and the walk ends on a
+// barrier: the caller may read scanned entries.
+struct TileTotals {
+  u64 n, bytes;
+};
+__device__ inline TileTotals tile_scan(u32* __restrict__ cnt, u64* __restrict__ bytes, u32 n) {
+  __shared__ u32 wn[kSweepBlock / 64];
+  __shared__ u64 wb[kSweepBlock / 64];
+  // (uniform in a wave, and told so: the sums of the waves before this one are
+  // then scalar selects, not eight lane masks held through the chunk)
+  const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  u64 carry_n = 0, carry_b = 0;
+  for (u32 base = 0; base < n; base += kSweepBlock) {
+    const u32 i = base + threadIdx.x;
+    const u32 c = i < n ? cnt[i] : 0u;
+    const u64 b = i < n ? bytes[i] : 0ull;
+    const u32 sc = wave_incl_scan(c);
+    const u64 sb = wave_incl_scan64(b);
+    if (__lane_id() == 63) { wn[wv] = sc; wb[wv] = sb; }
+    __syncthreads();
+    u64 pn = 0, pb = 0, tn = 0, tb = 0;
+    for (u32 w = 0; w < kSweepBlock / 64; ++w) {
+      if (w < wv) { pn += wn[w]; pb += wb[w]; }
+      tn += wn[w];
+      tb += wb[w];
+    }
+    if (i < n) {
+      cnt[i] = (u32)(carry_n + pn + sc - c);   // (at most 2^31 slots or datagrams: the u32 holds)
+      bytes[i] = carry_b + pb + sb - b;
+    }
+    carry_n += tn;
+    carry_b += tb;
+    __syncthreads();   // (the totals are read before the next chunk overwrites them)
+  }
+  return {carry_n, carry_b};
+}
+
 // Count pass.  kTiles: workgroup t sums tile t of the window [s0, s_end) into
 // tile_cnt[t] / tile_bytes[t] (plain stores, no atomics).  Otherwise (count
 // mode over the whole table) k_evict_count's grid: a few workgroups per
@@ -6113,74 +6224,19 @@ __global__ __launch_bounds__(kBlock) void k_sweep_count(const Rec* __restrict__ 
       b += sz;
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    n += __shfl_xor(n, d);
-    b += __shfl_xor(b, d);
-  }
-  if (kTiles) {
-    __shared__ u32 wn[kBlock / 64];
-    __shared__ u64 wb[kBlock / 64];
-    if (__lane_id() == 0) { wn[threadIdx.x >> 6] = n; wb[threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      u32 tn = 0;
-      u64 tb = 0;
-      for (u32 i = 0; i < kBlock / 64; ++i) { tn += wn[i]; tb += wb[i]; }
-      tile_cnt[blockIdx.x] = tn;
-      tile_bytes[blockIdx.x] = tb;
-    }
-  } else if (__lane_id() == 0) {
-    if (n) atomicAdd(&ctr[kSwN], (u64)n);
-    if (b) atomicAdd(&ctr[kSwBytes], b);
-  }
+  count_finish<kTiles>(n, b, tile_cnt, tile_bytes, ctr);
 }
 
-__device__ inline u64 wave_incl_scan64(u64 v) {
-  const u32 lane = __lane_id();
-#pragma unroll
-  for (u32 d = 1; d < 64; d <<= 1) {
-    const u64 o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// Exclusive scans of tile_cnt / tile_bytes in place, one workgroup walking
-// the tiles in chunks of its size with a running carry.  The totals are what
-// k_sweep_write leaves standing when every record fits: n, bytes, no next slot.
+// Exclusive scans of tile_cnt / tile_bytes in place (tile_scan).  The totals
+// are what k_sweep_write leaves standing when every record fits: n, bytes, no
+// next slot.
 __global__ __launch_bounds__(kSweepBlock) void k_sweep_scan(u32* __restrict__ tile_cnt,
                                                             u64* __restrict__ tile_bytes,
                                                             u32 ntiles, u64* ctr) {
-  __shared__ u32 wn[kSweepBlock / 64];
-  __shared__ u64 wb[kSweepBlock / 64];
-  const u32 wv = threadIdx.x >> 6;
-  u64 carry_n = 0, carry_b = 0;
-  for (u32 base = 0; base < ntiles; base += kSweepBlock) {
-    const u32 i = base + threadIdx.x;
-    const u32 c = i < ntiles ? tile_cnt[i] : 0u;
-    const u64 b = i < ntiles ? tile_bytes[i] : 0ull;
-    const u32 sc = wave_incl_scan(c);
-    const u64 sb = wave_incl_scan64(b);
-    if (__lane_id() == 63) { wn[wv] = sc; wb[wv] = sb; }
-    __syncthreads();
-    u64 pn = 0, pb = 0, tn = 0, tb = 0;
-    for (u32 w = 0; w < kSweepBlock / 64; ++w) {
-      if (w < wv) { pn += wn[w]; pb += wb[w]; }
-      tn += wn[w];
-      tb += wb[w];
-    }
-    if (i < ntiles) {
-      tile_cnt[i] = (u32)(carry_n + pn + sc - c);   // (at most 2^31 slots: the u32 holds)
-      tile_bytes[i] = carry_b + pb + sb - b;
-    }
-    carry_n += tn;
-    carry_b += tb;
-    __syncthreads();   // (the totals are read before the next chunk overwrites them)
-  }
+  const TileTotals tot = tile_scan(tile_cnt, tile_bytes, ntiles);
   if (threadIdx.x == 0) {
-    ctr[kSwN] = carry_n;
-    ctr[kSwBytes] = carry_b;
+    ctr[kSwN] = tot.n;
+    ctr[kSwBytes] = tot.bytes;
     ctr[kSwNext] = ~0ull;
     ctr[kSwErr] = 0;
   }
@@ -6432,63 +6488,26 @@ __global__ __launch_bounds__(kBlock) void k_egress_count(
     n += (u32)(sz != 0) | ((u32)(iz != 0) << 16);
     b += (u64)sz | ((u64)iz << 32);
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    n += __shfl_xor(n, d);
-    b += __shfl_xor(b, d);
-  }
-  __shared__ u32 wn[kBlock / 64];
-  __shared__ u64 wb[kBlock / 64];
-  if (__lane_id() == 0) { wn[threadIdx.x >> 6] = n; wb[threadIdx.x >> 6] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u32 tn = 0;
-    u64 tb = 0;
-    for (u32 i = 0; i < kBlock / 64; ++i) { tn += wn[i]; tb += wb[i]; }
-    tile_cnt[blockIdx.x] = tn >> 16;
-    tile_bytes[blockIdx.x] = tb >> 32;
-    tile_cnt[ntiles + blockIdx.x] = tn & 0xFFFFu;
-    tile_bytes[ntiles + blockIdx.x] = tb & 0xFFFFFFFFull;
+  if (tile_sum(n, b)) {
+    tile_cnt[blockIdx.x] = n >> 16;
+    tile_bytes[blockIdx.x] = b >> 32;
+    tile_cnt[ntiles + blockIdx.x] = n & 0xFFFFu;
+    tile_bytes[ntiles + blockIdx.x] = b & 0xFFFFFFFFull;
   }
 }
 
+// tile_scan over the 2 * ntiles entries, the requests' tiles in front.
 __global__ __launch_bounds__(kSweepBlock) void k_egress_scan(u32* __restrict__ tile_cnt,
                                                              u64* __restrict__ tile_bytes,
                                                              u32 ntiles, u32* ctr) {
-  // (k_sweep_scan's loop over the 2 * ntiles entries; that kernel keeps its own copy)
-  __shared__ u32 wn[kSweepBlock / 64];
-  __shared__ u64 wb[kSweepBlock / 64];
-  const u32 wv = threadIdx.x >> 6, nt = 2 * ntiles;
-  u64 carry_n = 0, carry_b = 0;
-  for (u32 base = 0; base < nt; base += kSweepBlock) {
-    const u32 i = base + threadIdx.x;
-    const u32 c = i < nt ? tile_cnt[i] : 0u;
-    const u64 b = i < nt ? tile_bytes[i] : 0ull;
-    const u32 sc = wave_incl_scan(c);
-    const u64 sb = wave_incl_scan64(b);
-    if (__lane_id() == 63) { wn[wv] = sc; wb[wv] = sb; }
-    __syncthreads();
-    u64 pn = 0, pb = 0, tn = 0, tb = 0;
-    for (u32 w = 0; w < kSweepBlock / 64; ++w) {
-      if (w < wv) { pn += wn[w]; pb += wb[w]; }
-      tn += wn[w];
-      tb += wb[w];
-    }
-    if (i < nt) {
-      tile_cnt[i] = (u32)(carry_n + pn + sc - c);   // (at most 2^31 datagrams)
-      tile_bytes[i] = carry_b + pb + sb - b;
-    }
-    carry_n += tn;
-    carry_b += tb;
-    __syncthreads();   // (the totals are read before the next chunk overwrites them)
-  }
+  const TileTotals tot = tile_scan(tile_cnt, tile_bytes, 2 * ntiles);
   if (threadIdx.x == 0) {
-    // (the first state tile's base is the requests' total; the loop ended on a barrier)
+    // (the first state tile's base is the requests' total)
     ctr[kCtrEgIncast] = tile_cnt[ntiles];
-    ctr[kCtrEgN] = (u32)carry_n;
+    ctr[kCtrEgN] = (u32)tot.n;
     ctr[kCtrEgErr] = 0;
     *reinterpret_cast<u64*>(ctr + kCtrEgIncastBytes) = tile_bytes[ntiles];
-    *reinterpret_cast<u64*>(ctr + kCtrEgBytes) = carry_b;
+    *reinterpret_cast<u64*>(ctr + kCtrEgBytes) = tot.bytes;
   }
 }
 
@@ -7196,8 +7215,8 @@ __device__ __forceinline__ Throttled throttle_eval(const Rec& r, const ThrottleR
   return o;
 }
 
-// Count pass: k_sweep_count's two grids (kTiles: workgroup t sums tile t of
-// the window; otherwise count mode's striding grid with one add per wave).
+// Count pass on k_sweep_count's two grids (kTiles: workgroup t sums tile t of
+// the window; otherwise count mode's striding grid), count_finish at its end.
 template <bool kTiles>
 __global__ __launch_bounds__(kBlock) void k_throttle_count(const Rec* __restrict__ recs, u64 s0,
                                                            u64 s_end, i64 now, i64 later,
@@ -7224,27 +7243,7 @@ __global__ __launch_bounds__(kBlock) void k_throttle_count(const Rec* __restrict
       b += v.q ? v.len : 0u;
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    n += __shfl_xor(n, d);
-    b += __shfl_xor(b, d);
-  }
-  if (kTiles) {
-    __shared__ u32 wn[kBlock / 64];
-    __shared__ u64 wb[kBlock / 64];
-    if (__lane_id() == 0) { wn[threadIdx.x >> 6] = n; wb[threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      u32 tn = 0;
-      u64 tb = 0;
-      for (u32 i = 0; i < kBlock / 64; ++i) { tn += wn[i]; tb += wb[i]; }
-      tile_cnt[blockIdx.x] = tn;
-      tile_bytes[blockIdx.x] = tb;
-    }
-  } else if (__lane_id() == 0) {
-    if (n) atomicAdd(&ctr[kSwN], (u64)n);
-    if (b) atomicAdd(&ctr[kSwBytes], b);
-  }
+  count_finish<kTiles>(n, b, tile_cnt, tile_bytes, ctr);
 }
 
 // The `len` name bytes of record r at d, put_datagram's name part: whole
@@ -7296,16 +7295,15 @@ struct ThrottledOut {
 // are counted from the window's first (win = recs + s0, nwin of them, 32 bits:
 // the host adds s0 to the next-slot word); a lane past the window reads the
 // window's last record and drops it.  The tile arrays stand behind the counter
-// words, one entry per workgroup.
+// words (SweepBuf).
 __global__ __launch_bounds__(kSweepBlock) void k_throttle_write(
     const Rec* __restrict__ win, u32 nwin, const u8* __restrict__ arena, u64 arena_used, i64 now,
     i64 later, u32 max_entries, u64 budget, ThrottledOut out, u64* ctr, ThrottleRules R) {
   __shared__ u32 wtot[2][kSweepBlock / 64];
-  // the sweep buffer's layout: the counters, the tiles' byte sums, their counts
-  const u64* tile_bytes = ctr + kSwWords;
-  const u32* tile_cnt = (const u32*)(tile_bytes + gridDim.x);
+  const SweepBuf sw(ctr, 0, gridDim.x);   // (no mask, one entry per workgroup)
+  const u32* tile_cnt = sw.tile_cnt;
   u64 rank0 = tile_cnt[blockIdx.x];
-  u64 byte0 = tile_bytes[blockIdx.x];
+  u64 byte0 = sw.tile_bytes[blockIdx.x];
   if (blockIdx.x == 0 && threadIdx.x == 0) out.offs[0] = 0;
   if (rank0 > max_entries) return;
   // (a tile the count pass found without an entry -- by its count, not its
@@ -7602,41 +7600,16 @@ __global__ __launch_bounds__(kBlock) void k_reply_count(Src src, const u8* __res
   }
 }
 
-// Exclusive scans of the tile arrays in place (k_sweep_scan's walk); the
-// totals are what k_reply_place leaves standing when every reply fits.
+// Exclusive scans of the tile arrays in place (tile_scan); the totals are what
+// k_reply_place leaves standing when every reply fits.
 __global__ __launch_bounds__(kSweepBlock) void k_reply_scan(u32* __restrict__ tile_cnt,
                                                             u64* __restrict__ tile_bytes,
                                                             u32 ntiles, u64* ctr) {
-  __shared__ u32 wn[kSweepBlock / 64];
-  __shared__ u64 wb[kSweepBlock / 64];
-  const u32 wv = threadIdx.x >> 6;
-  u64 carry_n = 0, carry_b = 0;
-  for (u32 base = 0; base < ntiles; base += kSweepBlock) {
-    const u32 i = base + threadIdx.x;
-    const u32 c = i < ntiles ? tile_cnt[i] : 0u;
-    const u64 b = i < ntiles ? tile_bytes[i] : 0ull;
-    const u32 sc = wave_incl_scan(c);
-    const u64 sb = wave_incl_scan64(b);
-    if (__lane_id() == 63) { wn[wv] = sc; wb[wv] = sb; }
-    __syncthreads();
-    u64 pn = 0, pb = 0, tn = 0, tb = 0;
-    for (u32 w = 0; w < kSweepBlock / 64; ++w) {
-      if (w < wv) { pn += wn[w]; pb += wb[w]; }
-      tn += wn[w];
-      tb += wb[w];
-    }
-    if (i < ntiles) {
-      tile_cnt[i] = (u32)(carry_n + pn + sc - c);
-      tile_bytes[i] = carry_b + pb + sb - b;
-    }
-    carry_n += tn;
-    carry_b += tb;
-    __syncthreads();
-  }
+  const TileTotals tot = tile_scan(tile_cnt, tile_bytes, ntiles);
   if (threadIdx.x == 0) {
-    ctr[kRqN] = carry_n;
-    ctr[kRqBytes] = carry_b;
-    atomicAdd(&ctr[kRqReplies], carry_n);   // (beside the skipped ones k_reply_count added)
+    ctr[kRqN] = tot.n;
+    ctr[kRqBytes] = tot.bytes;
+    atomicAdd(&ctr[kRqReplies], tot.n);   // (beside the skipped ones k_reply_count added)
   }
 }
 

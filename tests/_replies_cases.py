@@ -139,3 +139,27 @@ def check_case(c, st, ra, rt, re, *, replies=0, absent=0, zero=0, negzero=0, twi
 def dirty_mask(a, t, e):
     """The messages whose place in the batch matters: requests and -0.0 fields."""
     return ((a == 0) & (t == 0) & (e == 0)) | (a == NEG0) | (t == NEG0)
+
+
+SUFFIX_TILE = 256        # messages per tile of the ordered suffix's reply egress (kBlock)
+CHUNK_TILES = 512        # tiles per chunk of k_reply_scan's walk
+
+
+def chunk_case(seed=15, K=8, requests=48):
+    """512 * 256 + 1 messages over K buckets with arena names, the first a
+    request (a dirty name over 14 bytes: the whole batch is the ordered
+    suffix), `requests` more at random places and one as the last message,
+    alone in tile 512 -- the tile whose bases come through the carry of the
+    scan's second chunk.  -> make_case's dict, tags["reply"] the requests."""
+    rng = np.random.default_rng(seed)
+    n = CHUNK_TILES * SUFFIX_TILE + 1
+    s_names = [long_name(k) for k in range(K)]
+    sa, st, se = _gen.clean_states(rng, K)
+    created = _gen.T0 - rng.integers(0, SEC, K)
+    names = [s_names[int(i)] for i in rng.integers(0, K, n)]
+    a, t, e = _gen.clean_states(rng, n)
+    pos = sorted({0, n - 1} | {int(p) for p in rng.choice(n, requests, replace=False)})
+    for p in pos:
+        a[p], t[p], e[p] = 0, 0, 0
+    return dict(seed=(s_names, sa, st, se, created), names=names, a=a, t=t, e=e,
+                tags={"reply": pos})

@@ -62,6 +62,42 @@ A1, T1 = G.f2b(10.0), G.f2b(3.0)
 NOW = EC.NOW
 SEC = EC.SEC
 
+# One window over more than 512 tiles: the tile scan walks the tile arrays in
+# chunks of 512 entries and carries the running totals from chunk to chunk, so
+# only such a window has a tile whose base comes out of the carry.
+# 4 * CHUNK_MSGS slots are 513 tiles.
+CHUNK_TILES = 512
+CHUNK_MSGS = (CHUNK_TILES + 1) * TILE // 4
+CHUNK_LOG2_SLOTS = 22
+CHUNK_CAP = 1 << 21      # bytes: more than every datagram of chunk_rows() together
+CHUNK_RULE = [(b"", 3, SEC, 1)]   # the throttled sweep's catch-all: denies the drained half at NOW
+
+
+def chunk_rows(count=6000):
+    """A few thousand buckets for a table of 2^22 slots (about six a tile):
+    the empty name once, inline names and arena names in turn; every other
+    state has no token left under CHUNK_RULE, the others all three."""
+    rows = {b"": (G.f2b(3.0), G.f2b(3.0), 0, NOW)}
+    for k in range(1, count):
+        L = (5, 14, 15, 22, 23, 40, 231)[k % 7]
+        taken = G.f2b(3.0) if k % 2 else 0
+        rows[(b"%05d" % k).ljust(L, b"n")] = (G.f2b(3.0), taken, k, NOW)
+    return rows
+
+
+def chunk_repo(pa, zeros=64, **kw):
+    """chunk_rows() seeded into 2^22 slots, and zero states beside them (left
+    by zero-state Receives: a sweep skips them)."""
+    repo = pa.GPURepo(log2_slots=CHUNK_LOG2_SLOTS, arena_bytes=1 << 20, **kw)
+    rows = chunk_rows()
+    ks = list(rows)
+    repo.seed(ks, *[[rows[k][j] for k in ks] for j in range(4)])
+    zn = [b"zero-state-%d" % k for k in range(zeros)]
+    out = repo.receive_soa(zn, [0] * zeros, [0] * zeros, [0] * zeros, NOW + 1)
+    assert (out["status"] & 0x80).all()
+    assert repo.capacity == 1 << CHUNK_LOG2_SLOTS and len(repo) == len(rows) + zeros
+    return repo
+
 
 def filter_rows():
     """{name: (added bits, taken bits, elapsed, created)} around NOW: the

@@ -307,6 +307,37 @@ def test_tile_edges(pa, K):
     g.close()
 
 
+@pytest.mark.parametrize("log2_slots", [21, 22])
+def test_scan_past_one_chunk_of_the_tile_scan(pa, log2_slots):
+    """k_egress_scan walks 2 * ntiles entries in chunks of 512, the requests'
+    tiles in front, and stores the requests' total from entry ntiles.  2^21
+    slots are 512 tiles: the requests fill the first chunk, and entry 512, the
+    first of the second, is the carry itself.  2^22 slots: the requests' tiles
+    lie on both sides of a chunk's edge and the boundary opens the third chunk.
+    One mixed batch that leaves requests and states pending, count mode, one
+    export_changed of everything."""
+    rng = np.random.default_rng(log2_slots)
+    g, m = tracked(pa, log2_slots=log2_slots)
+    apply(g, m, EC.gen_ops(rng, 5000, EC.name_pool(3000)))
+    want_req, want_st = m.expected()
+    assert len(want_req) >= 100 and len(want_st) >= 200
+    ntiles = g.capacity // 4096
+    assert g.capacity == 1 << log2_slots and 2 * ntiles > 512
+    # the table's upper half in slot order (one sweep window): requests are
+    # pending in tiles on both sides of ntiles / 2 (2^22 slots: of tile 512)
+    half = g.capacity // 2
+    layout = g.export_sweep(None, 1)[1][1]
+    dgs, cur, st = g.export_sweep((half, layout), half // 4, out_cap=1 << 20)
+    assert (st["slots_scanned"], st["done"]) == (half, 1)
+    upper = {d[EC.FIXED:] for d in dgs}
+    assert 20 <= len(upper & set(want_req)) <= len(want_req) - 20
+    calls = check_drain(g, m, max_msgs=1 << 13)
+    assert len(calls) == 1 and calls[0]["n_incast"] == len(want_req)
+    assert g.changes_count()["pending"] == 0
+    assert gpu_dump(g) == m.o.dump()
+    g.close()
+
+
 # 5 ----------------------------------------------------------- accumulation --
 def test_accumulation_with_receives_between(pa):
     """Three apply_mixed batches with receive_soa batches between them: merges

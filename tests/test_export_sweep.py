@@ -417,3 +417,53 @@ def test_collisions(pa):
     got, _, _ = sweep_all(repo, 16)
     assert got == one
     repo.close()
+
+
+# ------------------------------------- a window of more than 512 tiles ----
+@pytest.fixture(scope="module")
+def chunk_table(pa):
+    """SC.chunk_repo's table and its datagrams in slot order, taken in windows
+    of 64 tiles: each is one chunk of the tile scan, none needs a carry.
+    Shared, never changed."""
+    repo = SC.chunk_repo(pa)
+    model = SC.exported(gpu_dump(repo))
+    assert len(model) == len(SC.chunk_rows()) and {len(k) for k in model} >= {0, 5, 22, 23, 231}
+    ref, calls, sts = sweep_all(repo, 1 << 16, out_cap=SC.CHUNK_CAP)
+    assert calls == 16 and all(s["slots_scanned"] == 64 * SC.TILE for s in sts)
+    assert_exact(ref, model)
+    yield repo, ref, sum(s["n"] for s in sts[:SC.CHUNK_TILES // 64])
+    repo.close()
+
+
+def one_call(repo, dev, cursor, max_msgs):
+    """export_sweep with host or device pointers -> (datagrams, cursor, stats)."""
+    if not dev:
+        dgs, cursor, st = repo.export_sweep(cursor, max_msgs, out_cap=SC.CHUNK_CAP)
+        check_call(dgs, st, max_msgs, SC.CHUNK_CAP)
+        return dgs, cursor, st
+    import torch
+    out = torch.zeros(SC.CHUNK_CAP, dtype=torch.uint8, device="cuda:0")
+    offs = torch.full((max_msgs + 1,), -1, dtype=torch.int64, device="cuda:0")
+    n, cursor, st = repo.export_sweep_device(out, offs, cursor, max_msgs)
+    st["offs"] = offs[:n + 1].cpu().numpy().view(np.uint64)
+    raw = out[:st["bytes"]].cpu().numpy().tobytes()
+    dgs = [raw[int(st["offs"][i]):int(st["offs"][i + 1])] for i in range(n)]
+    check_call(dgs, st, max_msgs, SC.CHUNK_CAP - 8)
+    return dgs, cursor, st
+
+
+@pytest.mark.parametrize("dev", [False, True])
+def test_window_past_one_chunk_of_the_tile_scan(chunk_table, dev):
+    """max_msgs = 525312: one window of 513 tiles, so tile 512's rank and byte
+    bases, and the totals, come through the scan's carry."""
+    repo, ref, before512 = chunk_table
+    first, cur, st = one_call(repo, dev, None, SC.CHUNK_MSGS)
+    assert st["slots_scanned"] == (SC.CHUNK_TILES + 1) * SC.TILE > SC.CHUNK_TILES * SC.TILE
+    assert (st["done"], st["restarted"], cur[0]) == (0, 0, st["slots_scanned"])
+    # tile 512 alone (a window of one tile) holds records, and they end the call
+    in512 = repo.export_sweep((SC.CHUNK_TILES * SC.TILE, cur[1]), 1024)[0]
+    assert in512 and first[before512:] == in512
+    assert first == ref[:len(first)]
+    rest, cur, st = one_call(repo, dev, cur, SC.CHUNK_MSGS)
+    assert (st["done"], cur[0]) == (1, repo.capacity)
+    assert first + rest == ref

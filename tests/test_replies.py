@@ -475,3 +475,33 @@ def test_replies_feed_a_peer_unchanged(pa, deferred_case):
     po = O.Repo()
     assert po.receive(RC.datagrams_of(e), RC.NOW + 1)[4] == e["n"]
     same(dump(peer), po.dump())
+
+
+# 10 ------------------------------------- more tiles than one scan chunk --
+def test_suffix_past_one_chunk_of_the_tile_scan(pa):
+    """An ordered suffix of 512 * 256 + 1 messages: 513 tiles, so the last
+    tile's bases and the totals come through the carry of k_reply_scan's second
+    chunk.  Then max_msgs below the replies of the first chunk: the cut still
+    reports every reply."""
+    c = RC.chunk_case()
+    n, pos = len(c["names"]), c["tags"]["reply"]
+    assert n == 512 * 256 + 1 and pos[0] == 0 and pos[-1] == n - 1 and len(pos) >= 40
+    o, st, ra, rt, re, _ = oracle_run(c)
+    assert all((st[p] & 0x7F) == RC.REPLY for p in pos)
+    for max_msgs in (4096, 10):
+        e = RC.expected(c["names"], st, ra, rt, re, max_msgs=max_msgs)
+        assert e["replies"] == len(pos) and e["n"] == min(len(pos), max_msgs)
+        if max_msgs >= len(pos):
+            assert int(e["src"][-1]) == n - 1                          # the last tile's reply
+        else:
+            assert max_msgs < sum(p < 512 * 256 for p in pos)          # cut inside the first chunk
+        g = handle(pa, c, isolate=True)
+        g.set_timing(True)
+        r = call_device(g, c, False, max_msgs=max_msgs)
+        assert g.last_stats()[4] == n, g.last_stats()                  # all of it the suffix
+        ks = [k for k, _ in g.timings()]
+        assert [ks.count(k) for k in ("k_reply_count", "k_reply_scan", "k_reply_place")] == [1, 1, 1]
+        assert_replies(r, e)
+        assert RC.datagrams_of(e)[-1] == got_bytes(r)[0][int(e["offs"][-2]):]
+        same(dump(g), o.dump())
+        g.close()

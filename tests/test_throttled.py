@@ -407,3 +407,35 @@ def test_sees_a_queued_batch(pa):
     assert set(hit) <= set(exp) and not set(hit) & set(exp0)     # the merges are what it saw
     assert len(rows) == 600 + 5000
     g.close()
+
+
+# ------------------------------------- a window of more than 512 tiles ----
+def test_window_past_one_chunk_of_the_tile_scan(pa):
+    """The export sweep's table of 2^22 slots (tests/_sweep_cases.chunk_repo)
+    under one rule that denies half of it; max_entries = 525312 makes a window
+    of 513 tiles, whose last tile's bases and whose totals come through the
+    carry of k_sweep_scan's second chunk."""
+    from tests import _sweep_cases as SC
+    rules, now, M, cap = SC.CHUNK_RULE, SC.NOW, SC.CHUNK_MSGS, SC.CHUNK_CAP
+    g = SC.chunk_repo(pa)
+    rows = gpu_dump(g)
+    exp, _ = TC.expected(rows, rules, now)
+    assert 0.4 * len(rows) <= len(exp) <= 0.6 * len(rows)
+    d = g.export_throttled(rules, now, 0, None, M, names_cap=cap)
+    check_call(d, M, cap)
+    assert d["slots_scanned"] == 513 * TC.TILE and (d["done"], d["cursor"][0]) == (0, 513 * TC.TILE)
+    d2 = g.export_throttled(rules, now, 0, d["cursor"], M, names_cap=cap)
+    check_call(d2, M, cap)
+    assert (d2["done"], d2["cursor"][0]) == (1, g.capacity)
+    got = entries(d) + entries(d2)
+    assert_exact(got, exp, rules, now)
+    cnt = g.throttled_count(rules, now)
+    assert (cnt["n"], cnt["bytes"]) == (d["n"] + d2["n"], d["bytes"] + d2["bytes"])
+    # slot order: windows of 64 tiles, one chunk of the scan each, no carry
+    ref, calls = sweep_all(g, rules, now, 0, 1 << 16, names_cap=cap)
+    assert len(calls) == 16 and got == ref
+    # tile 512 alone (a window of one tile) holds entries, and they end the first call
+    in512 = entries(g.export_throttled(rules, now, 0, (512 * TC.TILE, d["cursor"][1]), 1024))
+    assert in512 and entries(d)[-len(in512):] == in512
+    assert sum(c["n"] for c in calls[:8]) + len(in512) == d["n"]
+    g.close()
