@@ -946,6 +946,113 @@ int phip_export_throttled(phip_handle* h, phip_sweep_cursor* cur, const phip_thr
 int phip_throttle_match(const phip_throttle_rule* rules, uint32_t n_rules, const uint8_t* name,
                         uint32_t len, int32_t* rule_out);
 
+/* Top talkers: the k buckets that took the most.
+ * The exports above report, in slot order, whatever passes a per-record test.
+ * This one answers "who uses the service most": the k qualifying buckets with
+ * the largest `taken` (a bucket's lifetime token count, the cluster-wide max
+ * after merges), found by a radix select on the device in a few passes over
+ * the table instead of a dump and a host sort.
+ *
+ * Which buckets qualify.  A record qualifies iff it is published, its name is
+ * at most PHIP_MAX_NAME_LEN bytes, the prefix matches -- phip_throttle_match's
+ * rule for the one prefix of the query: len >= prefix_len and the first
+ * prefix_len bytes equal, prefix_len == 0 matches every name, bytes of
+ * `prefix` past prefix_len are ignored -- with idle_ns > 0 it is not idle at
+ * `now` by phip_evict_idle's rule (idle = now - (created + elapsed), exact,
+ * 0 when that is negative, saturating; idle iff idle >= idle_ns), and its
+ * decoded `taken` bits t satisfy 0 < t <= 0x7FF0000000000000: positive, +Inf
+ * included.  +0.0, -0.0, negatives and NaNs never rank.  On that range the
+ * order of the raw bits, the float order and the order of the stored codes are
+ * one order.  idle_ns == 0: no idle filter; idle_ns < 0: PHIP_ERR_INVALID.
+ * metric selects the ranking key: 0 = taken, anything else PHIP_ERR_INVALID.
+ *
+ * Order.  Entries come out by `taken` descending, equal `taken` in ascending
+ * slot order.  The list is the first min(k, population) entries of that total
+ * order, so on an unchanged table top(k) is exactly the first k entries of
+ * top(k') for every k < k'.  Slots follow from the handle's placement seed:
+ * which of several buckets tied at the cut are reported depends on that seed
+ * (and on the table's layout), and on nothing else.
+ *
+ * Output.  Entry i's name is names[offs[i] .. offs[i+1]), offs[0] = 0, the
+ * names back to back as in phip_throttled_out.  taken[i] (float64 bits) and
+ * state[i] are bit-exact copies of the record, decoded as phip_get gives them;
+ * each may be NULL.  Only entries [0, n) and offs[0 .. n] are written, nothing
+ * past them.
+ *
+ * Bounds.  k is 1..PHIP_TOP_MAX.  names_cap < PHIP_MAX_NAME_LEN is
+ * PHIP_ERR_INVALID.  A list that runs out of name bytes is cut at an entry,
+ * from the bottom ranks: it is then the first n entries of the uncut list and
+ * st->truncated = 1.
+ *
+ * Stats.  n and bytes (= offs[n]); population, the buckets that qualified;
+ * passes, the kernels of this call that read every slot of the table -- at
+ * most 8 (six 12-bit digits of the key, the tie count, the collect), far fewer
+ * when the top keys differ in their leading digits.
+ *
+ * Count mode.  PHIP_SWEEP_COUNT with out == NULL: one pass, st->population
+ * only (n and bytes 0).
+ *
+ * Pointers.  q, st and the phip_top_out struct are host memory.  The buffers
+ * in it are host memory, or device memory with PHIP_DEVICE_PTRS (no alignment
+ * asked beyond each column's type; every byte of names_cap is budget).  A
+ * host-pointer call copies back only what was written.
+ *
+ * Errors and locking.  k outside 1..PHIP_TOP_MAX, prefix_len over
+ * PHIP_THROTTLE_MAX_PREFIX, a metric other than 0, idle_ns < 0, NULL q or st,
+ * a missing out / names / offs outside count mode (an `out` in count mode),
+ * names_cap below one name, or any flag bit other than PHIP_DEVICE_PTRS and
+ * PHIP_SWEEP_COUNT is PHIP_ERR_INVALID, with nothing read from the table and
+ * nothing written.  The call is serialised with the handle's other calls; a
+ * batch queued with PHIP_RECV_ASYNC is finished first, its error is this
+ * call's, and the list sees its merges.
+ *
+ * Nothing is written to the handle: table, arena, change set, layout count,
+ * the hot directory and phip_len stay as they are.
+ *
+ * Stated limits.  `taken` is a lifetime total, not a rate: a caller who wants
+ * a rate diffs two lists, or divides by the state's elapsed.  Not here: other
+ * metrics, prefixes over 16 bytes, k above PHIP_TOP_MAX.
+ *
+ * phip_top_merge (host only, no handle, no GPU): the top k of n_lists lists in
+ * phip_export_top's layout, list i holding ns[i] entries -- the members of a
+ * shard group, whose tables are disjoint, or replicas of different nodes.
+ * `taken` is required in every list and `state` may be NULL (its entries then
+ * merge as zero states); of `out`, names, names_cap and offs are required,
+ * taken and state may be NULL.  The result is in the same order, by `taken`
+ * descending; slots mean nothing across lists, so equal `taken` falls by list
+ * index, then by position in the list.  A name present more than once is kept
+ * once, with the larger `taken` and that entry's state and place (equal
+ * `taken`: the first).  The list is cut at an entry when names_cap runs out.
+ * *n_out receives the entries written, offs[0 .. *n_out] their bounds.
+ * PHIP_ERR_INVALID for n_lists == 0, k outside 1..PHIP_TOP_MAX, NULL lists /
+ * ns / out / n_out / out->names / out->offs, or a list with entries and no
+ * names, offs or taken. */
+#define PHIP_TOP_MAX 4096          /* largest k */
+typedef struct phip_top_query {    /* host memory */
+  uint8_t prefix[PHIP_THROTTLE_MAX_PREFIX];
+  uint32_t prefix_len; /* 0..16; 0 matches every name */
+  uint32_t metric;     /* 0 = taken */
+  int64_t now, idle_ns;/* idle_ns > 0: skip buckets idle at now; 0: no filter */
+  uint32_t k, reserved;/* 1..PHIP_TOP_MAX */
+} phip_top_query;
+typedef struct phip_top_out {      /* names and offs required outside count mode */
+  uint8_t* names;      /* entry i's name is names[offs[i] .. offs[i+1]) */
+  uint64_t names_cap;
+  uint64_t* offs;      /* k + 1 entries, offs[0] = 0 */
+  uint64_t* taken;     /* may be NULL: float64 bits of entry i's taken */
+  phip_state* state;   /* may be NULL: the record's state as phip_get gives it */
+} phip_top_out;
+typedef struct phip_top_stats {
+  uint64_t n, bytes;   /* entries written, offs[n] */
+  uint64_t population; /* buckets that qualified */
+  uint32_t passes;     /* kernels of this call that read every slot of the table */
+  uint32_t truncated;  /* 1: names_cap ended the list before min(k, population) */
+} phip_top_stats;
+int phip_export_top(phip_handle* h, const phip_top_query* q, const phip_top_out* out,
+                    phip_top_stats* st, uint32_t flags);
+int phip_top_merge(const phip_top_out* lists, const uint64_t* ns, uint32_t n_lists, uint32_t k,
+                   const phip_top_out* out, uint64_t* n_out);
+
 /* ---- host helpers (no device work) ---- */
 /* ParseRate: returns 0 or <0 on error; freq and per receive the values Go
  * returns beside the error (api.go:61 uses them). */

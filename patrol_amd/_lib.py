@@ -45,6 +45,7 @@ EXPORTS = [
     "phip_group_receive_datagrams_replies", "phip_group_receive_replies",
     "phip_group_ring_receive_replies", "phip_group_reply_stats",
     "phip_group_peek",
+    "phip_export_top", "phip_top_merge",
 ]
 
 PHIP_OK = 0
@@ -80,6 +81,7 @@ DIGEST_MAX_LOG2_PARTS = 20
 MAX_NAME_LEN = 231         # PHIP_MAX_NAME_LEN
 THROTTLE_MAX_RULES = 8     # PHIP_THROTTLE_MAX_RULES
 THROTTLE_MAX_PREFIX = 16   # PHIP_THROTTLE_MAX_PREFIX
+TOP_MAX = 4096             # PHIP_TOP_MAX: the largest k of phip_export_top
 
 
 class phip_config(C.Structure):
@@ -187,6 +189,22 @@ class phip_throttled_out(C.Structure):
     _fields_ = [("names", C.c_void_p), ("names_cap", C.c_uint64), ("offs", C.c_void_p),
                 ("max_entries", C.c_uint32), ("reserved", C.c_uint32), ("retry_at", C.c_void_p),
                 ("remaining", C.c_void_p), ("rule", C.c_void_p)]
+
+
+class phip_top_query(C.Structure):
+    _fields_ = [("prefix", C.c_uint8 * 16), ("prefix_len", C.c_uint32), ("metric", C.c_uint32),
+                ("now", C.c_int64), ("idle_ns", C.c_int64), ("k", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class phip_top_out(C.Structure):
+    _fields_ = [("names", C.c_void_p), ("names_cap", C.c_uint64), ("offs", C.c_void_p),
+                ("taken", C.c_void_p), ("state", C.c_void_p)]
+
+
+class phip_top_stats(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("bytes", C.c_uint64), ("population", C.c_uint64),
+                ("passes", C.c_uint32), ("truncated", C.c_uint32)]
 
 
 _lib = None
@@ -376,5 +394,10 @@ def load(path: str = LIB_PATH):
     if hasattr(L, "phip_group_peek"):
         L.phip_group_peek.argtypes = [vp, C.POINTER(phip_ops), C.POINTER(phip_peek_results),
                                       C.POINTER(u64), C.POINTER(u64), u32]
+    if hasattr(L, "phip_export_top"):
+        L.phip_export_top.argtypes = [vp, C.POINTER(phip_top_query), C.POINTER(phip_top_out),
+                                      C.POINTER(phip_top_stats), u32]
+        L.phip_top_merge.argtypes = [C.POINTER(phip_top_out), C.POINTER(u64), u32, u32,
+                                     C.POINTER(phip_top_out), C.POINTER(u64)]
     _lib = L
     return L

@@ -64,7 +64,7 @@ enum BufId {
   B_DLIST, B_DTAB, B_DMARK, B_SMAP, B_SOFF, B_SLEN, B_SA, B_ST, B_SE, B_SSTAT, B_SREP, B_NCHK,
   B_EVICT, B_ULOG, B_ULCNT, B_SWEEP, B_DIGEST, B_DIGOUT,
   B_EGSZ, B_EGTILE, B_EGOUT, B_EGOFFS,
-  B_PEEKAT, B_PEEKST,
+  B_PEEKAT, B_PEEKST, B_TOP,
   B_RQCTR, B_RQSEL, B_RQTILE, B_RQOUT, B_RQOFFS, B_RQSRC, B_RQSTAT, B_RQREP,
   B_COUNT_
 };
@@ -4615,6 +4615,136 @@ int phip_export_throttled(phip_handle* h, phip_sweep_cursor* cur, const phip_thr
         (rc = copy_back(h, reinterpret_cast<i64*>(o.retry_at), d.retry_at, st->n, false)) ||
         (rc = copy_back(h, reinterpret_cast<u64*>(o.remaining), d.remaining, st->n, false)) ||
         (rc = copy_back(h, o.rule, d.rule, st->n, false)))
+      return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return PHIP_OK;
+}
+
+// Top talkers (patrolhip.h "Top talkers"; kernels in phip_kernels.hpp "top
+// talkers").  Every launch of the longest case is enqueued at once -- six
+// digit passes, the tie count, its scan, the collect, the sort -- and the
+// counter words on the device tell each kernel whether its stage is still
+// wanted, so there is no round trip between the passes: the one read-back is
+// at the end.  Scratch: the sweep's tile arrays (one count per tile, for the
+// ties) and the top buffer of O(bins + k) words; nothing per slot.  A
+// host-pointer call stages its columns by the caller's caps (at most k entries
+// and k names) and copies back what was written.
+int phip_export_top(phip_handle* h, const phip_top_query* q, const phip_top_out* out,
+                    phip_top_stats* st, uint32_t flags) {
+  if (!h || !q || !st) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;   // (finishes a queued PHIP_RECV_ASYNC batch)
+  if (flags & ~(PHIP_DEVICE_PTRS | PHIP_SWEEP_COUNT))
+    return set_err(h, PHIP_ERR_INVALID, "top: unknown flag bits 0x%x", flags);
+  if (q->k < 1 || q->k > PHIP_TOP_MAX)
+    return set_err(h, PHIP_ERR_INVALID, "top: k must be 1..%d", PHIP_TOP_MAX);
+  if (q->prefix_len > PHIP_THROTTLE_MAX_PREFIX)
+    return set_err(h, PHIP_ERR_INVALID, "top: a prefix over %d bytes", PHIP_THROTTLE_MAX_PREFIX);
+  if (q->metric != 0) return set_err(h, PHIP_ERR_INVALID, "top: metric %u is not known", q->metric);
+  if (q->idle_ns < 0) return set_err(h, PHIP_ERR_INVALID, "top: idle_ns must not be negative");
+  TopQuery Q{};
+  {
+    phip_throttle_rule r{};
+    memcpy(r.prefix, q->prefix, sizeof r.prefix);
+    r.prefix_len = q->prefix_len;
+    Q.R.n = 1;
+    Q.R.r[0] = throttle_rule(r);
+    Q.now = q->now;
+    Q.idle_ns = q->idle_ns;
+  }
+  const bool dev = flags & PHIP_DEVICE_PTRS;
+  int rc;
+  if (flags & PHIP_SWEEP_COUNT) {
+    if (out) return set_err(h, PHIP_ERR_INVALID, "top: count mode takes no output");
+    phip_sweep_stats cs{};
+    if ((rc = sweep_count_mode(h, 0, [&](unsigned grid, const SweepBuf& b) -> int {
+          Launch l(h, "k_top_count");
+          k_top_count<<<grid, kBlock, 0, h->stream>>>(h->recs, h->cap, Q, b.ctr);
+          return PHIP_OK;
+        }, &cs)))
+      return rc;
+    phip_top_stats s{};
+    s.population = cs.n;
+    s.passes = 1;
+    *st = s;
+    return PHIP_OK;
+  }
+  if (!out || !out->names || !out->offs)
+    return set_err(h, PHIP_ERR_INVALID, "top: out, its names and its offs are required");
+  const phip_top_out o = *out;
+  if (o.names_cap < PHIP_MAX_NAME_LEN)
+    return set_err(h, PHIP_ERR_INVALID, "top: names_cap below one name (%d bytes)",
+                   PHIP_MAX_NAME_LEN);
+  const u32 k = q->k;
+  const u32 ntiles = (u32)((h->cap + kSweepTile - 1) / kSweepTile);
+  u64 *sw, *tb;
+  if ((rc = ensure(h, B_SWEEP, SweepBuf::words(0, ntiles), &sw)) ||
+      (rc = ensure(h, B_TOP, TopBuf::words(), &tb)))
+    return rc;
+  const SweepBuf b(sw, 0, ntiles);
+  const TopBuf t(tb);
+  TopOut d{o.names, reinterpret_cast<u64*>(o.offs), reinterpret_cast<u64*>(o.taken), o.state};
+  if (!dev) {
+    const size_t nb = (size_t)std::min<u64>(o.names_cap, (u64)k * PHIP_MAX_NAME_LEN);
+    if ((rc = ensure(h, B_EXPORT, nb, &d.names)) || (rc = ensure(h, B_OFFS, (size_t)k + 1, &d.offs)) ||
+        (rc = out_buf(h, B_REM, reinterpret_cast<u64*>(o.taken), k, false, &d.taken)) ||
+        (rc = out_buf(h, B_PEEKST, o.state, k, false, &d.state)))
+      return rc;
+  }
+  HIPCHK(h, hipMemsetAsync(t.ctr, 0, TopBuf::clear_bytes(), h->stream));
+  const unsigned grid = std::min<unsigned>(grid_for(h->cap), 8u * (unsigned)h->ncu);
+  for (u32 done = 0; done < 64; done += kTopBits) {
+    {
+      Launch l(h, "k_top_hist");
+      k_top_hist<<<grid, kBlock, 0, h->stream>>>(h->recs, h->cap, Q, t.ctr, t.hist);
+    }
+    {
+      Launch l(h, "k_top_pick");
+      k_top_pick<<<1, kTopPickBlock, 0, h->stream>>>(t.ctr, t.hist, k);
+    }
+  }
+  {
+    Launch l(h, "k_top_ties");
+    k_top_ties<<<ntiles, kBlock, 0, h->stream>>>(h->recs, h->cap, Q, t.ctr, b.tile_cnt, b.tile_bytes);
+  }
+  {
+    Launch l(h, "k_top_scan");
+    k_top_scan<<<1, kSweepBlock, 0, h->stream>>>(t.ctr, b.tile_cnt, b.tile_bytes, ntiles);
+  }
+  {
+    Launch l(h, "k_top_collect");
+    k_top_collect<<<ntiles, kSweepBlock, 0, h->stream>>>(h->recs, h->cap, Q, t.ctr, b.tile_cnt, t.key,
+                                                         t.slot);
+  }
+  {
+    // (long names are bounded by the arena's size, as in export_sweep)
+    Launch l(h, "k_top_emit");
+    k_top_emit<<<1, kTopEmitBlock, 0, h->stream>>>(h->recs, h->arena, h->arena_cap, t.ctr, t.key,
+                                                   t.slot, d, o.names_cap);
+  }
+  HIPCHK(h, hipGetLastError());
+  u64 c[kTpWords];
+  HIPCHK(h, hipMemcpyAsync(c, t.ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (c[kTpErr] || c[kTpMode] == kTopRefine || c[kTpN] > k || c[kTpBytes] > o.names_cap ||
+      (c[kTpMode] != kTopEmpty && c[kTpCnt] < c[kTpK]))
+    return set_err(h, PHIP_ERR_INVALID,
+                   "internal: top wrote %llu entries, %llu bytes of %llu candidates (mode %llu, flag %llu)",
+                   (unsigned long long)c[kTpN], (unsigned long long)c[kTpBytes],
+                   (unsigned long long)c[kTpCnt], (unsigned long long)c[kTpMode],
+                   (unsigned long long)c[kTpErr]);
+  phip_top_stats s{};
+  s.n = c[kTpN];
+  s.bytes = c[kTpBytes];
+  s.population = c[kTpPop];
+  s.passes = (uint32_t)c[kTpPasses];
+  s.truncated = (uint32_t)c[kTpTrunc];
+  *st = s;
+  if (!dev) {
+    if ((rc = datagrams_back(h, o.names, d.names, s.bytes, o.offs, d.offs, s.n)) ||
+        (rc = copy_back(h, reinterpret_cast<u64*>(o.taken), d.taken, s.n, false)) ||
+        (rc = copy_back(h, o.state, d.state, s.n, false)))
       return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }

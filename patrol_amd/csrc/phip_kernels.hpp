@@ -7644,5 +7644,404 @@ __global__ __launch_bounds__(kBlock) void k_reply_place(Src src, const u8* __res
   }
 }
 
+// -------------------------------------------------------- top talkers ----
+// phip_export_top (patrolhip.h "Top talkers"): the k qualifying buckets with
+// the largest key, by an MSD radix select over the live table -- no sort of
+// the table, no per-slot scratch.  The key is read through top_key alone.
+//   k_top_hist     streams the records on the count pass's striding grid and,
+//                  among the keys that share the prefix selected so far,
+//                  histograms the next kTopBits-bit digit: a workgroup's LDS
+//                  histogram, then one global add per non-empty bin;
+//   k_top_pick     one workgroup walks the bins from the top, extends the
+//                  prefix by the digit the cut falls in and leaves the
+//                  remaining k in the counter words, where the next pass finds
+//                  them: no host round trip between passes.  It stops the
+//                  refinement as soon as the bins at or above the cut hold at
+//                  most kTopCap keys ("early": the final sort decides among
+//                  them), or when the key has no digit left ("ties": more
+//                  than the cap share the threshold key itself);
+//   k_top_ties     ties only: per tile, the records whose key is the threshold;
+//   k_top_scan     ties only: tile_scan over those counts;
+//   k_top_collect  one workgroup per tile: every key above the threshold
+//                  prefix is a candidate; of those at it, all (early) or, by
+//                  their rank in slot order over the scanned tile counts, the
+//                  first `remaining` (ties).  Membership is decided by keys
+//                  and ranks alone; the wave-aggregated add only hands out
+//                  places in the candidate buffer, which the sort reorders;
+//   k_top_emit     one workgroup sorts the at most kTopCap (key, slot) pairs
+//                  in LDS (key descending, slot ascending), scans the name
+//                  lengths in rank order, applies the names_cap cut and writes
+//                  names, offs, taken and state.
+// The host enqueues every launch of the longest case; a kernel whose stage the
+// counter words say is over, or not needed, returns before it reads a slot, and
+// kTpPasses counts those that did read the table.
+constexpr u32 kTopBits = 12;              // digit width: 2^12 bins, 16 KB of LDS (as k_digest)
+constexpr u32 kTopBins = 1u << kTopBits;
+constexpr u32 kTopCap = PHIP_TOP_MAX;     // the early-stop cap = the candidate buffer
+constexpr u32 kTopPickBlock = 512;
+constexpr u32 kTopEmitBlock = 1024;
+static_assert(kTopBits >= 8 && kTopBins % kTopPickBlock == 0 && kTopCap % kTopEmitBlock == 0 &&
+                  (kTopCap & (kTopCap - 1)) == 0 && kTopCap >= PHIP_TOP_MAX,
+              "top talkers");
+// Counter words (u64) at the head of the top buffer.
+constexpr u32 kTpPfx = 0;      // the key bits selected so far, key >> (64 - kTpDone)
+constexpr u32 kTpDone = 1;     // how many leading key bits they are
+constexpr u32 kTpRem = 2;      // how many of the keys at the prefix the list still takes
+constexpr u32 kTpAbove = 3;    // keys above the prefix: all are in the list
+constexpr u32 kTpLimit = 4;    // collect: keys at the prefix admitted (ties: the first, in slot order)
+constexpr u32 kTpMode = 5;     // kTopRefine .. kTopEmpty
+constexpr u32 kTpPasses = 6;   // kernels that read every slot
+constexpr u32 kTpPop = 7;      // buckets that qualified
+constexpr u32 kTpK = 8;        // min(k, population)
+constexpr u32 kTpCnt = 9;      // candidates collected
+constexpr u32 kTpN = 10;       // entries written
+constexpr u32 kTpBytes = 11;   // their name bytes (= offs[n])
+constexpr u32 kTpTrunc = 12;   // names_cap cut the list
+constexpr u32 kTpErr = 13;     // internal: a long name outside the arena, a candidate past the cap
+constexpr u32 kTpWords = 16;
+constexpr u64 kTopRefine = 0, kTopEarly = 1, kTopTies = 2, kTopEmpty = 3;
+
+// The top buffer: the counter words, the digit histogram (one memset clears
+// both), the candidates' keys and slots.  O(bins + k).
+struct TopBuf {
+  u64* ctr;
+  u32* hist;
+  u64* key;
+  u32* slot;
+  __host__ __device__ explicit TopBuf(u64* c)
+      : ctr(c), hist((u32*)(c + kTpWords)), key(c + kTpWords + kTopBins / 2),
+        slot((u32*)(c + kTpWords + kTopBins / 2 + kTopCap)) {}
+  static constexpr size_t words() { return kTpWords + kTopBins / 2 + kTopCap + kTopCap / 2; }
+  static constexpr size_t clear_bytes() { return (kTpWords + kTopBins / 2) * sizeof(u64); }
+};
+
+// The query as the kernels take it: the prefix as the throttled sweep's rule 0
+// (throttle_match is the match), the idle filter's two readings.
+struct TopQuery {
+  ThrottleRules R;
+  i64 now, idle_ns;
+};
+
+// The ranking key of a record, 0 for one that does not qualify: published, a
+// name of at most PHIP_MAX_NAME_LEN bytes, the prefix, not idle, and taken
+// bits t with 0 < t <= +Inf's.  The stored code of such a t is kInfBits + 1 +
+// t (enc_f64), so t is one subtraction, and every other code -- negatives,
+// the zeros, NaNs -- lands outside [1, kInfBits] by it.
+__device__ __forceinline__ u64 top_key(const Rec& r, const TopQuery& q) {
+  const u32 len = (u32)(r.name0 & 0xFFu);
+  const bool inl = len <= kInlineName;   // (the first 16 name bytes: throttle_parts)
+  const u64 n0 = inl ? (r.name0 >> 16) | (r.name1 << 48) : r.name1;
+  const u64 n1 = inl ? (r.name1 >> 16) | (r.name2 << 48) : r.name2;
+  const u64 t = r.taken - (kInfBits + 1);
+  bool ok = r.tag && (rec_flags(r) & kRecPublished) && len <= PHIP_MAX_NAME_LEN &&
+            t - 1 < kInfBits && throttle_match(q.R, n0, n1, len).rule >= 0;
+  if (ok && q.idle_ns > 0) ok = !bucket_idle(r.created, r.elapsed, q.now, q.idle_ns);
+  return ok ? t : 0ull;
+}
+
+// Count mode: the population alone, on the count pass's striding grid.
+__global__ __launch_bounds__(kBlock) void k_top_count(const Rec* __restrict__ recs, u64 cap,
+                                                      TopQuery q, u64* ctr) {
+  u32 n = 0;
+  const u64 stride = (u64)gridDim.x * kBlock;
+  for (u64 s = (u64)blockIdx.x * kBlock + threadIdx.x; s < cap; s += stride)
+    n += top_key(load_rec(&recs[s]), q) != 0;
+  count_finish<false>(n, 0, nullptr, nullptr, ctr);
+}
+
+// One digit's histogram.  The loop is uniform (a lane past the table reads the
+// last record and drops it), so the wave votes below see whole waves.  A wave
+// whose keys all fall in one bin -- the leading digits of most tables, and
+// every digit of a table of equal keys -- adds its count once; only a mixed
+// wave adds per lane.
+__global__ __launch_bounds__(kBlock) void k_top_hist(const Rec* __restrict__ recs, u64 cap,
+                                                     TopQuery q, const u64* __restrict__ ctr,
+                                                     u32* __restrict__ ghist) {
+  __shared__ u32 h[kTopBins];
+  if (ctr[kTpMode] != kTopRefine) return;
+  const u32 done = (u32)ctr[kTpDone];
+  const u64 pfx = ctr[kTpPfx];
+  const u32 width = 64 - done < kTopBits ? 64 - done : kTopBits;
+  const u32 nshift = 64 - done - width;
+  for (u32 i = threadIdx.x; i < kTopBins; i += kBlock) h[i] = 0;
+  __syncthreads();
+  const u32 lane = __lane_id();
+  const u64 stride = (u64)gridDim.x * kBlock;
+  for (u64 base = (u64)blockIdx.x * kBlock; base < cap; base += stride) {
+    const u64 s = base + threadIdx.x;
+    const u64 key = top_key(load_rec(&recs[s < cap ? s : cap - 1]), q);
+    const u64 hi = done ? key >> (64 - done) : 0ull;
+    const bool in = s < cap && key != 0 && hi == pfx;
+    const u32 d = (u32)(key >> nshift) & ((1u << width) - 1);
+    const u64 m = __ballot(in);
+    if (!m) continue;
+    const u32 lead = (u32)__ffsll((long long)m) - 1;
+    const u32 d0 = __shfl(d, lead);
+    if (__ballot(in && d == d0) == m) {
+      if (lane == lead) atomicAdd(&h[d0], (u32)__popcll(m));
+    } else if (in) {
+      atomicAdd(&h[d], 1u);
+    }
+  }
+  __syncthreads();
+  for (u32 i = threadIdx.x; i < kTopBins; i += kBlock) {
+    const u32 c = h[i];
+    if (c) atomicAdd(&ghist[i], c);
+  }
+}
+
+// The cut's digit.  Thread t holds the bins kTopBins - 1 - (8t .. 8t + 7), so
+// an exclusive scan over the threads counts the keys in the bins above each;
+// the cut falls in the one bin with above < remaining <= above + its count.
+// That thread alone rewrites the counter words (every thread has read them
+// before the scan's barrier) and clears nothing but its own bins, which all
+// threads do for the next pass.  The first pass also learns the population
+// (the histogram's total) and with it min(k, population).
+__global__ __launch_bounds__(kTopPickBlock) void k_top_pick(u64* ctr, u32* __restrict__ ghist,
+                                                            u32 k) {
+  constexpr u32 kPer = kTopBins / kTopPickBlock;
+  __shared__ u64 wsum[kTopPickBlock / 64];
+  if (ctr[kTpMode] != kTopRefine) return;
+  const u32 done = (u32)ctr[kTpDone];
+  const u64 pfx = ctr[kTpPfx], above0 = ctr[kTpAbove], rem0 = ctr[kTpRem], passes = ctr[kTpPasses];
+  const u32 width = 64 - done < kTopBits ? 64 - done : kTopBits;
+  u32 c[kPer];
+  u64 loc = 0;
+#pragma unroll
+  for (u32 j = 0; j < kPer; ++j) {
+    const u32 b = kTopBins - 1 - (threadIdx.x * kPer + j);
+    c[j] = ghist[b];
+    ghist[b] = 0;
+    loc += c[j];
+  }
+  const u64 incl = wave_incl_scan64(loc);
+  const u32 wv = threadIdx.x >> 6;
+  if (__lane_id() == 63) wsum[wv] = incl;
+  __syncthreads();
+  u64 pre = 0, tot = 0;
+  for (u32 w = 0; w < kTopPickBlock / 64; ++w) {
+    if (w < wv) pre += wsum[w];
+    tot += wsum[w];
+  }
+  const u64 rem = done ? rem0 : (tot < k ? tot : (u64)k);
+  if (!done && threadIdx.x == 0) {
+    ctr[kTpPop] = tot;
+    ctr[kTpK] = rem;
+    ctr[kTpPasses] = passes + 1;
+    if (!rem) ctr[kTpMode] = kTopEmpty;
+  }
+  if (!rem) return;
+  u64 ex = pre + incl - loc;
+#pragma unroll
+  for (u32 j = 0; j < kPer; ++j) {
+    if (ex < rem && rem <= ex + c[j]) {
+      const u64 b = kTopBins - 1 - (threadIdx.x * kPer + j);
+      const u64 above = above0 + ex, left = rem - ex, at = c[j];
+      ctr[kTpPfx] = (pfx << width) | b;
+      ctr[kTpDone] = done + width;
+      ctr[kTpRem] = left;
+      ctr[kTpAbove] = above;
+      if (done) ctr[kTpPasses] = passes + 1;
+      if (above + at <= kTopCap) {
+        ctr[kTpMode] = kTopEarly;
+        ctr[kTpLimit] = at;
+      } else if (done + width == 64) {
+        ctr[kTpMode] = kTopTies;
+        ctr[kTpLimit] = left;
+      }
+    }
+    ex += c[j];
+  }
+}
+
+// Ties: the records of tile t whose key is the threshold (every key bit is
+// selected: the prefix is the key), into tile_cnt[t]; the byte sums tile_scan
+// also walks are zeros.
+__global__ __launch_bounds__(kBlock) void k_top_ties(const Rec* __restrict__ recs, u64 cap,
+                                                     TopQuery q, u64* ctr,
+                                                     u32* __restrict__ tile_cnt,
+                                                     u64* __restrict__ tile_bytes) {
+  if (ctr[kTpMode] != kTopTies) return;
+  const u64 thr = ctr[kTpPfx];
+  u32 n = 0;
+  const u64 t0 = (u64)blockIdx.x * kSweepTile;
+#pragma unroll 4
+  for (u32 k = 0; k < kSweepTile / kBlock; ++k) {
+    const u64 s = t0 + (u64)k * kBlock + threadIdx.x;
+    if (s >= cap) break;
+    n += top_key(load_rec(&recs[s]), q) == thr;
+  }
+  count_finish<true>(n, 0, tile_cnt, tile_bytes, nullptr);
+  if (blockIdx.x == 0 && threadIdx.x == 0) ctr[kTpPasses] += 1;
+}
+
+__global__ __launch_bounds__(kSweepBlock) void k_top_scan(const u64* __restrict__ ctr,
+                                                          u32* __restrict__ tile_cnt,
+                                                          u64* __restrict__ tile_bytes, u32 ntiles) {
+  if (ctr[kTpMode] != kTopTies) return;
+  (void)tile_scan(tile_cnt, tile_bytes, ntiles);
+}
+
+// Collect, k_sweep_write's workgroup and steps.  Ties: a step scans the "key
+// is the threshold" bits per wave and adds the waves before it through LDS
+// (two buffers by step parity, one barrier a step), which with the tile's
+// scanned base is the record's rank among the table's ties in slot order; it
+// is admitted iff that rank is below the limit.  Early: every key at the
+// prefix is admitted, and no rank is needed.
+__global__ __launch_bounds__(kSweepBlock) void k_top_collect(const Rec* __restrict__ recs, u64 cap,
+                                                             TopQuery q, u64* ctr,
+                                                             const u32* __restrict__ tile_cnt,
+                                                             u64* __restrict__ ckey,
+                                                             u32* __restrict__ cslot) {
+  __shared__ u32 wtot[2][kSweepBlock / 64];
+  const u64 mode = ctr[kTpMode];
+  if (mode != kTopEarly && mode != kTopTies) return;
+  const bool ties = mode == kTopTies;
+  const u32 shift = 64 - (u32)ctr[kTpDone];   // (at most 52: a digit is selected)
+  const u64 pfx = ctr[kTpPfx], limit = ctr[kTpLimit];
+  u64 rank0 = ties ? tile_cnt[blockIdx.x] : 0ull;
+  const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const u32 lane = __lane_id();
+  const u64 t0 = (u64)blockIdx.x * kSweepTile;
+  for (u32 k = 0; k < kSweepTile / kSweepBlock; ++k) {
+    const u64 s = t0 + (u64)k * kSweepBlock + threadIdx.x;
+    const u64 key = top_key(load_rec(&recs[s < cap ? s : cap - 1]), q);
+    const bool live = s < cap && key != 0;
+    const u64 hi = key >> shift;
+    bool at = live && hi == pfx;
+    if (ties) {
+      const u32 v = at ? 1u : 0u;
+      const u32 sc = wave_incl_scan(v);
+      if (lane == 63) wtot[k & 1][wv] = sc;
+      __syncthreads();   // (uniform: the mode is the grid's)
+      u32 pre = 0, tot = 0;
+#pragma unroll
+      for (u32 w = 0; w < kSweepBlock / 64; ++w) {
+        const u32 x = wtot[k & 1][w];
+        if (w < wv) pre += x;
+        tot += x;
+      }
+      at = at && rank0 + pre + sc - v < limit;
+      rank0 += tot;
+    }
+    const bool take = at || (live && hi > pfx);
+    const u64 m = __ballot(take);
+    if (!m) continue;
+    const u32 lead = (u32)__ffsll((long long)m) - 1;
+    u64 base = 0;
+    if (lane == lead) base = atomicAdd(&ctr[kTpCnt], (u64)__popcll(m));
+    base = __shfl(base, lead);
+    if (take) {
+      const u64 pos = base + (u64)__popcll(m & ((1ull << lane) - 1));
+      if (pos < kTopCap) {
+        ckey[pos] = key;
+        cslot[pos] = (u32)s;   // (a table has at most 2^31 slots)
+      } else {
+        ctr[kTpErr] = 1;
+      }
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) ctr[kTpPasses] += 1;
+}
+
+struct TopOut {
+  u8* names;
+  u64* offs;
+  u64* taken;          // the two columns may be null
+  phip_state* state;
+};
+
+// Sort and write.  A bitonic network over kTopCap pairs in LDS (the buffer's
+// tail padded with key 0, which no candidate has) orders them by key
+// descending, slot ascending -- a total order, slots being distinct, so the
+// list does not depend on the places the collect handed out.  Thread t then
+// owns ranks 4t .. 4t + 3: their name lengths are scanned across the
+// workgroup, each entry's end replaces its key in LDS, and entry i is written
+// iff its end fits names_cap -- ends grow with the rank, so the written
+// entries are a prefix of the list, and the last of them stores n and bytes.
+__global__ __launch_bounds__(kTopEmitBlock) void k_top_emit(const Rec* __restrict__ recs,
+                                                            const u8* __restrict__ arena,
+                                                            u64 arena_used, u64* ctr,
+                                                            const u64* __restrict__ ckey,
+                                                            const u32* __restrict__ cslot,
+                                                            TopOut out, u64 names_cap) {
+  constexpr u32 kPer = kTopCap / kTopEmitBlock;
+  __shared__ u64 sk[kTopCap];
+  __shared__ u32 ss[kTopCap];
+  __shared__ u64 wsum[kTopEmitBlock / 64];
+  const u64 mode = ctr[kTpMode];
+  if (threadIdx.x == 0) out.offs[0] = 0;
+  if (mode != kTopEarly && mode != kTopTies) return;   // (empty: n = bytes = 0 stand)
+  const u64 cnt = ctr[kTpCnt], want = ctr[kTpK];
+  const u32 nc = (u32)(cnt < kTopCap ? cnt : kTopCap);
+  const u32 nout = (u32)(want < nc ? want : nc);
+  for (u32 i = threadIdx.x; i < kTopCap; i += kTopEmitBlock) {
+    sk[i] = i < nc ? ckey[i] : 0ull;
+    ss[i] = i < nc ? cslot[i] : ~0u;
+  }
+  __syncthreads();
+  for (u32 size = 2; size <= kTopCap; size <<= 1) {
+    for (u32 stride = size >> 1; stride; stride >>= 1) {
+      for (u32 p = threadIdx.x; p < kTopCap / 2; p += kTopEmitBlock) {
+        const u32 i = 2 * p - (p & (stride - 1)), j = i + stride;
+        const u64 ki = sk[i], kj = sk[j];
+        const u32 si = ss[i], sj = ss[j];
+        // (j_first: the pair at j ranks before the pair at i)
+        const bool j_first = kj > ki || (kj == ki && sj < si);
+        const bool fwd = (i & size) == 0;
+        if (fwd == j_first && (ki != kj || si != sj)) {
+          sk[i] = kj; sk[j] = ki;
+          ss[i] = sj; ss[j] = si;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // the name lengths in rank order
+  const u32 i0 = threadIdx.x * kPer;
+  u32 len[kPer];
+  u64 loc = 0;
+#pragma unroll
+  for (u32 j = 0; j < kPer; ++j) {
+    const u32 i = i0 + j;
+    len[j] = i < nout ? (u32)(recs[ss[i]].name0 & 0xFFu) : 0u;
+    loc += len[j];
+  }
+  const u64 incl = wave_incl_scan64(loc);
+  const u32 wv = threadIdx.x >> 6;
+  if (__lane_id() == 63) wsum[wv] = incl;
+  __syncthreads();   // (the sort's last reads of sk are behind this barrier too)
+  u64 end = incl - loc;
+  for (u32 w = 0; w < wv; ++w) end += wsum[w];
+#pragma unroll
+  for (u32 j = 0; j < kPer; ++j) {
+    end += len[j];
+    sk[i0 + j] = end;
+  }
+  __syncthreads();
+#pragma unroll
+  for (u32 j = 0; j < kPer; ++j) {
+    const u32 i = i0 + j;
+    if (i >= nout) break;
+    const u64 e = sk[i], start = e - len[j];
+    if (e > names_cap) break;
+    const Rec r = load_rec(&recs[ss[i]]);
+    out.offs[i + 1] = e;
+    put_name(out.names + start, r, len[j], arena, arena_used, &ctr[kTpErr]);
+    if (out.taken) out.taken[i] = dec_f64(r.taken);
+    if (out.state) {
+      phip_state st;
+      st.added = dec_f64(r.added); st.taken = dec_f64(r.taken);
+      st.elapsed = r.elapsed; st.created = r.created;
+      out.state[i] = st;
+    }
+    if (i + 1 == nout || sk[i + 1] > names_cap) {
+      ctr[kTpN] = i + 1;
+      ctr[kTpBytes] = e;
+      ctr[kTpTrunc] = i + 1 < nout;
+    }
+  }
+}
+
 }  // namespace phip
 

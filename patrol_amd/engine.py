@@ -518,6 +518,60 @@ class GPURepo:
             if d["done"]:
                 return
 
+    # -------------------------------------------------------- top talkers --
+    def _top_call(self, k, prefix, now, idle_ns, out, flags, metric=0):
+        prefix = bytes(prefix)
+        q = _lib.phip_top_query()
+        head = prefix[:_lib.THROTTLE_MAX_PREFIX]   # (a longer one keeps its length: refused)
+        q.prefix[:len(head)] = list(head)
+        q.prefix_len, q.metric, q.now, q.idle_ns, q.k = len(prefix), int(metric), int(now), \
+            int(idle_ns), int(k)
+        st = _lib.phip_top_stats()
+        rc = self.L.phip_export_top(self.h, C.byref(q), out, C.byref(st), flags)
+        self._queued = None   # a queued batch is finished (or failed)
+        self._check(rc)
+        return {f: int(getattr(st, f)) for f, _ in _lib.phip_top_stats._fields_}
+
+    def top(self, k: int, prefix: bytes = b"", now: int = 0, idle_ns: int = 0,
+            names_cap: int | None = None, state: bool = False) -> dict:
+        """phip_export_top: the k buckets with the largest `taken` among those
+        whose name starts with `prefix` (at most 16 bytes) and, with idle_ns >
+        0, that evict_idle's rule does not call idle at `now`; only positive
+        `taken` (+Inf included) ranks.  By `taken` descending, equal values in
+        slot order.  -> dict(names list[bytes], taken uint64 (float64 bits),
+        state (None, or a structured array a/t/e/c), n, bytes, population (the
+        buckets that qualified), passes (kernels that read the whole table),
+        truncated (names_cap, default 231 * k, cut the list))."""
+        z = max(int(k), 1)
+        if names_cap is None:
+            names_cap = _lib.MAX_NAME_LEN * z
+        names = np.zeros(max(int(names_cap), 1), np.uint8)
+        offs = np.zeros(z + 1, np.uint64)
+        taken = np.zeros(z, np.uint64)
+        sta = np.zeros(z, dtype=[("a", "<u8"), ("t", "<u8"), ("e", "<i8"), ("c", "<i8")]) \
+            if state else None
+        out = _lib.phip_top_out(_ptr(names), int(names_cap), _ptr(offs), _ptr(taken), _ptr(sta))
+        d = self._top_call(k, prefix, now, idle_ns, C.byref(out), 0)
+        n = d["n"]
+        raw = names[:d["bytes"]].tobytes()
+        d.update(names=[raw[int(offs[i]):int(offs[i + 1])] for i in range(n)], taken=taken[:n],
+                 state=None if sta is None else sta[:n])
+        return d
+
+    def top_device(self, k: int, names, offs, taken=None, state=None, prefix: bytes = b"",
+                   now: int = 0, idle_ns: int = 0) -> dict:
+        """phip_export_top with device pointers: names (uint8 CUDA tensor, every
+        byte of it is budget), offs (int64[k + 1]), taken (int64[k]) and state
+        (int64[k, 4]) where wanted.  -> the stats dict."""
+        cap = int(names.numel() * names.element_size())
+        out = _lib.phip_top_out(_ptr(names), cap, _ptr(offs), _ptr(taken), _ptr(state))
+        return self._top_call(k, prefix, now, idle_ns, C.byref(out), DEVICE_PTRS)
+
+    def top_count(self, prefix: bytes = b"", now: int = 0, idle_ns: int = 0) -> dict:
+        """How many buckets qualify for top() (PHIP_SWEEP_COUNT): one pass,
+        dict(population, passes, ...)."""
+        return self._top_call(1, prefix, now, idle_ns, None, _lib.SWEEP_COUNT)
+
     # -------------------------------------------------------- change set --
     @staticmethod
     def _changes_dict(st) -> dict:
@@ -1068,6 +1122,56 @@ def throttle_match(rules, name: bytes) -> int:
     return int(out.value)
 
 
+_STATE_DT = [("a", "<u8"), ("t", "<u8"), ("e", "<i8"), ("c", "<i8")]
+
+
+def top_merge(lists, k: int, names_cap: int | None = None) -> dict:
+    """phip_top_merge (host only, no handle, no GPU): the top k of several
+    GPURepo.top() results (dicts with names, taken and, optionally, state) --
+    a shard group's members, or replicas of different nodes.  By `taken`
+    descending, equal values by list index and then position; a name present
+    more than once is kept once, with the larger `taken` and that entry's
+    state.  -> dict(names, taken, state (None unless every list carries one),
+    n)."""
+    lists = list(lists)
+    n_l = len(lists)
+    arr = (_lib.phip_top_out * max(n_l, 1))()
+    ns = (C.c_uint64 * max(n_l, 1))()
+    keep = []
+    want_state = n_l > 0 and all(d.get("state") is not None for d in lists)
+    total = 0
+    for i, d in enumerate(lists):
+        nm = d["names"]
+        offs = np.zeros(len(nm) + 1, np.uint64)
+        if nm:
+            offs[1:] = np.cumsum(np.fromiter((len(x) for x in nm), np.int64, len(nm)))
+        blob = np.frombuffer(b"".join(nm) + b"\0", np.uint8).copy()
+        tk = _np(d["taken"], np.uint64)
+        st = np.ascontiguousarray(d["state"], _STATE_DT) if d.get("state") is not None else None
+        if st is not None and not st.size:
+            st = np.zeros(1, _STATE_DT)
+        keep.append((blob, offs, tk, st))
+        arr[i] = _lib.phip_top_out(_ptr(blob), int(offs[-1]), _ptr(offs), _ptr(tk), _ptr(st))
+        ns[i] = len(nm)
+        total += int(offs[-1])
+    z = max(int(k), 1)
+    if names_cap is None:
+        names_cap = total
+    names = np.zeros(max(int(names_cap), 1), np.uint8)
+    offs = np.zeros(z + 1, np.uint64)
+    taken = np.zeros(z, np.uint64)
+    sta = np.zeros(z, _STATE_DT) if want_state else None
+    out = _lib.phip_top_out(_ptr(names), int(names_cap), _ptr(offs), _ptr(taken), _ptr(sta))
+    n = C.c_uint64()
+    rc = _lib.load().phip_top_merge(arr, ns, n_l, int(k), C.byref(out), C.byref(n))
+    if rc < 0:
+        raise PatrolHipError(rc, "phip_top_merge")
+    n = int(n.value)
+    raw = names[:int(offs[n])].tobytes()
+    return dict(names=[raw[int(offs[i]):int(offs[i + 1])] for i in range(n)], taken=taken[:n],
+                state=None if sta is None else sta[:n], n=n)
+
+
 class GPUGroup:
     """A shard group over RCCL (phip_group_*, include/patrolhip.h): the
     buckets hash-sharded by name over several GPUs, owner-routed Receive and
@@ -1406,6 +1510,19 @@ class GPUGroup:
             (_lib.GROUP_PEEK_STATE if want_state else 0)
         self._check(self.L.phip_group_peek(self.g, ops, res, sent, answered, flags))
         return out, [int(x) for x in sent], [int(x) for x in answered]
+
+    def top(self, k: int, prefix: bytes = b"", now: int = 0, idle_ns: int = 0,
+            state: bool = False) -> dict:
+        """The group's top talkers: GPURepo.top of every local member (their
+        tables are disjoint), then top_merge.  -> top_merge's dict, with
+        population and passes summed over the members and `members`, their own
+        results."""
+        parts = [r.top(k, prefix, now, idle_ns, state=state) for r in self.repos]
+        d = top_merge(parts, k)
+        d.update(bytes=sum(map(len, d["names"])), population=sum(p["population"] for p in parts),
+                 passes=sum(p["passes"] for p in parts),
+                 truncated=int(any(p["truncated"] for p in parts)), members=parts)
+        return d
 
     def set_timing(self, on: bool = True):
         """phip_group_set_timing: per-stage event timing of later calls."""
