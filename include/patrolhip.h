@@ -1305,6 +1305,114 @@ int phip_ring_receive_replies(phip_ring* r, uint32_t slot, int64_t now, const ph
 /* host only: out_peers[k] = peers[src[k]] (PHIP_PEER_BYTES each), for phip_udp_send_batch */
 int phip_reply_peers(const uint8_t* peers, const uint32_t* src, uint32_t n, uint8_t* out_peers);
 
+/* ---- Packed frames ----
+ * Between two patrol-hip nodes nothing forces one bucket record per UDP
+ * datagram.  A run of back-to-back MarshalBinary records (bucket.go:51-68) is
+ * self-delimiting -- byte 24 of a record is its name length -- and every
+ * export here writes such a run, every wire receive takes one as (bytes,
+ * offs).  A frame is a UDP payload of 1..N whole records: a coarser offsets
+ * column over the same bytes.  phip_frame_cuts makes that column for the
+ * egress side (phip_udp_send_batch then sends frames, the bytes untouched);
+ * phip_unframe recovers the per-record offsets from received frames, and the
+ * phip_*receive_frames* calls put it in front of the receive calls.
+ *
+ * Opt-in per peer.  The reference reads 256 bytes and UnmarshalBinary ignores
+ * what follows the name (bucket.go:71-91, repo.go:57,114): a Go peer sees only
+ * a frame's first record.  A frame of one record is byte for byte today's
+ * datagram, and no datagram call changes.
+ *
+ * Splitting rule (phip_unframe).  Frame f is bytes[foffs[f] .. foffs[f+1]).
+ * Walked from its start: while at least PHIP_BUCKET_FIXED_SIZE bytes are left
+ * and 25 + bytes[p+24] fits in what is left, that is one record; whatever is
+ * left when that fails, 1 byte or more, is one last record -- malformed by
+ * construction, so the receive calls' stop rule (repo.go:70-74) fires there;
+ * an empty frame yields one empty record.  Every frame yields at least one
+ * record, records are contiguous in frame order: record k is
+ * bytes[rec_offs[k] .. rec_offs[k+1]), rec_frame[k] its frame.  One difference
+ * from the datagram calls: a datagram's bytes after the name are ignored, a
+ * frame's are parsed as further records.
+ *
+ * Cut rule (phip_frame_cuts).  Records are taken in runs of PHIP_FRAME_TILE; a
+ * new frame starts at each run's first record, and inside a run cuts are
+ * greedy: a frame takes records while its size stays at most frame_bytes.
+ * Records are never split (one longer than frame_bytes is PHIP_ERR_INVALID)
+ * and keep their order, so an export's "requests in front" survives.
+ *
+ * Pointers and flags.  flags is 0 (host pointers) or PHIP_DEVICE_PTRS.  The
+ * host forms are plain host walks that touch no device and ignore h (NULL is
+ * fine): they run on a machine without a GPU.  With PHIP_DEVICE_PTRS the
+ * kernels run on the handle's stream, every array is device memory, and
+ * `bytes` is aligned and padded as phip_receive_datagrams demands; the only
+ * host wait is the read-back of the count.
+ *
+ * phip_unframe errors (PHIP_ERR_INVALID, nothing written): frame_bytes outside
+ * [PHIP_FRAME_MIN_BYTES, PHIP_FRAME_MAX_BYTES]; a frame longer than
+ * frame_bytes or a decreasing entry; in a checked batch (bytes_len != 0) an
+ * entry that breaks foffs[f] <= foffs[f+1] <= bytes_len.  The check runs from
+ * the offsets alone before any byte is read: nothing is read at a bad entry
+ * and no frame is walked, and a walk takes at most frame_bytes / 25 + 1 steps
+ * whatever the bytes hold.  n_recs > max_recs is PHIP_ERR_INVALID too:
+ * *n_recs_out holds the count needed and rec_offs is unspecified.  rec_offs
+ * has max_recs + 1 entries, rec_frame (optional) max_recs.
+ *
+ * phip_frame_cuts: frame_offs has max_frames + 1 entries, of which
+ * n_frames + 1 are written, a subset of offs; frame_first (optional) receives
+ * each frame's first record.  n = 0 gives 0 frames and frame_offs[0] =
+ * offs[0]; n_frames > max_frames is PHIP_ERR_INVALID with the count needed in
+ * *n_frames_out.
+ *
+ * One-call ingest.  phip_receive_frames / phip_receive_frames_replies are
+ * phip_unframe followed by phip_receive_datagrams / _replies over the records
+ * (on the same stream for device pointers): the same statuses, results, table
+ * effects, stop rule and reply egress, with max_recs the capacity of the
+ * result columns.  *stop_index and the reply egress's src[] are record
+ * indices; rec_frame (optional, max_recs entries) maps them to frames, and
+ * phip_frame_reply_peers to the senders.  An unframe error, n_recs > max_recs
+ * included, merges nothing.  The ring forms run over a slot that was filled
+ * with frames (offs = frame offsets, phip_ring_submit(slot, n_frames)
+ * unchanged; the ring is opened with max_msgs = frames and max_bytes >=
+ * frame_bytes * frames; res, rec_frame and rq's buffers are host memory). */
+#define PHIP_FRAME_MIN_BYTES     256     /* any record fits */
+#define PHIP_FRAME_DEFAULT_BYTES 1472    /* 1500 - 20 - 8 */
+#define PHIP_FRAME_MAX_BYTES     65507
+#define PHIP_FRAME_TILE          4096    /* records: a frame never spans a tile boundary */
+int phip_unframe(phip_handle* h, const uint8_t* bytes, const uint64_t* foffs, uint32_t n_frames,
+                 uint64_t bytes_len, uint32_t frame_bytes, uint64_t* rec_offs,
+                 uint32_t* rec_frame /* optional */, uint32_t max_recs, uint32_t* n_recs_out,
+                 uint32_t flags);
+int phip_frame_cuts(phip_handle* h, const uint64_t* offs, uint32_t n, uint32_t frame_bytes,
+                    uint64_t* frame_offs, uint32_t* frame_first /* optional */,
+                    uint32_t max_frames, uint32_t* n_frames_out, uint32_t flags);
+int phip_receive_frames(phip_handle* h, const uint8_t* bytes, const uint64_t* foffs,
+                        uint32_t n_frames, int64_t now, const phip_results* res,
+                        uint32_t* stop_index, uint32_t frame_bytes,
+                        uint32_t* rec_frame /* optional */, uint32_t max_recs,
+                        uint32_t* n_recs_out, uint32_t flags);
+int phip_receive_frames_replies(phip_handle* h, const uint8_t* bytes, const uint64_t* foffs,
+                                uint32_t n_frames, int64_t now, const phip_results* res,
+                                uint32_t* stop_index, phip_reply_egress* rq, uint32_t frame_bytes,
+                                uint32_t* rec_frame /* optional */, uint32_t max_recs,
+                                uint32_t* n_recs_out, uint32_t flags);
+int phip_ring_receive_frames(phip_ring* r, uint32_t slot, int64_t now, const phip_results* res,
+                             uint32_t frame_bytes, uint32_t* rec_frame /* optional */,
+                             uint32_t max_recs, uint32_t* n_recs_out, uint32_t* stop_index);
+int phip_ring_receive_frames_replies(phip_ring* r, uint32_t slot, int64_t now,
+                                     const phip_results* res, uint32_t frame_bytes,
+                                     uint32_t* rec_frame /* optional */, uint32_t max_recs,
+                                     uint32_t* n_recs_out, uint32_t* stop_index,
+                                     phip_reply_egress* rq);
+/* host only: phip_udp_recv_batch with windows of frame_bytes instead of
+ * PHIP_BUCKET_PACKET_SIZE -- a longer datagram is cut to frame_bytes -- so that
+ * frame f is bytes[foffs[f] .. foffs[f+1]), foffs[0] = 0; frame_bytes outside
+ * [PHIP_FRAME_MIN_BYTES, PHIP_FRAME_MAX_BYTES] is PHIP_ERR_INVALID. */
+int phip_udp_recv_frames(int fd, uint8_t* bytes, uint64_t cap, uint64_t* foffs,
+                         uint32_t max_frames, uint32_t frame_bytes, uint8_t* peers, int timeout_ms,
+                         uint32_t* n_out);
+/* host only: out_peers[k] = peers[rec_frame[src[k]]] (PHIP_PEER_BYTES each): the
+ * senders of a frames call's reply datagrams, peers by frame */
+int phip_frame_reply_peers(const uint8_t* peers, const uint32_t* rec_frame, const uint32_t* src,
+                           uint32_t n, uint8_t* out_peers);
+
 /* ---- shard layer ---- */
 /* FNV-1a 64 of each name (the table's probe key; also the shard map:
  * owner = ((hash >> 32) * world) >> 32).  Host pointers need no GPU (h may be

@@ -12,6 +12,7 @@ from .engine import (BucketState, GPUGroup, GPURepo, PatrolHipError, Ring, TakeB
 from .engine import peek_eval, throttle_match  # noqa: F401
 from .engine import reply_peers  # noqa: F401
 from .engine import top_merge  # noqa: F401
+from .engine import frame_cuts, frame_reply_peers, udp_recv_frames, unframe  # noqa: F401
 
 __all__ = ["GPURepo", "GPUGroup", "BucketState", "PatrolHipError", "Ring", "TakeBatcher", "parse_rate", "marshal",
            "names_blob", "udp_recv_batch", "udp_send_batch", "incast_replies", "digest_diff",

@@ -46,6 +46,9 @@ EXPORTS = [
     "phip_group_ring_receive_replies", "phip_group_reply_stats",
     "phip_group_peek",
     "phip_export_top", "phip_top_merge",
+    "phip_unframe", "phip_frame_cuts", "phip_receive_frames", "phip_receive_frames_replies",
+    "phip_ring_receive_frames", "phip_ring_receive_frames_replies", "phip_udp_recv_frames",
+    "phip_frame_reply_peers",
 ]
 
 PHIP_OK = 0
@@ -82,6 +85,10 @@ MAX_NAME_LEN = 231         # PHIP_MAX_NAME_LEN
 THROTTLE_MAX_RULES = 8     # PHIP_THROTTLE_MAX_RULES
 THROTTLE_MAX_PREFIX = 16   # PHIP_THROTTLE_MAX_PREFIX
 TOP_MAX = 4096             # PHIP_TOP_MAX: the largest k of phip_export_top
+FRAME_MIN_BYTES = 256      # PHIP_FRAME_MIN_BYTES: any record fits
+FRAME_DEFAULT_BYTES = 1472 # PHIP_FRAME_DEFAULT_BYTES: 1500 - 20 - 8
+FRAME_MAX_BYTES = 65507    # PHIP_FRAME_MAX_BYTES
+FRAME_TILE = 4096          # PHIP_FRAME_TILE: records; a frame never spans a tile boundary
 
 
 class phip_config(C.Structure):
@@ -399,5 +406,21 @@ def load(path: str = LIB_PATH):
                                       C.POINTER(phip_top_stats), u32]
         L.phip_top_merge.argtypes = [C.POINTER(phip_top_out), C.POINTER(u64), u32, u32,
                                      C.POINTER(phip_top_out), C.POINTER(u64)]
+    if hasattr(L, "phip_unframe"):
+        rqp = C.POINTER(phip_reply_egress)
+        L.phip_unframe.argtypes = [vp, vp, vp, u32, u64, u32, vp, vp, u32, C.POINTER(u32), u32]
+        L.phip_frame_cuts.argtypes = [vp, vp, u32, u32, vp, vp, u32, C.POINTER(u32), u32]
+        L.phip_receive_frames.argtypes = [vp, vp, vp, u32, i64, C.POINTER(phip_results),
+                                          C.POINTER(u32), u32, vp, u32, C.POINTER(u32), u32]
+        L.phip_receive_frames_replies.argtypes = [vp, vp, vp, u32, i64, C.POINTER(phip_results),
+                                                  C.POINTER(u32), rqp, u32, vp, u32,
+                                                  C.POINTER(u32), u32]
+        L.phip_ring_receive_frames.argtypes = [vp, u32, i64, C.POINTER(phip_results), u32, vp, u32,
+                                               C.POINTER(u32), C.POINTER(u32)]
+        L.phip_ring_receive_frames_replies.argtypes = [vp, u32, i64, C.POINTER(phip_results), u32,
+                                                       vp, u32, C.POINTER(u32), C.POINTER(u32), rqp]
+        L.phip_udp_recv_frames.argtypes = [C.c_int, vp, u64, vp, u32, u32, vp, C.c_int,
+                                           C.POINTER(u32)]
+        L.phip_frame_reply_peers.argtypes = [vp, vp, vp, u32, vp]
     _lib = L
     return L

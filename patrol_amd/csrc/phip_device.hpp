@@ -314,6 +314,63 @@ __host__ __device__ inline ThrottleHit throttle_match(const ThrottleRules& R, u6
   return h;
 }
 
+// ------------------------------------------------------------ frames -----
+// phip_unframe / phip_frame_cuts (patrolhip.h "Packed frames"): the two rules,
+// once, for the host forms and the kernels alike.
+//
+// The splitting rule over frame bytes[o .. end): emit(j, p) for record j of
+// the frame, which starts at byte p; returns the frame's record count (>= 1).
+// While PHIP_BUCKET_FIXED_SIZE bytes are left and the record its length byte
+// announces fits, that is a record; what is left when that fails becomes one
+// last, malformed record; an empty frame is one empty record.  Every step but
+// the last advances by at least PHIP_BUCKET_FIXED_SIZE bytes: at most
+// (end - o) / PHIP_BUCKET_FIXED_SIZE + 1 steps, whatever the bytes hold.
+template <class Emit>
+__host__ __device__ inline u32 frame_walk(const u8* bytes, u64 o, u64 end, Emit emit) {
+  u64 p = o;
+  u32 j = 0;
+  while (end - p >= PHIP_BUCKET_FIXED_SIZE) {
+    const u64 sz = PHIP_BUCKET_FIXED_SIZE + (u64)bytes[p + PHIP_BUCKET_FIXED_SIZE - 1];
+    if (sz > end - p) break;
+    emit(j++, p);
+    p += sz;
+  }
+  if (p < end || j == 0) emit(j++, p);
+  return j;
+}
+
+// A frame entry as the unframe check takes it, from the offsets alone: false
+// when it decreases, is longer than frame_bytes, or (lim != 0, a checked
+// batch) ends past lim.
+__host__ __device__ inline bool frame_entry_ok(u64 o, u64 end, u64 lim, u32 frame_bytes) {
+  return end >= o && end - o <= frame_bytes && (lim == 0 || end <= lim);
+}
+
+// The cut rule's test: a frame that starts at byte o0 may take the record
+// that ends at byte e (a decreasing entry never fits).
+__host__ __device__ inline bool frame_fits(u64 o0, u64 e, u32 frame_bytes) {
+  return e >= o0 && e - o0 <= frame_bytes;
+}
+
+// The cut rule over one run of records [r0, r1) (r1 - r0 <= PHIP_FRAME_TILE):
+// greedy frames, emit(k, first) for the run's frame k and its first record;
+// returns the run's frame count, or ~0u at a record that fits no frame.
+template <class Emit>
+__host__ __device__ inline u32 frame_cut_run(const uint64_t* offs, u64 r0, u64 r1, u32 frame_bytes,
+                                             Emit emit) {
+  u32 k = 0;
+  u64 first = r0;
+  while (first < r1) {
+    const u64 o0 = offs[first];
+    u64 j = first;
+    while (j < r1 && frame_fits(o0, offs[j + 1], frame_bytes)) ++j;
+    if (j == first) return ~0u;
+    emit(k++, first);
+    first = j;
+  }
+  return k;
+}
+
 // Bucket.Merge for one `other` (bucket.go:250-260) on raw values.
 __host__ __device__ inline void go_merge(double& a, double& t, i64& e, double oa, double ot,
                                          i64 oe) {

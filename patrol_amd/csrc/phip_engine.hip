@@ -66,6 +66,7 @@ enum BufId {
   B_EGSZ, B_EGTILE, B_EGOUT, B_EGOFFS,
   B_PEEKAT, B_PEEKST, B_TOP,
   B_RQCTR, B_RQSEL, B_RQTILE, B_RQOUT, B_RQOFFS, B_RQSRC, B_RQSTAT, B_RQREP,
+  B_FRAME, B_FRRECS, B_FRMAP,
   B_COUNT_
 };
 
@@ -3513,9 +3514,177 @@ int receive_datagrams_dev(phip_handle* h, const u8* d_bytes, const uint64_t* d_o
   if (stop < n) return set_err(h, PHIP_ERR_SHORT_BUFFER, "short buffer at datagram %u", stop);
   return PHIP_OK;
 }
+
+// ---- packed frames (patrolhip.h "Packed frames"; kernels in phip_kernels.hpp
+// "packed frames") ----
+// The call's device buffer: the counters, the tile arrays of the scan, and
+// (unframe) a record count per frame.
+struct FrameBuf {
+  u64* ctr;
+  u64* tile_bytes;
+  u32* tile_cnt;
+  u32* fcnt;
+  FrameBuf(u64* p, u32 ntiles)
+      : ctr(p), tile_bytes(p + kFrWords), tile_cnt(reinterpret_cast<u32*>(p + kFrWords + ntiles)),
+        fcnt(reinterpret_cast<u32*>(p + kFrWords + ntiles + ((size_t)ntiles + 1) / 2)) {}
+  static size_t words(u32 ntiles, u32 per_entry) {
+    return kFrWords + (size_t)ntiles + ((size_t)ntiles + 1) / 2 + ((size_t)per_entry + 1) / 2;
+  }
+};
+
+bool frame_bytes_ok(uint32_t fb) { return fb >= PHIP_FRAME_MIN_BYTES && fb <= PHIP_FRAME_MAX_BYTES; }
+
+// The counters behind a frames call's write pass, read back: the one
+// synchronise of a device-pointer call.  *total: the records or frames the
+// call needs (saturated), also when they do not fit `cap`.
+int frame_close(phip_handle* h, const u64* ctr, const char* what, const char* unit, u32 cap,
+                u32* total) {
+  u64 c[kFrWords];
+  HIPCHK(h, hipMemcpyAsync(c, ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (c[kFrBad] != ~0ull)
+    return set_err(h, PHIP_ERR_INVALID, "%s: entry %llu is malformed or longer than frame_bytes", what,
+                   (unsigned long long)c[kFrBad]);
+  *total = (u32)std::min<u64>(c[kFrN], ~0u);
+  if (c[kFrN] > cap)
+    return set_err(h, PHIP_ERR_INVALID, "%s: %llu %s, room for %u", what, (unsigned long long)c[kFrN],
+                   unit, cap);
+  return PHIP_OK;
+}
+
+// phip_unframe over device memory, queued on the handle's stream: check,
+// count, scan, write, then the counters' read-back.
+int unframe_dev(phip_handle* h, const u8* d_bytes, const uint64_t* d_foffs, u32 n, u64 lim, u32 fb,
+                uint64_t* d_rec_offs, u32* d_rec_frame, u32 max_recs, u32* n_recs) {
+  *n_recs = 0;
+  if (n == 0) {
+    HIPCHK(h, hipMemcpyAsync(d_rec_offs, d_foffs, sizeof(uint64_t), hipMemcpyDeviceToDevice,
+                             h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PHIP_OK;
+  }
+  int rc;
+  u64* p;
+  const u32 ntiles = grid_for(n);
+  if ((rc = ensure(h, B_FRAME, FrameBuf::words(ntiles, n), &p))) return rc;
+  const FrameBuf b(p, ntiles);
+  HIPCHK(h, hipMemsetAsync(b.ctr, 0xFF, kFrWords * sizeof(u64), h->stream));
+  {
+    Launch l(h, "k_frame_check");
+    k_frame_check<<<ntiles, kBlock, 0, h->stream>>>(d_foffs, n, lim, fb, b.ctr);
+  }
+  {
+    Launch l(h, "k_frame_count");
+    k_frame_count<<<ntiles, kBlock, 0, h->stream>>>(d_bytes, d_foffs, n, b.ctr, b.fcnt, b.tile_cnt,
+                                                    b.tile_bytes);
+  }
+  {
+    Launch l(h, "k_frame_scan");
+    k_frame_scan<<<1, kSweepBlock, 0, h->stream>>>(b.tile_cnt, b.tile_bytes, ntiles, b.ctr);
+  }
+  {
+    Launch l(h, "k_frame_write");
+    k_frame_write<<<ntiles, kBlock, 0, h->stream>>>(d_bytes, d_foffs, n, b.ctr, b.fcnt, b.tile_cnt,
+                                                    max_recs, d_rec_offs, d_rec_frame);
+  }
+  HIPCHK(h, hipGetLastError());
+  return frame_close(h, b.ctr, "unframe", "records", max_recs, n_recs);
+}
+
+// phip_frame_cuts over device memory, likewise.
+int frame_cuts_dev(phip_handle* h, const uint64_t* d_offs, u32 n, u32 fb, uint64_t* d_frame_offs,
+                   u32* d_frame_first, u32 max_frames, u32* n_frames) {
+  *n_frames = 0;
+  if (n == 0) {
+    HIPCHK(h, hipMemcpyAsync(d_frame_offs, d_offs, sizeof(uint64_t), hipMemcpyDeviceToDevice,
+                             h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PHIP_OK;
+  }
+  int rc;
+  u64* p;
+  const u32 ntiles = (u32)(((u64)n + PHIP_FRAME_TILE - 1) / PHIP_FRAME_TILE);
+  const unsigned grid = (ntiles + kCutWaves - 1) / kCutWaves;
+  if ((rc = ensure(h, B_FRAME, FrameBuf::words(ntiles, 0), &p))) return rc;
+  const FrameBuf b(p, ntiles);
+  HIPCHK(h, hipMemsetAsync(b.ctr, 0xFF, kFrWords * sizeof(u64), h->stream));
+  {
+    Launch l(h, "k_frame_cut_count");
+    k_frame_cut_count<<<grid, kBlock, 0, h->stream>>>(d_offs, n, fb, b.ctr, b.tile_cnt,
+                                                      b.tile_bytes, ntiles);
+  }
+  {
+    Launch l(h, "k_frame_scan");
+    k_frame_scan<<<1, kSweepBlock, 0, h->stream>>>(b.tile_cnt, b.tile_bytes, ntiles, b.ctr);
+  }
+  {
+    Launch l(h, "k_frame_cut_write");
+    k_frame_cut_write<<<grid, kBlock, 0, h->stream>>>(d_offs, n, fb, b.ctr, b.tile_cnt, ntiles,
+                                                      max_frames, d_frame_offs, d_frame_first);
+  }
+  HIPCHK(h, hipGetLastError());
+  return frame_close(h, b.ctr, "frame cuts", "frames", max_frames, n_frames);
+}
+
+// The host walk of phip_unframe: every entry checked from the offsets before
+// any byte is read, then frame_walk per frame; emit(k, frame, p) for record k.
+// Touches no device and no handle.  *total: the records the frames hold.
+template <class Emit>
+int unframe_host(const uint8_t* bytes, const uint64_t* foffs, u32 n, u64 lim, u32 fb, Emit emit,
+                 u64* total) {
+  *total = 0;
+  for (u32 f = 0; f < n; ++f)
+    if (!frame_entry_ok(foffs[f], foffs[f + 1], lim, fb)) return PHIP_ERR_INVALID;
+  u64 k = 0;
+  for (u32 f = 0; f < n; ++f) {
+    const u32 c = frame_walk(bytes, foffs[f], foffs[f + 1], [&](u32 j, u64 p) { emit(k + j, f, p); });
+    k += c;
+  }
+  *total = k;
+  return PHIP_OK;
+}
+
+// What the frames forms of a receive call add to it.
+struct FrameAsk {
+  u32 frame_bytes;
+  u32* rec_frame;   // the caller's column (optional)
+  u32 max_recs;
+  u32* n_recs_out;
+};
+
+// Unframe over a device batch into the handle's record columns, then the
+// datagram path over the records, all on the handle's stream (lock held,
+// begin_call done).  dev: the caller's pointers are device memory (else host:
+// a ring slot's device copy, rec_frame copied back).
+int frames_receive_dev(phip_handle* h, const u8* d_bytes, const uint64_t* d_foffs, u32 n_frames,
+                       u64 lim, const FrameAsk& fr, int64_t now, const phip_results* res,
+                       uint32_t* stop_index, bool dev, ReplyEg* eg) {
+  int rc;
+  uint64_t* d_ro;
+  u32* d_rf = nullptr;
+  if ((rc = ensure(h, B_FRRECS, (size_t)fr.max_recs + 1, &d_ro))) return rc;
+  if (fr.rec_frame && dev) d_rf = fr.rec_frame;
+  else if (fr.rec_frame && (rc = ensure(h, B_FRMAP, (size_t)fr.max_recs, &d_rf))) return rc;
+  u32 nrec = 0;
+  rc = unframe_dev(h, d_bytes, d_foffs, n_frames, lim, fr.frame_bytes, d_ro, d_rf, fr.max_recs, &nrec);
+  *fr.n_recs_out = nrec;
+  if (rc) return rc;
+  if (fr.rec_frame && !dev && nrec) {
+    HIPCHK(h, hipMemcpyAsync(fr.rec_frame, d_rf, (size_t)nrec * sizeof(u32), hipMemcpyDeviceToHost,
+                             h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  if (stop_index) *stop_index = nrec;
+  if (nrec == 0) return eg ? reply_collect(h, eg, true) : PHIP_OK;
+  return receive_datagrams_dev(h, d_bytes, d_ro, nrec, now, res, stop_index, dev, eg);
+}
 }  // namespace
 
 extern "C" {
+
+static int receive_datagrams_begun(phip_handle* h, const uint8_t* bytes, const uint64_t* offs,
+                                   uint32_t n, int64_t now, const phip_results* res,
+                                   uint32_t* stop_index, uint32_t flags, ReplyEg* eg);
 
 // phip_receive_datagrams, and with rq phip_receive_datagrams_replies.
 static int receive_datagrams(phip_handle* h, const uint8_t* bytes, const uint64_t* offs, uint32_t n,
@@ -3527,6 +3696,15 @@ static int receive_datagrams(phip_handle* h, const uint8_t* bytes, const uint64_
   if (rq)
     if (int rc0 = reply_enter(h, rq, flags, eg)) return rc0;
   if (int rc0 = begin_call(h)) return rc0;
+  return receive_datagrams_begun(h, bytes, offs, n, now, res, stop_index, flags, eg);
+}
+
+// The datagram call behind its entry (lock held, reply_enter and begin_call
+// done): phip_receive_frames' device form comes in here behind its unframe.
+static int receive_datagrams_begun(phip_handle* h, const uint8_t* bytes, const uint64_t* offs,
+                                   uint32_t n, int64_t now, const phip_results* res,
+                                   uint32_t* stop_index, uint32_t flags, ReplyEg* eg) {
+  phip_reply_egress* rq = eg ? eg->rq : nullptr;
   if (stop_index) *stop_index = n;
   if (n == 0) return eg ? reply_collect(h, eg, true) : PHIP_OK;
   bool dev = flags & PHIP_DEVICE_PTRS;
@@ -3673,9 +3851,12 @@ int phip_ring_submit(phip_ring* r, uint32_t slot, uint32_t n) {
   return PHIP_OK;
 }
 
-// phip_ring_receive, and with rq (host memory) phip_ring_receive_replies.
+// phip_ring_receive, and with rq (host memory) phip_ring_receive_replies; with
+// fr the slot holds frames (phip_ring_receive_frames, _replies): they are
+// split on the device copy, and the records take the datagram path.
 static int ring_receive(phip_ring* r, uint32_t slot, int64_t now, const phip_results* res,
-                        uint32_t* stop_index, phip_reply_egress* rq) {
+                        uint32_t* stop_index, phip_reply_egress* rq,
+                        const FrameAsk* fr = nullptr) {
   if (!r || slot >= r->slots.size()) return PHIP_ERR_INVALID;
   phip_ring::Slot* s;
   {
@@ -3696,7 +3877,7 @@ static int ring_receive(phip_ring* r, uint32_t slot, int64_t now, const phip_res
     // device copy is not waited for; the slot is freed only after it
     // finished, below); a larger one from the device copy.
     bool done = false;
-    if (s->n && s->n <= kSmallMax) {
+    if (!fr && s->n && s->n <= kSmallMax) {
       rc = small_datagrams(h, s->hbytes, s->hoffs, s->n, now, res, stop_index, &done, rq);
       if (done || (rc && rc != PHIP_ERR_SHORT_BUFFER)) {
         if (rc && rc != PHIP_ERR_SHORT_BUFFER) rc = after_error(h, rc);
@@ -3710,6 +3891,9 @@ static int ring_receive(phip_ring* r, uint32_t slot, int64_t now, const phip_res
       hipError_t e = hipStreamWaitEvent(h->stream, s->copied, 0);
       if (e != hipSuccess)
         rc = set_err(h, PHIP_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
+      else if (fr)   // (a checked batch: phip_ring_submit read the slot's byte count)
+        rc = frames_receive_dev(h, s->dbytes, s->doffs, s->n, s->hoffs[s->n], *fr, now, res,
+                                stop_index, false, eg);
       else if (s->n == 0)
         rc = eg ? reply_collect(h, eg) : PHIP_OK;
       else
@@ -3735,6 +3919,145 @@ int phip_ring_receive_replies(phip_ring* r, uint32_t slot, int64_t now, const ph
   if (!rq) return PHIP_ERR_INVALID;
   reply_zero(rq);
   return ring_receive(r, slot, now, res, stop_index, rq);
+}
+
+// ---- packed frames: the entry points ----
+int phip_unframe(phip_handle* h, const uint8_t* bytes, const uint64_t* foffs, uint32_t n_frames,
+                 uint64_t bytes_len, uint32_t frame_bytes, uint64_t* rec_offs, uint32_t* rec_frame,
+                 uint32_t max_recs, uint32_t* n_recs_out, uint32_t flags) {
+  if (!n_recs_out) return PHIP_ERR_INVALID;
+  *n_recs_out = 0;
+  if ((flags & ~PHIP_DEVICE_PTRS) || !foffs || !rec_offs || !frame_bytes_ok(frame_bytes))
+    return PHIP_ERR_INVALID;
+  if (!(flags & PHIP_DEVICE_PTRS)) {   // the host walk: no handle, no device
+    u64 total;
+    const int rc = unframe_host(bytes, foffs, n_frames, bytes_len, frame_bytes,
+                                [&](u64 k, u32 f, u64 p) {
+                                  if (k >= max_recs) return;
+                                  rec_offs[k] = p;
+                                  if (rec_frame) rec_frame[k] = f;
+                                }, &total);
+    if (rc) return rc;
+    *n_recs_out = (uint32_t)std::min<u64>(total, ~0u);
+    if (total > max_recs) return PHIP_ERR_INVALID;
+    rec_offs[total] = foffs[n_frames];
+    return PHIP_OK;
+  }
+  if (!h || (n_frames && !bytes)) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;
+  return unframe_dev(h, bytes, foffs, n_frames, bytes_len, frame_bytes, rec_offs, rec_frame,
+                     max_recs, n_recs_out);
+}
+
+int phip_frame_cuts(phip_handle* h, const uint64_t* offs, uint32_t n, uint32_t frame_bytes,
+                    uint64_t* frame_offs, uint32_t* frame_first, uint32_t max_frames,
+                    uint32_t* n_frames_out, uint32_t flags) {
+  if (!n_frames_out) return PHIP_ERR_INVALID;
+  *n_frames_out = 0;
+  if ((flags & ~PHIP_DEVICE_PTRS) || !offs || !frame_offs || !frame_bytes_ok(frame_bytes))
+    return PHIP_ERR_INVALID;
+  if (!(flags & PHIP_DEVICE_PTRS)) {   // frame_cut_run per run of records: no handle, no device
+    u64 total = 0;
+    for (u64 r0 = 0; r0 < n; r0 += PHIP_FRAME_TILE) {
+      const u64 r1 = std::min<u64>(n, r0 + PHIP_FRAME_TILE);
+      const u32 k = frame_cut_run(offs, r0, r1, frame_bytes, [&](u32 j, u64 first) {
+        if (total + j >= max_frames) return;
+        frame_offs[total + j] = offs[first];
+        if (frame_first) frame_first[total + j] = (uint32_t)first;
+      });
+      if (k == ~0u) return PHIP_ERR_INVALID;
+      total += k;
+    }
+    *n_frames_out = (uint32_t)total;   // (a frame holds a record: at most n)
+    if (total > max_frames) return PHIP_ERR_INVALID;
+    frame_offs[total] = offs[n];
+    return PHIP_OK;
+  }
+  if (!h) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;
+  return frame_cuts_dev(h, offs, n, frame_bytes, frame_offs, frame_first, max_frames, n_frames_out);
+}
+
+// phip_receive_frames, and with rq phip_receive_frames_replies.  Host
+// pointers: the host walk, then the datagram call over the records.  Device
+// pointers: unframe and the datagram path on the handle's stream.
+static int receive_frames(phip_handle* h, const uint8_t* bytes, const uint64_t* foffs,
+                          uint32_t n_frames, int64_t now, const phip_results* res,
+                          uint32_t* stop_index, phip_reply_egress* rq, const FrameAsk& fr,
+                          uint32_t flags) {
+  if (!fr.n_recs_out) return PHIP_ERR_INVALID;
+  *fr.n_recs_out = 0;
+  if (!h || !foffs || (n_frames && !bytes)) return PHIP_ERR_INVALID;
+  if (!frame_bytes_ok(fr.frame_bytes)) {
+    std::lock_guard<std::mutex> g(h->mu);
+    return set_err(h, PHIP_ERR_INVALID, "frames: frame_bytes %u outside [%d, %d]", fr.frame_bytes,
+                   PHIP_FRAME_MIN_BYTES, PHIP_FRAME_MAX_BYTES);
+  }
+  if (!(flags & PHIP_DEVICE_PTRS)) {
+    std::vector<uint64_t> ro;
+    u64 total;
+    const int rc = unframe_host(bytes, foffs, n_frames, foffs[n_frames], fr.frame_bytes,
+                                [&](u64 k, u32 f, u64 p) {
+                                  if (k >= fr.max_recs) return;
+                                  ro.push_back(p);
+                                  if (fr.rec_frame) fr.rec_frame[k] = f;
+                                }, &total);
+    *fr.n_recs_out = (uint32_t)std::min<u64>(total, ~0u);
+    if (rc || total > fr.max_recs) {
+      std::lock_guard<std::mutex> g(h->mu);
+      return set_err(h, PHIP_ERR_INVALID, rc ? "frames: a malformed or oversized frame entry"
+                                             : "frames: more records than max_recs");
+    }
+    ro.push_back(foffs[n_frames]);
+    return receive_datagrams(h, bytes, ro.data(), (uint32_t)total, now, res, stop_index, flags, rq);
+  }
+  std::lock_guard<std::mutex> g(h->mu);
+  ReplyEg egs{}, *eg = rq ? &egs : nullptr;
+  if (rq)
+    if (int rc0 = reply_enter(h, rq, flags, eg)) return rc0;
+  if (int rc0 = begin_call(h)) return rc0;
+  return frames_receive_dev(h, bytes, foffs, n_frames, 0, fr, now, res, stop_index, true, eg);
+}
+
+int phip_receive_frames(phip_handle* h, const uint8_t* bytes, const uint64_t* foffs,
+                        uint32_t n_frames, int64_t now, const phip_results* res,
+                        uint32_t* stop_index, uint32_t frame_bytes, uint32_t* rec_frame,
+                        uint32_t max_recs, uint32_t* n_recs_out, uint32_t flags) {
+  return receive_frames(h, bytes, foffs, n_frames, now, res, stop_index, nullptr,
+                        FrameAsk{frame_bytes, rec_frame, max_recs, n_recs_out}, flags);
+}
+
+int phip_receive_frames_replies(phip_handle* h, const uint8_t* bytes, const uint64_t* foffs,
+                                uint32_t n_frames, int64_t now, const phip_results* res,
+                                uint32_t* stop_index, phip_reply_egress* rq, uint32_t frame_bytes,
+                                uint32_t* rec_frame, uint32_t max_recs, uint32_t* n_recs_out,
+                                uint32_t flags) {
+  if (!rq) return PHIP_ERR_INVALID;
+  reply_zero(rq);
+  return receive_frames(h, bytes, foffs, n_frames, now, res, stop_index, rq,
+                        FrameAsk{frame_bytes, rec_frame, max_recs, n_recs_out}, flags);
+}
+
+int phip_ring_receive_frames(phip_ring* r, uint32_t slot, int64_t now, const phip_results* res,
+                             uint32_t frame_bytes, uint32_t* rec_frame, uint32_t max_recs,
+                             uint32_t* n_recs_out, uint32_t* stop_index) {
+  if (!n_recs_out || !frame_bytes_ok(frame_bytes)) return PHIP_ERR_INVALID;
+  *n_recs_out = 0;
+  const FrameAsk fr{frame_bytes, rec_frame, max_recs, n_recs_out};
+  return ring_receive(r, slot, now, res, stop_index, nullptr, &fr);
+}
+
+int phip_ring_receive_frames_replies(phip_ring* r, uint32_t slot, int64_t now,
+                                     const phip_results* res, uint32_t frame_bytes,
+                                     uint32_t* rec_frame, uint32_t max_recs, uint32_t* n_recs_out,
+                                     uint32_t* stop_index, phip_reply_egress* rq) {
+  if (!rq || !n_recs_out || !frame_bytes_ok(frame_bytes)) return PHIP_ERR_INVALID;
+  reply_zero(rq);
+  *n_recs_out = 0;
+  const FrameAsk fr{frame_bytes, rec_frame, max_recs, n_recs_out};
+  return ring_receive(r, slot, now, res, stop_index, rq, &fr);
 }
 
 int phip_upsert_soa(phip_handle* h, const phip_msgs* m, int64_t now, const phip_results* res,

@@ -8043,5 +8043,184 @@ __global__ __launch_bounds__(kTopEmitBlock) void k_top_emit(const Rec* __restric
   }
 }
 
+// ----------------------------------------------------------- packed frames --
+// phip_unframe and phip_frame_cuts (patrolhip.h "Packed frames"): the two
+// rules of phip_device.hpp (frame_walk, frame_fits) as count / scan / write
+// passes over the sweep's tile scan.
+//
+// Counters (u64 words of the call's device buffer, all set to ~0 before the
+// first launch).
+constexpr u32 kFrN = 0;     // the call's records (unframe) or frames (cuts): k_frame_scan's total
+constexpr u32 kFrBad = 1;   // min-reduced: the first entry refused (~0: none) -- unframe: a frame
+                            // entry frame_entry_ok rejects; cuts: the first record of a frame
+                            // that cannot take it
+constexpr u32 kFrWords = 4;
+// One wave cuts one run of PHIP_FRAME_TILE records; a workgroup holds kBlock / 64 of them.
+constexpr u32 kCutWaves = kBlock / 64;
+
+__device__ inline void note_min64(bool d, u64 i, u64* word) {
+  const u64 m = __ballot(d);
+  if (m && __lane_id() == (u32)(__ffsll((long long)m) - 1)) atomicMin(word, i);
+}
+
+// Unframe, pass 0: every entry checked from the offsets alone, before any
+// kernel reads a byte (k_frame_count and k_frame_write return at once when an
+// entry was refused: nothing is read at it and no frame is walked).
+__global__ __launch_bounds__(kBlock) void k_frame_check(const uint64_t* __restrict__ foffs, u32 n,
+                                                        u64 lim, u32 frame_bytes, u64* ctr) {
+  const u64 i = (u64)blockIdx.x * kBlock + threadIdx.x;
+  const bool bad = i < n && !frame_entry_ok(foffs[i], foffs[i + 1], lim, frame_bytes);
+  note_min64(bad, i, &ctr[kFrBad]);
+}
+
+// Unframe, pass 1: one lane per frame walks the length bytes (frame_walk) and
+// stores the frame's record count; the workgroup's sum goes to its tile slot.
+// Bound: k_frame_check let every entry pass, so end - o <= frame_bytes, and
+// every step of the walk but the last advances by at least
+// PHIP_BUCKET_FIXED_SIZE bytes: a lane takes at most frame_bytes / 25 + 1
+// steps, whatever the bytes hold, and reads inside [o, end) only.
+__global__ __launch_bounds__(kBlock) void k_frame_count(const u8* __restrict__ bytes,
+                                                        const uint64_t* __restrict__ foffs, u32 n,
+                                                        const u64* ctr, u32* __restrict__ fcnt,
+                                                        u32* __restrict__ tile_cnt,
+                                                        u64* __restrict__ tile_bytes) {
+  if (ctr[kFrBad] != ~0ull) return;   // (uniform: the whole grid leaves)
+  const u64 i = (u64)blockIdx.x * kBlock + threadIdx.x;
+  u32 c = 0;
+  u64 b = 0;
+  if (i < n) {
+    const u64 o = foffs[i], end = foffs[i + 1];
+    c = frame_walk(bytes, o, end, [](u32, u64) {});
+    fcnt[i] = c;
+    b = end - o;
+  }
+  if (tile_sum(c, b)) {
+    tile_cnt[blockIdx.x] = c;
+    tile_bytes[blockIdx.x] = b;
+  }
+}
+
+// Both scans: exclusive bases per tile in place, the total into kFrN.
+__global__ __launch_bounds__(kSweepBlock) void k_frame_scan(u32* __restrict__ tile_cnt,
+                                                            u64* __restrict__ tile_bytes,
+                                                            u32 ntiles, u64* ctr) {
+  if (ctr[kFrBad] != ~0ull) return;
+  const TileTotals tot = tile_scan(tile_cnt, tile_bytes, ntiles);
+  if (threadIdx.x == 0) ctr[kFrN] = tot.n;
+}
+
+// Unframe, pass 2: the same walk, storing rec_offs[base + j] and
+// rec_frame[base + j] from the frame's base (its tile's, plus the counts of
+// the workgroup's frames before it); the last frame's lane stores the final
+// rec_offs[n_recs].  Nothing is written when the count does not fit max_recs,
+// and no store goes past a frame's counted records or past max_recs.
+__global__ __launch_bounds__(kBlock) void k_frame_write(const u8* __restrict__ bytes,
+                                                        const uint64_t* __restrict__ foffs, u32 n,
+                                                        const u64* ctr, const u32* __restrict__ fcnt,
+                                                        const u32* __restrict__ tile_cnt,
+                                                        u32 max_recs, uint64_t* __restrict__ rec_offs,
+                                                        u32* __restrict__ rec_frame) {
+  __shared__ u32 wtot[kBlock / 64];
+  if (ctr[kFrBad] != ~0ull || ctr[kFrN] > max_recs) return;   // (uniform)
+  const u64 i = (u64)blockIdx.x * kBlock + threadIdx.x;
+  const u32 c = i < n ? fcnt[i] : 0u;
+  const u32 sc = wave_incl_scan(c);
+  if (__lane_id() == 63) wtot[threadIdx.x >> 6] = sc;
+  __syncthreads();
+  u32 base = tile_cnt[blockIdx.x] + sc - c;
+  for (u32 w = 0; w < (threadIdx.x >> 6); ++w) base += wtot[w];
+  if (i >= n) return;
+  const u64 o = foffs[i], end = foffs[i + 1];
+  frame_walk(bytes, o, end, [&](u32 j, u64 p) {
+    if (j < c && base + j < max_recs) {
+      rec_offs[base + j] = p;
+      if (rec_frame) rec_frame[base + j] = (u32)i;
+    }
+  });
+  if (i + 1 == n && base + c <= max_recs) rec_offs[base + c] = end;
+}
+
+// Cuts: one wave over the run of records [r0, r1).  Each step loads the next
+// 64 end offsets, ballots the ones the open frame still takes and advances by
+// the leading run of them; it repeats while all 64 fit (a large frame holds
+// more than 64 records).  The end offset of the last record taken is the next
+// frame's start, so a frame costs one dependent load per 64 records.  Returns
+// the run's frame count, or ~0u with *bad_at = the record no frame can take
+// (frame_cut_run's result; every step advances by a record or leaves).
+// kWrite: lane 0 stores frame k's start and first record at base + k, below
+// max_frames.
+template <bool kWrite>
+__device__ inline u32 frame_cut_wave(const uint64_t* __restrict__ offs, u64 r0, u64 r1,
+                                     u32 frame_bytes, u32 base, u32 max_frames,
+                                     uint64_t* __restrict__ frame_offs,
+                                     u32* __restrict__ frame_first, u64* bad_at) {
+  const u32 lane = __lane_id();
+  u32 k = 0;
+  u64 first = r0;
+  u64 o0 = offs[r0];
+  while (first < r1) {
+    u64 j = first, endv = o0;
+    for (;;) {
+      const u64 idx = j + lane;
+      const u64 e = idx < r1 ? (u64)offs[idx + 1] : 0ull;
+      const u64 m = __ballot(idx < r1 && frame_fits(o0, e, frame_bytes));
+      const u32 take = m == ~0ull ? 64u : (u32)__ffsll((long long)~m) - 1u;
+      if (take) endv = __shfl(e, (int)take - 1);
+      j += take;
+      if (take < 64) break;
+    }
+    if (j == first) {
+      *bad_at = first;
+      return ~0u;
+    }
+    if (kWrite && lane == 0 && base + k < max_frames) {
+      frame_offs[base + k] = o0;
+      if (frame_first) frame_first[base + k] = (u32)first;
+    }
+    ++k;
+    first = j;
+    o0 = endv;
+  }
+  return k;
+}
+
+__global__ __launch_bounds__(kBlock) void k_frame_cut_count(const uint64_t* __restrict__ offs, u32 n,
+                                                            u32 frame_bytes, u64* ctr,
+                                                            u32* __restrict__ tile_cnt,
+                                                            u64* __restrict__ tile_bytes,
+                                                            u32 ntiles) {
+  const u32 tile = blockIdx.x * kCutWaves + (threadIdx.x >> 6);
+  if (tile >= ntiles) return;   // (uniform in a wave)
+  const u64 r0 = (u64)tile * PHIP_FRAME_TILE, r1 = min((u64)n, r0 + PHIP_FRAME_TILE);
+  u64 bad_at = 0;
+  const u32 k = frame_cut_wave<false>(offs, r0, r1, frame_bytes, 0, 0, nullptr, nullptr, &bad_at);
+  if (__lane_id() == 0) {
+    if (k == ~0u) atomicMin(&ctr[kFrBad], bad_at);
+    tile_cnt[tile] = k == ~0u ? 0u : k;
+    tile_bytes[tile] = 0;
+  }
+}
+
+// The same walk storing frame_offs and frame_first; the last run's wave stores
+// the final frame_offs[n_frames].  Nothing is written after a refused record
+// or when the count does not fit max_frames.
+__global__ __launch_bounds__(kBlock) void k_frame_cut_write(const uint64_t* __restrict__ offs, u32 n,
+                                                            u32 frame_bytes, const u64* ctr,
+                                                            const u32* __restrict__ tile_cnt,
+                                                            u32 ntiles, u32 max_frames,
+                                                            uint64_t* __restrict__ frame_offs,
+                                                            u32* __restrict__ frame_first) {
+  if (ctr[kFrBad] != ~0ull || ctr[kFrN] > max_frames) return;   // (uniform)
+  const u32 tile = blockIdx.x * kCutWaves + (threadIdx.x >> 6);
+  if (tile >= ntiles) return;
+  const u64 r0 = (u64)tile * PHIP_FRAME_TILE, r1 = min((u64)n, r0 + PHIP_FRAME_TILE);
+  const u32 base = tile_cnt[tile];
+  u64 bad_at = 0;
+  const u32 k = frame_cut_wave<true>(offs, r0, r1, frame_bytes, base, max_frames, frame_offs,
+                                     frame_first, &bad_at);
+  if (tile + 1 == ntiles && __lane_id() == 0 && k != ~0u && base + k <= max_frames)
+    frame_offs[base + k] = offs[n];
+}
+
 }  // namespace phip
 

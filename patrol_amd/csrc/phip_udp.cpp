@@ -10,7 +10,9 @@
 //   phip_incast_replies    MarshalBinary of every INCAST_REPLY the batch
 //                          produced, with the peer each one goes back to;
 //   phip_udp_send_batch    sendmmsg of a run of datagrams (replies, or the
-//                          phip_export_datagrams egress batch to one peer).
+//                          phip_export_datagrams egress batch to one peer);
+//   phip_udp_recv_frames   phip_udp_recv_batch for packed frames (patrolhip.h
+//                          "Packed frames"): windows of frame_bytes.
 #include <errno.h>
 #include <poll.h>
 #include <sys/socket.h>
@@ -35,12 +37,10 @@ socklen_t peer_len(const uint8_t* p) {
   return sizeof(sockaddr_storage);
 }
 
-}  // namespace
-
-extern "C" {
-
-int phip_udp_recv_batch(int fd, uint8_t* bytes, uint64_t cap, uint64_t* offs, uint32_t max_msgs,
-                        uint8_t* peers, int timeout_ms, uint32_t* n_out) {
+// phip_udp_recv_batch (window = PHIP_BUCKET_PACKET_SIZE) and phip_udp_recv_frames
+// (window = frame_bytes).
+int recv_windows(int fd, uint8_t* bytes, uint64_t cap, uint64_t* offs, uint32_t max_msgs,
+                 uint32_t window, uint8_t* peers, int timeout_ms, uint32_t* n_out) {
   static_assert(sizeof(sockaddr_storage) == PHIP_PEER_BYTES, "peer record size");
   if (!n_out) return PHIP_ERR_INVALID;
   *n_out = 0;
@@ -58,16 +58,16 @@ int phip_udp_recv_batch(int fd, uint8_t* bytes, uint64_t cap, uint64_t* offs, ui
   uint64_t pos = 0;
   uint32_t n = 0;
   while (n < max_msgs) {
-    // Each datagram lands in its own 256-byte window (Go's buffer: a longer
-    // datagram is cut to bucketPacketSize bytes, repo.go:56), then is packed
-    // down to the end of the previous one.
-    const uint64_t fit = (cap - pos) / PHIP_BUCKET_PACKET_SIZE;
+    // Each datagram lands in its own window (256 bytes is Go's buffer: a
+    // longer datagram is cut to bucketPacketSize bytes, repo.go:56; a frame's
+    // is frame_bytes), then is packed down to the end of the previous one.
+    const uint64_t fit = (cap - pos) / window;
     const uint32_t want = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(kVec, max_msgs - n), fit);
     if (!want) break;
     std::memset(hdr, 0, sizeof(mmsghdr) * want);
     for (uint32_t k = 0; k < want; ++k) {
-      iov[k].iov_base = bytes + pos + (uint64_t)k * PHIP_BUCKET_PACKET_SIZE;
-      iov[k].iov_len = PHIP_BUCKET_PACKET_SIZE;
+      iov[k].iov_base = bytes + pos + (uint64_t)k * window;
+      iov[k].iov_len = window;
       hdr[k].msg_hdr.msg_iov = &iov[k];
       hdr[k].msg_hdr.msg_iovlen = 1;
       if (peers) {
@@ -83,8 +83,8 @@ int phip_udp_recv_batch(int fd, uint8_t* bytes, uint64_t cap, uint64_t* offs, ui
     }
     const uint64_t base = pos;
     for (int k = 0; k < got; ++k) {
-      const uint32_t len = std::min<uint32_t>(hdr[k].msg_len, PHIP_BUCKET_PACKET_SIZE);
-      const uint64_t from = base + (uint64_t)k * PHIP_BUCKET_PACKET_SIZE;
+      const uint32_t len = std::min<uint32_t>(hdr[k].msg_len, window);
+      const uint64_t from = base + (uint64_t)k * window;
       if (from != pos) std::memmove(bytes + pos, bytes + from, len);   // pos <= from
       pos += len;
       offs[++n] = pos;
@@ -93,6 +93,26 @@ int phip_udp_recv_batch(int fd, uint8_t* bytes, uint64_t cap, uint64_t* offs, ui
   }
   *n_out = n;
   return PHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int phip_udp_recv_batch(int fd, uint8_t* bytes, uint64_t cap, uint64_t* offs, uint32_t max_msgs,
+                        uint8_t* peers, int timeout_ms, uint32_t* n_out) {
+  return recv_windows(fd, bytes, cap, offs, max_msgs, PHIP_BUCKET_PACKET_SIZE, peers, timeout_ms,
+                      n_out);
+}
+
+int phip_udp_recv_frames(int fd, uint8_t* bytes, uint64_t cap, uint64_t* foffs,
+                         uint32_t max_frames, uint32_t frame_bytes, uint8_t* peers, int timeout_ms,
+                         uint32_t* n_out) {
+  if (frame_bytes < PHIP_FRAME_MIN_BYTES || frame_bytes > PHIP_FRAME_MAX_BYTES) {
+    if (n_out) *n_out = 0;
+    return PHIP_ERR_INVALID;
+  }
+  return recv_windows(fd, bytes, cap, foffs, max_frames, frame_bytes, peers, timeout_ms, n_out);
 }
 
 int phip_incast_replies(const uint8_t* bytes, const uint64_t* offs, uint32_t n,
@@ -129,6 +149,15 @@ int phip_reply_peers(const uint8_t* peers, const uint32_t* src, uint32_t n, uint
   for (uint32_t k = 0; k < n; ++k)
     std::memcpy(out_peers + (uint64_t)k * PHIP_PEER_BYTES, peers + (uint64_t)src[k] * PHIP_PEER_BYTES,
                 PHIP_PEER_BYTES);
+  return PHIP_OK;
+}
+
+int phip_frame_reply_peers(const uint8_t* peers, const uint32_t* rec_frame, const uint32_t* src,
+                           uint32_t n, uint8_t* out_peers) {
+  if (n && (!peers || !rec_frame || !src || !out_peers)) return PHIP_ERR_INVALID;
+  for (uint32_t k = 0; k < n; ++k)
+    std::memcpy(out_peers + (uint64_t)k * PHIP_PEER_BYTES,
+                peers + (uint64_t)rec_frame[src[k]] * PHIP_PEER_BYTES, PHIP_PEER_BYTES);
   return PHIP_OK;
 }
 

@@ -864,6 +864,119 @@ class GPURepo:
         self._check(rc, allow=(-5,))
         return self._reply_dict(rq, status, out, offs, src, rc=rc, stop=stop.value)
 
+    # -- packed frames (patrolhip.h "Packed frames") --
+    def _frames_check(self, rc: int, needed: int, allow=()):
+        """_check for a frames call: the error carries the count the call
+        needs (`needed`: *n_recs_out / *n_frames_out)."""
+        try:
+            self._check(rc, allow=allow)
+        except PatrolHipError as e:
+            e.needed = int(needed)
+            raise
+
+    def unframe(self, frames, frame_bytes: int = _lib.FRAME_DEFAULT_BYTES, max_recs=None):
+        """The host form of phip_unframe (module function `unframe`)."""
+        return unframe(frames, frame_bytes, max_recs)
+
+    def unframe_device(self, data, foffs, n_frames: int, rec_offs, rec_frame=None,
+                       frame_bytes: int = _lib.FRAME_DEFAULT_BYTES, max_recs=None,
+                       bytes_len=None) -> int:
+        """phip_unframe with device pointers: data (uint8 CUDA tensor, 8-byte
+        aligned, 8 bytes of slack), foffs (int64[n_frames + 1]); rec_offs
+        (int64[max_recs + 1]) and rec_frame (int32[max_recs], optional) are
+        written.  bytes_len: the length the frame offsets are checked against
+        (default: data's size; 0 = trusted).  -> the record count; on error
+        PatrolHipError carries `needed`."""
+        max_recs = int(rec_offs.numel()) - 1 if max_recs is None else int(max_recs)
+        lim = int(data.numel()) if bytes_len is None else int(bytes_len)
+        n = C.c_uint32()
+        rc = self.L.phip_unframe(self.h, _ptr(data), _ptr(foffs), int(n_frames), lim,
+                                 int(frame_bytes), _ptr(rec_offs), _ptr(rec_frame), max_recs,
+                                 C.byref(n), DEVICE_PTRS)
+        self._frames_check(rc, n.value)
+        return n.value
+
+    def frame_cuts(self, offs, frame_bytes: int = _lib.FRAME_DEFAULT_BYTES, max_frames=None):
+        """The host form of phip_frame_cuts (module function `frame_cuts`)."""
+        return frame_cuts(offs, frame_bytes, max_frames)
+
+    def frame_cuts_device(self, offs, n: int, frame_offs, frame_first=None,
+                          frame_bytes: int = _lib.FRAME_DEFAULT_BYTES, max_frames=None) -> int:
+        """phip_frame_cuts with device pointers: offs (int64[n + 1]) is an
+        export's offsets column; frame_offs (int64[max_frames + 1]) and
+        frame_first (int32[max_frames], optional) are written.  -> the frame
+        count; on error PatrolHipError carries `needed`."""
+        max_frames = int(frame_offs.numel()) - 1 if max_frames is None else int(max_frames)
+        k = C.c_uint32()
+        rc = self.L.phip_frame_cuts(self.h, _ptr(offs), int(n), int(frame_bytes), _ptr(frame_offs),
+                                    _ptr(frame_first), max_frames, C.byref(k), DEVICE_PTRS)
+        self._frames_check(rc, k.value)
+        return k.value
+
+    def receive_frames(self, frames: Sequence[bytes], now: int,
+                       frame_bytes: int = _lib.FRAME_DEFAULT_BYTES, max_recs=None, replies=None):
+        """phip_receive_frames over host frames (each a run of whole records):
+        -> dict(status, reply, stop, n_recs, rec_frame) as receive_datagrams
+        over the frames' records; `stop` is a record index, rec_frame[k] the
+        frame of record k.  replies=dict(max_msgs=, out_cap=) (or {}):
+        phip_receive_frames_replies -> the reply dict of
+        receive_datagrams_replies plus n_recs and rec_frame; its src[] are
+        record indices too."""
+        blob, foffs = _frames_blob(frames)
+        nf = len(frames)
+        cap = _frame_bound(int(foffs[-1]), nf) if max_recs is None else int(max_recs)
+        rec_frame = np.zeros(max(cap, 1), np.uint32)
+        stop, nrec = C.c_uint32(), C.c_uint32()
+        if replies is not None:
+            res, st, _, _, _ = self._results(cap)
+            rq, out, offs, src = self._reply_host(cap, replies.get("max_msgs"),
+                                                  replies.get("out_cap"))
+            rc = self.L.phip_receive_frames_replies(
+                self.h, blob.ctypes.data, foffs.ctypes.data, nf, int(now), C.byref(res),
+                C.byref(stop), C.byref(rq), int(frame_bytes), rec_frame.ctypes.data, cap,
+                C.byref(nrec), 0)
+            self._frames_check(rc, nrec.value, allow=(-5,))
+            k = nrec.value
+            return self._reply_dict(rq, st[:k], out, offs, src, rc=rc, stop=stop.value, n_recs=k,
+                                    rec_frame=rec_frame[:k])
+        res, status, _, _, reply = self._results(cap, want_reply=True)
+        rc = self.L.phip_receive_frames(self.h, blob.ctypes.data, foffs.ctypes.data, nf, int(now),
+                                        C.byref(res), C.byref(stop), int(frame_bytes),
+                                        rec_frame.ctypes.data, cap, C.byref(nrec), 0)
+        self._frames_check(rc, nrec.value, allow=(-5,))
+        k = nrec.value
+        return dict(status=status[:k], reply=reply[:k], stop=stop.value, n_recs=k,
+                    rec_frame=rec_frame[:k], rc=rc)
+
+    def receive_frames_device(self, data, foffs, n_frames: int, now: int, max_recs: int,
+                              frame_bytes: int = _lib.FRAME_DEFAULT_BYTES, status=None,
+                              rec_frame=None, replies=None):
+        """phip_receive_frames with device pointers (data / foffs as
+        unframe_device takes them; status uint8[max_recs] and rec_frame
+        int32[max_recs] optional CUDA tensors).  -> dict(stop, n_recs, rc).
+        replies=dict(out=, offs=, src=, max_msgs=[, out_cap=]) of CUDA tensors:
+        phip_receive_frames_replies -> the reply dict plus n_recs."""
+        res = phip_results(_ptr(status), None, None, None)
+        stop, nrec = C.c_uint32(0), C.c_uint32(0)
+        if replies is not None:
+            out = replies["out"]
+            cap = int(out.numel()) if replies.get("out_cap") is None else int(replies["out_cap"])
+            rq = _lib.phip_reply_egress(_ptr(out), cap, _ptr(replies["offs"]),
+                                        _ptr(replies.get("src")), int(replies["max_msgs"]),
+                                        0, 0, 0, 0)
+            rc = self.L.phip_receive_frames_replies(
+                self.h, _ptr(data), _ptr(foffs), int(n_frames), int(now),
+                C.byref(res) if status is not None else None, C.byref(stop), C.byref(rq),
+                int(frame_bytes), _ptr(rec_frame), int(max_recs), C.byref(nrec), DEVICE_PTRS)
+            self._frames_check(rc, nrec.value, allow=(-5,))
+            return self._reply_dict(rq, status, out, replies["offs"], replies.get("src"), rc=rc,
+                                    stop=stop.value, n_recs=nrec.value)
+        rc = self.L.phip_receive_frames(self.h, _ptr(data), _ptr(foffs), int(n_frames), int(now),
+                                        C.byref(res), C.byref(stop), int(frame_bytes),
+                                        _ptr(rec_frame), int(max_recs), C.byref(nrec), DEVICE_PTRS)
+        self._frames_check(rc, nrec.value, allow=(-5,))
+        return dict(stop=stop.value, n_recs=nrec.value, rc=rc)
+
     def upsert_soa(self, names, added, taken, elapsed, now: int):
         """LocalRepo.UpsertBucket for each state (repo.go:215-235)."""
         n = len(names)
@@ -1373,6 +1486,37 @@ class GPUGroup:
         rc = self.L.phip_group_receive_datagrams(self.g, ws, int(now), sent, merged, stopped, flags)
         return self._wire_call(rc, sent, merged, stopped)
 
+    def receive_frames(self, batches, now: int, frame_bytes: int = _lib.FRAME_DEFAULT_BYTES,
+                       replies=None, **kw):
+        """receive_datagrams over packed frames (patrolhip.h "Packed frames"):
+        batches holds, per local member, the frames that arrived there, as a
+        (bytes uint8, foffs int64[n_frames+1]) pair of CUDA tensors or as a
+        list of `bytes` frames.  Composition only: each member's
+        unframe_device on its own handle, then receive_datagrams over the
+        records; `stopped` and the replies' src[] are record indices, and
+        last_rec_frame[i] (an int32 CUDA tensor) maps member i's records to
+        its frames.  kw: receive_datagrams' other arguments."""
+        import torch
+        recs, self.last_rec_frame = [], []
+        for i, b in enumerate(batches):
+            repo = self.repos[i]
+            dev = torch.device("cuda", repo.device)
+            if isinstance(b, (list, tuple)) and (len(b) != 2 or not _is_torch(b[0])):
+                blob, foffs = _frames_blob(b)
+                pad = np.zeros((blob.size + 7) // 8 * 8, np.uint8)
+                pad[:blob.size] = blob
+                b = (torch.from_numpy(pad).to(dev), torch.from_numpy(foffs.astype(np.int64)).to(dev))
+            data, foffs = b
+            nf = int(foffs.numel()) - 1
+            cap = _frame_bound(int(data.numel()), nf)
+            rec_offs = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+            rec_frame = torch.zeros(max(cap, 1), dtype=torch.int32, device=dev)
+            n = repo.unframe_device(data, foffs, nf, rec_offs, rec_frame, frame_bytes=frame_bytes,
+                                    max_recs=cap)
+            recs.append((data, rec_offs[:n + 1]))
+            self.last_rec_frame.append(rec_frame[:n])
+        return self.receive_datagrams(recs, now, replies=replies, **kw)
+
     def ring_receive(self, rings, slots, now: int, combine: bool = True, rccl_self: bool = False,
                      small_chunks: bool = False, replies=None):
         """The socket edge (phip_group_ring_receive): rings[i] is a Ring over
@@ -1825,6 +1969,53 @@ class Ring:
                                    stop=stop.value)
 
 
+    # -- packed frames: a slot filled with frames (fill() / recv_frames()) --
+    def recv_frames(self, sock, frame_bytes: int = _lib.FRAME_DEFAULT_BYTES,
+                    timeout_ms: int = 3000, peers: bool = True):
+        """Acquire a slot and fill it with frames from a UDP socket
+        (phip_udp_recv_frames) -> (slot, n_frames, peers by frame or None).
+        The ring was opened with max_msgs = frames and max_bytes >=
+        frame_bytes * frames."""
+        slot, bv, ov = self.acquire()
+        pbuf = np.zeros((self.max_msgs, _lib.PEER_BYTES), np.uint8) if peers else None
+        n = C.c_uint32()
+        self.repo._check(self.L.phip_udp_recv_frames(sock.fileno(), bv.ctypes.data, self.max_bytes,
+                                                     ov.ctypes.data, self.max_msgs,
+                                                     int(frame_bytes), _ptr(pbuf), int(timeout_ms),
+                                                     C.byref(n)))
+        return slot, n.value, (pbuf[:n.value] if peers else None)
+
+    def receive_frames(self, slot: int, max_recs: int, now: int,
+                       frame_bytes: int = _lib.FRAME_DEFAULT_BYTES, want_reply: bool = False,
+                       replies=None):
+        """phip_ring_receive_frames over a submitted slot of frames -> the
+        dict of GPURepo.receive_frames (max_recs: the capacity of the result
+        columns); replies=dict(max_msgs=, out_cap=) (or {}):
+        phip_ring_receive_frames_replies -> its reply dict."""
+        cap = int(max_recs)
+        rec_frame = np.zeros(max(cap, 1), np.uint32)
+        stop, nrec = C.c_uint32(), C.c_uint32()
+        if replies is not None:
+            res, st, _, _, _ = GPURepo._results(cap)
+            rq, out, offs, src = GPURepo._reply_host(cap, replies.get("max_msgs"),
+                                                     replies.get("out_cap"))
+            rc = self.L.phip_ring_receive_frames_replies(
+                self.r, slot, int(now), C.byref(res), int(frame_bytes), rec_frame.ctypes.data, cap,
+                C.byref(nrec), C.byref(stop), C.byref(rq))
+            self.repo._frames_check(rc, nrec.value, allow=(-5,))
+            k = nrec.value
+            return GPURepo._reply_dict(rq, st[:k], out, offs, src, rc=rc, stop=stop.value,
+                                       n_recs=k, rec_frame=rec_frame[:k])
+        res, status, _, _, reply = GPURepo._results(cap, want_reply=want_reply)
+        rc = self.L.phip_ring_receive_frames(self.r, slot, int(now), C.byref(res),
+                                             int(frame_bytes), rec_frame.ctypes.data, cap,
+                                             C.byref(nrec), C.byref(stop))
+        self.repo._frames_check(rc, nrec.value, allow=(-5,))
+        k = nrec.value
+        return dict(status=status[:k], reply=reply[:k] if reply is not None else None,
+                    stop=stop.value, n_recs=k, rec_frame=rec_frame[:k], rc=rc)
+
+
 def udp_send_batch(sock, data: bytes | np.ndarray, offs: np.ndarray, peers=None,
                    peer_stride: int = 0) -> int:
     """sendmmsg of datagrams data[offs[i]:offs[i+1]] (phip_udp_send_batch)."""
@@ -1888,6 +2079,112 @@ def reply_peers(peers: np.ndarray, src) -> np.ndarray:
     if rc != 0:
         raise PatrolHipError(rc, "reply peers")
     return out[:len(src)]
+
+
+def _frames_blob(frames: Sequence[bytes]):
+    """list of frames -> (bytes uint8 with 8 bytes of slack, foffs uint64[n+1])."""
+    n = len(frames)
+    foffs = np.zeros(n + 1, np.uint64)
+    if n:
+        foffs[1:] = np.cumsum(np.fromiter((len(f) for f in frames), np.int64, n))
+    blob = np.zeros(int(foffs[-1]) + 8, np.uint8)
+    if foffs[-1]:
+        blob[:int(foffs[-1])] = np.frombuffer(b"".join(frames), np.uint8)
+    return blob, foffs
+
+
+def _frame_bound(total_bytes: int, n_frames: int) -> int:
+    """No more records than this come out of n_frames frames of total_bytes
+    bytes: a frame of s bytes holds at most s // 25 whole records and a tail."""
+    return total_bytes // _lib.BUCKET_FIXED_SIZE + n_frames
+
+
+def _frames_error(rc: int, what: str, needed: int):
+    e = PatrolHipError(rc, what)
+    e.needed = int(needed)
+    return e
+
+
+def unframe(frames, frame_bytes: int = _lib.FRAME_DEFAULT_BYTES, max_recs=None, bytes_len=None):
+    """phip_unframe on the host (no GPU, no handle): `frames` is a list of
+    `bytes` frames or a (data uint8, foffs uint64[n+1]) pair of numpy arrays ->
+    dict(rec_offs uint64[n+1], rec_frame uint32[n], n).  bytes_len: the length
+    the entries are checked against (a pair's default: len(data); 0 = not
+    checked).  On error PatrolHipError carries `needed`, the record count."""
+    L = _lib.load()
+    if isinstance(frames, tuple):
+        data, foffs = frames
+        data = np.ascontiguousarray(data, np.uint8)
+        foffs = np.ascontiguousarray(foffs, np.uint64)
+        lim = int(data.size) if bytes_len is None else int(bytes_len)
+    else:
+        data, foffs = _frames_blob(frames)
+        lim = int(foffs[-1]) if bytes_len is None else int(bytes_len)
+    nf = len(foffs) - 1
+    if max_recs is None:
+        max_recs = _frame_bound(int(data.size), nf)
+    rec_offs = np.zeros(int(max_recs) + 1, np.uint64)
+    rec_frame = np.zeros(max(int(max_recs), 1), np.uint32)
+    n = C.c_uint32()
+    rc = L.phip_unframe(None, data.ctypes.data, foffs.ctypes.data, nf, lim, int(frame_bytes),
+                        rec_offs.ctypes.data, rec_frame.ctypes.data, int(max_recs), C.byref(n), 0)
+    if rc != 0:
+        raise _frames_error(rc, "unframe", n.value)
+    return dict(rec_offs=rec_offs[:n.value + 1], rec_frame=rec_frame[:n.value], n=n.value)
+
+
+def frame_cuts(offs, frame_bytes: int = _lib.FRAME_DEFAULT_BYTES, max_frames=None):
+    """phip_frame_cuts on the host (no GPU, no handle): offs is an export's
+    offsets column (n + 1 entries) -> dict(frame_offs uint64[k+1], frame_first
+    uint32[k], n=k); phip_udp_send_batch(fd, bytes, frame_offs, k, ...) sends
+    the frames.  On error PatrolHipError carries `needed`, the frame count."""
+    L = _lib.load()
+    offs = np.ascontiguousarray(offs, np.uint64)
+    n = len(offs) - 1
+    if max_frames is None:
+        max_frames = n
+    frame_offs = np.zeros(int(max_frames) + 1, np.uint64)
+    frame_first = np.zeros(max(int(max_frames), 1), np.uint32)
+    k = C.c_uint32()
+    rc = L.phip_frame_cuts(None, offs.ctypes.data, n, int(frame_bytes), frame_offs.ctypes.data,
+                           frame_first.ctypes.data, int(max_frames), C.byref(k), 0)
+    if rc != 0:
+        raise _frames_error(rc, "frame cuts", k.value)
+    return dict(frame_offs=frame_offs[:k.value + 1], frame_first=frame_first[:k.value], n=k.value)
+
+
+def frame_reply_peers(peers: np.ndarray, rec_frame, src) -> np.ndarray:
+    """phip_frame_reply_peers: peers[rec_frame[src[k]]] for the reply datagrams
+    of a *_frames_replies call (peers by frame, uint8[n_frames, PEER_BYTES])."""
+    L = _lib.load()
+    src = np.ascontiguousarray(src, np.uint32)
+    rec_frame = np.ascontiguousarray(rec_frame, np.uint32)
+    peers = np.ascontiguousarray(peers, np.uint8)
+    out = np.zeros((max(len(src), 1), _lib.PEER_BYTES), np.uint8)
+    rc = L.phip_frame_reply_peers(peers.ctypes.data if peers.size else None,
+                                  rec_frame.ctypes.data if rec_frame.size else None,
+                                  src.ctypes.data if src.size else None, len(src), out.ctypes.data)
+    if rc != 0:
+        raise PatrolHipError(rc, "frame reply peers")
+    return out[:len(src)]
+
+
+def udp_recv_frames(sock, max_frames: int, frame_bytes: int = _lib.FRAME_DEFAULT_BYTES,
+                    timeout_ms: int = 3000, cap: int | None = None):
+    """recvmmsg of packed frames into plain host arrays (phip_udp_recv_frames)
+    -> (list of frames, peers uint8[n, PEER_BYTES])."""
+    L = _lib.load()
+    cap = cap if cap is not None else int(frame_bytes) * max_frames
+    buf = np.zeros(cap + 8, np.uint8)
+    foffs = np.zeros(max_frames + 1, np.uint64)
+    peers = np.zeros((max(max_frames, 1), _lib.PEER_BYTES), np.uint8)
+    n = C.c_uint32()
+    rc = L.phip_udp_recv_frames(sock.fileno(), buf.ctypes.data, cap, foffs.ctypes.data, max_frames,
+                                int(frame_bytes), peers.ctypes.data, int(timeout_ms), C.byref(n))
+    if rc != 0:
+        raise PatrolHipError(rc, "recvmmsg of frames failed")
+    k = n.value
+    return [bytes(buf[int(foffs[i]):int(foffs[i + 1])]) for i in range(k)], peers[:k]
 
 
 def parse_rate(s: bytes):
