@@ -149,6 +149,11 @@ enum {
                                    UPSERT ops touched, for phip_export_changed ("Change set"
                                    below).  Two bits per slot; without the flag a handle
                                    launches exactly what it launched before the flag existed */
+#define PHIP_CFG_TRACK_USAGE 0x40u /* the handle keeps a usage baseline: every bucket's `taken`
+                                   at the last phip_usage_mark, for phip_export_top's metric
+                                   PHIP_TOP_SINCE_MARK ("Windowed top talkers" below).  One
+                                   uint64 per slot beside the table: 8 bytes a slot, 256 MB
+                                   at 2^25 slots */
 
 typedef struct phip_config {
   int32_t device;        /* HIP device ordinal                                          */
@@ -964,7 +969,9 @@ int phip_throttle_match(const phip_throttle_rule* rules, uint32_t n_rules, const
  * included.  +0.0, -0.0, negatives and NaNs never rank.  On that range the
  * order of the raw bits, the float order and the order of the stored codes are
  * one order.  idle_ns == 0: no idle filter; idle_ns < 0: PHIP_ERR_INVALID.
- * metric selects the ranking key: 0 = taken, anything else PHIP_ERR_INVALID.
+ * metric selects the ranking key: 0 = taken, PHIP_TOP_SINCE_MARK = taken since
+ * the last usage mark ("Windowed top talkers" below), anything else
+ * PHIP_ERR_INVALID.
  *
  * Order.  Entries come out by `taken` descending, equal `taken` in ascending
  * slot order.  The list is the first min(k, population) entries of that total
@@ -998,20 +1005,78 @@ int phip_throttle_match(const phip_throttle_rule* rules, uint32_t n_rules, const
  * host-pointer call copies back only what was written.
  *
  * Errors and locking.  k outside 1..PHIP_TOP_MAX, prefix_len over
- * PHIP_THROTTLE_MAX_PREFIX, a metric other than 0, idle_ns < 0, NULL q or st,
- * a missing out / names / offs outside count mode (an `out` in count mode),
- * names_cap below one name, or any flag bit other than PHIP_DEVICE_PTRS and
- * PHIP_SWEEP_COUNT is PHIP_ERR_INVALID, with nothing read from the table and
- * nothing written.  The call is serialised with the handle's other calls; a
- * batch queued with PHIP_RECV_ASYNC is finished first, its error is this
- * call's, and the list sees its merges.
+ * PHIP_THROTTLE_MAX_PREFIX, a metric above PHIP_TOP_SINCE_MARK, idle_ns < 0,
+ * NULL q or st, a missing out / names / offs outside count mode (an `out` in
+ * count mode), names_cap below one name, or any flag bit other than
+ * PHIP_DEVICE_PTRS, PHIP_SWEEP_COUNT and PHIP_TOP_MARK is PHIP_ERR_INVALID,
+ * with nothing read from the table and nothing written.  The call is
+ * serialised with the handle's other calls; a batch queued with
+ * PHIP_RECV_ASYNC is finished first, its error is this call's, and the list
+ * sees its merges.
  *
  * Nothing is written to the handle: table, arena, change set, layout count,
- * the hot directory and phip_len stay as they are.
+ * the hot directory and phip_len stay as they are (PHIP_TOP_MARK rewrites the
+ * usage baseline, and nothing else).
  *
- * Stated limits.  `taken` is a lifetime total, not a rate: a caller who wants
- * a rate diffs two lists, or divides by the state's elapsed.  Not here: other
- * metrics, prefixes over 16 bytes, k above PHIP_TOP_MAX.
+ * Stated limits.  Metric 0's `taken` is a lifetime total, not a rate, and two
+ * of its lists cannot be diffed into one: a bucket in neither list may have
+ * taken the most in between.  "Who took the most since then" is metric
+ * PHIP_TOP_SINCE_MARK on a handle that tracks usage.  Not here: metrics above
+ * 1, more than one baseline per handle, prefixes over 16 bytes, k above
+ * PHIP_TOP_MAX.
+ *
+ * Windowed top talkers: a usage baseline and the top k since the mark.
+ * A handle opened with PHIP_CFG_TRACK_USAGE keeps base[slot], the float64 bits
+ * of the bucket's `taken` at the last mark, beside its table (8 bytes a slot).
+ * The column starts as zeros, and +0.0 is the baseline of every bucket created
+ * after a mark: before any mark, and for such a bucket, "since the mark" is
+ * "since the bucket began".  `taken` only rises, and after merges it is the
+ * cluster-wide max, so a difference of two readings is cluster-wide usage in
+ * between, with nothing to add up across nodes.
+ *
+ * phip_usage_mark(h, st, 0): one streaming pass.  base becomes the decoded
+ * `taken` of every published record and 0 in every other slot.  st (may be
+ * NULL): buckets, the published records baselined; active, of those the ones
+ * with 0 < taken - base <= +Inf just before the call, names of any length --
+ * the population metric 1 would have reported with no prefix and no idle
+ * filter, plus the names over PHIP_MAX_NAME_LEN.  flags must be 0; that, and a
+ * handle opened without PHIP_CFG_TRACK_USAGE, is PHIP_ERR_INVALID with nothing
+ * read or written.  Serialised with the handle's other calls; a batch queued
+ * with PHIP_RECV_ASYNC is finished first, and its error is this call's.  A
+ * mark writes nothing but the column: table, arena, change set, hot directory,
+ * phip_len and the layout count stay, and a sweep cursor taken before it
+ * continues without `restarted`.
+ *
+ * metric = PHIP_TOP_SINCE_MARK.  The key of a record is the bits of d = taken -
+ * base, one IEEE-754 double subtraction (round to nearest, denormals kept).  A
+ * record ranks iff it passes every test above except the one on `taken`
+ * itself, and 0 < bits(d) <= 0x7FF0000000000000: +Inf - finite ranks first;
+ * Inf - Inf, a NaN `taken`, a zero and a negative difference never rank.
+ * Everything else is metric 0's contract with "key" read for `taken`: the
+ * order (key descending, equal keys in ascending slot order), top(k) the head
+ * of top(k'), the names_cap cut, the stats, count mode (the population is the
+ * buckets active since the mark) and the refusals.  out->taken[i] holds the
+ * key bits, the difference; out->state[i] is the record, so its taken is the
+ * current total.  phip_top_merge orders whatever the taken column holds, so
+ * lists of this metric merge as they are.  On a handle opened without
+ * PHIP_CFG_TRACK_USAGE the metric is PHIP_ERR_INVALID, with nothing read.
+ *
+ * PHIP_TOP_MARK: report and re-mark in one call.  With phip_usage_mark and
+ * phip_export_top as two calls, the takes that land between them are in the
+ * new baseline and in no list.  With this flag the call marks the whole table
+ * (whatever the prefix) right behind its list, under the handle's lock: no op
+ * of the handle falls between the two, and successive calls tile time exactly.
+ * The mark happens iff the call returns PHIP_OK, truncated or not: a caller
+ * who sizes names_cap too small loses the tail of that window.  Allowed with
+ * either metric; with PHIP_SWEEP_COUNT, or on a handle that does not track
+ * usage, PHIP_ERR_INVALID with nothing touched.
+ *
+ * Layout changes.  The baseline belongs to the bucket, not the slot: table
+ * growth and phip_evict_idle's move (PHIP_EVICT_SHRINK included) carry a
+ * surviving bucket's baseline along, an evicted bucket's baseline goes with it
+ * (if the bucket comes back it counts from zero, as after a node restart), and
+ * phip_restore clears the column (a snapshot does not hold it, and
+ * phip_snapshot_bytes does not count it).
  *
  * phip_top_merge (host only, no handle, no GPU): the top k of n_lists lists in
  * phip_export_top's layout, list i holding ns[i] entries -- the members of a
@@ -1028,10 +1093,12 @@ int phip_throttle_match(const phip_throttle_rule* rules, uint32_t n_rules, const
  * ns / out / n_out / out->names / out->offs, or a list with entries and no
  * names, offs or taken. */
 #define PHIP_TOP_MAX 4096          /* largest k */
+#define PHIP_TOP_SINCE_MARK 1      /* phip_top_query.metric: taken since the last usage mark */
+#define PHIP_TOP_MARK 0x400u       /* phip_export_top: mark the whole table behind the list */
 typedef struct phip_top_query {    /* host memory */
   uint8_t prefix[PHIP_THROTTLE_MAX_PREFIX];
   uint32_t prefix_len; /* 0..16; 0 matches every name */
-  uint32_t metric;     /* 0 = taken */
+  uint32_t metric;     /* 0 = taken, PHIP_TOP_SINCE_MARK */
   int64_t now, idle_ns;/* idle_ns > 0: skip buckets idle at now; 0: no filter */
   uint32_t k, reserved;/* 1..PHIP_TOP_MAX */
 } phip_top_query;
@@ -1052,6 +1119,11 @@ int phip_export_top(phip_handle* h, const phip_top_query* q, const phip_top_out*
                     phip_top_stats* st, uint32_t flags);
 int phip_top_merge(const phip_top_out* lists, const uint64_t* ns, uint32_t n_lists, uint32_t k,
                    const phip_top_out* out, uint64_t* n_out);
+typedef struct phip_usage_stats {
+  uint64_t buckets;    /* published records baselined by this call */
+  uint64_t active;     /* of those, 0 < taken - base <= +Inf just before it */
+} phip_usage_stats;
+int phip_usage_mark(phip_handle* h, phip_usage_stats* st /* may be NULL */, uint32_t flags);
 
 /* ---- host helpers (no device work) ---- */
 /* ParseRate: returns 0 or <0 on error; freq and per receive the values Go

@@ -49,6 +49,7 @@ EXPORTS = [
     "phip_unframe", "phip_frame_cuts", "phip_receive_frames", "phip_receive_frames_replies",
     "phip_ring_receive_frames", "phip_ring_receive_frames_replies", "phip_udp_recv_frames",
     "phip_frame_reply_peers",
+    "phip_usage_mark",
 ]
 
 PHIP_OK = 0
@@ -68,6 +69,7 @@ CFG_FIXED_SEED = 0x4
 CFG_ISOLATE = 0x8
 CFG_CLASSIFY_FIRST = 0x10
 CFG_TRACK_CHANGES = 0x20
+CFG_TRACK_USAGE = 0x40       # PHIP_CFG_TRACK_USAGE: keep the usage baseline (8 bytes a slot)
 ROUTE_COMBINE = 0x2
 GROUP_RCCL_SELF = 0x4
 GROUP_SMALL_CHUNKS = 0x8
@@ -85,6 +87,8 @@ MAX_NAME_LEN = 231         # PHIP_MAX_NAME_LEN
 THROTTLE_MAX_RULES = 8     # PHIP_THROTTLE_MAX_RULES
 THROTTLE_MAX_PREFIX = 16   # PHIP_THROTTLE_MAX_PREFIX
 TOP_MAX = 4096             # PHIP_TOP_MAX: the largest k of phip_export_top
+TOP_SINCE_MARK = 1         # PHIP_TOP_SINCE_MARK: phip_top_query.metric, taken since the mark
+TOP_MARK = 0x400           # PHIP_TOP_MARK: phip_export_top marks the table behind its list
 FRAME_MIN_BYTES = 256      # PHIP_FRAME_MIN_BYTES: any record fits
 FRAME_DEFAULT_BYTES = 1472 # PHIP_FRAME_DEFAULT_BYTES: 1500 - 20 - 8
 FRAME_MAX_BYTES = 65507    # PHIP_FRAME_MAX_BYTES
@@ -212,6 +216,10 @@ class phip_top_out(C.Structure):
 class phip_top_stats(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bytes", C.c_uint64), ("population", C.c_uint64),
                 ("passes", C.c_uint32), ("truncated", C.c_uint32)]
+
+
+class phip_usage_stats(C.Structure):
+    _fields_ = [("buckets", C.c_uint64), ("active", C.c_uint64)]
 
 
 _lib = None
@@ -406,6 +414,8 @@ def load(path: str = LIB_PATH):
                                       C.POINTER(phip_top_stats), u32]
         L.phip_top_merge.argtypes = [C.POINTER(phip_top_out), C.POINTER(u64), u32, u32,
                                      C.POINTER(phip_top_out), C.POINTER(u64)]
+    if hasattr(L, "phip_usage_mark"):
+        L.phip_usage_mark.argtypes = [vp, C.POINTER(phip_usage_stats), u32]
     if hasattr(L, "phip_unframe"):
         rqp = C.POINTER(phip_reply_egress)
         L.phip_unframe.argtypes = [vp, vp, vp, u32, u64, u32, vp, vp, u32, C.POINTER(u32), u32]

@@ -193,6 +193,11 @@ struct phip_handle {
   // and freed with the table; null pointers on a handle that keeps none
   bool track = false;
   Marks marks{};
+  // PHIP_CFG_TRACK_USAGE: the usage baseline (phip_kernels.hpp "top talkers"),
+  // one u64 per slot, allocated, replaced and freed where the marks are; null
+  // on a handle that keeps none
+  bool usage = false;
+  u64* base = nullptr;
   u8* arena = nullptr;
   u64 arena_cap = 0;
   u64 arena_open = 0;        // arena bytes at phip_open: a compacted arena is no smaller
@@ -461,6 +466,21 @@ int alloc_marks(phip_handle* h, u64 cap, Marks* out) {
   *out = Marks{p, p + w};
   return PHIP_OK;
 }
+// The usage baseline of a table of `cap` slots, cleared (+0.0) on the stream.
+int alloc_base(phip_handle* h, u64 cap, u64** out) {
+  u64* p = nullptr;
+  if (hipMalloc(&p, cap * sizeof(u64)) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(h, PHIP_ERR_FULL, "usage baseline of %llu slots: device memory",
+                   (unsigned long long)cap);
+  }
+  if (hipMemsetAsync(p, 0, cap * sizeof(u64), h->stream) != hipSuccess) {
+    (void)hipFree(p);
+    return set_err(h, PHIP_ERR_HIP, "usage baseline: clearing failed");
+  }
+  *out = p;
+  return PHIP_OK;
+}
 
 // Rehash the table into 2^newL slots (k_rehash).  Both tables are resident
 // while records move; the old one is freed after.
@@ -469,6 +489,7 @@ int grow_table(phip_handle* h, u32 newL) {
   Rec* nrecs = nullptr;
   u32* naux = nullptr;
   Marks nmarks{};
+  u64* nbase = nullptr;
   if (hipMalloc(&nrecs, ncap * sizeof(Rec)) != hipSuccess) {
     (void)hipGetLastError();
     return set_err(h, PHIP_ERR_FULL, "table growth to 2^%u slots: device memory", newL);
@@ -484,10 +505,13 @@ int grow_table(phip_handle* h, u32 newL) {
     (void)hipFree(nrecs);
     (void)hipFree(naux);
     if (nmarks.state) (void)hipFree(nmarks.state);
+    if (nbase) (void)hipFree(nbase);
     return rc;
   };
   if (h->track)
     if (int rc = alloc_marks(h, ncap, &nmarks)) return drop_new(rc);
+  if (h->usage)
+    if (int rc = alloc_base(h, ncap, &nbase)) return drop_new(rc);
   if (hipMemsetAsync(nrecs, 0, ncap * sizeof(Rec), h->stream) != hipSuccess ||
       hipMemsetAsync(naux, 0, ncap * sizeof(u32), h->stream) != hipSuccess ||
       hipMemsetAsync(h->ctr + kCtrTableFull, 0, sizeof(u32), h->stream) != hipSuccess)
@@ -499,7 +523,7 @@ int grow_table(phip_handle* h, u32 newL) {
   {
     Launch l(h, "k_rehash");
     k_rehash<<<grid_for(h->cap), kBlock, 0, h->stream>>>(h->recs, h->aux, h->cap, nt, h->ctr,
-                                                         h->marks, nmarks);
+                                                         h->marks, nmarks, h->base, nbase);
   }
   if (hipGetLastError() != hipSuccess)
     return drop_new(set_err(h, PHIP_ERR_HIP, "k_rehash launch failed"));
@@ -510,9 +534,11 @@ int grow_table(phip_handle* h, u32 newL) {
   HIPCHK(h, hipFree(h->recs));
   HIPCHK(h, hipFree(h->aux));
   if (h->marks.state) HIPCHK(h, hipFree(h->marks.state));
+  if (h->base) HIPCHK(h, hipFree(h->base));
   h->recs = nrecs;
   h->aux = naux;
   h->marks = nmarks;
+  h->base = nbase;
   h->L = newL;
   h->cap = ncap;
   h->max_load = load_limit(ncap, h->load_pct);
@@ -2887,6 +2913,7 @@ int phip_open(const phip_config* cfg, phip_handle** out) {
   h->classify_first = cfg->flags & PHIP_CFG_CLASSIFY_FIRST;
   h->small = !(cfg->flags & PHIP_CFG_NO_SMALL);
   h->track = cfg->flags & PHIP_CFG_TRACK_CHANGES;
+  h->usage = cfg->flags & PHIP_CFG_TRACK_USAGE;
   h->arena_cap = h->arena_open = cfg->arena_bytes ? cfg->arena_bytes : (1ull << 20);
   if (cfg->debug_tag_bits && cfg->debug_tag_bits < 64) h->tag_mask = (1ull << cfg->debug_tag_bits) - 1;
   if (cfg->flags & PHIP_CFG_FIXED_SEED) {
@@ -2933,6 +2960,7 @@ int phip_open(const phip_config* cfg, phip_handle** out) {
   if ((e = hipMemsetAsync(h->recs, 0, h->cap * sizeof(Rec), h->stream)) != hipSuccess) return fail(e);
   if ((e = hipMemsetAsync(h->aux, 0, h->cap * sizeof(u32), h->stream)) != hipSuccess) return fail(e);
   if (h->track && alloc_marks(h, h->cap, &h->marks)) return fail(hipErrorOutOfMemory);
+  if (h->usage && alloc_base(h, h->cap, &h->base)) return fail(hipErrorOutOfMemory);
   if ((e = hipMemsetAsync(h->arena_cursor, 0, 64, h->stream)) != hipSuccess) return fail(e);
   if ((e = hipMemsetAsync(h->ctr, 0, 3 * kCtrWords * sizeof(u32), h->stream)) != hipSuccess)
     return fail(e);
@@ -2960,6 +2988,7 @@ void phip_close(phip_handle* h) {
   if (h->recs) (void)hipFree(h->recs);
   if (h->aux) (void)hipFree(h->aux);
   if (h->marks.state) (void)hipFree(h->marks.state);
+  if (h->base) (void)hipFree(h->base);
   if (h->arena) (void)hipFree(h->arena);
   if (h->arena_cursor) (void)hipFree(h->arena_cursor);
   if (h->ctr) (void)hipFree(h->ctr);
@@ -3145,21 +3174,26 @@ int phip_restore(phip_handle* h, const uint8_t* in, uint64_t len) {
     Rec* nrecs = nullptr;
     u32* naux = nullptr;
     Marks nmarks{};
+    u64* nbase = nullptr;
     if (hipMalloc(&nrecs, scap * sizeof(Rec)) != hipSuccess ||
         hipMalloc(&naux, scap * sizeof(u32)) != hipSuccess ||
-        (h->track && alloc_marks(h, scap, &nmarks))) {
+        (h->track && alloc_marks(h, scap, &nmarks)) ||
+        (h->usage && alloc_base(h, scap, &nbase))) {
       (void)hipGetLastError();
       if (nrecs) (void)hipFree(nrecs);
       if (naux) (void)hipFree(naux);
+      if (nmarks.state) (void)hipFree(nmarks.state);
       return set_err(h, PHIP_ERR_FULL, "restore: no device memory for 2^%u slots", hd.log2_slots);
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipFree(h->recs));
     HIPCHK(h, hipFree(h->aux));
     if (h->marks.state) HIPCHK(h, hipFree(h->marks.state));
+    if (h->base) HIPCHK(h, hipFree(h->base));
     h->recs = nrecs;
     h->aux = naux;
     h->marks = nmarks;
+    h->base = nbase;
     h->L = hd.log2_slots;
     h->cap = scap;
     h->max_load = load_limit(scap, h->load_pct);
@@ -3173,6 +3207,8 @@ int phip_restore(phip_handle* h, const uint8_t* in, uint64_t len) {
   // (a snapshot holds no change set: the image's buckets start unmarked)
   if (h->marks.state)
     HIPCHK(h, hipMemsetAsync(h->marks.state, 0, 2 * mark_words(h->cap) * sizeof(u32), h->stream));
+  // (nor a usage baseline: the image's buckets count from zero)
+  if (h->base) HIPCHK(h, hipMemsetAsync(h->base, 0, h->cap * sizeof(u64), h->stream));
   HIPCHK(h, hipMemcpyAsync(h->arena_cursor, &hd.arena_used, sizeof(u64), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->n_buckets = hd.n_buckets;
@@ -4522,14 +4558,17 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
   u32* naux = nullptr;
   u8* narena = nullptr;
   Marks nmarks{};
+  u64* nbase = nullptr;
   if (hipMalloc(&nrecs, ncap * sizeof(Rec)) != hipSuccess ||
       hipMalloc(&naux, ncap * sizeof(u32)) != hipSuccess ||
       (narena_cap && hipMalloc(&narena, narena_cap + 64) != hipSuccess) ||
-      (h->track && alloc_marks(h, ncap, &nmarks))) {
+      (h->track && alloc_marks(h, ncap, &nmarks)) ||
+      (h->usage && alloc_base(h, ncap, &nbase))) {
     (void)hipGetLastError();
     if (nrecs) (void)hipFree(nrecs);
     if (naux) (void)hipFree(naux);
     if (narena) (void)hipFree(narena);
+    if (nmarks.state) (void)hipFree(nmarks.state);
     return set_err(h, PHIP_ERR_FULL, "evict: device memory for 2^%u slots and %llu arena bytes",
                    newL, (unsigned long long)narena_cap);
   }
@@ -4540,6 +4579,7 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
     (void)hipFree(naux);
     if (narena) (void)hipFree(narena);
     if (nmarks.state) (void)hipFree(nmarks.state);
+    if (nbase) (void)hipFree(nbase);
     return err;
   };
   if (hipMemsetAsync(nrecs, 0, ncap * sizeof(Rec), h->stream) != hipSuccess ||
@@ -4556,7 +4596,7 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
     Launch l(h, "k_evict_move");
     k_evict_move<<<grid_for(h->cap, kEvictBlock), kEvictBlock, 0, h->stream>>>(
         h->recs, h->aux, h->cap, h->arena, used, now, idle_ns, nt, ncap, narena, narena_cap, ev,
-        h->ctr, h->marks, nmarks);
+        h->ctr, h->marks, nmarks, h->base, nbase);
   }
   if (hipGetLastError() != hipSuccess)
     return drop_new(set_err(h, PHIP_ERR_HIP, "k_evict_move launch failed"));
@@ -4577,10 +4617,12 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
   Rec* orecs = h->recs;
   u32* oaux = h->aux;
   u32* omarks = h->marks.state;
+  u64* obase = h->base;
   u8* oarena = narena ? h->arena : nullptr;
   h->recs = nrecs;
   h->aux = naux;
   h->marks = nmarks;
+  h->base = nbase;
   h->L = newL;
   h->cap = ncap;
   h->max_load = load_limit(ncap, h->load_pct);
@@ -4599,6 +4641,7 @@ static int evict_idle(phip_handle* h, i64 now, i64 idle_ns, u64 min_evict, phip_
   HIPCHK(h, hipFree(orecs));
   HIPCHK(h, hipFree(oaux));
   if (omarks) HIPCHK(h, hipFree(omarks));
+  if (obase) HIPCHK(h, hipFree(obase));
   if (oarena) HIPCHK(h, hipFree(oarena));
   return PHIP_OK;
 }
@@ -4958,13 +5001,19 @@ int phip_export_top(phip_handle* h, const phip_top_query* q, const phip_top_out*
   if (!h || !q || !st) return PHIP_ERR_INVALID;
   std::lock_guard<std::mutex> g(h->mu);
   if (int rc0 = begin_call(h)) return rc0;   // (finishes a queued PHIP_RECV_ASYNC batch)
-  if (flags & ~(PHIP_DEVICE_PTRS | PHIP_SWEEP_COUNT))
+  if (flags & ~(PHIP_DEVICE_PTRS | PHIP_SWEEP_COUNT | PHIP_TOP_MARK))
     return set_err(h, PHIP_ERR_INVALID, "top: unknown flag bits 0x%x", flags);
   if (q->k < 1 || q->k > PHIP_TOP_MAX)
     return set_err(h, PHIP_ERR_INVALID, "top: k must be 1..%d", PHIP_TOP_MAX);
   if (q->prefix_len > PHIP_THROTTLE_MAX_PREFIX)
     return set_err(h, PHIP_ERR_INVALID, "top: a prefix over %d bytes", PHIP_THROTTLE_MAX_PREFIX);
-  if (q->metric != 0) return set_err(h, PHIP_ERR_INVALID, "top: metric %u is not known", q->metric);
+  if (q->metric > PHIP_TOP_SINCE_MARK)
+    return set_err(h, PHIP_ERR_INVALID, "top: metric %u is not known", q->metric);
+  const bool since = q->metric == PHIP_TOP_SINCE_MARK, mark = flags & PHIP_TOP_MARK;
+  if ((since || mark) && !h->usage)
+    return set_err(h, PHIP_ERR_INVALID, "top: the handle was opened without PHIP_CFG_TRACK_USAGE");
+  if (mark && (flags & PHIP_SWEEP_COUNT))
+    return set_err(h, PHIP_ERR_INVALID, "top: count mode does not mark");
   if (q->idle_ns < 0) return set_err(h, PHIP_ERR_INVALID, "top: idle_ns must not be negative");
   TopQuery Q{};
   {
@@ -4977,13 +5026,22 @@ int phip_export_top(phip_handle* h, const phip_top_query* q, const phip_top_out*
     Q.idle_ns = q->idle_ns;
   }
   const bool dev = flags & PHIP_DEVICE_PTRS;
+  // the table-reading kernels by metric: launch(the baseline, or its empty form)
+  auto by_metric = [&](auto launch) {
+    if (since)
+      launch(TopBase<true>{h->base});
+    else
+      launch(TopBase<false>{});
+  };
   int rc;
   if (flags & PHIP_SWEEP_COUNT) {
     if (out) return set_err(h, PHIP_ERR_INVALID, "top: count mode takes no output");
     phip_sweep_stats cs{};
     if ((rc = sweep_count_mode(h, 0, [&](unsigned grid, const SweepBuf& b) -> int {
           Launch l(h, "k_top_count");
-          k_top_count<<<grid, kBlock, 0, h->stream>>>(h->recs, h->cap, Q, b.ctr);
+          by_metric([&](auto tb) {
+            k_top_count<<<grid, kBlock, 0, h->stream>>>(h->recs, h->cap, Q, b.ctr, tb);
+          });
           return PHIP_OK;
         }, &cs)))
       return rc;
@@ -5020,7 +5078,9 @@ int phip_export_top(phip_handle* h, const phip_top_query* q, const phip_top_out*
   for (u32 done = 0; done < 64; done += kTopBits) {
     {
       Launch l(h, "k_top_hist");
-      k_top_hist<<<grid, kBlock, 0, h->stream>>>(h->recs, h->cap, Q, t.ctr, t.hist);
+      by_metric([&](auto tb) {
+        k_top_hist<<<grid, kBlock, 0, h->stream>>>(h->recs, h->cap, Q, t.ctr, t.hist, tb);
+      });
     }
     {
       Launch l(h, "k_top_pick");
@@ -5029,7 +5089,10 @@ int phip_export_top(phip_handle* h, const phip_top_query* q, const phip_top_out*
   }
   {
     Launch l(h, "k_top_ties");
-    k_top_ties<<<ntiles, kBlock, 0, h->stream>>>(h->recs, h->cap, Q, t.ctr, b.tile_cnt, b.tile_bytes);
+    by_metric([&](auto tb) {
+      k_top_ties<<<ntiles, kBlock, 0, h->stream>>>(h->recs, h->cap, Q, t.ctr, b.tile_cnt,
+                                                   b.tile_bytes, tb);
+    });
   }
   {
     Launch l(h, "k_top_scan");
@@ -5037,14 +5100,23 @@ int phip_export_top(phip_handle* h, const phip_top_query* q, const phip_top_out*
   }
   {
     Launch l(h, "k_top_collect");
-    k_top_collect<<<ntiles, kSweepBlock, 0, h->stream>>>(h->recs, h->cap, Q, t.ctr, b.tile_cnt, t.key,
-                                                         t.slot);
+    by_metric([&](auto tb) {
+      k_top_collect<<<ntiles, kSweepBlock, 0, h->stream>>>(h->recs, h->cap, Q, t.ctr, b.tile_cnt,
+                                                           t.key, t.slot, tb);
+    });
   }
   {
     // (long names are bounded by the arena's size, as in export_sweep)
     Launch l(h, "k_top_emit");
     k_top_emit<<<1, kTopEmitBlock, 0, h->stream>>>(h->recs, h->arena, h->arena_cap, t.ctr, t.key,
-                                                   t.slot, d, o.names_cap);
+                                                   t.slot, d, o.names_cap,
+                                                   since ? h->base : nullptr);
+  }
+  if (mark) {
+    // PHIP_TOP_MARK: the new baseline behind the list, under this call's lock
+    // (its two counts land in spare words of the top buffer and are not read)
+    Launch l(h, "k_usage_mark");
+    k_usage_mark<<<grid, kBlock, 0, h->stream>>>(h->recs, h->cap, h->base, t.ctr + kTpMark);
   }
   HIPCHK(h, hipGetLastError());
   u64 c[kTpWords];
@@ -5070,6 +5142,30 @@ int phip_export_top(phip_handle* h, const phip_top_query* q, const phip_top_out*
         (rc = copy_back(h, o.state, d.state, s.n, false)))
       return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return PHIP_OK;
+}
+
+// The usage mark (patrolhip.h "Windowed top talkers"): one pass of k_usage_mark
+// on count mode's grid, its two sums read back.  Nothing but the baseline
+// column is written.
+int phip_usage_mark(phip_handle* h, phip_usage_stats* st, uint32_t flags) {
+  if (!h) return PHIP_ERR_INVALID;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc0 = begin_call(h)) return rc0;   // (finishes a queued PHIP_RECV_ASYNC batch)
+  if (flags) return set_err(h, PHIP_ERR_INVALID, "usage mark: unknown flag bits 0x%x", flags);
+  if (!h->usage)
+    return set_err(h, PHIP_ERR_INVALID, "usage mark: the handle was opened without PHIP_CFG_TRACK_USAGE");
+  phip_sweep_stats cs{};
+  if (int rc = sweep_count_mode(h, 0, [&](unsigned grid, const SweepBuf& b) -> int {
+        Launch l(h, "k_usage_mark");
+        k_usage_mark<<<grid, kBlock, 0, h->stream>>>(h->recs, h->cap, h->base, b.ctr);
+        return PHIP_OK;
+      }, &cs))
+    return rc;
+  if (st) {
+    st->buckets = cs.n;
+    st->active = cs.bytes;
   }
   return PHIP_OK;
 }

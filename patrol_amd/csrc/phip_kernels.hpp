@@ -2763,11 +2763,20 @@ __device__ inline void carry_marks(const Marks& from, u64 s, const Marks& to, u3
   if (from.state[s >> 5] & bit) atomicOr(&to.state[d >> 5], nbit);
   if (from.req[s >> 5] & bit) atomicOr(&to.req[d >> 5], nbit);
 }
+// The usage baseline of a handle opened with PHIP_CFG_TRACK_USAGE ("windowed
+// top talkers" below): one u64 per slot, null without the flag.  It moves with
+// the record as the marks do; slot d is the record's alone and the new column
+// starts cleared, so the carry is one plain store.
+__device__ inline void carry_base(const u64* __restrict__ from, u64 s, u64* __restrict__ to, u32 d) {
+  if (from) to[d] = from[s];
+}
 
 __global__ __launch_bounds__(kBlock) void k_rehash(const Rec* __restrict__ old,
                                                    const u32* __restrict__ old_aux, u64 old_cap,
                                                    Table T, u32* ctr, Marks old_marks,
-                                                   Marks new_marks) {
+                                                   Marks new_marks,
+                                                   const u64* __restrict__ old_base,
+                                                   u64* __restrict__ new_base) {
   const u64 s = (u64)blockIdx.x * kBlock + threadIdx.x;
   if (s >= old_cap) return;
   const Rec r = load_rec(&old[s]);
@@ -2783,6 +2792,7 @@ __global__ __launch_bounds__(kBlock) void k_rehash(const Rec* __restrict__ old,
   q->name0 = r.name0; q->name1 = r.name1; q->created = r.created; q->name2 = r.name2;
   T.aux[d] = old_aux[s];
   carry_marks(old_marks, s, new_marks, d);
+  carry_base(old_base, s, new_base, d);
 }
 
 // Placement quality (phip_table_stats): every bucket's probe distance from
@@ -5953,7 +5963,7 @@ __global__ __launch_bounds__(kEvictBlock) void k_evict_move(
     const Rec* __restrict__ old, const u32* __restrict__ old_aux, u64 old_cap,
     const u8* __restrict__ old_arena, u64 old_used, i64 now, i64 idle_ns, Table T, u64 new_cap,
     u8* __restrict__ new_arena, u64 new_arena_cap, u64* ev, u32* ctr, Marks old_marks,
-    Marks new_marks) {
+    Marks new_marks, const u64* __restrict__ old_base, u64* __restrict__ new_base) {
   __shared__ u32 wave_off[kEvictBlock / 64];
   __shared__ u64 block_base;
   const u64 s = (u64)blockIdx.x * kEvictBlock + threadIdx.x;
@@ -6012,6 +6022,7 @@ __global__ __launch_bounds__(kEvictBlock) void k_evict_move(
   q->name0 = r.name0; q->name1 = r.name1; q->created = r.created; q->name2 = r.name2;
   T.aux[d] = old_aux[s];
   carry_marks(old_marks, s, new_marks, d);   // (an evicted bucket's marks stay behind)
+  carry_base(old_base, s, new_base, d);      // (and its baseline)
 }
 
 // ------------------------------------------------------ export sweep -----
@@ -7671,7 +7682,9 @@ __global__ __launch_bounds__(kBlock) void k_reply_place(Src src, const u8* __res
 //   k_top_emit     one workgroup sorts the at most kTopCap (key, slot) pairs
 //                  in LDS (key descending, slot ascending), scans the name
 //                  lengths in rank order, applies the names_cap cut and writes
-//                  names, offs, taken and state.
+//                  names, offs, taken and state;
+//   k_usage_mark   PHIP_TOP_MARK only: the baseline column rewritten behind
+//                  the emit, which has read what it needed of it.
 // The host enqueues every launch of the longest case; a kernel whose stage the
 // counter words say is over, or not needed, returns before it reads a slot, and
 // kTpPasses counts those that did read the table.
@@ -7698,7 +7711,9 @@ constexpr u32 kTpN = 10;       // entries written
 constexpr u32 kTpBytes = 11;   // their name bytes (= offs[n])
 constexpr u32 kTpTrunc = 12;   // names_cap cut the list
 constexpr u32 kTpErr = 13;     // internal: a long name outside the arena, a candidate past the cap
+constexpr u32 kTpMark = 14;    // PHIP_TOP_MARK: k_usage_mark's two counts, kSwN and kSwBytes from here
 constexpr u32 kTpWords = 16;
+static_assert(kTpErr < kTpMark && kTpMark + kSwBytes < kTpWords, "top counter words");
 constexpr u64 kTopRefine = 0, kTopEarly = 1, kTopTies = 2, kTopEmpty = 3;
 
 // The top buffer: the counter words, the digit histogram (one memset clears
@@ -7727,12 +7742,34 @@ struct TopQuery {
 // bits t with 0 < t <= +Inf's.  The stored code of such a t is kInfBits + 1 +
 // t (enc_f64), so t is one subtraction, and every other code -- negatives,
 // the zeros, NaNs -- lands outside [1, kInfBits] by it.
-__device__ __forceinline__ u64 top_key(const Rec& r, const TopQuery& q) {
+//
+// Metric 1 (PHIP_TOP_SINCE_MARK, "Windowed top talkers"): the key is the bits
+// of taken - base[s], one IEEE double subtraction (round to nearest, denormals
+// kept), under the same range test: a zero or negative difference, Inf - Inf
+// and a NaN taken land outside [1, kInfBits] too.  The table-reading kernels
+// take the baseline as their last argument, empty in the metric-0
+// instantiations (SweepParts' pattern), which stay the code they were.
+template <bool kSince>
+struct TopBase {};
+template <>
+struct TopBase<true> {
+  const u64* base;   // the handle's baseline column, one word per slot
+};
+
+template <bool kSince = false>
+__device__ __forceinline__ u64 top_key(const Rec& r, const TopQuery& q, u64 s,
+                                       TopBase<kSince> tb = TopBase<kSince>{}) {
   const u32 len = (u32)(r.name0 & 0xFFu);
   const bool inl = len <= kInlineName;   // (the first 16 name bytes: throttle_parts)
   const u64 n0 = inl ? (r.name0 >> 16) | (r.name1 << 48) : r.name1;
   const u64 n1 = inl ? (r.name1 >> 16) | (r.name2 << 48) : r.name2;
-  const u64 t = r.taken - (kInfBits + 1);
+  u64 t;
+  if constexpr (kSince) {
+    t = as_bits(as_f64(dec_f64(r.taken)) - as_f64(tb.base[s]));
+  } else {
+    (void)s;
+    t = r.taken - (kInfBits + 1);
+  }
   bool ok = r.tag && (rec_flags(r) & kRecPublished) && len <= PHIP_MAX_NAME_LEN &&
             t - 1 < kInfBits && throttle_match(q.R, n0, n1, len).rule >= 0;
   if (ok && q.idle_ns > 0) ok = !bucket_idle(r.created, r.elapsed, q.now, q.idle_ns);
@@ -7740,13 +7777,36 @@ __device__ __forceinline__ u64 top_key(const Rec& r, const TopQuery& q) {
 }
 
 // Count mode: the population alone, on the count pass's striding grid.
+template <bool kSince>
 __global__ __launch_bounds__(kBlock) void k_top_count(const Rec* __restrict__ recs, u64 cap,
-                                                      TopQuery q, u64* ctr) {
+                                                      TopQuery q, u64* ctr, TopBase<kSince> tb) {
   u32 n = 0;
   const u64 stride = (u64)gridDim.x * kBlock;
   for (u64 s = (u64)blockIdx.x * kBlock + threadIdx.x; s < cap; s += stride)
-    n += top_key(load_rec(&recs[s]), q) != 0;
+    n += top_key<kSince>(load_rec(&recs[s]), q, s, tb) != 0;
   count_finish<false>(n, 0, nullptr, nullptr, ctr);
+}
+
+// phip_usage_mark, and phip_export_top's PHIP_TOP_MARK behind its emit: every
+// slot's baseline becomes the decoded taken of its published record, 0 (+0.0)
+// where there is none -- consecutive lanes store consecutive words, on the
+// count pass's striding grid.  n: the records baselined; b: of those, the ones
+// active since the previous mark (metric 1's range test on any name length).
+__global__ __launch_bounds__(kBlock) void k_usage_mark(const Rec* __restrict__ recs, u64 cap,
+                                                       u64* __restrict__ base, u64* ctr) {
+  u32 n = 0;
+  u64 b = 0;
+  const u64 stride = (u64)gridDim.x * kBlock;
+  for (u64 s = (u64)blockIdx.x * kBlock + threadIdx.x; s < cap; s += stride) {
+    const Rec r = load_rec(&recs[s]);
+    const bool pub = r.tag && (rec_flags(r) & kRecPublished);
+    const u64 t = pub ? dec_f64(r.taken) : 0ull;
+    const u64 d = as_bits(as_f64(t) - as_f64(base[s]));
+    n += pub;
+    b += pub && d - 1 < kInfBits;
+    base[s] = t;
+  }
+  count_finish<false>(n, b, nullptr, nullptr, ctr);
 }
 
 // One digit's histogram.  The loop is uniform (a lane past the table reads the
@@ -7754,9 +7814,10 @@ __global__ __launch_bounds__(kBlock) void k_top_count(const Rec* __restrict__ re
 // whose keys all fall in one bin -- the leading digits of most tables, and
 // every digit of a table of equal keys -- adds its count once; only a mixed
 // wave adds per lane.
+template <bool kSince>
 __global__ __launch_bounds__(kBlock) void k_top_hist(const Rec* __restrict__ recs, u64 cap,
                                                      TopQuery q, const u64* __restrict__ ctr,
-                                                     u32* __restrict__ ghist) {
+                                                     u32* __restrict__ ghist, TopBase<kSince> tb) {
   __shared__ u32 h[kTopBins];
   if (ctr[kTpMode] != kTopRefine) return;
   const u32 done = (u32)ctr[kTpDone];
@@ -7769,7 +7830,8 @@ __global__ __launch_bounds__(kBlock) void k_top_hist(const Rec* __restrict__ rec
   const u64 stride = (u64)gridDim.x * kBlock;
   for (u64 base = (u64)blockIdx.x * kBlock; base < cap; base += stride) {
     const u64 s = base + threadIdx.x;
-    const u64 key = top_key(load_rec(&recs[s < cap ? s : cap - 1]), q);
+    const u64 sr = s < cap ? s : cap - 1;
+    const u64 key = top_key<kSince>(load_rec(&recs[sr]), q, sr, tb);
     const u64 hi = done ? key >> (64 - done) : 0ull;
     const bool in = s < cap && key != 0 && hi == pfx;
     const u32 d = (u32)(key >> nshift) & ((1u << width) - 1);
@@ -7857,10 +7919,12 @@ __global__ __launch_bounds__(kTopPickBlock) void k_top_pick(u64* ctr, u32* __res
 // Ties: the records of tile t whose key is the threshold (every key bit is
 // selected: the prefix is the key), into tile_cnt[t]; the byte sums tile_scan
 // also walks are zeros.
+template <bool kSince>
 __global__ __launch_bounds__(kBlock) void k_top_ties(const Rec* __restrict__ recs, u64 cap,
                                                      TopQuery q, u64* ctr,
                                                      u32* __restrict__ tile_cnt,
-                                                     u64* __restrict__ tile_bytes) {
+                                                     u64* __restrict__ tile_bytes,
+                                                     TopBase<kSince> tb) {
   if (ctr[kTpMode] != kTopTies) return;
   const u64 thr = ctr[kTpPfx];
   u32 n = 0;
@@ -7869,7 +7933,7 @@ __global__ __launch_bounds__(kBlock) void k_top_ties(const Rec* __restrict__ rec
   for (u32 k = 0; k < kSweepTile / kBlock; ++k) {
     const u64 s = t0 + (u64)k * kBlock + threadIdx.x;
     if (s >= cap) break;
-    n += top_key(load_rec(&recs[s]), q) == thr;
+    n += top_key<kSince>(load_rec(&recs[s]), q, s, tb) == thr;
   }
   count_finish<true>(n, 0, tile_cnt, tile_bytes, nullptr);
   if (blockIdx.x == 0 && threadIdx.x == 0) ctr[kTpPasses] += 1;
@@ -7888,11 +7952,13 @@ __global__ __launch_bounds__(kSweepBlock) void k_top_scan(const u64* __restrict_
 // scanned base is the record's rank among the table's ties in slot order; it
 // is admitted iff that rank is below the limit.  Early: every key at the
 // prefix is admitted, and no rank is needed.
+template <bool kSince>
 __global__ __launch_bounds__(kSweepBlock) void k_top_collect(const Rec* __restrict__ recs, u64 cap,
                                                              TopQuery q, u64* ctr,
                                                              const u32* __restrict__ tile_cnt,
                                                              u64* __restrict__ ckey,
-                                                             u32* __restrict__ cslot) {
+                                                             u32* __restrict__ cslot,
+                                                             TopBase<kSince> tb) {
   __shared__ u32 wtot[2][kSweepBlock / 64];
   const u64 mode = ctr[kTpMode];
   if (mode != kTopEarly && mode != kTopTies) return;
@@ -7905,7 +7971,8 @@ __global__ __launch_bounds__(kSweepBlock) void k_top_collect(const Rec* __restri
   const u64 t0 = (u64)blockIdx.x * kSweepTile;
   for (u32 k = 0; k < kSweepTile / kSweepBlock; ++k) {
     const u64 s = t0 + (u64)k * kSweepBlock + threadIdx.x;
-    const u64 key = top_key(load_rec(&recs[s < cap ? s : cap - 1]), q);
+    const u64 sr = s < cap ? s : cap - 1;
+    const u64 key = top_key<kSince>(load_rec(&recs[sr]), q, sr, tb);
     const bool live = s < cap && key != 0;
     const u64 hi = key >> shift;
     bool at = live && hi == pfx;
@@ -7964,7 +8031,8 @@ __global__ __launch_bounds__(kTopEmitBlock) void k_top_emit(const Rec* __restric
                                                             u64 arena_used, u64* ctr,
                                                             const u64* __restrict__ ckey,
                                                             const u32* __restrict__ cslot,
-                                                            TopOut out, u64 names_cap) {
+                                                            TopOut out, u64 names_cap,
+                                                            const u64* __restrict__ base) {
   constexpr u32 kPer = kTopCap / kTopEmitBlock;
   __shared__ u64 sk[kTopCap];
   __shared__ u32 ss[kTopCap];
@@ -8028,7 +8096,10 @@ __global__ __launch_bounds__(kTopEmitBlock) void k_top_emit(const Rec* __restric
     const Rec r = load_rec(&recs[ss[i]]);
     out.offs[i + 1] = e;
     put_name(out.names + start, r, len[j], arena, arena_used, &ctr[kTpErr]);
-    if (out.taken) out.taken[i] = dec_f64(r.taken);
+    // (base: metric 1, whose taken column is the key -- the difference again,
+    // the entry's end having replaced the sorted key in LDS)
+    if (out.taken)
+      out.taken[i] = base ? as_bits(as_f64(dec_f64(r.taken)) - as_f64(base[ss[i]])) : dec_f64(r.taken);
     if (out.state) {
       phip_state st;
       st.added = dec_f64(r.added); st.taken = dec_f64(r.taken);

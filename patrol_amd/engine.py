@@ -150,7 +150,8 @@ class GPURepo:
     def __init__(self, device: int = 0, log2_slots: int = 20, arena_bytes: int = 1 << 24,
                  max_load_pct: int = 90, debug_tag_bits: int = 0, grow: bool = True,
                  small: bool = True, hash_seed: int | None = None, isolate: bool = False,
-                 classify_first: bool = False, track_changes: bool = False):
+                 classify_first: bool = False, track_changes: bool = False,
+                 track_usage: bool = False):
         """hash_seed: None = a random placement seed per handle (the default,
         as Go's map seeds its hash per process); an int pins it
         (PHIP_CFG_FIXED_SEED; 0 = the unseeded placement).  isolate: set every
@@ -158,7 +159,9 @@ class GPURepo:
         after a dirty batch).  classify_first: classify every decoded Receive
         batch before merging it instead of merging optimistically
         (PHIP_CFG_CLASSIFY_FIRST; same results).  track_changes: keep the change
-        set export_changed drains (PHIP_CFG_TRACK_CHANGES)."""
+        set export_changed drains (PHIP_CFG_TRACK_CHANGES).  track_usage: keep
+        the usage baseline of usage_mark() and top(metric=1)
+        (PHIP_CFG_TRACK_USAGE; 8 bytes a slot)."""
         self.L = _lib.load()
         flags = (0 if grow else _lib.CFG_NO_GROW) | (0 if small else _lib.CFG_NO_SMALL)
         if isolate:
@@ -167,6 +170,8 @@ class GPURepo:
             flags |= _lib.CFG_CLASSIFY_FIRST
         if track_changes:
             flags |= _lib.CFG_TRACK_CHANGES
+        if track_usage:
+            flags |= _lib.CFG_TRACK_USAGE
         if hash_seed is not None:
             flags |= _lib.CFG_FIXED_SEED
         cfg = phip_config(device, log2_slots, arena_bytes, max_load_pct, debug_tag_bits, flags, 0,
@@ -533,7 +538,8 @@ class GPURepo:
         return {f: int(getattr(st, f)) for f, _ in _lib.phip_top_stats._fields_}
 
     def top(self, k: int, prefix: bytes = b"", now: int = 0, idle_ns: int = 0,
-            names_cap: int | None = None, state: bool = False) -> dict:
+            names_cap: int | None = None, state: bool = False, metric: int = 0,
+            mark: bool = False) -> dict:
         """phip_export_top: the k buckets with the largest `taken` among those
         whose name starts with `prefix` (at most 16 bytes) and, with idle_ns >
         0, that evict_idle's rule does not call idle at `now`; only positive
@@ -541,7 +547,13 @@ class GPURepo:
         slot order.  -> dict(names list[bytes], taken uint64 (float64 bits),
         state (None, or a structured array a/t/e/c), n, bytes, population (the
         buckets that qualified), passes (kernels that read the whole table),
-        truncated (names_cap, default 231 * k, cut the list))."""
+        truncated (names_cap, default 231 * k, cut the list)).
+
+        On a repo opened with track_usage=True: metric=1 (PHIP_TOP_SINCE_MARK)
+        ranks by `taken` since the last usage mark, and the taken column then
+        holds that difference (state["t"] stays the current total);
+        mark=True (PHIP_TOP_MARK) marks the whole table behind the list, in
+        the same call."""
         z = max(int(k), 1)
         if names_cap is None:
             names_cap = _lib.MAX_NAME_LEN * z
@@ -551,7 +563,8 @@ class GPURepo:
         sta = np.zeros(z, dtype=[("a", "<u8"), ("t", "<u8"), ("e", "<i8"), ("c", "<i8")]) \
             if state else None
         out = _lib.phip_top_out(_ptr(names), int(names_cap), _ptr(offs), _ptr(taken), _ptr(sta))
-        d = self._top_call(k, prefix, now, idle_ns, C.byref(out), 0)
+        d = self._top_call(k, prefix, now, idle_ns, C.byref(out), _lib.TOP_MARK if mark else 0,
+                           metric)
         n = d["n"]
         raw = names[:d["bytes"]].tobytes()
         d.update(names=[raw[int(offs[i]):int(offs[i + 1])] for i in range(n)], taken=taken[:n],
@@ -559,18 +572,33 @@ class GPURepo:
         return d
 
     def top_device(self, k: int, names, offs, taken=None, state=None, prefix: bytes = b"",
-                   now: int = 0, idle_ns: int = 0) -> dict:
+                   now: int = 0, idle_ns: int = 0, metric: int = 0, mark: bool = False) -> dict:
         """phip_export_top with device pointers: names (uint8 CUDA tensor, every
         byte of it is budget), offs (int64[k + 1]), taken (int64[k]) and state
-        (int64[k, 4]) where wanted.  -> the stats dict."""
+        (int64[k, 4]) where wanted; metric and mark as in top().  -> the stats
+        dict."""
         cap = int(names.numel() * names.element_size())
         out = _lib.phip_top_out(_ptr(names), cap, _ptr(offs), _ptr(taken), _ptr(state))
-        return self._top_call(k, prefix, now, idle_ns, C.byref(out), DEVICE_PTRS)
+        return self._top_call(k, prefix, now, idle_ns, C.byref(out),
+                              DEVICE_PTRS | (_lib.TOP_MARK if mark else 0), metric)
 
-    def top_count(self, prefix: bytes = b"", now: int = 0, idle_ns: int = 0) -> dict:
+    def top_count(self, prefix: bytes = b"", now: int = 0, idle_ns: int = 0,
+                  metric: int = 0) -> dict:
         """How many buckets qualify for top() (PHIP_SWEEP_COUNT): one pass,
-        dict(population, passes, ...)."""
-        return self._top_call(1, prefix, now, idle_ns, None, _lib.SWEEP_COUNT)
+        dict(population, passes, ...).  metric=1: the buckets active since the
+        mark."""
+        return self._top_call(1, prefix, now, idle_ns, None, _lib.SWEEP_COUNT, metric)
+
+    def usage_mark(self, flags: int = 0) -> dict:
+        """phip_usage_mark on a repo opened with track_usage=True: every
+        bucket's `taken` becomes its baseline for top(metric=1).  ->
+        dict(buckets, the published records baselined; active, of those the
+        ones that took anything since the previous mark)."""
+        st = _lib.phip_usage_stats()
+        rc = self.L.phip_usage_mark(self.h, C.byref(st), int(flags))
+        self._queued = None   # a queued batch is finished (or failed)
+        self._check(rc)
+        return dict(buckets=int(st.buckets), active=int(st.active))
 
     # -------------------------------------------------------- change set --
     @staticmethod
@@ -1308,13 +1336,15 @@ class GPUGroup:
 
     @classmethod
     def open_all(cls, devices, log2_slots: int = 20, arena_bytes: int = 1 << 24,
-                 max_load_pct: int = 90, track_changes: bool = False):
+                 max_load_pct: int = 90, track_changes: bool = False, track_usage: bool = False):
         """track_changes: every member keeps a change set (PHIP_CFG_TRACK_CHANGES):
         an owner marks the buckets it applied ops to, and repos[i].export_changed
-        is that owner's egress."""
+        is that owner's egress.  track_usage: every member keeps a usage
+        baseline (PHIP_CFG_TRACK_USAGE) for usage_mark() and top(metric=1)."""
         L = _lib.load()
         cfg = phip_config(0, log2_slots, arena_bytes, max_load_pct, 0,
-                          _lib.CFG_TRACK_CHANGES if track_changes else 0, 0, 0)
+                          (_lib.CFG_TRACK_CHANGES if track_changes else 0) |
+                          (_lib.CFG_TRACK_USAGE if track_usage else 0), 0, 0)
         devs = (C.c_int32 * len(devices))(*devices)
         g = C.c_void_p()
         rc = L.phip_group_open_all(C.byref(cfg), devs, len(devices), C.byref(g))
@@ -1656,17 +1686,25 @@ class GPUGroup:
         return out, [int(x) for x in sent], [int(x) for x in answered]
 
     def top(self, k: int, prefix: bytes = b"", now: int = 0, idle_ns: int = 0,
-            state: bool = False) -> dict:
+            state: bool = False, metric: int = 0, mark: bool = False) -> dict:
         """The group's top talkers: GPURepo.top of every local member (their
         tables are disjoint), then top_merge.  -> top_merge's dict, with
         population and passes summed over the members and `members`, their own
-        results."""
-        parts = [r.top(k, prefix, now, idle_ns, state=state) for r in self.repos]
+        results.  metric and mark go to every member as they are: each marks
+        its own table behind its own list."""
+        parts = [r.top(k, prefix, now, idle_ns, state=state, metric=metric, mark=mark)
+                 for r in self.repos]
         d = top_merge(parts, k)
         d.update(bytes=sum(map(len, d["names"])), population=sum(p["population"] for p in parts),
                  passes=sum(p["passes"] for p in parts),
                  truncated=int(any(p["truncated"] for p in parts)), members=parts)
         return d
+
+    def usage_mark(self) -> dict:
+        """GPURepo.usage_mark of every local member, the stats summed."""
+        parts = [r.usage_mark() for r in self.repos]
+        return dict(buckets=sum(p["buckets"] for p in parts),
+                    active=sum(p["active"] for p in parts), members=parts)
 
     def set_timing(self, on: bool = True):
         """phip_group_set_timing: per-stage event timing of later calls."""
